@@ -35,6 +35,19 @@ cpu_baseline: the oracle/ CPU restatement of the reference algorithm
 loss pass) on the host cores this job may use, threaded over trees, both the
 turbo=true-like vectorised build and the turbo=false-like scalar build on
 the same bounded row sample of the same workload.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up,
+times the K steps and prints the result line of the headline figure, with
+what those steps give for free (their per-step times, and the roofline of the
+dominant kernel from their HIP events). `--full` adds everything else the
+benchmark measures, each a run of its own after the timed steps: the CPU
+baseline, the config #5 row-shard leg and, with tree shards at N > 1, the
+weak-scaling figure (`--no-cpu`, `--no-row-shard` and `--no-weak` drop single
+legs of a full run; `cpu_baseline`, `row_shard` and `weak` are null in a
+plain run's line).
+`--dump-outputs DIR` writes what the last timed step returned to its caller
+as DIR/<name>.npy (DUMP_NOTE below); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -61,6 +74,10 @@ HBM_PEAK_GBS = 8000.0
 # SRHIP_BENCH_SHARED_GPU=1: every rank on GPU 0 over gloo (rehearsing the N > 1
 # code paths on a one-GPU box; the numbers are not a measurement)
 SHARED_GPU = os.environ.get("SRHIP_BENCH_SHARED_GPU") == "1"
+DUMP_NOTE = ("loss_sums.npy: float64 [ntrees], \u03a3w\u00b7\u2113 per tree over the rows, stored finite (the NaN of a "
+             "failed tree as 0, a sum that overflowed to \u00b1inf as \u00b1 the largest float64); "
+             "weight_sum.npy: float64 [1], \u03a3w; did_succeed.npy: float32 [ntrees], 1 or 0; tree order of the "
+             "seeded batch, at N > 1 with --shard trees rank 0's share")
 
 
 def available_cpus() -> int:
@@ -98,10 +115,15 @@ def parse():
     ap.add_argument("--shard", default="rows", choices=["trees", "rows"],
                     help="N > 1: trees split over the ranks (no collective) or rows split over the ranks "
                          "(every rank all trees, partials all-reduced on the device per step)")
-    ap.add_argument("--no-weak", action="store_true", help="skip the secondary weak-scaling measurement")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the CPU baseline, the config #5 row-shard leg and "
+                         "(tree shards, N > 1) weak scaling; off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-weak", action="store_true", help="--full: skip the secondary weak-scaling measurement")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-row-shard", action="store_true",
-                    help="skip the config #5 row-shard leg (rows over the GPUs, device-side all-reduce)")
+                    help="--full: skip the config #5 row-shard leg (rows over the GPUs, device-side all-reduce)")
     ap.add_argument("--rs-rows", type=int, default=10_000_000)
     ap.add_argument("--rs-trees", type=int, default=16384)
     ap.add_argument("--rs-nfeat", type=int, default=20)
@@ -204,6 +226,8 @@ def main():
 
     step_ms = []  # per-step wall time of the headline loop (each call returns synchronised)
 
+    last = [None]  # what the last step of the last timed() call returned
+
     def timed(p, steps, warmup, record=None):
         # one step: the loss of every tree on this rank's rows (rows mode: + the
         # all-reduce of the per-tree partials over the ranks)
@@ -215,7 +239,7 @@ def main():
         t_ = time.perf_counter()
         t_prev = t_
         for _ in range(steps):
-            step()
+            last[0] = step()
             kms.append(ctx.last_kernel_time()[0])
             if record is not None:
                 t_now = time.perf_counter()
@@ -239,10 +263,12 @@ def main():
     elapsed, kernel_ms = timed(prog, args.steps, args.warmup, step_ms)
     elapsed, total_node_rows = reduce_max_sum(elapsed, node_rows * args.steps)
     tree_code = prog.jit_info()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), rshard, last[0])
 
     # secondary: weak scaling (the whole batch on every rank)
     weak = None
-    if world > 1 and not args.no_weak and not rows_mode:
+    if args.full and world > 1 and not args.no_weak and not rows_mode:
         wprog = srhip.Program(ctx, srhip.flatten(all_trees, options, dtype=T), T)
         _, wnodes, _ = wprog.info()
         w_el, _ = timed(wprog, max(args.steps // 2, 3), 1)
@@ -251,7 +277,7 @@ def main():
                 "ms_per_step": w_el * 1e3 / max(args.steps // 2, 3)}
         del wprog
 
-    row_shard = None if args.no_row_shard else row_shard_leg(args, world, rank, ctx, dist, barrier)
+    row_shard = None if (args.no_row_shard or not args.full) else row_shard_leg(args, world, rank, ctx, dist, barrier)
 
     value = total_node_rows / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
@@ -264,6 +290,7 @@ def main():
         return
 
     # ---- roofline of the dominant kernel (eval_kernel) --------------------------------
+    # (from the HIP events of the timed steps themselves: no run of its own)
     roof = {
         "bound": "valu",
         "achieved": kernel_rate / 1e12,
@@ -300,7 +327,7 @@ def main():
 
     # ---- CPU baseline (oracle, host cores) ----------------------------------------------
     cpu = None
-    if not args.no_cpu and world == 1:  # rank 0 at N = 1 only
+    if args.full and not args.no_cpu and world == 1:  # rank 0 at N = 1 only
         sys.path.insert(0, str(ROOT / "oracle"))
         import oracle
 
@@ -369,9 +396,30 @@ def main():
         "setup_s": {"tree_gen": round(t_gen, 2), "compile_upload": round(t_compile, 3)},
         "steps_detail": step_stats(step_ms, kernel_ms),
     }
+    if args.dump_outputs:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": DUMP_NOTE}
     print(json.dumps(out))
     if dist:
         dist[1].destroy_process_group()
+
+
+def dump_outputs(out_dir, rshard, ret):
+    """--dump-outputs: what the last timed step gave its caller (DUMP_NOTE).
+    Single GPU or tree shards: eval_loss's (Σw·ℓ per tree, Σw, did_succeed);
+    row shards: the all-reduced partials of DeviceRowShard, unpacked. Every
+    stored value is finite, so that two dumps can be subtracted: a failed
+    tree's NaN becomes 0 (did_succeed tells it from a loss of 0) and a sum
+    that overflowed to ±inf becomes ± the largest float64."""
+    from srhip.distributed import unpack_partials
+
+    if rshard is not None:
+        sums, wsum, ok = unpack_partials(rshard.host if rshard.buf is None else rshard.buf.cpu().numpy())
+    else:
+        sums, wsum, ok = ret
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "loss_sums.npy", np.nan_to_num(np.asarray(sums, dtype=np.float64), nan=0.0))
+    np.save(out_dir / "weight_sum.npy", np.asarray([wsum], dtype=np.float64).reshape(1))
+    np.save(out_dir / "did_succeed.npy", np.asarray(ok).astype(np.float32))
 
 
 def step_stats(wall_ms, kern_ms):

@@ -30,6 +30,12 @@ def test_bench_launches_two_ranks_itself():
     assert out["rank_sum"] == 3.0  # ranks 0 and 1 both took part in the all-reduce
 
 
+def test_bench_takes_full_and_dump_outputs(tmp_path):
+    # the options of a full run and of the output dump reach every rank the launcher starts
+    out = _run(["--gpus", "2", "--stub", "--full", "--dump-outputs", str(tmp_path / "dump"), "--steps", "2"])
+    assert out["stub"] and out["n_gpus"] == 2 and out["steps"] == 2
+
+
 def test_bench_single_rank_does_not_launch():
     out = _run(["--gpus", "1", "--stub"])
     assert out["n_gpus"] == 1 and out["rank_sum"] == 1.0

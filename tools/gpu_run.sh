@@ -40,6 +40,8 @@ run_smoke() {
   tail -1 gpurun_out/smoke.log
 }
 run_bench() {
+  # the record run measures every leg (CPU baseline, row shards): --full unless BENCH_ARGS says otherwise
+  [ -n "${BENCH_ARGS+set}" ] || BENCH_ARGS=--full
   timeout -k 10 400 python -u bench.py ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.err || exit $?
   tail -c 600 gpurun_out/bench.json
 }
@@ -95,9 +97,9 @@ run_search() {
   tail -5 gpurun_out/search_c4.log | cut -c1-600
 }
 run_n2() {
-  SRHIP_BENCH_SHARED_GPU=1 timeout -k 10 300 python3 bench.py --gpus 2 --steps 5 --warmup 2 --rs-steps 2 \
+  SRHIP_BENCH_SHARED_GPU=1 timeout -k 10 300 python3 bench.py --gpus 2 --full --steps 5 --warmup 2 --rs-steps 2 \
     > gpurun_out/bench_n2_rows.json 2> gpurun_out/bench_n2_rows.err || { tail -20 gpurun_out/bench_n2_rows.err; exit 1; }
-  SRHIP_BENCH_SHARED_GPU=1 timeout -k 10 300 python3 bench.py --gpus 2 --shard trees --steps 5 --warmup 2 --no-row-shard \
+  SRHIP_BENCH_SHARED_GPU=1 timeout -k 10 300 python3 bench.py --gpus 2 --full --shard trees --steps 5 --warmup 2 --no-row-shard \
     > gpurun_out/bench_n2_trees.json 2> gpurun_out/bench_n2_trees.err || { tail -20 gpurun_out/bench_n2_trees.err; exit 1; }
   tail -c 300 gpurun_out/bench_n2_rows.json gpurun_out/bench_n2_trees.json
 }
