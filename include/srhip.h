@@ -129,7 +129,31 @@ extern "C" {
  * else Float64 power by squaring rounded once), Float64 by compensated power
  * by squaring; params[0] = n, integral with |n| < 2^31 (else INVALID). */
 #define SRHIP_LOSS_LPINT 10
-#define SRHIP_NUM_LOSSES 11
+/* ---- margin (classification) losses (LossFunctions.jl margin losses on the
+ * agreement a = y·ŷ, docs/src/losses.md:226-520): out_loss_sum[t] =
+ * Σ w_i·L(y_i·ŷ_i). y is used as given: the reference does not check that it
+ * is ±1, and neither does the engine. a is computed in T; the nine losses
+ * without a parameter are evaluated in T, the two parametric ones in Float64
+ * and rounded once (as the parametric distance losses). The gradient seed is
+ * dℓ/dŷ = y·L'(a), L' as LossFunctions.jl defines it. h = max(0, 1 - a). */
+#define SRHIP_LOSS_ZEROONE 11         /* a < 0 ? 1 : 0 (-0.0 gives 0); L' = 0            */
+#define SRHIP_LOSS_PERCEPTRON 12      /* max(0, -a)                                      */
+#define SRHIP_LOSS_LOGITMARGIN 13     /* log1p(exp(-a)) (+Inf where exp overflows)       */
+#define SRHIP_LOSS_L1HINGE 14         /* h                                               */
+#define SRHIP_LOSS_L2HINGE 15         /* h^2                                             */
+#define SRHIP_LOSS_SMOOTHEDL1HINGE 16 /* a >= 1-g ? (0.5/g) h^2 : 1 - g/2 - a, params[0] = g > 0 */
+#define SRHIP_LOSS_MODHUBER 17        /* a >= -1 ? h^2 : -4a                             */
+#define SRHIP_LOSS_L2MARGIN 18        /* (1 - a)^2                                       */
+#define SRHIP_LOSS_EXP 19             /* exp(-a)                                         */
+#define SRHIP_LOSS_SIGMOID 20         /* 1 - tanh(a)                                     */
+/* a >= q/(q+1) ? 1 - a : (q^q / (q+1)^(q+1)) / a^q; params[0] = q > 0 (else
+ * INVALID), integral and below 2^31 (else UNSUPPORTED: the reference raises a
+ * DomainError for a negative agreement under a non-integer power, so that case
+ * stays with the CPU path). */
+#define SRHIP_LOSS_DWDMARGIN 21
+#define SRHIP_NUM_LOSSES 22
+/* ids from here on are margin losses (a = y·ŷ), below it distance losses (r = ŷ - y) */
+#define SRHIP_MARGIN_LOSS_BEGIN 11
 
 typedef struct srhip_ctx srhip_ctx;
 typedef struct srhip_dataset srhip_dataset;
@@ -391,7 +415,9 @@ int32_t srhip_program_update_stats(const srhip_program* prog, int64_t* out_inpla
 /* Gradient tree code of this program (reverse-mode ∂L/∂c for
  * srhip_eval_loss_grad, built on the first gradient call; Float32: L2 and the
  * losses with a dℓ/dr routine — all but Periodic; Float64 (jit64.cpp): all
- * but LP, the non-integer LPDistLoss; LPINT has its routines in both):
+ * but LP, the non-integer LPDistLoss; LPINT has its routines in both; the
+ * margin losses have none in either, their gradients run in the forward-mode
+ * interpreter):
  * trees compiled, trees left to the forward-mode interpreter, code bytes,
  * codegen and load times (ms). All zero before the first gradient call. */
 int32_t srhip_program_grad_jit_info(const srhip_program* prog, int32_t* out_ntrees, int32_t* out_nrejected,
@@ -427,7 +453,9 @@ int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int
  * for the elementwise loss `loss` (SRHIP_LOSS_*) with its parameter; fast
  * bit 3: Float64 trees through the Float64 tree compiler with that loss's
  * routine in the tile tail, or with grad = 1 their gradient tree code. SRHIP_ERR_UNSUPPORTED when Float32 tree code has no routine for that
- * loss (a Float64 tree without one is not compiled). */
+ * loss (a Float64 tree without one is not compiled). The margin losses have
+ * Float32 loss tree code only: grad = 1 or fast bit 3 with one of them is
+ * SRHIP_ERR_UNSUPPORTED, and those calls run in the interpreter. */
 int32_t srhip_jit_compile_loss(const srhip_trees* trees, int32_t grad, int32_t fast, int32_t loss, double loss_param,
                                uint8_t* out_bytes, int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext,
                                int32_t* out_offsets, int64_t* inout_noffsets);

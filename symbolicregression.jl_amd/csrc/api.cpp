@@ -2755,9 +2755,22 @@ int32_t srhip_program_set_constants(srhip_program* prog, const void* consts) {
 
 // A SRHIP_LOSS_* kind and its parameter: UNSUPPORTED beyond the table,
 // INVALID without a needed parameter or for LPDistLoss{n} with n not an integer
-// of magnitude below 2^31
+// of magnitude below 2^31. Of the margin losses only SmoothedL1Hinge (γ > 0) and
+// DWDMargin take one (q > 0; a q that is not integral, or not below 2^31, is
+// UNSUPPORTED: the reference raises a DomainError for a negative agreement under
+// a non-integer power, so the CPU path owns that case).
 static void check_loss(int32_t kind, const double* params) {
   if (kind < 0 || kind >= SRHIP_NUM_LOSSES) throw Error(SRHIP_ERR_UNSUPPORTED, "unsupported loss");
+  if (kind >= SRHIP_MARGIN_LOSS_BEGIN) {
+    if (kind != SRHIP_LOSS_SMOOTHEDL1HINGE && kind != SRHIP_LOSS_DWDMARGIN) return;
+    if (!params) throw Error(SRHIP_ERR_INVALID, "loss needs a parameter");
+    if (!(params[0] > 0.0))
+      throw Error(SRHIP_ERR_INVALID, kind == SRHIP_LOSS_DWDMARGIN ? "DWDMarginLoss needs q > 0"
+                                                                  : "SmoothedL1HingeLoss needs gamma > 0");
+    if (kind == SRHIP_LOSS_DWDMARGIN && !(params[0] == std::trunc(params[0]) && params[0] < 2147483648.0))
+      throw Error(SRHIP_ERR_UNSUPPORTED, "DWDMarginLoss with a q that is not an integer below 2^31");
+    return;
+  }
   const bool needs = kind != SRHIP_LOSS_L2 && kind != SRHIP_LOSS_L1 && kind != SRHIP_LOSS_LOGCOSH &&
                      kind != SRHIP_LOSS_LOGITDIST;
   if (needs && !params) throw Error(SRHIP_ERR_INVALID, "loss needs a parameter");
@@ -2997,6 +3010,8 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
       throw Error(SRHIP_ERR_UNSUPPORTED, "no gradient tree code for this loss");
     if (mode != 2 && mode != 5 && mode != 6 && !jit::has_loss_routine(loss))
       throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for this loss");
+    if (mode == 5 && !out_mode && loss >= SRHIP_MARGIN_LOSS_BEGIN)  // margin losses: Float32 loss code only
+      throw Error(SRHIP_ERR_UNSUPPORTED, "no Float64 tree code for this loss");
     if (mode == 6) {  // Float64 gradient tree code (jit64.cpp GradGen64)
       if (!jit::has_dloss_routine64(loss)) throw Error(SRHIP_ERR_UNSUPPORTED, "no Float64 gradient tree code for this loss");
       CompiledBatch<double> cb = compile_batch<double>(*trees, /*grad=*/true);

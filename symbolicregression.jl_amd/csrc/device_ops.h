@@ -479,7 +479,7 @@ __device__ __forceinline__ T uop(T x) {
   }
 }
 
-// ---- elementwise losses, r = ŷ - y -------------------------------------------------
+// ---- elementwise losses, r = ŷ - y (the margin losses on a = y·ŷ follow them) -------
 // r = ŷ - y in T (LossFunctions' DistanceLoss: value(L, output - target)).
 // L2, L1, LogCosh and LogitDist have no parameter and stay in T (abs2 / abs of
 // the T residual). The parametric losses hold a Float64 field (LPDistLoss's P,
@@ -644,6 +644,86 @@ __device__ __forceinline__ double ipow(double x, long long n) {
   return (__builtin_isfinite(x) && __builtin_isfinite(err)) ? __builtin_fma(x, y, err) : x * y;
 }
 
+// ---- margin losses, a = y·ŷ (LossFunctions' MarginLoss: value(L, target * output)) ----
+// The nine without a parameter stay in T; SmoothedL1Hinge(γ) and DWDMargin(q)
+// hold a Float64 field, so they are evaluated in Float64 on the T-valued a and
+// rounded once (elem_loss_param's convention). max(0, 1 - a) is written a < 1 ? 1 - a : 0
+// (the same value for every x that is not NaN; a NaN ŷ fails the tree).
+// log1p / tanh / cosh are OCML's, the interpreter's m_log1p / m_tanh / m_cosh values,
+// called directly: margin_loss_ool below must stay a leaf function.
+__device__ __forceinline__ float mg_log1p(float x) { return log1pf(x); }
+__device__ __forceinline__ double mg_log1p(double x) { return log1p(x); }
+__device__ __forceinline__ float mg_tanh(float x) { return tanhf(x); }
+__device__ __forceinline__ double mg_tanh(double x) { return tanh(x); }
+__device__ __forceinline__ float mg_cosh(float x) { return coshf(x); }
+__device__ __forceinline__ double mg_cosh(double x) { return cosh(x); }
+// a^n of DWDMargin for its integral q (check_loss) by squaring: a loop over the
+// wave-uniform n that fits the tree code's loss routine, as LPINT's, and keeps
+// margin_loss_ool free of pow's registers.
+template <typename T>
+__device__ __forceinline__ double margin_pow(double a, double q) {
+  return pow_by_squaring(a, (long long)q);
+}
+template <typename T>
+__device__ __forceinline__ double margin_loss_param(int kind, double p, double a) {
+  const double h = a < 1.0 ? 1.0 - a : 0.0;
+  switch (kind) {
+    case SRHIP_LOSS_SMOOTHEDL1HINGE: return a >= 1.0 - p ? (0.5 / p) * (h * h) : 1.0 - p / 2.0 - a;
+    case SRHIP_LOSS_DWDMARGIN:
+      return a >= p / (p + 1.0) ? 1.0 - a
+                                : (margin_pow<T>(p, p) / margin_pow<T>(p + 1.0, p + 1.0)) / margin_pow<T>(a, p);
+  }
+  return qnan<double>();
+}
+template <typename T>
+__device__ __forceinline__ T margin_loss(int kind, double p, T a) {
+  const T h = a < T(1) ? T(1) - a : T(0);
+  switch (kind) {
+    case SRHIP_LOSS_ZEROONE: return a < T(0) ? T(1) : T(0);
+    case SRHIP_LOSS_PERCEPTRON: return a < T(0) ? -a : T(0);
+    case SRHIP_LOSS_LOGITMARGIN: return mg_log1p(m_exp(-a));
+    case SRHIP_LOSS_L1HINGE: return h;
+    case SRHIP_LOSS_L2HINGE: return h * h;
+    case SRHIP_LOSS_MODHUBER: return a >= T(-1) ? h * h : T(-4) * a;
+    case SRHIP_LOSS_L2MARGIN: return (T(1) - a) * (T(1) - a);
+    case SRHIP_LOSS_EXP: return m_exp(-a);
+    case SRHIP_LOSS_SIGMOID: return T(1) - mg_tanh(a);
+  }
+  return (T)margin_loss_param<T>(kind, p, (double)a);
+}
+// L'(a) as LossFunctions.jl's deriv; the caller multiplies by y (dℓ/dŷ = y·L'(y·ŷ))
+template <typename T>
+__device__ __forceinline__ T margin_dloss(int kind, double p, T a) {
+  switch (kind) {
+    case SRHIP_LOSS_ZEROONE: return T(0);
+    case SRHIP_LOSS_PERCEPTRON: return a >= T(0) ? T(0) : T(-1);
+    case SRHIP_LOSS_LOGITMARGIN: return T(-1) / (T(1) + m_exp(a));
+    case SRHIP_LOSS_L1HINGE: return a >= T(1) ? T(0) : T(-1);
+    case SRHIP_LOSS_L2HINGE: return a >= T(1) ? T(0) : T(2) * (a - T(1));
+    case SRHIP_LOSS_MODHUBER: return a >= T(-1) ? (a > T(1) ? T(0) : T(2) * (a - T(1))) : T(-4);
+    case SRHIP_LOSS_L2MARGIN: return T(2) * (a - T(1));
+    case SRHIP_LOSS_EXP: return -m_exp(-a);
+    case SRHIP_LOSS_SIGMOID: { const T c = mg_cosh(a); return T(-1) / (c * c); }  // -sech(a)^2
+  }
+  const double ad = (double)a;
+  switch (kind) {
+    case SRHIP_LOSS_SMOOTHEDL1HINGE: return (T)(ad >= 1.0 - p ? (ad >= 1.0 ? 0.0 : (ad - 1.0) / p) : -1.0);
+    case SRHIP_LOSS_DWDMARGIN: {
+      const double s = p / (p + 1.0);
+      return (T)(ad >= s ? -1.0 : -margin_pow<T>(s, p + 1.0) / margin_pow<T>(ad, p + 1.0));
+    }
+  }
+  return qnan<T>();
+}
+// The interpreters take a margin loss through these out-of-line copies (one call per
+// value, the kind switched on inside): inlined into the kernels' loss switch, the
+// eleven bodies cost the generic-loss kernels registers, occupancy and scratch. The
+// tree code's loss routines inline margin_loss itself (gen_jit.py).
+template <typename T>
+__device__ SR_NOINLINE T margin_loss_ool(int kind, double p, T a) { return margin_loss<T>(kind, p, a); }
+template <typename T>
+__device__ SR_NOINLINE T margin_dloss_ool(int kind, double p, T a) { return margin_dloss<T>(kind, p, a); }
+
 template <typename T>
 __device__ __forceinline__ double elem_loss_param(int kind, double p, double r) {
   const double ar = __builtin_fabs(r);
@@ -662,6 +742,7 @@ __device__ __forceinline__ double elem_loss_param(int kind, double p, double r) 
 }
 template <typename T>
 __device__ __forceinline__ T elem_loss(int kind, double p, T yhat, T y) {
+  if (kind >= SRHIP_MARGIN_LOSS_BEGIN) return margin_loss_ool<T>(kind, p, yhat * y);
   const T r = yhat - y;
   const T ar = m_fabs(r);
   switch (kind) {
@@ -738,10 +819,11 @@ __device__ __forceinline__ void uop_d(T x, T& f, T& fx) {
   else fx = T(0);
 }
 
-// dℓ/dŷ of the elementwise losses (r = ŷ - y); the parametric ones in
-// Float64 like their values (elem_loss)
+// dℓ/dŷ of the elementwise losses (r = ŷ - y; a margin loss: y·L'(y·ŷ)); the
+// parametric ones in Float64 like their values (elem_loss)
 template <typename T>
 __device__ __forceinline__ T elem_dloss(int kind, double p, T yhat, T y) {
+  if (kind >= SRHIP_MARGIN_LOSS_BEGIN) return y * margin_dloss_ool<T>(kind, p, yhat * y);
   const T r = yhat - y;
   const T sg = r > T(0) ? T(1) : (r < T(0) ? T(-1) : T(0));
   switch (kind) {

@@ -66,6 +66,24 @@ __device__ __forceinline__ T tile_loss(const T (&acc)[R], const T (&yv)[R], cons
   return s0 + s1;
 }
 
+// tile_loss with the loss kind at run time
+template <bool W, bool MASK, typename T, int R>
+__device__ __forceinline__ T tile_loss_rt(int lk, const T (&acc)[R], const T (&yv)[R], const T (&wv)[R],
+                                          double lp, int lane, int valid) {
+  T s0 = T(0), s1 = T(0);
+#pragma unroll
+  for (int e = 0; e < R; ++e) {
+    T l = dev::elem_loss<T>(lk, lp, acc[e], yv[e]);
+    if constexpr (W) l = wv[e] * l;
+    if constexpr (MASK) {
+      const int row = row_of<T, R>(e, lane);
+      l = row < valid ? l : T(0);
+    }
+    if (e & 1) s1 += l; else s0 += l;
+  }
+  return s0 + s1;
+}
+
 // Kernel mode of a MODE_LOSS launch whose loss is L2 (the default loss):
 // the tile epilogue is compiled for it instead of switching on a.loss.
 constexpr int kModeLossL2 = 2;
@@ -101,6 +119,9 @@ __device__ __forceinline__ bool run_program_ti(const uint4* recs, uint32_t lane_
 template <bool W, bool MASK, typename T, int R>
 __device__ __forceinline__ T tile_loss_any(int lk, const T (&acc)[R], const T (&yv)[R],
                                            const T (&wv)[R], double lp, int lane, int valid) {
+  // a margin loss: the kind stays a run-time value, switched on inside the out-of-line
+  // dev::margin_loss_ool (one case per id here costs the kernel registers and scratch)
+  if (lk >= SRHIP_MARGIN_LOSS_BEGIN) return tile_loss_rt<W, MASK>(lk, acc, yv, wv, lp, lane, valid);
   switch (lk) {
     case SRHIP_LOSS_L2: return tile_loss<SRHIP_LOSS_L2, W, MASK>(acc, yv, wv, lp, lane, valid);
     case SRHIP_LOSS_L1: return tile_loss<SRHIP_LOSS_L1, W, MASK>(acc, yv, wv, lp, lane, valid);

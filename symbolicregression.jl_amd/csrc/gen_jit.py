@@ -183,6 +183,12 @@ LOSSES = losses()
 # no loss routine: L2 is inline (LPDistLoss{n} with an integer n has one: its
 # power-by-squaring loop runs over the wave-uniform n in SGPRs)
 NO_LOSS_ROUTINE = {"L2"}
+# the margin losses (a = y·ŷ in the tile tail's block instead of r = ŷ - y): ids from
+# SRHIP_MARGIN_LOSS_BEGIN on. They have a loss routine (ℓ(a), dev::margin_loss) but no
+# dℓ routine: the gradient tree code's seed is written for a residual, so their
+# gradients run in the interpreter (jit_grad.cpp has_dloss_routine)
+MARGIN_BEGIN = int(re.search(r"#define SRHIP_MARGIN_LOSS_BEGIN\s+(\d+)", open(G.INCLUDE).read()).group(1))
+MARGIN_LOSSES = {n for n, i in LOSSES.items() if i >= MARGIN_BEGIN}
 
 
 def routine_list():
@@ -273,12 +279,26 @@ def routine_list():
                     " s.s_flag = (unsigned)fl; s.s_flag_hi = (unsigned)(fl >> 32);")
             rs.append((f"l_{name.lower()}", body, True))
             continue
+        if name == "LOGITMARGIN":
+            # dev::margin_loss's log1p(exp(-a)), bit for bit, in two passes over the rows: exp, then
+            # log1p of the value made opaque. Row by row the Float64 constants of both are live at
+            # once and the routine borrows six of the pinned SGPRs (saved to VGPR lanes, as
+            # l_logcosh / l_logitdist do); two plain passes reach v30; this form stays within both
+            rs.append(("l_logitmargin",
+                       rows_serial("s.a[r] = dev::m_exp(-s.a[r]);") + " " +
+                       rows_serial('float t = s.a[r]; asm volatile("" : "+v"(t)); s.a[r] = dev::mg_log1p(t);'), False))
+            continue
+        if name in MARGIN_LOSSES:  # a in A -> ℓ(a) in A
+            rs.append((f"l_{name.lower()}",
+                       imm + rows_serial(f"s.a[r] = dev::margin_loss<float>(SRHIP_LOSS_{name}, imm, s.a[r]);"),
+                       False))
+            continue
         rs.append((f"l_{name.lower()}",
                    imm + rows_serial(f"s.a[r] = dev::elem_loss<float>(SRHIP_LOSS_{name}, imm, s.a[r], 0.0f);"),
                    False))
     # dℓ/dr of the same losses (the gradient tree code's seed, jit_grad.cpp)
     for name in sorted(LOSSES, key=lambda k: LOSSES[k]):
-        if name in NO_LOSS_ROUTINE:
+        if name in NO_LOSS_ROUTINE or name in MARGIN_LOSSES:
             continue
         imm = ("const double imm = __builtin_bit_cast(double, ((unsigned long long)s.s_kh << 32) | "
                "(unsigned long long)s.s_k); ")
@@ -711,9 +731,10 @@ def build(hipcc, outdir, R):
         f.write("// ℓ routine of each elementwise loss in the gradient tree code (the loss routine, but\n"
                 "// Periodic's without the hand-back)\n")
         f.write("#define SR_JIT_GRAD_LOSS_ROUTINE {" + ", ".join(
-            str(-1 if n in NO_LOSS_ROUTINE else rid("g_periodic" if n == "PERIODIC" else f"l_{n.lower()}"))
+            str(-1 if n in NO_LOSS_ROUTINE or n in MARGIN_LOSSES
+                else rid("g_periodic" if n == "PERIODIC" else f"l_{n.lower()}"))
             for n in sorted(LOSSES, key=lambda k: LOSSES[k])) + "}\n")
-        f.write("// dℓ/dr routine of each elementwise loss (-1: L2, inline, or left out)\n")
+        f.write("// dℓ/dr routine of each elementwise loss (-1: L2, inline, a margin loss, or left out)\n")
         f.write("#define SR_JIT_DLOSS_ROUTINE {" + ", ".join(
             str(-1 if n in NO_LOSS_ROUTINE else rid(f"d_{n.lower()}")) for n in sorted(LOSSES, key=lambda k: LOSSES[k])) + "}\n")
         f.write("// the gradient forward's sin / cos with the reverse factor in B (-1: not built)\n")

@@ -34,6 +34,11 @@ LOSSY_UOPS, LOSSY_LHS, LOSSY_RHS = G.LOSSY_UOPS, G.LOSSY_LHS, G.LOSSY_RHS
 LOSSES = {m.group(1): int(m.group(2)) for m in
           re.finditer(r"#define SRHIP_LOSS_(\w+)\s+(\d+)", open(G.INCLUDE).read())}
 NO_LOSS_ROUTINE = {"L2"}  # L2 inline
+# the margin losses (ids from SRHIP_MARGIN_LOSS_BEGIN on, a = y·ŷ) have no Float64
+# routines: the tails and seeds of jit64.cpp are written for a residual, so they run
+# in the interpreter (SR_JIT64_LOSS_ROUTINE / SR_JIT64_DLOSS_ROUTINE -1)
+MARGIN_BEGIN = int(re.search(r"#define SRHIP_MARGIN_LOSS_BEGIN\s+(\d+)", open(G.INCLUDE).read()).group(1))
+MARGIN_LOSSES = {n for n, i in LOSSES.items() if i >= MARGIN_BEGIN}
 INLINE_BOPS = {"ADD", "SUB", "MUL"}
 INLINE_UOPS = {"NEG", "ABS", "SQUARE", "CUBE"}
 
@@ -161,7 +166,7 @@ def routine_list():
     # (Float64 bits) in s_k : s_kh — device_ops.h elem_loss with ŷ = r, y = 0
     # (r - 0 = r exactly), the Float64 interpreter's loss code
     for name in sorted(LOSSES, key=lambda k: LOSSES[k]):
-        if name in NO_LOSS_ROUTINE:
+        if name in NO_LOSS_ROUTINE or name in MARGIN_LOSSES:
             continue
         rs.append((f"l_{name.lower()}",
                    imm + rows(f"s.a[r] = dev::elem_loss<double>(SRHIP_LOSS_{name}, imm, s.a[r], 0.0);")))
@@ -169,7 +174,7 @@ def routine_list():
     # LP's Float64 pow runs its two rows one after the other (scheduler fenced between them:
     # both at once exceed the routine registers)
     for name in sorted(LOSSES, key=lambda k: LOSSES[k]):
-        if name in NO_LOSS_ROUTINE:
+        if name in NO_LOSS_ROUTINE or name in MARGIN_LOSSES:
             continue
         body = f"s.a[r] = dev::elem_dloss<double>(SRHIP_LOSS_{name}, imm, s.a[r], 0.0);"
         if name == "LP":  # elem_dloss's value with only pow's temporaries live, one row at a time

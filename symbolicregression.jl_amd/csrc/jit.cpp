@@ -1155,10 +1155,15 @@ struct Gen {
       as.bind(L_skip);
     }
     // ---- L2 loss of the tile: the residuals here, their squares in emit_tail
+    // (a margin loss: the agreements ŷ·y for its routine, emit_tail_loss)
+    const bool margin = loss >= SRHIP_MARGIN_LOSS_BEGIN;
     if (packed) {
       Src r[R], y[R];
       for (int e = 0; e < R; ++e) { r[e] = V(rreg + e); y[e] = V(VY + e); }
-      pk_block(VOP3P_ADD_F32, "v_pk_add_f32", VY, r, y, true);
+      if (margin) pk_block(VOP3P_MUL_F32, "v_pk_mul_f32", VY, r, y, false);
+      else pk_block(VOP3P_ADD_F32, "v_pk_add_f32", VY, r, y, true);
+    } else if (margin) {
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", VY + e, V(rreg + e), VY + e);
     } else {
       for (int e = 0; e < R; ++e) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", VY + e, V(rreg + e), VY + e);
     }
@@ -1198,8 +1203,8 @@ struct Gen {
                         std::to_string(S_TGT) + ":" + std::to_string(S_TGT + 1) + "]";
   }
 
-  // the tile tail of a loss other than L2: ℓ(r) of the residual block VY by
-  // the loss routine, weighted, masked and summed as eval_kernel.h's
+  // the tile tail of a loss other than L2: ℓ(r) of the residual block VY (ℓ(a)
+  // of the agreement block for a margin loss) by the loss routine, weighted, masked and summed as eval_kernel.h's
   // tile_loss does ((ℓ0 + ℓ2) + (ℓ1 + ℓ3)), then the loop
   void emit_tail_loss() {
     mov_block_reg(VA, VY);

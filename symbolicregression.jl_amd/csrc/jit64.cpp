@@ -1671,12 +1671,14 @@ void grad64_part(const GradModule64* m, int k, int* slot0, int* nslots) {
   *nslots = m->parts[k].nslots;
 }
 int grad64_nraw(const GradModule64* m) { return m ? m->nraw : 0; }
+// (a margin loss has neither: the Float64 tails and seeds are written for the residual
+// ŷ - y, so Float64 margin losses and their gradients run in the interpreter)
 bool has_loss_routine64(int loss) {
-  return loss == SRHIP_LOSS_L2 || (loss >= 0 && loss < SRHIP_NUM_LOSSES && kLoss64[loss] >= 0);
+  return loss == SRHIP_LOSS_L2 || (loss >= 0 && loss < SRHIP_MARGIN_LOSS_BEGIN && kLoss64[loss] >= 0);
 }
 bool has_dloss_routine64(int loss) {
   return loss == SRHIP_LOSS_L2 ||
-         (loss >= 0 && loss < SRHIP_NUM_LOSSES && kLoss64[loss] >= 0 && kDLoss64[loss] >= 0);
+         (loss >= 0 && loss < SRHIP_MARGIN_LOSS_BEGIN && kLoss64[loss] >= 0 && kDLoss64[loss] >= 0);
 }
 
 hipError_t launch_grad_code64(GradModule64* m, int part, const EvalPlan& plan, const EvalArgs<double>& a,

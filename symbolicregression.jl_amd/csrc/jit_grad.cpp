@@ -1561,9 +1561,11 @@ void destroy_grad(GradModule* m) {
   delete m;
 }
 
+// (a margin loss has none: emit_loss_seed is written for the residual ŷ - y, so its
+// gradients run in the interpreter)
 bool has_dloss_routine(int loss) {
   return loss == SRHIP_LOSS_L2 ||
-         (loss >= 0 && loss < SRHIP_NUM_LOSSES && kGradLossRoutine[loss] >= 0 && kDLossRoutine[loss] >= 0);
+         (loss >= 0 && loss < SRHIP_MARGIN_LOSS_BEGIN && kGradLossRoutine[loss] >= 0 && kDLossRoutine[loss] >= 0);
 }
 
 int grad_nslots(const GradModule* m) { return m ? m->nslots : 0; }

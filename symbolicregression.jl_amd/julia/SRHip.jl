@@ -12,7 +12,9 @@ module SRHip
 
 using DynamicExpressions: Node, count_nodes, set_constants
 using LossFunctions: L2DistLoss, L1DistLoss, LPDistLoss, HuberLoss, LogCoshLoss, L1EpsilonInsLoss,
-    L2EpsilonInsLoss, QuantileLoss, PeriodicLoss, LogitDistLoss
+    L2EpsilonInsLoss, QuantileLoss, PeriodicLoss, LogitDistLoss,
+    ZeroOneLoss, PerceptronLoss, LogitMarginLoss, L1HingeLoss, L2HingeLoss, SmoothedL1HingeLoss,
+    ModifiedHuberLoss, L2MarginLoss, ExpLoss, SigmoidLoss, DWDMarginLoss
 import ..CoreModule: Options, Dataset
 
 const libsrhip = get(ENV, "SRHIP_LIB", joinpath(@__DIR__, "..", "lib", "libsrhip.so"))
@@ -25,6 +27,11 @@ const X_JULIA = Int32(0)
 const LOSS_L2, LOSS_L1, LOSS_LP, LOSS_HUBER, LOSS_LOGCOSH = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const LOSS_L1EPSINS, LOSS_L2EPSINS, LOSS_QUANTILE, LOSS_PERIODIC, LOSS_LOGITDIST, LOSS_LPINT =
     Int32(5), Int32(6), Int32(7), Int32(8), Int32(9), Int32(10)
+# margin losses (a = y·ŷ)
+const LOSS_ZEROONE, LOSS_PERCEPTRON, LOSS_LOGITMARGIN, LOSS_L1HINGE, LOSS_L2HINGE, LOSS_SMOOTHEDL1HINGE =
+    Int32(11), Int32(12), Int32(13), Int32(14), Int32(15), Int32(16)
+const LOSS_MODHUBER, LOSS_L2MARGIN, LOSS_EXP, LOSS_SIGMOID, LOSS_DWDMARGIN =
+    Int32(17), Int32(18), Int32(19), Int32(20), Int32(21)
 
 struct SrhipTrees              # include/srhip.h: srhip_trees
     ntrees::Int32
@@ -55,7 +62,7 @@ dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 dtype_code(::Type) = throw(Unsupported("only Float32/Float64 run on the GPU"))
 
-# ---- elementwise losses -> SRHIP_LOSS_* (LossFunctions.jl distance losses,
+# ---- elementwise losses -> SRHIP_LOSS_* (LossFunctions.jl distance and margin losses,
 # src/Options.jl:429-431 default L2DistLoss; docs/src/losses.md) ----------------
 loss_code(::L2DistLoss) = (LOSS_L2, 0.0)
 loss_code(::L1DistLoss) = (LOSS_L1, 0.0)
@@ -69,6 +76,19 @@ loss_code(l::QuantileLoss) = (LOSS_QUANTILE, Float64(l.τ))
 # PeriodicLoss stores k = 2π/circumference; the engine takes the circumference
 loss_code(l::PeriodicLoss) = (LOSS_PERIODIC, 2π / Float64(l.k))
 loss_code(::LogitDistLoss) = (LOSS_LOGITDIST, 0.0)
+# margin losses (docs/src/losses.md:226-520; HingeLoss is L1HingeLoss). The engine checks
+# the parameters: γ > 0, q > 0, and a q that is not integral is Unsupported (CPU path).
+loss_code(::ZeroOneLoss) = (LOSS_ZEROONE, 0.0)
+loss_code(::PerceptronLoss) = (LOSS_PERCEPTRON, 0.0)
+loss_code(::LogitMarginLoss) = (LOSS_LOGITMARGIN, 0.0)
+loss_code(::L1HingeLoss) = (LOSS_L1HINGE, 0.0)
+loss_code(::L2HingeLoss) = (LOSS_L2HINGE, 0.0)
+loss_code(l::SmoothedL1HingeLoss) = (LOSS_SMOOTHEDL1HINGE, Float64(l.gamma))
+loss_code(::ModifiedHuberLoss) = (LOSS_MODHUBER, 0.0)
+loss_code(::L2MarginLoss) = (LOSS_L2MARGIN, 0.0)
+loss_code(::ExpLoss) = (LOSS_EXP, 0.0)
+loss_code(::SigmoidLoss) = (LOSS_SIGMOID, 0.0)
+loss_code(l::DWDMarginLoss) = (LOSS_DWDMARGIN, Float64(l.q))
 loss_code(l) = throw(Unsupported("elementwise loss $(typeof(l)) is not in the engine's table"))
 
 # ---- contexts: one per (thread, device); calls through a context are serialised.

@@ -15,8 +15,12 @@ BOP = {n: i for i, n in enumerate(BOPS)}
 UOP = {n: i for i, n in enumerate(UOPS)}
 
 LOSSES = ["L2", "L1", "LP", "HUBER", "LOGCOSH", "L1EPSINS", "L2EPSINS", "QUANTILE", "PERIODIC",
-          "LOGITDIST", "LPINT"]
+          "LOGITDIST", "LPINT",
+          # margin losses (a = y·ŷ): ids from MARGIN_LOSS_BEGIN on
+          "ZEROONE", "PERCEPTRON", "LOGITMARGIN", "L1HINGE", "L2HINGE", "SMOOTHEDL1HINGE", "MODHUBER",
+          "L2MARGIN", "EXP", "SIGMOID", "DWDMARGIN"]
 LOSS = {n: i for i, n in enumerate(LOSSES)}
+MARGIN_LOSS_BEGIN = LOSS["ZEROONE"]
 
 # Julia operator names → (arity, id), applying binopmap / unaopmap
 # (src/Options.jl:86-120). Mirrors srhip_op_lookup.

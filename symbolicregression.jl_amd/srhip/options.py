@@ -70,6 +70,58 @@ def LogitDistLoss():
     return SupervisedLoss(K.LOSS["LOGITDIST"])
 
 
+# ---- LossFunctions.jl margin losses (docs/src/losses.md: L(a), a = y·ŷ, y ∈ {-1, +1};
+# y is used as given, srhip.h) --------------------------------------------------
+def ZeroOneLoss():
+    return SupervisedLoss(K.LOSS["ZEROONE"])
+
+
+def PerceptronLoss():
+    return SupervisedLoss(K.LOSS["PERCEPTRON"])
+
+
+def LogitMarginLoss():
+    return SupervisedLoss(K.LOSS["LOGITMARGIN"])
+
+
+def L1HingeLoss():
+    return SupervisedLoss(K.LOSS["L1HINGE"])
+
+
+HingeLoss = L1HingeLoss  # LossFunctions' alias
+
+
+def L2HingeLoss():
+    return SupervisedLoss(K.LOSS["L2HINGE"])
+
+
+def SmoothedL1HingeLoss(gamma: float):
+    """γ > 0 (the engine answers an invalid-argument error otherwise)."""
+    return SupervisedLoss(K.LOSS["SMOOTHEDL1HINGE"], gamma)
+
+
+def ModifiedHuberLoss():
+    return SupervisedLoss(K.LOSS["MODHUBER"])
+
+
+def L2MarginLoss():
+    return SupervisedLoss(K.LOSS["L2MARGIN"])
+
+
+def ExpLoss():
+    return SupervisedLoss(K.LOSS["EXP"])
+
+
+def SigmoidLoss():
+    return SupervisedLoss(K.LOSS["SIGMOID"])
+
+
+def DWDMarginLoss(q: float):
+    """q > 0. The engine takes an integral q; another q raises Unsupported (the
+    reference's own DomainError case stays with the CPU path, srhip.h)."""
+    return SupervisedLoss(K.LOSS["DWDMARGIN"], q)
+
+
 # Keywords of the reference's Options (src/Options.jl:315-379) that steer only
 # its search control plane (mutation/crossover schedule, constraints, output,
 # recorder, stopping rules): accepted, stored, not used by this engine.
