@@ -422,6 +422,20 @@ int32_t srhip_program_update_stats(const srhip_program* prog, int64_t* out_inpla
  * codegen and load times (ms). All zero before the first gradient call. */
 int32_t srhip_program_grad_jit_info(const srhip_program* prog, int32_t* out_ntrees, int32_t* out_nrejected,
                                     int64_t* out_code_bytes, double* out_ms_codegen, double* out_ms_load);
+/* Which kernel passes this program's trees go to (read-only, for tests that
+ * pin a batch to one interpreter variant; NULL outputs are skipped).
+ * out_eval[4]: trees in the shallow list (at most 2 stack slots and 63
+ * instructions; its leading trees are the tree code's), trees in the deep list,
+ * trees of the shallow list compiled as tree code, operator set of the shallow
+ * pass (0: the basic operators only, 1: all).
+ * out_grad_items[4]: gradient work items (one per tree and group of up to 4
+ * constants) of the passes with 1, 2 and 4 tangents and of the deep pass (more
+ * than 4 stack slots); out_grad_rest[4]: the same counts over the trees left to
+ * the interpreter when gradient tree code exists; out_grad_opset: operator set
+ * of the shallow gradient passes. The gradient fields are all zero before the
+ * first gradient call. */
+int32_t srhip_program_pass_info(const srhip_program* prog, int32_t* out_eval, int32_t* out_grad_items,
+                                int32_t* out_grad_rest, int32_t* out_grad_opset);
 /* Trees of the last eval on this context whose tree code handed a tile back
  * (a sin/cos argument beyond the fast reduction) and were re-evaluated, and
  * tiles that tree code redid with the Float64-evaluated routines (a FAST-path

@@ -2955,6 +2955,27 @@ int32_t srhip_program_grad_jit_info(const srhip_program* prog, int32_t* out_ntre
   });
 }
 
+int32_t srhip_program_pass_info(const srhip_program* prog, int32_t* out_eval, int32_t* out_grad_items,
+                                int32_t* out_grad_rest, int32_t* out_grad_opset) {
+  return guarded([&] {
+    if (!prog) throw Error(SRHIP_ERR_INVALID, "null program");
+    if (out_eval) {
+      out_eval[0] = prog->nlist_a;
+      out_eval[1] = prog->nlist_b;
+      out_eval[2] = (prog->jit != nullptr || prog->jit64 != nullptr) ? prog->nlist_j : 0;
+      out_eval[3] = prog->opset;
+    }
+    const bool g = prog->grad_built;  // the counts of an earlier build are stale
+    const bool gj = g && (prog->gjit != nullptr || prog->gjit64 != nullptr);
+    for (int k = 0; k < 4; ++k) {
+      if (out_grad_items) out_grad_items[k] = g ? prog->ngitems[k] : 0;
+      if (out_grad_rest) out_grad_rest[k] = gj ? prog->ngitems_rest[k] : 0;
+    }
+    if (out_grad_opset) *out_grad_opset = g ? prog->g_opset : 0;
+    return SRHIP_OK;
+  });
+}
+
 int32_t srhip_program_jit_info(const srhip_program* prog, int32_t* out_ntrees, int32_t* out_nfast,
                                int64_t* out_code_bytes, double* out_ms_codegen, double* out_ms_load) {
   return guarded([&] {

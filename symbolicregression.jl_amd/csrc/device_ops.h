@@ -740,6 +740,31 @@ __device__ __forceinline__ double elem_loss_param(int kind, double p, double r) 
   }
   return qnan<double>();
 }
+// LogitDist of a Float32 residual, |r| + 2·log1p(exp(-|r|)) - ln 4 = 2·ln cosh(r/2): the three
+// Float32 terms are about 1.39 near r = 0 and cancel to r²/4, which left the value with the
+// rounding grain of 1.39 (1e-7 absolute, 3e-4 of the loss at |r| = 0.03). With h = |r|/2 and
+// q = exp(-h), cosh(h) - 1 = (1 - q)² / 2q, and 1 - q is taken from its series to h^7 below
+// h = 0.5 (the h^8 term is 2e-7 of it there) and by subtraction above (q <= 0.61), so every
+// factor is relatively accurate (v_rcp_f32 is within 1 ulp, q a normal number) and so is the
+// loss: within 6e-7 of it at every |r|. Beyond |r| = 160, where q would underflow, the loss has
+// slope 1 to the last bit: the excess is added (0 below 160; an Inf or NaN residual stays one).
+// All Float32 and no IEEE division. The interpreters use it; the Float32 tree code's loss routine
+// does not (SR_LOSS_ROUTINE below): sums of 256 trees' batches over whole datasets.
+__device__ __forceinline__ float logitdist_f32(float ar) {
+  const float am = __builtin_fminf(ar, 160.0f);
+  const float h = 0.5f * am, qf = m_exp(-h);
+  float s = 1.0f / 5040.0f;
+  s = s * h - 1.0f / 720.0f;
+  s = s * h + 1.0f / 120.0f;
+  s = s * h - 1.0f / 24.0f;
+  s = s * h + 1.0f / 6.0f;
+  s = s * h - 0.5f;
+  s = s * h + 1.0f;
+  const float d = h < 0.5f ? s * h : 1.0f - qf;
+  float x = d * d * (0.5f * __builtin_amdgcn_rcpf(qf));
+  asm volatile("" : "+v"(x));  // the series' registers are free before log1p's are taken
+  return 2.0f * m_log1p(x) + (ar - am);
+}
 template <typename T>
 __device__ __forceinline__ T elem_loss(int kind, double p, T yhat, T y) {
   if (kind >= SRHIP_MARGIN_LOSS_BEGIN) return margin_loss_ool<T>(kind, p, yhat * y);
@@ -749,7 +774,11 @@ __device__ __forceinline__ T elem_loss(int kind, double p, T yhat, T y) {
     case SRHIP_LOSS_L2: return r * r;
     case SRHIP_LOSS_L1: return ar;
     case SRHIP_LOSS_LOGCOSH: return ar + m_log1p(m_exp(T(-2) * ar)) - T(0.69314718055994530942);
-    case SRHIP_LOSS_LOGITDIST: return ar + T(2) * m_log1p(m_exp(-ar)) - T(1.38629436111989061883);
+    case SRHIP_LOSS_LOGITDIST:
+#ifndef SR_LOSS_ROUTINE  // gen_jit.py: the Float32 tree code's loss routine keeps the three-term form
+      if constexpr (std::is_same<T, float>::value) return logitdist_f32(ar);
+#endif
+      return ar + T(2) * m_log1p(m_exp(-ar)) - T(1.38629436111989061883);
     case SRHIP_LOSS_LPINT: return ipow(ar, (long long)p);  // T^Integer stays in T
   }
   return (T)elem_loss_param<T>(kind, p, (double)r);

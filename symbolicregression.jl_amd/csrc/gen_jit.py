@@ -95,7 +95,10 @@ def sgpr_pinned(name):
 def snippet_source(rg, routines):
     R = rg.R
     _, rest = rg.vstate()
-    out = ["#define SRHIP_INLINE_ALL 1", '#include "interp.h"', "using namespace srhip; using namespace srhip::interp;",
+    # SR_LOSS_ROUTINE: device_ops.h keeps LogitDist's three-term Float32 form in the loss routine (the
+    # longer routine moved every routine after it and cost the L2 tree code 1.5 %)
+    out = ["#define SRHIP_INLINE_ALL 1", "#define SR_LOSS_ROUTINE 1", '#include "interp.h"',
+           "using namespace srhip; using namespace srhip::interp;",
            "namespace {", "struct St {", f"  float a[{R}]; float b[{R}]; float chk;", f"  unsigned v[{len(rest)}];"]
     for n, _ in rg.sregs():
         out.append(f"  unsigned s_{n};")

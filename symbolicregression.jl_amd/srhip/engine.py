@@ -205,6 +205,17 @@ class Program:
         return dict(ntrees=nt.value, nrejected=nr.value, code_bytes=nb.value, ms_codegen=mc.value,
                     ms_load=ml.value)
 
+    def pass_info(self):
+        """Which kernel passes the trees go to (srhip_program_pass_info): the evaluation lists
+        and, after the first gradient call, the gradient work items per pass
+        (G = 1, 2, 4 tangents, deep); opsets are "BASIC" or "FULL"."""
+        ev, gi, gr = (C.c_int32 * 4)(), (C.c_int32 * 4)(), (C.c_int32 * 4)()
+        go = C.c_int32()
+        check(lib().srhip_program_pass_info(self.handle, ev, gi, gr, C.byref(go)))
+        names = ("BASIC", "FULL")
+        return dict(shallow=ev[0], deep=ev[1], tree_code=ev[2], opset=names[ev[3]], grad_items=tuple(gi),
+                    grad_rest=tuple(gr), grad_opset=names[go.value])
+
     def update_stats(self):
         """How set_constants applied new constants: {"inplace": n, "rebuilt": n}."""
         a, b = C.c_int64(), C.c_int64()
