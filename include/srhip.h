@@ -155,6 +155,55 @@ extern "C" {
 /* ids from here on are margin losses (a = y·ŷ), below it distance losses (r = ŷ - y) */
 #define SRHIP_MARGIN_LOSS_BEGIN 11
 
+/* ---- expression losses: a custom elementwise_loss as an engine tree --------
+ * The reference accepts any function as elementwise_loss
+ * (src/LossFunctions.jl:17-19: sum(loss.(x, y)) / length(y); :27-31:
+ * sum(loss.(x, y, w)) / sum(w)). An expression loss is such a function written
+ * as a postfix tree in this header's node format (SRHIP_NODE_*, SRHIP_UOP_*,
+ * SRHIP_BOP_*) whose feature leaves are 0: the prediction ŷ, 1: the target y,
+ * 2: the weight w. It is registered once (process-wide, immutable, one handle
+ * for both element types) and the handle it gets — a loss kind >=
+ * SRHIP_EXPR_LOSS_BEGIN — is accepted wherever a loss_kind is taken
+ * (srhip_eval_loss, _packed, _batch, _batch_ctx, _rowsets, _batch_rowsets_ctx,
+ * srhip_eval_loss_grad, srhip_constopt_options.loss_kind); loss_params is
+ * ignored there and may be NULL. For every tree t:
+ *   out_ok[t]       = did_succeed of the candidate tree alone; values inside the
+ *                     loss expression are never checked, a non-finite loss value
+ *                     does not fail the tree (the sum is then non-finite, ok = 1)
+ *   out_loss_sum[t] = Σ_i ℓ(ŷ_i, y_i, w_i): NO implicit weight, the reference's
+ *                     loss.(x, y, w) contract; ℓ is computed in T with the
+ *                     operators' semantics above (safe operators give NaN), its
+ *                     constants rounded to T once
+ *   out_weight_sum  = Σ w, or the row count when unweighted, as for every loss
+ *   out_dloss[c]    = Σ_i (dℓ/dŷ)_i · ∂ŷ_i/∂c, dℓ/dŷ one forward-mode tangent
+ *                     through the expression (1 on feature 0, 0 elsewhere) with
+ *                     the derivative rules of the constant gradients
+ * Limits: at most 64 nodes; at most 4 values live on the postfix stack; finite
+ * constants; feature index <= 2; exactly one value left on the stack. A
+ * malformed stream is SRHIP_ERR_INVALID; a well-formed one beyond the node or
+ * stack limits, or with an operator id beyond the tables, is
+ * SRHIP_ERR_UNSUPPORTED (the caller falls back to the CPU path).
+ * Deviations from the reference: an expression that reads feature 2 on an
+ * unweighted dataset is SRHIP_ERR_INVALID, and one that ignores feature 2 is
+ * allowed on a weighted dataset (the reference would call a 2-argument function
+ * with 3 arguments there); Julia promotes Float32 ^ 2.5 (a Float64 literal) to
+ * Float64, the engine stays in T. These kinds always run in the interpreter
+ * kernels (no tree code: srhip_last_tree_code gives 0, and the
+ * srhip_jit_compile_loss hook answers SRHIP_ERR_UNSUPPORTED for them). */
+#define SRHIP_EXPR_LOSS_BEGIN 1024 /* loss kinds from here on are handles of expression losses */
+/* consts[nconsts]: the constant leaves in stream order (as srhip_trees). */
+int32_t srhip_loss_expr_create(const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
+                               const double* consts, int32_t nconsts, int32_t* out_loss_kind);
+/* A destroyed (or never registered) kind >= SRHIP_EXPR_LOSS_BEGIN is
+ * SRHIP_ERR_INVALID everywhere; handles are not reused. */
+int32_t srhip_loss_expr_destroy(int32_t loss_kind);
+/* Host statement of the semantics, no device: out[i] = ℓ(yhat[i], y[i],
+ * w ? w[i] : unused) in dtype T (arrays of T), with the host routines that
+ * constant folding and srhip_op_eval use. w == NULL with an expression that
+ * reads feature 2 is SRHIP_ERR_INVALID. */
+int32_t srhip_loss_expr_eval(int32_t loss_kind, int32_t dtype, const void* yhat, const void* y,
+                             const void* w, int64_t n, void* out);
+
 typedef struct srhip_ctx srhip_ctx;
 typedef struct srhip_dataset srhip_dataset;
 typedef struct srhip_program srhip_program;

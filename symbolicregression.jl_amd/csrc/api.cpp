@@ -210,6 +210,11 @@ struct srhip_ctx {
   DevBuf gpart;  // [nrg][nconst] per-row-group ∂L/∂c of the gradient tree code
   std::vector<double> h_sum;
   std::vector<uint8_t> h_ok;
+  // device copies of the expression-loss programs this context has run, by
+  // (handle, dtype): uploaded at first use, freed when the context closes
+  // (handles are never reused, so an entry cannot go stale)
+  struct LossProg { int kind, dtype; void* d; };
+  std::vector<LossProg> lprogs;
 };
 
 struct srhip_dataset {
@@ -343,6 +348,184 @@ struct srhip_program {
 };
 
 namespace {
+
+// ---- expression losses (srhip.h "expression losses") ----------------------------
+// A registered loss tree: its postfix stream (the host statement of the
+// semantics, srhip_loss_expr_eval) and its loss program for both element types
+// (srhip_internal.h "expression-loss programs"). Entries are immutable; the
+// registry is process-wide and hands out kinds from SRHIP_EXPR_LOSS_BEGIN on,
+// never twice.
+struct ExprLoss {
+  std::vector<uint8_t> kind;
+  std::vector<uint16_t> arg;
+  std::vector<double> consts;
+  bool uses_w = false;
+  std::vector<Ins<float>> p32;
+  std::vector<Ins<double>> p64;
+};
+std::mutex g_expr_mu;
+std::vector<std::pair<int32_t, std::shared_ptr<const ExprLoss>>> g_expr;
+int32_t g_expr_next = SRHIP_EXPR_LOSS_BEGIN;
+
+std::shared_ptr<const ExprLoss> expr_loss_lookup(int32_t kind) {
+  std::lock_guard<std::mutex> lk(g_expr_mu);
+  for (const auto& e : g_expr)
+    if (e.first == kind) return e.second;
+  throw Error(SRHIP_ERR_INVALID, "loss kind " + std::to_string(kind) + " is not a registered expression loss");
+}
+
+// an expression loss that reads the weight needs a weighted dataset
+void check_expr_loss_weights(int32_t kind, bool weighted) {
+  if (kind < SRHIP_EXPR_LOSS_BEGIN) return;
+  if (expr_loss_lookup(kind)->uses_w && !weighted)
+    throw Error(SRHIP_ERR_INVALID, "the expression loss reads the weight (feature 2) but the dataset has no weights");
+}
+
+// Validate a postfix loss stream and compile it. Malformed: INVALID; well formed
+// but beyond the limits (nodes, stack depth, operator tables): UNSUPPORTED.
+std::shared_ptr<const ExprLoss> expr_loss_compile(const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
+                                                  const double* consts, int32_t nconsts) {
+  if (!kind || !arg || nnodes <= 0 || nconsts < 0 || (nconsts > 0 && !consts))
+    throw Error(SRHIP_ERR_INVALID, "expression loss: null or empty node stream");
+  struct N { int l = -1, r = -1; };
+  std::vector<N> nd((size_t)nnodes);
+  std::vector<int> st;
+  int nc = 0, maxdepth = 0;
+  bool beyond_ops = false, uses_w = false;
+  for (int i = 0; i < nnodes; ++i) {
+    switch (kind[i]) {
+      case SRHIP_NODE_CONST:
+        if (nc >= nconsts) throw Error(SRHIP_ERR_INVALID, "expression loss: more constant leaves than constants");
+        if (!std::isfinite(consts[nc])) throw Error(SRHIP_ERR_INVALID, "expression loss: non-finite constant");
+        ++nc;
+        break;
+      case SRHIP_NODE_FEATURE:
+        if (arg[i] > 2) throw Error(SRHIP_ERR_INVALID, "expression loss: feature index beyond 2 (0: prediction, 1: target, 2: weight)");
+        uses_w = uses_w || arg[i] == 2;
+        break;
+      case SRHIP_NODE_UNARY:
+        if (st.empty()) throw Error(SRHIP_ERR_INVALID, "expression loss: stack underflow");
+        beyond_ops = beyond_ops || arg[i] >= SRHIP_NUM_UOPS;
+        nd[i].l = st.back();
+        st.pop_back();
+        break;
+      case SRHIP_NODE_BINARY:
+        if (st.size() < 2) throw Error(SRHIP_ERR_INVALID, "expression loss: stack underflow");
+        beyond_ops = beyond_ops || arg[i] >= SRHIP_NUM_BOPS;
+        nd[i].r = st.back();
+        st.pop_back();
+        nd[i].l = st.back();
+        st.pop_back();
+        break;
+      default: throw Error(SRHIP_ERR_INVALID, "expression loss: unknown node kind");
+    }
+    st.push_back(i);
+    maxdepth = std::max(maxdepth, (int)st.size());
+  }
+  if (st.size() != 1) throw Error(SRHIP_ERR_INVALID, "expression loss: the stream leaves " + std::to_string(st.size()) + " values");
+  if (nc != nconsts) throw Error(SRHIP_ERR_INVALID, "expression loss: constant count mismatch");
+  if (beyond_ops) throw Error(SRHIP_ERR_UNSUPPORTED, "expression loss: operator id beyond the engine's table");
+  if (nnodes > kLossMaxNodes) throw Error(SRHIP_ERR_UNSUPPORTED, "expression loss: more than 64 nodes");
+  if (maxdepth > kLossMaxDepth) throw Error(SRHIP_ERR_UNSUPPORTED, "expression loss: more than 4 values live on the stack");
+
+  auto e = std::make_shared<ExprLoss>();
+  e->kind.assign(kind, kind + nnodes);
+  e->arg.assign(arg, arg + nnodes);
+  e->consts.assign(consts, consts + nconsts);
+  e->uses_w = uses_w;
+  // constant index of each constant leaf
+  std::vector<int> cidx((size_t)nnodes, -1);
+  for (int i = 0, c = 0; i < nnodes; ++i)
+    if (kind[i] == SRHIP_NODE_CONST) cidx[i] = c++;
+  struct I { uint32_t code; double imm; };
+  std::vector<I> prog;
+  auto is_leaf = [&](int i) { return kind[i] == SRHIP_NODE_CONST || kind[i] == SRHIP_NODE_FEATURE; };
+  auto leaf_of = [&](int i) { return kind[i] == SRHIP_NODE_CONST ? (int)LEAF_IMM : (int)arg[i]; };
+  auto imm_of = [&](int i) { return kind[i] == SRHIP_NODE_CONST ? consts[cidx[i]] : 0.0; };
+  std::function<void(int, int)> emit = [&](int i, int k) {  // k: slots in use
+    if (is_leaf(i)) {
+      prog.push_back({make_loss_code(LOP_LD, leaf_of(i)), imm_of(i)});
+    } else if (kind[i] == SRHIP_NODE_UNARY) {
+      emit(nd[i].l, k);
+      prog.push_back({make_loss_code(LOP_UN0 + arg[i], 0), 0.0});
+    } else {
+      const int l = nd[i].l, r = nd[i].r, b = arg[i];
+      if (is_leaf(r)) {
+        emit(l, k);
+        prog.push_back({make_loss_code(LOP_AX0 + b, leaf_of(r)), imm_of(r)});
+      } else if (is_leaf(l)) {
+        emit(r, k);
+        prog.push_back({make_loss_code(LOP_XA0 + b, leaf_of(l)), imm_of(l)});
+      } else {
+        if (k >= kLossSlots) throw Error(SRHIP_ERR_UNSUPPORTED, "expression loss: needs more than 3 stack slots");
+        emit(l, k);
+        prog.push_back({make_loss_code(LOP_PUSH0 + k, 0), 0.0});
+        emit(r, k + 1);
+        prog.push_back({make_loss_code(LOP_POP0 + k, 0), 0.0});
+        prog.push_back({make_loss_code(LOP_TA0 + b, 0), 0.0});
+      }
+    }
+  };
+  emit(nnodes - 1, 0);
+  for (int k = 0; k < 3; ++k) prog.push_back({make_loss_code(LOP_END, 0), 0.0});  // END + the prefetch's slack
+  for (const I& in : prog) {
+    Ins<float> a;
+    a.code = in.code;
+    a.imm = (float)in.imm;
+    e->p32.push_back(a);
+    Ins<double> d;
+    d.code = in.code;
+    d.pad = 0u;
+    d.imm = in.imm;
+    e->p64.push_back(d);
+  }
+  return e;
+}
+
+// ℓ(ŷ, y, w) per row on the host, in T, with the routines constant folding uses
+template <typename T>
+void expr_loss_eval_host(const ExprLoss& e, const T* yhat, const T* y, const T* w, int64_t n, T* out) {
+  const int nn = (int)e.kind.size();
+  for (int64_t i = 0; i < n; ++i) {
+    T st[kLossMaxDepth];
+    int sp = 0, c = 0;
+    for (int k = 0; k < nn; ++k) {
+      switch (e.kind[k]) {
+        case SRHIP_NODE_CONST: st[sp++] = (T)e.consts[c++]; break;
+        case SRHIP_NODE_FEATURE: st[sp++] = e.arg[k] == 0 ? yhat[i] : e.arg[k] == 1 ? y[i] : w[i]; break;
+        case SRHIP_NODE_UNARY: st[sp - 1] = host::unop<T>(e.arg[k], st[sp - 1]); break;
+        default:
+          st[sp - 2] = host::binop<T>(e.arg[k], st[sp - 2], st[sp - 1]);
+          --sp;
+      }
+    }
+    out[i] = st[0];
+  }
+}
+
+// The loss program of an expression loss in the context's device memory
+// (uploaded once per context, handle and element type; the context's mutex is held).
+template <typename T>
+const Ins<T>* expr_loss_device(srhip_ctx* c, int32_t kind) {
+  const int dtype = sizeof(T) == 4 ? SRHIP_F32 : SRHIP_F64;
+  for (const auto& lp : c->lprogs)
+    if (lp.kind == kind && lp.dtype == dtype) return static_cast<const Ins<T>*>(lp.d);
+  const std::shared_ptr<const ExprLoss> e = expr_loss_lookup(kind);
+  const void* src;
+  size_t bytes;
+  if constexpr (sizeof(T) == 4) { src = e->p32.data(); bytes = e->p32.size() * sizeof(Ins<float>); }
+  else { src = e->p64.data(); bytes = e->p64.size() * sizeof(Ins<double>); }
+  void* d = nullptr;
+  hipError_t err = hipMalloc(&d, bytes);
+  if (err != hipSuccess) throw Error(SRHIP_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(err));
+  err = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);  // synchronous: in place before any launch reads it
+  if (err != hipSuccess) {
+    (void)hipFree(d);
+    throw Error(SRHIP_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(err));
+  }
+  c->lprogs.push_back({kind, dtype, d});
+  return static_cast<const Ins<T>*>(d);
+}
 
 // Programs are rebuilt by every srhip_program_set_constants (the batched
 // constant optimiser does so once per line-search round) and hipFree
@@ -1704,6 +1887,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
     if (pass == -1 && jm && rg_xcd()) a.rotate = rotate_mode();  // tree code: row groups per XCD
     if (pass >= 0 && interp_dyn()) a.rotate |= 4;  // interpreter: trees from an LDS counter
     a.lparam = lparam;
+    if (mode == MODE_LOSS && loss >= SRHIP_EXPR_LOSS_BEGIN) a.lprog = expr_loss_device<T>(c, loss);
     c->partial.ensure((size_t)plan.nrg * plan.ntg * plan.tpb * sizeof(Part<T>));
     a.partial = static_cast<Part<T>*>(c->partial.p);
     a.out = out;
@@ -2216,6 +2400,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     a.nrg = plan.nrg;
     a.loss = loss;
     a.lparam = lparam;
+    if (mode == GRAD_LOSS && loss >= SRHIP_EXPR_LOSS_BEGIN) a.lprog = expr_loss_device<T>(c, loss);
     a.G = G;
     a.opset = deep ? OPSET_FULL : p->g_opset;
     c->partial.ensure((size_t)plan.nrg * plan.ntg * plan.tpb * (2 + G) * sizeof(T));
@@ -2490,6 +2675,8 @@ int32_t srhip_close(srhip_ctx* ctx) {
     ctx->gsum.release();
     ctx->gok.release();
     ctx->gti.release();
+    for (auto& lp : ctx->lprogs)
+      if (lp.d) (void)hipFree(lp.d);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return SRHIP_OK;
@@ -2531,6 +2718,50 @@ int32_t srhip_op_eval(int32_t dtype, int32_t arity, int32_t id, double a, double
     } else {
       *out = arity == 1 ? host::unop<double>(id, a) : host::binop<double>(id, a, b);
     }
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_loss_expr_create(const uint8_t* kind, const uint16_t* arg, int32_t nnodes, const double* consts,
+                               int32_t nconsts, int32_t* out_loss_kind) {
+  return guarded([&] {
+    if (!out_loss_kind) throw Error(SRHIP_ERR_INVALID, "null out_loss_kind");
+    std::shared_ptr<const ExprLoss> e = expr_loss_compile(kind, arg, nnodes, consts, nconsts);
+    std::lock_guard<std::mutex> lk(g_expr_mu);
+    if (g_expr_next == std::numeric_limits<int32_t>::max()) throw Error(SRHIP_ERR_NOMEM, "expression loss handles exhausted");
+    const int32_t id = g_expr_next++;
+    g_expr.emplace_back(id, std::move(e));
+    *out_loss_kind = id;
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_loss_expr_destroy(int32_t loss_kind) {
+  return guarded([&] {
+    std::lock_guard<std::mutex> lk(g_expr_mu);
+    for (size_t i = 0; i < g_expr.size(); ++i)
+      if (g_expr[i].first == loss_kind) {
+        g_expr.erase(g_expr.begin() + (std::ptrdiff_t)i);
+        return SRHIP_OK;
+      }
+    throw Error(SRHIP_ERR_INVALID, "loss kind " + std::to_string(loss_kind) + " is not a registered expression loss");
+  });
+}
+
+int32_t srhip_loss_expr_eval(int32_t loss_kind, int32_t dtype, const void* yhat, const void* y, const void* w,
+                             int64_t n, void* out) {
+  return guarded([&] {
+    if (loss_kind < SRHIP_EXPR_LOSS_BEGIN) throw Error(SRHIP_ERR_INVALID, "not an expression loss kind");
+    const std::shared_ptr<const ExprLoss> e = expr_loss_lookup(loss_kind);
+    if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
+    if (n < 0 || (n > 0 && (!yhat || !y || !out))) throw Error(SRHIP_ERR_INVALID, "null array or negative length");
+    if (e->uses_w && !w) throw Error(SRHIP_ERR_INVALID, "the expression loss reads the weight (feature 2) but w is NULL");
+    if (dtype == SRHIP_F32)
+      expr_loss_eval_host<float>(*e, static_cast<const float*>(yhat), static_cast<const float*>(y),
+                                 static_cast<const float*>(w), n, static_cast<float*>(out));
+    else
+      expr_loss_eval_host<double>(*e, static_cast<const double*>(yhat), static_cast<const double*>(y),
+                                  static_cast<const double*>(w), n, static_cast<double*>(out));
     return SRHIP_OK;
   });
 }
@@ -2760,6 +2991,10 @@ int32_t srhip_program_set_constants(srhip_program* prog, const void* consts) {
 // UNSUPPORTED: the reference raises a DomainError for a negative agreement under
 // a non-integer power, so the CPU path owns that case).
 static void check_loss(int32_t kind, const double* params) {
+  if (kind >= SRHIP_EXPR_LOSS_BEGIN) {  // an expression loss: a registered handle, no parameter
+    (void)expr_loss_lookup(kind);
+    return;
+  }
   if (kind < 0 || kind >= SRHIP_NUM_LOSSES) throw Error(SRHIP_ERR_UNSUPPORTED, "unsupported loss");
   if (kind >= SRHIP_MARGIN_LOSS_BEGIN) {
     if (kind != SRHIP_LOSS_SMOOTHEDL1HINGE && kind != SRHIP_LOSS_DWDMARGIN) return;
@@ -2784,6 +3019,7 @@ int32_t srhip_eval_loss(srhip_dataset* ds, const srhip_program* prog, int32_t lo
   return guarded([&] {
     check_program_vs_dataset(ds, prog);
     check_loss(loss_kind, loss_params);
+    check_expr_loss_weights(loss_kind, ds->w != nullptr);
     std::lock_guard<std::mutex> lk(prog->ctx->mu);
     HIP_CHECK(hipSetDevice(prog->ctx->device));
     if (ds->dtype == SRHIP_F32)
@@ -2798,6 +3034,7 @@ int32_t srhip_eval_loss_packed(srhip_dataset* ds, srhip_program* prog, int32_t l
     check_program_vs_dataset(ds, prog);
     if (!d_out) throw Error(SRHIP_ERR_INVALID, "null output");
     check_loss(loss_kind, loss_params);
+    check_expr_loss_weights(loss_kind, ds->w != nullptr);
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, d_out) != hipSuccess || at.type != hipMemoryTypeDevice)
       throw Error(SRHIP_ERR_INVALID, "d_out is not device memory");
@@ -2840,6 +3077,7 @@ int32_t srhip_eval_loss_rowsets(srhip_dataset* ds, const srhip_program* prog, in
   return guarded([&] {
     check_program_vs_dataset(ds, prog);
     check_loss(loss_kind, loss_params);
+    check_expr_loss_weights(loss_kind, ds->w != nullptr);
     std::lock_guard<std::mutex> lk(prog->ctx->mu);
     HIP_CHECK(hipSetDevice(prog->ctx->device));
     if (ds->dtype == SRHIP_F32)
@@ -2884,6 +3122,7 @@ int32_t srhip_eval_loss_grad(srhip_dataset* ds, const srhip_program* prog, int32
   return guarded([&] {
     check_program_vs_dataset(ds, prog);
     check_loss(loss_kind, loss_params);
+    check_expr_loss_weights(loss_kind, ds->w != nullptr);
     std::lock_guard<std::mutex> lk(prog->ctx->mu);
     HIP_CHECK(hipSetDevice(prog->ctx->device));
     auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
@@ -3024,6 +3263,7 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
     std::vector<uint8_t> bytes;
     std::string text;
     std::vector<int32_t> offs;
+    if (loss >= SRHIP_EXPR_LOSS_BEGIN) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for expression losses");
     if (loss < 0 || loss >= SRHIP_NUM_LOSSES) throw Error(SRHIP_ERR_INVALID, "unknown loss");
     uint64_t lbits;
     std::memcpy(&lbits, &lparam, 8);
@@ -3395,6 +3635,7 @@ int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const 
     if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
     if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
     check_loss(opts->loss_kind, opts->loss_params);
+    check_expr_loss_weights(opts->loss_kind, ds->w != nullptr);
     t_copt = CoptProfile();
     const auto t0 = std::chrono::steady_clock::now();
     copt::Problem pb = make_problem(trees, ds->dtype);

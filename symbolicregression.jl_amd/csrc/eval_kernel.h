@@ -87,6 +87,29 @@ __device__ __forceinline__ T tile_loss_rt(int lk, const T (&acc)[R], const T (&y
 // Kernel mode of a MODE_LOSS launch whose loss is L2 (the default loss):
 // the tile epilogue is compiled for it instead of switching on a.loss.
 constexpr int kModeLossL2 = 2;
+// Kernel mode of a MODE_LOSS launch whose loss is an expression loss (a.loss >=
+// SRHIP_EXPR_LOSS_BEGIN): the tile epilogue runs the loss program a.lprog
+// (interp.h run_loss). Instantiations of their own, for the full operator set
+// only: every other instantiation keeps its code. The weight column is a
+// run-time property of these (a.w), so there is one per (T, R, D).
+constexpr int kModeLossExpr = 3;
+
+// Σ over this lane's rows of the tile of ℓ(ŷ, y, w), ℓ the loss program: no
+// implicit weight (srhip.h); masked rows (past n) add 0.
+template <typename T, int R>
+__device__ __forceinline__ T tile_loss_expr(CIns<T>* lp, const T (&acc)[R], const T (&yv)[R], const T (&wv)[R],
+                                            int lane, int valid) {
+  T l[R];
+  run_loss<T, R>(lp, acc, yv, wv, lane, l);
+  T s0 = T(0), s1 = T(0);
+#pragma unroll
+  for (int e = 0; e < R; ++e) {
+    const int row = row_of<T, R>(e, lane);
+    const T v = row < valid ? l[e] : T(0);
+    if (e & 1) s1 += v; else s0 += v;
+  }
+  return s0 + s1;
+}
 
 template <typename T>
 __device__ __forceinline__ T qnan_v() { return __builtin_nan(""); }
@@ -143,6 +166,13 @@ __device__ __forceinline__ T tile_loss_any(int lk, const T (&acc)[R], const T (&
 // (R = 16 pins 130 VGPRs of threaded-interpreter state: 3 waves.)
 template <typename T, int R, int D>
 constexpr int kWavesPerEU = (sizeof(T) == 4 && D == kShallowSlots) ? (R > 8 ? 3 : 5) : 1;
+// The expression-loss variants: the loss program's registers (ŷ, y, w, acc, tmp,
+// the leaf operand and kLossSlots slots: 9 R-row values, 72 VGPRs at R = 8) are
+// live together with the operators' own temporaries, which does not fit the 96
+// VGPRs of 5 waves; the shallow f32 variant asks for 4 (128 VGPRs).
+template <typename T, int R, int D, int MODE>
+constexpr int kWavesPerEUm =
+    MODE == kModeLossExpr ? ((sizeof(T) == 4 && D == kShallowSlots && R <= 8) ? 4 : 1) : kWavesPerEU<T, R, D>;
 // One tree of a workgroup's group on its row tiles: the loss (or the per-row
 // outputs) of tree slot s into sPart[i], its failure flag set when a row fails
 // (the body of the interpreter's tree loop, static or dynamic deal).
@@ -181,7 +211,12 @@ __device__ __forceinline__ void eval_tree_in_group(const EvalArgs<T>& a, int i, 
       T yv[R], wv[R];
       lds_rows<T, R>(sY + tl * TILE, lane, yv);
       if constexpr (W) lds_rows<T, R>(sW + tl * TILE, lane, wv);
-      if constexpr (MODE == kModeLossL2) {  // L2 known at compile time: no loss switch
+      if constexpr (MODE == kModeLossExpr) {
+        if (a.w) lds_rows<T, R>(sW + tl * TILE, lane, wv);
+        else SR_UNROLL for (int r = 0; r < R; ++r) wv[r] = T(0);  // (a loss reading w is refused without weights)
+        const int valid = (tl < nt_valid - 1) ? TILE : last_valid;
+        lsum += tile_loss_expr<T, R>(const_prog(a.lprog), acc, yv, wv, lane, valid);
+      } else if constexpr (MODE == kModeLossL2) {  // L2 known at compile time: no loss switch
         if (tl < nt_valid - 1 || last_valid == TILE)
           lsum += tile_loss<SRHIP_LOSS_L2, W, false>(acc, yv, wv, lp, lane, TILE);
         else
@@ -204,14 +239,14 @@ __device__ __forceinline__ void eval_tree_in_group(const EvalArgs<T>& a, int i, 
 }
 
 template <typename T, int R, int D, int SET, int MODE, bool W>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWavesPerEU<T, R, D>)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWavesPerEUm<T, R, D, MODE>)))
 eval_kernel(EvalArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int TILE = 64 * R;
   using V = typename V16<T>::type;
   constexpr int N = V16<T>::N;
   const int rows = a.ntiles * TILE;
-  const int narr = a.nfeat + (MODE != MODE_OUT ? (W ? 2 : 1) : 0);
+  const int narr = a.nfeat + (MODE != MODE_OUT ? ((W || (MODE == kModeLossExpr && a.w)) ? 2 : 1) : 0);
   T* sX = reinterpret_cast<T*>(smem);
   T* sY = sX + (size_t)a.nfeat * rows;
   T* sW = sY + rows;
@@ -378,6 +413,7 @@ hipError_t launch_one(const EvalPlan& plan, const EvalArgs<T>& a, hipStream_t st
 template <typename T, int R, int D, int SET>
 hipError_t launch_rd(const EvalPlan& plan, const EvalArgs<T>& a, int mode, hipStream_t stream) {
   if (mode == MODE_OUT) return launch_one<T, R, D, SET, MODE_OUT, false>(plan, a, stream);
+  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_one<T, R, D, OPSET_FULL, kModeLossExpr, false>(plan, a, stream);
   if (a.loss == SRHIP_LOSS_L2) {
     if (a.w) return launch_one<T, R, D, SET, kModeLossL2, true>(plan, a, stream);
     return launch_one<T, R, D, SET, kModeLossL2, false>(plan, a, stream);

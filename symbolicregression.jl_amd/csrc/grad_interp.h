@@ -155,5 +155,85 @@ __device__ __forceinline__ void run_program_grad(CIns<T>* __restrict__ p,
   }
 }
 
+// ---- expression losses: the loss program in dual numbers --------------------------
+// run_loss (interp.h) with one tangent: the derivative with respect to ŷ (1 on
+// the ŷ leaf, 0 on y, w and immediates). Leaves out (ℓ, dℓ/dŷ) per row in a. The
+// rules are the gradient interpreter's: uop_d through un_grad, and bin_grad's
+// combination of bop_d's partials (an operand that is a leaf other than ŷ adds
+// no term). Nothing is checked (the marker is thrown away).
+template <int SL, int SR, int B, typename T, int R>
+__device__ __forceinline__ void loss_bin_dual(Dual<T, R, 1>& a, const Dual<T, R, 1>& t, const T (&x)[R], bool xd) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const T lv = SL == S_ACC ? a.v[r] : SL == S_TMP ? t.v[r] : x[r];
+    const T rv = SR == S_ACC ? a.v[r] : SR == S_TMP ? t.v[r] : x[r];
+    T fv, fx, fy;
+    dev::bop_d<B>(lv, rv, fv, fx, fy);
+    T nd;
+    if constexpr (SL == S_ACC) nd = fx * a.d[0][r];
+    else if constexpr (SL == S_TMP) nd = fx * t.d[0][r];
+    else nd = xd ? fx : T(0);
+    if constexpr (SR == S_ACC) nd = nd + fy * a.d[0][r];
+    else if constexpr (SR == S_TMP) nd = nd + fy * t.d[0][r];
+    else nd = xd ? nd + fy : nd;
+    a.d[0][r] = nd;
+    a.v[r] = fv;
+  }
+}
+
+#define SRLD_PUSH(K) case LOP_PUSH0 + K: slot[K] = a; break;
+#define SRLD_POP(K) case LOP_POP0 + K: t = slot[K]; break;
+#define SRLD_UN(U) case LOP_UN0 + U: un_grad<U, T, R, 1>(a, chk); break;
+#define SRLD_BIN(B)                                                               \
+  case LOP_AX0 + B: loss_bin_dual<S_ACC, S_X, B, T, R>(a, t, x, xd); break;       \
+  case LOP_XA0 + B: loss_bin_dual<S_X, S_ACC, B, T, R>(a, t, x, xd); break;       \
+  case LOP_TA0 + B: loss_bin_dual<S_TMP, S_ACC, B, T, R>(a, t, x, xd); break;
+
+template <typename T, int R>
+__device__ __forceinline__ void run_loss_dual(CIns<T>* __restrict__ p, const T (&yh)[R], const T (&yv)[R],
+                                              const T (&wv)[R], Dual<T, R, 1>& a) {
+  Dual<T, R, 1> t;
+  Dual<T, R, 1> slot[kLossSlots];
+  T x[R];
+  T chk = T(0);  // thrown away
+#pragma unroll
+  for (int r = 0; r < R; ++r) { a.v[r] = T(0); a.d[0][r] = T(0); t.v[r] = T(0); t.d[0][r] = T(0); x[r] = T(0); }
+  Ins<T> cur = fetch<T>(p);
+  for (;;) {
+    const Ins<T> nxt = fetch<T>(p + 1);
+    const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.code);
+    const T imm = uni(cur.imm);
+    const uint32_t opc = code & 0xffu;
+    const uint32_t leaf = (code >> 16) & 3u;
+    const bool xd = leaf == LEAF_YHAT;  // the leaf operand carries tangent 1
+    if (opc == LOP_LD || opc >= LOP_AX0) {
+      switch (leaf) {
+        case LEAF_YHAT: SR_UNROLL for (int r = 0; r < R; ++r) x[r] = yh[r]; break;
+        case LEAF_Y: SR_UNROLL for (int r = 0; r < R; ++r) x[r] = yv[r]; break;
+        case LEAF_W: SR_UNROLL for (int r = 0; r < R; ++r) x[r] = wv[r]; break;
+        default: SR_UNROLL for (int r = 0; r < R; ++r) x[r] = imm; break;
+      }
+    }
+    switch (opc) {
+      case LOP_END: return;
+      case LOP_LD:
+#pragma unroll
+        for (int r = 0; r < R; ++r) { a.v[r] = x[r]; a.d[0][r] = xd ? T(1) : T(0); }
+        break;
+      SRLD_PUSH(0) SRLD_PUSH(1) SRLD_PUSH(2)
+      SRLD_POP(0) SRLD_POP(1) SRLD_POP(2)
+      SRLD_UN(0) SRLD_UN(1) SRLD_UN(2) SRLD_UN(3) SRLD_UN(4) SRLD_UN(5) SRLD_UN(6) SRLD_UN(7) SRLD_UN(8)
+      SRLD_UN(9) SRLD_UN(10) SRLD_UN(11) SRLD_UN(12) SRLD_UN(13) SRLD_UN(14) SRLD_UN(15) SRLD_UN(16)
+      SRLD_UN(17) SRLD_UN(18) SRLD_UN(19) SRLD_UN(20) SRLD_UN(21) SRLD_UN(22) SRLD_UN(23) SRLD_UN(24)
+      SRLD_UN(25) SRLD_UN(26) SRLD_UN(27) SRLD_UN(28)
+      SRLD_BIN(0) SRLD_BIN(1) SRLD_BIN(2) SRLD_BIN(3) SRLD_BIN(4) SRLD_BIN(5) SRLD_BIN(6) SRLD_BIN(7)
+      SRLD_BIN(8) SRLD_BIN(9) SRLD_BIN(10)
+      default: break;
+    }
+    cur = nxt;
+    ++p;
+  }
+}
+
 }  // namespace interp
 }  // namespace srhip

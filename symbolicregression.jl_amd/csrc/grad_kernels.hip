@@ -18,6 +18,13 @@ namespace {
 
 using namespace interp;
 
+// Kernel mode of a GRAD_LOSS launch whose loss is an expression loss (a.loss >=
+// SRHIP_EXPR_LOSS_BEGIN): (ℓ, dℓ/dŷ) per row come from the loss program in dual
+// numbers (grad_interp.h run_loss_dual) in place of elem_loss / elem_dloss, with
+// no implicit weight. Instantiations of their own (full operator set; the weight
+// column is the run-time a.w): the others keep their code.
+constexpr int kGradLossExpr = 2;
+
 template <typename T, int R, int D, int MODE, bool W, int G, int SET>
 __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
   constexpr int S = 2 + G;
@@ -26,7 +33,7 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
   constexpr int N = V16<T>::N;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int rows = a.ntiles * TILE;
-  const int narr = a.nfeat + (MODE == GRAD_LOSS ? (W ? 2 : 1) : 0);
+  const int narr = a.nfeat + (MODE == GRAD_LOSS ? (W ? 2 : 1) : MODE == kGradLossExpr ? (a.w ? 2 : 1) : 0);
   T* sX = reinterpret_cast<T*>(smem);
   T* sY = sX + (size_t)a.nfeat * rows;
   T* sW = sY + rows;
@@ -95,15 +102,29 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
         lds_rows<T, R>(sY + tl * TILE, lane, yv);
         if constexpr (W) lds_rows<T, R>(sW + tl * TILE, lane, wv);
         const int valid = (tl < nt_valid - 1) ? TILE : last_valid;
+        if constexpr (MODE == kGradLossExpr) {
+          if (a.w) lds_rows<T, R>(sW + tl * TILE, lane, wv);
+          else SR_UNROLL for (int e = 0; e < R; ++e) wv[e] = T(0);  // (a loss reading w is refused without weights)
+          Dual<T, R, 1> ld;
+          run_loss_dual<T, R>(const_prog(a.lprog), d.v, yv, wv, ld);
 #pragma unroll
-        for (int e = 0; e < R; ++e) {
-          T l = dev::elem_loss<T>(a.loss, lp, d.v[e], yv[e]);
-          T dl = dev::elem_dloss<T>(a.loss, lp, d.v[e], yv[e]);
-          if constexpr (W) { l = wv[e] * l; dl = wv[e] * dl; }
-          const bool in = row_of<T, R>(e, lane) < valid;
-          acc[0] += in ? l : T(0);
+          for (int e = 0; e < R; ++e) {
+            const bool in = row_of<T, R>(e, lane) < valid;
+            acc[0] += in ? ld.v[e] : T(0);
 #pragma unroll
-          for (int j = 0; j < G; ++j) acc[2 + j] += in ? dl * d.d[j][e] : T(0);
+            for (int j = 0; j < G; ++j) acc[2 + j] += in ? ld.d[0][e] * d.d[j][e] : T(0);
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < R; ++e) {
+            T l = dev::elem_loss<T>(a.loss, lp, d.v[e], yv[e]);
+            T dl = dev::elem_dloss<T>(a.loss, lp, d.v[e], yv[e]);
+            if constexpr (W) { l = wv[e] * l; dl = wv[e] * dl; }
+            const bool in = row_of<T, R>(e, lane) < valid;
+            acc[0] += in ? l : T(0);
+#pragma unroll
+            for (int j = 0; j < G; ++j) acc[2 + j] += in ? dl * d.d[j][e] : T(0);
+          }
         }
       }
     }
@@ -179,6 +200,7 @@ hipError_t launch_grad_one(const EvalPlan& plan, const GradArgs<T>& a, hipStream
 template <typename T, int R, int D, int G, int SET>
 hipError_t launch_grad_rd(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
   if (mode == GRAD_OUT) return launch_grad_one<T, R, D, GRAD_OUT, false, G, SET>(plan, a, stream);
+  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_grad_one<T, R, D, kGradLossExpr, false, G, OPSET_FULL>(plan, a, stream);
   if (a.w) return launch_grad_one<T, R, D, GRAD_LOSS, true, G, SET>(plan, a, stream);
   return launch_grad_one<T, R, D, GRAD_LOSS, false, G, SET>(plan, a, stream);
 }

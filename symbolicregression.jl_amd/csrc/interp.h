@@ -377,6 +377,63 @@ __device__ __forceinline__ void run_program_v2(const VProg<T>& vp, const T* __re
     if (!exec_ins<T, R, D, SET>(c1, vp.imm_at(pc + 1), acc, tmp, slot, xb, sXt, rs, lane, chk)) return;
   }
 }
+// ---- expression losses: the loss program of one row tile -------------------------
+// (srhip_internal.h "expression-loss programs"). The program is wave-uniform and
+// fetched with scalar loads like a tree's; its leaves are the tile's ŷ / y / w
+// registers or the immediate; the operators are the tree interpreter's own
+// (un_apply / bin_apply) with a marker that is thrown away: nothing inside the
+// loss is checked (srhip.h).
+#define SRL_PUSH(K) \
+  case LOP_PUSH0 + K: SR_UNROLL for (int r = 0; r < R; ++r) slot[K][r] = acc[r]; break;
+#define SRL_POP(K) \
+  case LOP_POP0 + K: SR_UNROLL for (int r = 0; r < R; ++r) tmp[r] = slot[K][r]; break;
+#define SRL_UN(U) \
+  case LOP_UN0 + U: un_apply<U, T, R>(acc, chk); break;
+#define SRL_BIN(B)                                                                              \
+  case LOP_AX0 + B: bin_apply<V_AX, B, T, R>(acc, tmp, x, nullptr, 0, lane, imm, chk); break;  \
+  case LOP_XA0 + B: bin_apply<V_XA, B, T, R>(acc, tmp, x, nullptr, 0, lane, imm, chk); break;  \
+  case LOP_TA0 + B: bin_apply<V_TA, B, T, R>(acc, tmp, x, nullptr, 0, lane, imm, chk); break;
+
+template <typename T, int R>
+__device__ __forceinline__ void run_loss(CIns<T>* __restrict__ p, const T (&yh)[R], const T (&yv)[R],
+                                         const T (&wv)[R], int lane, T (&acc)[R]) {
+  T tmp[R], x[R];
+  T slot[kLossSlots][R];
+  T chk = T(0);  // thrown away
+#pragma unroll
+  for (int r = 0; r < R; ++r) { acc[r] = T(0); tmp[r] = T(0); x[r] = T(0); }
+  Ins<T> cur = fetch<T>(p);
+  for (;;) {
+    const Ins<T> nxt = fetch<T>(p + 1);  // prefetch; every loss program ends with END + slack
+    const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.code);
+    const T imm = uni(cur.imm);
+    const uint32_t opc = code & 0xffu;
+    if (opc == LOP_LD || opc >= LOP_AX0) {  // (TA ignores x)
+      switch ((code >> 16) & 3u) {
+        case LEAF_YHAT: SR_UNROLL for (int r = 0; r < R; ++r) x[r] = yh[r]; break;
+        case LEAF_Y: SR_UNROLL for (int r = 0; r < R; ++r) x[r] = yv[r]; break;
+        case LEAF_W: SR_UNROLL for (int r = 0; r < R; ++r) x[r] = wv[r]; break;
+        default: SR_UNROLL for (int r = 0; r < R; ++r) x[r] = imm; break;
+      }
+    }
+    switch (opc) {
+      case LOP_END: return;
+      case LOP_LD: SR_UNROLL for (int r = 0; r < R; ++r) acc[r] = x[r]; break;
+      SRL_PUSH(0) SRL_PUSH(1) SRL_PUSH(2)
+      SRL_POP(0) SRL_POP(1) SRL_POP(2)
+      SRL_UN(0) SRL_UN(1) SRL_UN(2) SRL_UN(3) SRL_UN(4) SRL_UN(5) SRL_UN(6) SRL_UN(7) SRL_UN(8) SRL_UN(9)
+      SRL_UN(10) SRL_UN(11) SRL_UN(12) SRL_UN(13) SRL_UN(14) SRL_UN(15) SRL_UN(16) SRL_UN(17) SRL_UN(18)
+      SRL_UN(19) SRL_UN(20) SRL_UN(21) SRL_UN(22) SRL_UN(23) SRL_UN(24) SRL_UN(25) SRL_UN(26) SRL_UN(27)
+      SRL_UN(28)
+      SRL_BIN(0) SRL_BIN(1) SRL_BIN(2) SRL_BIN(3) SRL_BIN(4) SRL_BIN(5) SRL_BIN(6) SRL_BIN(7) SRL_BIN(8)
+      SRL_BIN(9) SRL_BIN(10)
+      default: break;
+    }
+    cur = nxt;
+    ++p;
+  }
+}
+static_assert(kLossSlots == 3, "update SRL_PUSH / SRL_POP");
 static_assert(SRHIP_NUM_UOPS == 29 && SRHIP_NUM_BOPS == 11, "update the case lists");
 
 }  // namespace interp

@@ -51,6 +51,8 @@ struct EvalArgs {
   // finalize only: the launch wrote 4-byte partials (Σ; float at partial + rg·npos + pos) and a
   // failed tree is the one whose slot failure flag is set (the hand-written loss tree loops)
   int part4 = 0;
+  // the loss program of an expression loss (loss >= SRHIP_EXPR_LOSS_BEGIN), device memory
+  const Ins<T>* lprog = nullptr;
 };
 
 // Geometry of one evaluation launch, chosen by plan_eval().
@@ -112,6 +114,7 @@ struct GradArgs {
   T* out_grad;              // GRAD_OUT: [total consts][out_stride]
   int64_t out_stride;
   int dyn = 0;              // waves take their items from an LDS counter (SRHIP_INTERP_DYN)
+  const Ins<T>* lprog = nullptr;  // the loss program of an expression loss (loss >= SRHIP_EXPR_LOSS_BEGIN)
 };
 
 bool plan_grad(int dtype, bool deep, int G, int mode, bool weighted, int nfeat, int64_t n,

@@ -134,6 +134,35 @@ constexpr int uop_cost(int op) {
              : (op == SRHIP_UOP_EXP || op == SRHIP_UOP_SQRT || op == SRHIP_UOP_INV) ? 14 : 40;
 }
 
+// ---- expression-loss programs (srhip_loss_expr_create) ----------------------------
+// The loss tree over (ŷ, y, w) compiled to its own small accumulator machine,
+// run per row tile in the epilogue of the interpreter kernels (interp.h
+// run_loss, grad_interp.h run_loss_dual). Registers, R rows per lane each:
+//   acc, tmp, slot[0..kLossSlots)
+// Leaves are never pushed: a leaf operand is read by the instruction that uses
+// it, from the tile's ŷ / y / w registers or the immediate. A postfix stack of
+// at most kLossMaxDepth values needs at most kLossMaxDepth - 1 slots.
+constexpr int kLossMaxNodes = 64;
+constexpr int kLossMaxDepth = 4;
+constexpr int kLossSlots = kLossMaxDepth - 1;
+enum : int {
+  LOP_END = 0,
+  LOP_LD = 1,                            // acc = leaf
+  LOP_PUSH0 = 2,                         // slot[k] = acc
+  LOP_POP0 = LOP_PUSH0 + kLossSlots,     // tmp = slot[k]
+  LOP_UN0 = LOP_POP0 + kLossSlots,       // acc = u(acc)
+  LOP_AX0 = LOP_UN0 + SRHIP_NUM_UOPS,    // acc = b(acc, leaf)
+  LOP_XA0 = LOP_AX0 + SRHIP_NUM_BOPS,    // acc = b(leaf, acc)
+  LOP_TA0 = LOP_XA0 + SRHIP_NUM_BOPS,    // acc = b(tmp, acc)
+  kNumLossOpcodes = LOP_TA0 + SRHIP_NUM_BOPS,
+};
+// code word: [7:0] opcode, [17:16] leaf of LD / AX / XA
+enum LossLeaf : int { LEAF_YHAT = 0, LEAF_Y = 1, LEAF_W = 2, LEAF_IMM = 3 };
+constexpr uint32_t make_loss_code(int opc, int leaf) { return (uint32_t)opc | ((uint32_t)leaf << 16); }
+// instructions of the longest program: one per node, a PUSH and a POP per binary
+// node with two computed operands, END
+constexpr int kLossMaxIns = kLossMaxNodes + 2 * (kLossMaxNodes / 2) + 1;
+
 // The name of the main (evaluation) kernel the calling thread launched last:
 // set at each launch site, read by srhip_last_kernel_name (bench.py ties a
 // rocprofv3 PMC summary to the kernel that ran).

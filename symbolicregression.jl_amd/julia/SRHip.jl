@@ -11,6 +11,7 @@
 module SRHip
 
 using DynamicExpressions: Node, count_nodes, set_constants
+import DynamicExpressions  # DynamicExpressions.eval_tree_array: the CPU path of ExprLoss
 using LossFunctions: L2DistLoss, L1DistLoss, LPDistLoss, HuberLoss, LogCoshLoss, L1EpsilonInsLoss,
     L2EpsilonInsLoss, QuantileLoss, PeriodicLoss, LogitDistLoss,
     ZeroOneLoss, PerceptronLoss, LogitMarginLoss, L1HingeLoss, L2HingeLoss, SmoothedL1HingeLoss,
@@ -184,6 +185,65 @@ function flatten(trees::AbstractVector{Node{T}}, options::Options) where {T}
     end
     return node_off, kind, arg, const_off, consts
 end
+
+# ---- expression losses: a custom elementwise_loss written as a tree (srhip.h
+# "expression losses") ----------------------------------------------------------
+const SRHIP_EXPR_LOSS_BEGIN = Int32(1024)  # loss kinds from here on are handles of expression losses
+
+"""
+    ExprLoss(tree::Node{T}, operators)
+
+A custom `elementwise_loss` as a tree over x1 = the prediction, x2 = the target
+and x3 = the weight, built with `operators` (an `OperatorEnum`, e.g.
+`options.operators`). It is registered with the engine once (`kind` is the
+handle, >= SRHIP_EXPR_LOSS_BEGIN, destroyed by the finaliser) and is itself a
+function `(x, y)` / `(x, y, w)`, so the reference's CPU path
+(src/LossFunctions.jl:17-31) evaluates the same tree. The engine sums the loss
+values as they are: a weighted loss multiplies by x3 itself, and a tree that
+reads x3 needs a weighted dataset.
+"""
+mutable struct ExprLoss{T,O} <: Function
+    tree::Node{T}
+    operators::O
+    kind::Int32
+end
+
+function ExprLoss(tree::Node{T}, operators) where {T}
+    bin = [op_id(op, 2) for op in operators.binops]
+    una = [op_id(op, 1) for op in operators.unaops]
+    kind = UInt8[]; arg = UInt16[]; consts = Float64[]
+    function visit(t::Node{T})
+        if t.degree == 0
+            if t.constant
+                push!(kind, NODE_CONST); push!(arg, 0); push!(consts, Float64(t.val::T))
+            else
+                push!(kind, NODE_FEATURE); push!(arg, UInt16(t.feature - 1))
+            end
+        elseif t.degree == 1
+            visit(t.l); push!(kind, NODE_UNARY); push!(arg, una[t.op])
+        else
+            visit(t.l); visit(t.r); push!(kind, NODE_BINARY); push!(arg, bin[t.op])
+        end
+    end
+    visit(tree)
+    h = Ref{Int32}(0)
+    check(ccall((:srhip_loss_expr_create, libsrhip), Int32,
+                (Ptr{UInt8}, Ptr{UInt16}, Int32, Ptr{Float64}, Int32, Ptr{Int32}),
+                kind, arg, Int32(length(kind)), consts, Int32(length(consts)), h))
+    l = ExprLoss{T,typeof(operators)}(tree, operators, h[])
+    finalizer(l) do x
+        ccall((:srhip_loss_expr_destroy, libsrhip), Int32, (Int32,), x.kind)
+    end
+    return l
+end
+
+# the CPU path: the same tree on one (prediction, target, weight) triple
+function (l::ExprLoss{T})(x, y, w=zero(T)) where {T}
+    out, _ = DynamicExpressions.eval_tree_array(l.tree, reshape(T[x, y, w], 3, 1), l.operators)
+    return out[1]
+end
+
+loss_code(l::ExprLoss) = (l.kind, 0.0)
 
 # A compiled, device-resident batch of trees (srhip_program_create); destroyed
 # by the caller (`destroy`) or by the finaliser.

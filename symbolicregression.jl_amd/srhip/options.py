@@ -122,6 +122,90 @@ def DWDMarginLoss(q: float):
     return SupervisedLoss(K.LOSS["DWDMARGIN"], q)
 
 
+# ---- expression losses: a custom elementwise_loss as an engine tree (srhip.h) ----
+class ExprLoss:
+    """A custom elementwise loss written as a tree: `tree` is a `Node` built
+    under `options`' operator tables with x1 = the prediction, x2 = the target
+    and x3 = the weight (the reference's `loss(x, y)` / `loss(x, y, w)`,
+    src/LossFunctions.jl:17-31). It is registered with the engine once; the
+    handle (`.kind`, >= constants.EXPR_LOSS_BEGIN) goes wherever a built-in
+    loss's kind goes, and is destroyed when the object is finalised.
+
+    The engine sums the loss values as they are: a weighted loss multiplies by
+    x3 itself. A tree that reads x3 needs a weighted dataset (srhip.h lists the
+    limits and the deviations from the reference)."""
+
+    param = 0.0
+    params = None  # no parameter: the engine ignores loss_params for these kinds
+
+    def __init__(self, tree, options):
+        import ctypes as C
+        import weakref
+
+        import numpy as np
+
+        from ._lib import check, lib
+        from .node import flatten
+
+        flat = flatten([tree], options, dtype=np.float64)
+        kind = np.ascontiguousarray(flat.kind, dtype=np.uint8)
+        arg = np.ascontiguousarray(flat.arg, dtype=np.uint16)
+        consts = np.ascontiguousarray(flat.consts, dtype=np.float64)
+        out = C.c_int32(0)
+        check(lib().srhip_loss_expr_create(kind.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                           arg.ctypes.data_as(C.POINTER(C.c_uint16)), int(len(kind)),
+                                           consts.ctypes.data_as(C.POINTER(C.c_double)), int(len(consts)),
+                                           C.byref(out)))
+        self.kind = int(out.value)
+        self.tree = tree
+        self.uses_weights = bool(np.any((kind == K.NODE_FEATURE) & (arg == 2)))
+        self._finalizer = weakref.finalize(self, _destroy_expr_loss, self.kind)
+
+    def destroy(self):
+        """Destroy the handle now (later uses of `.kind` are invalid-argument errors)."""
+        self._finalizer()
+
+    def value(self, yhat, y, w=None):
+        """ℓ(ŷ, y, w) per element on the host with the engine's semantics
+        (srhip_loss_expr_eval), in the dtype of `yhat` (float32 or float64)."""
+        import ctypes as C
+
+        import numpy as np
+
+        from ._lib import check, lib
+
+        yhat = np.ascontiguousarray(yhat)
+        dt = yhat.dtype
+        if dt not in (np.float32, np.float64):
+            raise TypeError("yhat must be float32 or float64")
+        y = np.ascontiguousarray(y, dtype=dt)
+        if y.shape != yhat.shape:
+            raise ValueError("yhat and y differ in shape")
+        wp = None
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=dt)
+            if w.shape != yhat.shape:
+                raise ValueError("yhat and w differ in shape")
+            wp = w.ctypes.data_as(C.c_void_p)
+        out = np.empty_like(yhat)
+        check(lib().srhip_loss_expr_eval(self.kind, K.F32 if dt == np.float32 else K.F64,
+                                         yhat.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), wp,
+                                         int(yhat.size), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def __repr__(self):
+        return f"ExprLoss(kind={self.kind})"
+
+
+def _destroy_expr_loss(kind: int) -> None:
+    from ._lib import lib
+
+    try:
+        lib().srhip_loss_expr_destroy(kind)
+    except Exception:  # interpreter shutdown: the library may be gone
+        pass
+
+
 # Keywords of the reference's Options (src/Options.jl:315-379) that steer only
 # its search control plane (mutation/crossover schedule, constraints, output,
 # recorder, stopping rules): accepted, stored, not used by this engine.
