@@ -555,6 +555,63 @@ def manual_div_lc(rg):
             "v_pk_fma_f32 v[34:35], v[8:9], v[4:5], v[12:13]"]
 
 
+# The FAST-region division bodies check a lower bound only:
+# min(|a|, |rcp(b)|) >= 2^-50 keeps every intermediate of the sequence out of
+# the denormal range, where scaling by powers of two stops commuting with its
+# roundings. The upper bounds of the PRECISE bodies only keep an overflow
+# away, and an overflow is never silent: it leaves Inf or NaN in the result,
+# which the FAST verdict (jit.cpp) answers by redoing the tile with the
+# PRECISE region, whose bodies stay two-sided (tools/check_div_range.c).
+DIV_FAST_MIN = "0x26800000"  # 2^-50
+
+
+def manual_div_fast(rg):
+    """manual_div for the FAST region: the four reciprocals first, then one
+    chain min(|a0..a3|, |r0..r3|) against 2^-50 (NaN-true, as the verdict's
+    checks). r = rcp(b) bounds b from above (|b| <= 2^50), is 0 for an
+    infinite b and Inf for a zero or denormal one; nothing of A or B is
+    written before the branch, so b_div_full starts over from both. The |a|
+    part of the chain separates the last v_rcp from the first read of its
+    result (a non-trans read of a trans result needs one slot in between)."""
+    body = manual_div(rg)
+    k = body.index("s_cbranch_scc1 @DIVFULL@")
+    rcps, seq = body[k + 1:k + 5], body[k + 5:]
+    assert all(l.startswith("v_rcp_f32") for l in rcps)
+    return rcps + ["v_min3_f32 v1, |v32|, |v33|, |v34|",
+                   "v_min3_f32 v1, v1, |v35|, |v2|",
+                   "v_min3_f32 v1, v1, |v3|, |v4|",
+                   "v_min_f32_e64 v1, v1, |v5|",
+                   f"v_cmp_nle_f32_e32 vcc, {DIV_FAST_MIN}, v1",   # !(2^-50 <= min)
+                   "s_cbranch_vccnz @DIVFULL@"] + seq
+
+
+def manual_div_lc_fast(rg):
+    """manual_div_lc for the FAST region: the chain runs over |r0..r3| and
+    |c| (c rides along for nothing: five values fill two v_min3). The first
+    v_min3 reads r0 and r1 only, so r3 is read two slots after its v_rcp."""
+    k = rg.S["k"]
+    body = manual_div_lc(rg)
+    j = body.index("s_cbranch_scc1 @LCFULL@")
+    rcps, seq = body[j + 1:j + 5], body[j + 5:]
+    assert all(l.startswith("v_rcp_f32") for l in rcps)
+    return rcps + [f"v_min3_f32 v1, |v2|, |v3|, |s{k}|",
+                   "v_min3_f32 v1, v1, |v4|, |v5|",
+                   f"v_cmp_nle_f32_e32 vcc, {DIV_FAST_MIN}, v1",
+                   "s_cbranch_vccnz @LCFULL@"] + seq
+
+
+def manual_div_rk_fast(rg):
+    """manual_div_rk for the FAST region: the lower bound on |a0..a3| only
+    (the host's condition on c bounds y = RN(1/c) from below)."""
+    body = manual_div_rk(rg)
+    j = body.index("s_cbranch_scc1 .Lsrdk_fb_%=")
+    seq = body[j + 1:body.index(".Lsrdk_fb_%=:")]
+    return ["v_min3_f32 v1, |v32|, |v33|, |v34|",
+            "v_min_f32_e64 v1, v1, |v35|",
+            f"v_cmp_nle_f32_e32 vcc, {DIV_FAST_MIN}, v1",
+            "s_cbranch_vccnz @DIVRC@"] + seq
+
+
 def compile_bodies(hipcc, rg, routines, extra):
     src = snippet_source(rg, [(n, b) for n, b, _ in routines])
     with tempfile.TemporaryDirectory() as td:
@@ -598,14 +655,17 @@ def build(hipcc, outdir, R):
     prec = compile_bodies(hipcc, rg, routines, [])
     names = [n for n, _, _ in routines if n in fast and n in prec]
     manual = set()
-    if "b_div_rc" in names:  # hand-written, the same in both regions (IEEE exact)
-        fast["b_div_rk"] = prec["b_div_rk"] = manual_div_rk(rg)
+    if "b_div_rc" in names:  # hand-written (IEEE exact); the FAST region's checks a lower bound only
+        prec["b_div_rk"] = manual_div_rk(rg)
+        fast["b_div_rk"] = manual_div_rk_fast(rg)
         names.insert(names.index("b_div_rc") + 1, "b_div_rk")
     if os.environ.get("SR_JIT_MANUAL_DIV", "1") != "0" and "b_div_full" in names:
-        fast["b_div"] = prec["b_div"] = manual_div(rg)  # exact: the same in both regions
+        prec["b_div"] = manual_div(rg)  # exact in both regions
+        fast["b_div"] = manual_div_fast(rg)
         manual.add("b_div")
         if "b_div_lc_full" in names:
-            fast["b_div_lc"] = prec["b_div_lc"] = manual_div_lc(rg)
+            prec["b_div_lc"] = manual_div_lc(rg)
+            fast["b_div_lc"] = manual_div_lc_fast(rg)
             manual.add("b_div_lc")
     if os.environ.get("SR_JIT_MANUAL_EXP", "1") != "0" and "u_exp" in names:
         fast["u_exp"] = manual_exp()

@@ -547,12 +547,19 @@ struct Gen {
       if ((int)cpcs.size() > NSC) { why = "more constants than memory-constant SGPRs"; return false; }
     }
     // FAST eligibility, taint, zero sensitivity
-    bool elig = fast_opt, trans = false;
+    bool elig = fast_opt, trans = false, pdiv = false;
     for (auto& o : ops) {
       if (o.un ? !((kFastUops >> o.op) & 1u) : !((kFastBops >> o.op) & 1u)) elig = false;
       if (o.un && (o.op == SRHIP_UOP_EXP || o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS)) trans = true;
+      // a hand-scheduled division: its FAST-region body checks a lower bound
+      // only (gen_jit.py manual_div_fast) and leaves an overflow to the verdict
+      if (!o.un && o.op == SRHIP_BOP_DIV && !manual_off && !off_div) pdiv = true;
     }
-    fast = elig && trans;
+    // A tree without a transcendental has no FAST rounding, so no taint and no
+    // guard; with a packed division it still starts in the FAST region, for
+    // the cheaper range check, and keeps the verdict's NaN test of chk (a
+    // non-finite value cannot vanish before it).
+    fast = elig && (trans || pdiv);
     for (int i = 0; i < n; ++i) {
       IrOp& o = ops[i];
       o.taint = o.un && (o.op == SRHIP_UOP_EXP || o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS);
@@ -886,6 +893,10 @@ struct Gen {
       as.sop1(SOP1_MOV, "s_mov_b32", S_RECIP, K(yb), "s" + std::to_string(S_RECIP));
       rid = div_rk();
     }
+    // c / a: the packed routine only for a c inside its range (the FAST body's
+    // chain bounds |c| from below, nothing bounds it from above); any other c
+    // goes straight to the compiled routine, where the packed one would send it
+    if (!memc && !kr && o.op == SRHIP_BOP_DIV && !(ac >= 0x1p-45f && ac <= 0x1p45f)) rid = full_routine(rid);
     call_routine(rid);
     loc[i] = L_A;
     a_owner = i;

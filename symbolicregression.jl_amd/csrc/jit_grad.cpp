@@ -388,6 +388,22 @@ struct GradGen {
     static const bool fast_env = [] { const char* e = std::getenv("SRHIP_GJIT_FAST"); return e && e[0] == '1'; }();
     fast = fast_env && trans;
     if (fast) {
+      // The FAST region's packed division bodies leave an overflow to the loss
+      // code's tile verdict (gen_jit.py manual_div_fast); this code keeps its
+      // forward values for the reverse pass, so its divisions take the compiled
+      // IEEE routines (b_div_full, b_div_lc_full: the same in both regions).
+      auto full = [](int rid) {
+        if (rid < 0) return rid;
+        const std::string want = std::string(kRoutineName[rid]) + "_full";
+        for (int k = 0; k < kNumRoutines; ++k)
+          if (want == kRoutineName[k]) return k;
+        return rid;
+      };
+      for (GOp& o : ops)
+        if (o.kind == K_BIN && o.op == SRHIP_BOP_DIV && !g_inline(o)) {
+          o.rid = full(o.rid);
+          if (o.a.k == G_C) o.krid = full(o.krid);  // c / a (a / c: b_div_rc, compiled)
+        }
       for (int i = 0; i < n; ++i) {
         const GOp& o = ops[i];
         if (o.kind == K_UN && o.op == SRHIP_UOP_EXP) g_exp = true;
