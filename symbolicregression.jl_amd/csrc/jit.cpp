@@ -340,7 +340,7 @@ struct Gen {
   int load_idx[256];             // load number (0 = y)
   int nloads = 0, waited = 0;
   std::vector<int> next_call;    // first call index > i
-  int L_tile = -1, L_done = -1, L_redo = -1, L_bail = -1;
+  int L_tile = -1, L_done = -1, L_redo = -1, L_bail = -1, L_fail = -1;
   std::string why;
   bool out = false;              // per-row output code (Options::out)
   int out_rreg = -1;             // the root block of the tile (out mode)
@@ -413,6 +413,19 @@ struct Gen {
   // + - * (and square / cube, residuals, the root check) two rows per
   // instruction on v_pk_*_f32; block moves on v_pk_mov_b32
   bool packed = true, pkmov = true;
+  // SRHIP_JIT_TRIM_ROOT (read per build; "0": the earlier code): the root
+  // mark is two packed fmas, (r0, r1)·0 + (chk, chk), then (r2, r3)·0 + that,
+  // and one v_cmp_u of the pair, which the FAST verdict and the failure test
+  // share; chk is written on the failing path only, which leaves the tree at
+  // once (the driver reads chk after the call), and an L2 tile's tail, which
+  // writes no chk, tests nothing: 3 vector instructions per tile where there
+  // were 5 (4 PRECISE). In-process A/B on config #2 (profiles/
+  // rotate_trim_ab.json): 2.420 -> 2.402 ms. Measured beside it and dropped,
+  // each inside the spread: the tail's test skipped by a scalar test of the
+  // mode under the earlier mark (2.434), the guard accumulators set once per
+  // call instead of per tile (2.418).
+  bool trim_root = true;
+  bool root2 = false;  // this tree's root mark is the trimmed one
   // memory-constant code (Options::memc): every constant operand is an SGPR
   // s[SC0 + k], loaded in the prologue from the immediate of its program
   // instruction (s[SPROG:SPROG+1] = the tree's program in device memory), so
@@ -447,6 +460,8 @@ struct Gen {
     trig_full = tf && tf[0] == '1';
     const char* mo = std::getenv("SRHIP_JIT_MANUAL");
     manual_off = mo && mo[0] == '0';
+    const char* tr = std::getenv("SRHIP_JIT_TRIM_ROOT");
+    trim_root = !(tr && tr[0] == '0');
     // SRHIP_JIT_MANUAL_OFF=exp,trig,div (debugging): only these through the compiled routines
     if (const char* mf = std::getenv("SRHIP_JIT_MANUAL_OFF")) {
       const std::string l(mf);
@@ -1113,7 +1128,14 @@ struct Gen {
       for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGT + e, memc ? S(creg(root)) : K(root.c));
       rreg = VGT;
     }
-    if (packed && rreg != VGT) {
+    root2 = trim_root && packed && rreg != VGT && !out;
+    if (root2) {
+      // (r0, r1)·0 + (chk, chk), then (r2, r3)·0 + that: a NaN in the pair iff a
+      // row is not finite or chk was NaN; compared once, below
+      const Src r01 = V(rreg), r23 = V(rreg + 2), z = K(0), c = V(VCHK), t = V(VGT);
+      as.vop3p(VOP3P_FMA_F32, "v_pk_fma_f32", VGT, r01, z, &c, 0, 1, 0, 0);
+      as.vop3p(VOP3P_FMA_F32, "v_pk_fma_f32", VGT, r23, z, &t, 0, 5, 0, 0);
+    } else if (packed && rreg != VGT) {
       // (r0, r1)·0 + (r2, r3) is finite iff the four rows are: one packed fma, two into chk
       const Src r01 = V(rreg), r23 = V(rreg + 2), z = K(0);
       as.vop3p(VOP3P_FMA_F32, "v_pk_fma_f32", VGT, r01, z, &r23, 0, 5, 0, 0);
@@ -1133,11 +1155,12 @@ struct Gen {
       return true;
     }
     // ---- FAST-mode verdict: a failure or a guard redoes the tile precisely
+    if (root2) as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(VGT), VGT + 1);  // vcc: s_cmp leaves it
     if (fast) {
       const int L_skip = as.label();
       as.sopc(SOPC_LG_U32, "s_cmp_lg_u32", S(S_MODE), K(0));
       as.branch(SOPP_SCC1, "s_cbranch_scc1", L_skip);
-      as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(VCHK), VCHK);
+      if (!root2) as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(VCHK), VCHK);
       as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
       // the guards fire on NaN too: a FAST exp of an argument the exp guard
       // rejects returns garbage, possibly a signalling NaN, which poisons the
@@ -1164,6 +1187,12 @@ struct Gen {
         as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
       }
       as.bind(L_skip);
+    }
+    // PRECISE: a failed tile ends the tree (a FAST tile gets here with vcc = 0:
+    // its verdict's branches were not taken)
+    if (root2) {
+      L_fail = as.label();
+      as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_fail);
     }
     // ---- L2 loss of the tile: the residuals here, their squares in emit_tail
     // (a margin loss: the agreements ŷ·y for its routine, emit_tail_loss)
@@ -1301,8 +1330,10 @@ struct Gen {
       }
       as.bind(L_sum);
     }
-    // a failed tile ends the tree (out mode: every tile is stored)
-    if (!out) {
+    // a failed tile ends the tree (out mode: every tile is stored); the
+    // trimmed root mark has left already, and an L2 tail writes no chk (a
+    // loss routine may)
+    if (!out && !(root2 && loss == SRHIP_LOSS_L2)) {
       as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(VCHK), VCHK);
       as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_done);
     }
@@ -1340,6 +1371,12 @@ struct Gen {
       as.sop1(SOP1_MOV, "s_mov_b32", S_MODE, K(1), "s" + std::to_string(S_MODE));
       shift_base(true);
       as.branch(SOPP_BRANCH, "s_branch", (gany && gprefetch) ? L_reload : L_tile);  // the columns' blocks were reused
+    }
+    if (root2) {  // the failing path: the driver reads chk
+      as.bind(L_fail);
+      as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHK, K(0x7fc00000u));
+      as.sop1(SOP1_SETPC, "s_setpc_b64", 0, S(S_RT), "");
+      if (as.want_text) as.lines.back() = "s_setpc_b64 s[" + std::to_string(S_RT) + ":" + std::to_string(S_RT + 1) + "]";
     }
     if (has_trig) {
       as.bind(L_bail);
@@ -1933,6 +1970,7 @@ struct JitArgs {
   int nbig, ts;
   int dyn;
   const float* gcols;  // [ngcol][n_pad] shared-subtree columns of this call, or null
+  int rot_step, rot_nrg;  // the row groups' starting offsets into their tree walk (launch)
 };
 struct DeriveArgs {
   const float* X;
@@ -1979,6 +2017,13 @@ static bool dynloop() {
   return !(e && e[0] == '0');
 }
 
+// SRHIP_JIT_ROTATE's default (launch). One process, the mode alternating call
+// by call (profiles/rotate_trim_ab.json): config #2 at 1M rows 2.480 / 2.400 /
+// 2.421 ms for modes 0 / 1 / 2, at 125k rows 0.414 / 0.398 / 0.407; its
+// succeeding trees alone 2.264 / 2.260 / 2.294: mode 1 costs them nothing,
+// mode 2 the order it gives up.
+constexpr int kRotateDefault = 1;
+
 bool partials4(Module* m, int k) {
   const ModulePart& q = m->parts[k];
   return q.fn_dl && !m->out && dynloop();
@@ -2020,6 +2065,35 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
   {
     const char* e = std::getenv("SRHIP_JIT_STICKY_TREE");
     ja.dyn = (e && e[0] == '1') ? 1 : (e && e[0] == '0') ? 0 : (a.nrg <= 48 ? 1 : 0);
+  }
+  // Each row group starts its walk over the tree group's list at an offset of
+  // its own (jit_template.hip rot_of). Every workgroup used to walk from
+  // position 0, and the workgroups of the first round start together: all of
+  // its row groups then ran a failing tree at the same moment, before any of
+  // them had set the tree's failure flag for the others to skip it. The
+  // offsets are spread over tpb across the row groups resident together
+  // (compute units × workgroups per unit / tree groups). SRHIP_JIT_ROTATE
+  // (read per launch): 0 off, 1 the row groups of the first round only (the
+  // later ones keep the cost-descending order, whose waves end together), 2
+  // every row group. Per-row output code reads no flags: never rotated.
+  ja.rot_step = 0;
+  ja.rot_nrg = 0;
+  if (!m->out && a.tpb > 1 && a.ntg > 0) {
+    const char* e = std::getenv("SRHIP_JIT_ROTATE");
+    const int mode = e ? std::atoi(e) : kRotateDefault;
+    if (mode == 1 || mode == 2) {
+      static const int ncu = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+          n = 256;
+        return n;
+      }();
+      const int per_cu = std::max(1, 20 / std::max(1, plan.threads / 64));  // lds_per_workgroup
+      const int resident = std::max(1, std::min(a.nrg, ncu * per_cu / a.ntg));
+      ja.rot_step = std::max(1, a.tpb / resident);
+      ja.rot_nrg = mode == 2 ? a.nrg : resident;
+    }
   }
   if (ja.nraw > a.nfeat) return hipErrorInvalidValue;
   if (ja.nbig > a.nrg || ja.ts < 1 || ja.ts > plan.ntiles) return hipErrorInvalidValue;

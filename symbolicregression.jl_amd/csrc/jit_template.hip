@@ -87,7 +87,20 @@ struct JitArgs {
   int dyn;                  // hand-written prefetching loop: a tree redone PRECISE in one row group runs PRECISE in the later ones
   const float* gcols;       // [ngcol][n_pad] shared-subtree columns (jit.h Columns), or null: tree code
                             // reads column g of this row group at s[36:37] + g·s38 (literal code only)
+  int rot_step, rot_nrg;    // loss loops: row group rg < rot_nrg starts its tree walk at (rg·rot_step) mod tpb
+                            // (jit.cpp launch, SRHIP_JIT_ROTATE); 0, 0: every row group at tree 0
 };
+
+// Where row group rg starts its walk over the tree group's list positions:
+// claim k (or the static loop's k-th tree) is position (k + rot) mod tpb. The
+// row groups resident together then reach a tree at different times, so a
+// failure one of them finds is skipped by the others (they all ran it at once
+// before). Partials are stored per position and summed in a fixed order: the
+// results do not depend on the walk's order.
+__device__ __forceinline__ uint32_t rot_of(const JitArgs& ja, int rg) {
+  if (ja.rot_step <= 0 || rg >= ja.rot_nrg) return 0u;
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)(((int64_t)rg * ja.rot_step) % ja.e.tpb));
+}
 
 // A derived column's value: the PRECISE routine of the operator (the same
 // device_ops.h code as the tree code's PRECISE region and the interpreters).
@@ -295,23 +308,35 @@ __device__ __forceinline__ void jit_eval_body(const JitArgs& ja) {
       i = inx;
     }
   } else {
-    int m = wave < a.tpb ? (a.tpb - wave + nwaves - 1) / nwaves : 0;
-    while (m > 0 && slot_of(wave + (m - 1) * nwaves) >= a.nlist) --m;
-    m = __builtin_amdgcn_readfirstlane(m);
-    uint32_t fnext = m > 0 ? ld_flag(slot_of(wave)) : 0u;
+    // the wave's k-th tree is list position (wave + k·nwaves + rot) mod tpb
+    // (rot_of; 0 for per-row output); positions whose slot is past nlist are
+    // passed over wherever the walk meets them
+    const int m = __builtin_amdgcn_readfirstlane(wave < a.tpb ? (a.tpb - wave + nwaves - 1) / nwaves : 0);
+    const int rot = OUT ? 0 : (int)rot_of(ja, rg);
+    auto pos_of = [&](int k) {
+      const int i = wave + k * nwaves + rot;
+      return i >= a.tpb ? i - a.tpb : i;
+    };
+    auto next_valid = [&](int k) {
+      while (k < m && slot_of(pos_of(k)) >= a.nlist) ++k;
+      return __builtin_amdgcn_readfirstlane(k);
+    };
+    int k = next_valid(0);
+    uint32_t fnext = k < m ? ld_flag(slot_of(pos_of(k))) : 0u;
     // the next slot's code offset is loaded one tree ahead, like its flag
-    int32_t cnext = m > 0 ? code_of(slot_of(wave)) : 0;
-    for (int k = 0; k < m; ++k) {
-      const int i = __builtin_amdgcn_readfirstlane(wave + k * nwaves);
+    int32_t cnext = k < m ? code_of(slot_of(pos_of(k))) : 0;
+    while (k < m) {
+      const int i = __builtin_amdgcn_readfirstlane(pos_of(k));
       const int s = __builtin_amdgcn_readfirstlane(slot_of(i));
-      const bool more = k + 1 < m;
+      const int k2 = next_valid(k + 1);
       const bool skip = __builtin_amdgcn_readfirstlane((int)fnext) != 0;
       const int32_t coff = cnext;
-      if (more) {
-        fnext = ld_flag(slot_of(wave + (k + 1) * nwaves));
-        cnext = code_of(slot_of(wave + (k + 1) * nwaves));
+      if (k2 < m) {
+        fnext = ld_flag(slot_of(pos_of(k2)));
+        cnext = code_of(slot_of(pos_of(k2)));
       }
       run_tree(i, s, skip, coff);
+      k = k2;
     }
   }
   if (lane == 0 && __builtin_amdgcn_readfirstlane((int)redos) != 0)
@@ -364,6 +389,7 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
 // tree code, gen_jit.py SR_JIT_CLOBBERS):
 //   v30 the lane's LDS tile address, v31 the counter's LDS address, v43 lane*R
 //   s40 tpb, s41 ntg, s42 g, s43 ntg-1-g, s44 nlist (slots of this part)
+//   s45 rot (rot_of: claim k is list position i = (k + rot) mod tpb, in s60)
 //   s[46:47] failure flags, s[48:49] code offsets, s[50:51] this group's
 //   global partials, s52 partials in LDS (1) or global (0), s53 their LDS
 //   address, s[54:55] bail flags, s[92:93] counters, s[88:89] the code area,
@@ -371,12 +397,15 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
 //   list_off, each tree's program address into s[56:57] (SR_JIT_LOOP_PROG),
 //   s65-s68 / s79 / s84 as for the compiled loop; return address s[94:95];
 //   temps s58-s63, s96-s97, v0-v2, v89-v91.
+// The loop ends on a claim k >= tpb; a position whose slot is past nlist (the
+// ragged last positions, which a rotated walk meets before its end) is passed
+// over and the next one claimed.
 // Per tree i (slot s = i*ntg + (i odd ? ntg-1-g : g)): a set failure flag
 // skips it (partial {0, NaN}); else its code runs; a bail (s69 != 0) sets the
 // slot's bail flag and counts it; the loss is summed over the wave in the
 // order of interp.h wave_sum; lane 0 stores the partial {Σ, NaN or 0} and, if
 // some row failed, the slot's failure flag (vector stores only).
-#define SR_JIT_LOOP_TEXT(NAME, PROG)                                                              \
+#define SR_JIT_LOOP_TEXT(NAME, PROG, ROT)                                                         \
   ".globl " #NAME "\n.hidden " #NAME "\n.p2align 6\n" #NAME ":\n"               \
   "v_mov_b32_e32 v89, 1\n"                                                            \
   ".L" #NAME "_next:\n"                                                                     \
@@ -388,12 +417,16 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "v_readlane_b32 s60, v90, 0\n"                                                      \
   "s_cmp_ge_u32 s60, s40\n"                                                           \
   "s_cbranch_scc1 .L" #NAME "_done\n"                                                       \
+  "s_add_u32 s60, s60, " ROT "\n"                                                     \
+  "s_sub_u32 s62, s60, s40\n"                                                         \
+  "s_cmp_ge_u32 s60, s40\n"                                                           \
+  "s_cselect_b32 s60, s62, s60\n"                                                     \
   "s_mul_i32 s61, s60, s41\n"                                                         \
   "s_bitcmp1_b32 s60, 0\n"                                                            \
   "s_cselect_b32 s62, s43, s42\n"                                                     \
   "s_add_u32 s61, s61, s62\n"                                                         \
   "s_cmp_ge_u32 s61, s44\n"                                                           \
-  "s_cbranch_scc1 .L" #NAME "_done\n"                                                       \
+  "s_cbranch_scc1 .L" #NAME "_next\n"                                                       \
   "s_lshl_b32 s62, s61, 2\n"                                                          \
   "v_mov_b32_e32 v90, s62\n"                                                          \
   "global_load_dword v91, v90, s[46:47] sc1\n"                                        \
@@ -488,10 +521,12 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "s_setpc_b64 s[94:95]\n"
 // The same loop with the next tree claimed and its failure flag / code offset
 // loaded before the current tree runs (their latency under its work):
-// next i s58, slot s59, flag v92, code offset s23; exec saved in s[96:97].
+// next i s58, slot s59, flag v92, code offset s23; exec saved in s[96:97];
+// rot in s98 (s45 holds the FAST / sticky flags here).
 #define SR_JIT_LOOP_PF_TEXT(NAME)                                                      \
   ".globl " #NAME "\n.hidden " #NAME "\n.p2align 6\n" #NAME ":\n"               \
   "v_mov_b32_e32 v89, 1\n"                                                       \
+  ".L" #NAME "_claim0:\n"                                                   \
   "s_mov_b64 s[96:97], exec\n"                                                   \
   "s_mov_b64 exec, 1\n"                                                          \
   "ds_add_rtn_u32 v90, v31, v89\n"                                               \
@@ -500,12 +535,16 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "v_readlane_b32 s58, v90, 0\n"                                                 \
   "s_cmp_ge_u32 s58, s40\n"                                                      \
   "s_cbranch_scc1 .L" #NAME "_inv0\n"                                        \
+  "s_add_u32 s58, s58, s98\n"                                                    \
+  "s_sub_u32 s62, s58, s40\n"                                                    \
+  "s_cmp_ge_u32 s58, s40\n"                                                      \
+  "s_cselect_b32 s58, s62, s58\n"                                                \
   "s_mul_i32 s59, s58, s41\n"                                                    \
   "s_bitcmp1_b32 s58, 0\n"                                                       \
   "s_cselect_b32 s62, s43, s42\n"                                                \
   "s_add_u32 s59, s59, s62\n"                                                    \
   "s_cmp_ge_u32 s59, s44\n"                                                      \
-  "s_cbranch_scc1 .L" #NAME "_inv0\n"                                        \
+  "s_cbranch_scc1 .L" #NAME "_claim0\n"                                      \
   "s_lshl_b32 s62, s59, 2\n"                                                     \
   "v_mov_b32_e32 v90, s62\n"                                                     \
   "global_load_dword v92, v90, s[46:47] sc1\n"                                   \
@@ -523,6 +562,7 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "s_mov_b32 s61, s59\n"                                                         \
   "s_mov_b32 s63, s23\n"                                                         \
   "s_mov_b32 s91, s62\n"                                                         \
+  ".L" #NAME "_claim1:\n"                                                   \
   "s_mov_b64 s[96:97], exec\n"                                                   \
   "s_mov_b64 exec, 1\n"                                                          \
   "ds_add_rtn_u32 v90, v31, v89\n"                                               \
@@ -531,12 +571,16 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "v_readlane_b32 s58, v90, 0\n"                                                 \
   "s_cmp_ge_u32 s58, s40\n"                                                      \
   "s_cbranch_scc1 .L" #NAME "_inv1\n"                                        \
+  "s_add_u32 s58, s58, s98\n"                                                    \
+  "s_sub_u32 s62, s58, s40\n"                                                    \
+  "s_cmp_ge_u32 s58, s40\n"                                                      \
+  "s_cselect_b32 s58, s62, s58\n"                                                \
   "s_mul_i32 s59, s58, s41\n"                                                    \
   "s_bitcmp1_b32 s58, 0\n"                                                       \
   "s_cselect_b32 s62, s43, s42\n"                                                \
   "s_add_u32 s59, s59, s62\n"                                                    \
   "s_cmp_ge_u32 s59, s44\n"                                                      \
-  "s_cbranch_scc1 .L" #NAME "_inv1\n"                                        \
+  "s_cbranch_scc1 .L" #NAME "_claim1\n"                                      \
   "s_lshl_b32 s62, s59, 2\n"                                                     \
   "v_mov_b32_e32 v90, s62\n"                                                     \
   "global_load_dword v92, v90, s[46:47] sc1\n"                                   \
@@ -658,7 +702,7 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "s_add_u32 s56, s98, s91\n"                                                         \
   "s_addc_u32 s57, s99, 0\n"
 extern "C" __global__ void __launch_bounds__(64) sr_jit_loop_holder() {
-  asm volatile("s_endpgm\n" SR_JIT_LOOP_TEXT(sr_jit_loop, "") SR_JIT_LOOP_TEXT(sr_jit_loop_m, SR_JIT_LOOP_PROG)
+  asm volatile("s_endpgm\n" SR_JIT_LOOP_TEXT(sr_jit_loop, "", "s45") SR_JIT_LOOP_TEXT(sr_jit_loop_m, SR_JIT_LOOP_PROG, "s45")
                    SR_JIT_LOOP_PF_TEXT(sr_jit_loop_p));
 }
 
@@ -744,6 +788,7 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
   const uint64_t gcb = sgpr64(ja.gcols ? reinterpret_cast<uint64_t>(ja.gcols + row0) : 0ull);
   const uint32_t gstride = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a.n_pad * 4));
   uint32_t redos = 0;
+  const uint32_t rot = rot_of(ja, rg);  // s45 (sr_jit_loop, sr_jit_loop_m) / s98 (sr_jit_loop_p)
   if constexpr (MEMC) {
     const uint64_t progp = reinterpret_cast<uint64_t>(a.prog), lop = reinterpret_cast<uint64_t>(a.list_off);
     asm volatile(
@@ -755,7 +800,8 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
         : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
           "{s68}"(woff), "{s79}"(fastok), "{s40}"(tpb), "{s41}"(ntg), "{s42}"(gg), "{s43}"(g1), "{s44}"(nlist),
           "{s[46:47]}"(failp), "{s[48:49]}"(codep), "{s[50:51]}"(dstp), "{s52}"(plds), "{s53}"(spart),
-          "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[98:99]}"(progp), "{s[100:101]}"(lop)
+          "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[98:99]}"(progp), "{s[100:101]}"(lop),
+          "{s45}"(rot)
         : SR_JIT_CLOBBERS_MEMC, "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s69", "s91", "s94",
           "s95", "s96", "s97", "v40", "v41", "v42", "v89", "v90", "v91", "memory");
   } else if constexpr (PF) {
@@ -769,7 +815,8 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
         : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
           "{s68}"(woff), "{s45}"(fastflags), "{s40}"(tpb), "{s41}"(ntg), "{s42}"(gg), "{s43}"(g1), "{s44}"(nlist),
           "{s[46:47]}"(failp), "{s[48:49]}"(codep), "{s[50:51]}"(dstp), "{s52}"(plds), "{s53}"(spart),
-          "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[36:37]}"(gcb), "{s38}"(gstride)
+          "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[36:37]}"(gcb), "{s38}"(gstride),
+          "{s98}"(rot)
         : SR_JIT_CLOBBERS, "s23", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s69", "s79", "s91", "s94", "s95",
           "s96", "s97", "v40", "v41", "v42", "v89", "v90", "v91", "v92", "memory");
   } else {
@@ -782,7 +829,8 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
         : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
           "{s68}"(woff), "{s79}"(fastok), "{s40}"(tpb), "{s41}"(ntg), "{s42}"(gg), "{s43}"(g1), "{s44}"(nlist),
           "{s[46:47]}"(failp), "{s[48:49]}"(codep), "{s[50:51]}"(dstp), "{s52}"(plds), "{s53}"(spart),
-          "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[36:37]}"(gcb), "{s38}"(gstride)
+          "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[36:37]}"(gcb), "{s38}"(gstride),
+          "{s45}"(rot)
         : SR_JIT_CLOBBERS, "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s69", "s91", "s94", "s95", "s96", "s97",
           "v40", "v41", "v42", "v89", "v90", "v91", "memory");
   }
