@@ -204,6 +204,53 @@ int32_t srhip_loss_expr_destroy(int32_t loss_kind);
 int32_t srhip_loss_expr_eval(int32_t loss_kind, int32_t dtype, const void* yhat, const void* y,
                              const void* w, int64_t n, void* out);
 
+/* ---- expression operators: a custom operator as an engine tree ---------------
+ * The reference accepts any Julia function in binary_operators /
+ * unary_operators (test/test_custom_operators.jl: op2(x, y) = x^2 + 1/(y^2 + 0.1),
+ * op3(x) = sin(x) + cos(x)). An expression operator is such a function written
+ * as a postfix tree in this header's node format over the operators above,
+ * whose feature leaves are 0: the first argument, 1: the second. It is
+ * registered once (process-wide, immutable, one handle for both element types);
+ * the handle — an operator id >= SRHIP_EXPR_OP_BEGIN — goes in srhip_trees.arg
+ * of a SRHIP_NODE_UNARY / SRHIP_NODE_BINARY node wherever an operator id goes,
+ * and srhip_op_eval accepts it (the host statement of the semantics). These are
+ * the reference's semantics for an opaque function:
+ *   1. the value is the body evaluated in T with the operators' semantics above
+ *      (safe operators give NaN), body constants rounded to T once;
+ *   2. the arguments are checked: a non-finite argument value fails the tree, as
+ *      the reference checks every child array;
+ *   3. nothing inside the body is checked: inv(exp(x)) where exp overflows gives
+ *      0 and the tree succeeds (the same tree written with primitives fails);
+ *   4. a non-finite result fails the tree as any operator's does;
+ *   5. the node counts as one node (srhip_program_info);
+ *   6. in the static rules of the enclosing tree it is an ordinary operator of
+ *      its arity: a feature-free subtree holding it is folded, the result
+ *      checked once at the operator's output; the rules for non-finite constant
+ *      leaves apply to its arguments.
+ * Body constants are fixed: they are no constants of the tree (no entry in
+ * consts, no gradient). Limits: at most 64 nodes; at most 4 values live on the
+ * postfix stack; finite constants; feature index below the arity; primitives
+ * only (no expression operator inside a body). A malformed stream, a non-finite
+ * constant or a feature index beyond the arity is SRHIP_ERR_INVALID; a well-formed
+ * stream beyond the node or stack limits or with an operator id beyond the tables
+ * is SRHIP_ERR_UNSUPPORTED. In a tree, an operator id that was never handed out
+ * is SRHIP_ERR_UNSUPPORTED, a destroyed handle SRHIP_ERR_INVALID, a handle of
+ * the wrong arity for its node kind SRHIP_ERR_INVALID, and a tree whose expansion
+ * needs more than 16 stack slots SRHIP_ERR_UNSUPPORTED. Feature indices of such
+ * a tree stay below 32768. A program holds the definitions it uses: destroying a
+ * handle does not disturb programs that exist. Deviation from the reference, as
+ * for expression losses: a Float64 literal in a Julia body promotes a Float32
+ * argument to Float64, the engine stays in T. Trees whose program holds such an
+ * operator always run in the 16-slot interpreter kernels (no tree code: the
+ * srhip_jit_compile* hooks leave them out); the other trees of the program keep
+ * their kernels. */
+#define SRHIP_EXPR_OP_BEGIN 1024 /* operator ids from here on are handles of expression operators */
+/* arity 1 or 2; consts[nconsts]: the constant leaves in stream order. */
+int32_t srhip_op_expr_create(int32_t arity, const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
+                             const double* consts, int32_t nconsts, int32_t* out_op_id);
+/* Handles are not reused. */
+int32_t srhip_op_expr_destroy(int32_t op_id);
+
 typedef struct srhip_ctx srhip_ctx;
 typedef struct srhip_dataset srhip_dataset;
 typedef struct srhip_program srhip_program;

@@ -299,6 +299,11 @@ struct srhip_program {
   std::vector<unsigned char> h_cprev, h_gcprev;
   int64_t n_inplace = 0, n_rebuild = 0;
   int opset = OPSET_FULL;      // smallest operator set covering the compiled programs
+  // expression operators (srhip.h): the definitions this program's trees use, held
+  // so that a destroyed handle does not disturb it; whether the deep list of
+  // the loss / gradient programs holds their code (it then runs OPSET_EXPR)
+  std::vector<std::shared_ptr<const ExprOp>> xops;
+  bool has_expr = false, g_has_expr = false;
   // gradient programs (compiled on first use)
   bool grad_built = false;
   bool grad_stale = false;  // constants changed since the gradient programs were patched
@@ -858,9 +863,11 @@ void build_grad_program(srhip_program* p) {
   CompiledBatch<T> cb = compile_batch_par<T>(tr, /*grad=*/true, p->jit_memc);
   if (p->ntrees >= (1 << 24)) throw Error(SRHIP_ERR_UNSUPPORTED, "too many trees for gradient work items");
   p->g_static_fail = cb.static_fail;
+  p->g_has_expr = std::find(cb.expr.begin(), cb.expr.end(), (uint8_t)1) != cb.expr.end();
   p->g_opset = OPSET_BASIC;
   for (const Ins<T>& ins : cb.code) {
     const int opc = (int)(ins.code & 0xffu);
+    if (opc >= kNumOpcodes) continue;  // an expression operator's micro-instruction (deep list only)
     if (opc >= OP_BIN0 ? !opset_has_bop(OPSET_BASIC, (opc - OP_BIN0) % SRHIP_NUM_BOPS)
                        : opc >= OP_UN0 && !opset_has_uop(OPSET_BASIC, opc - OP_UN0))
       p->g_opset = OPSET_FULL;
@@ -882,7 +889,7 @@ void build_grad_program(srhip_program* p) {
   if constexpr (std::is_same<T, float>::value) {
     std::vector<int32_t> cand;
     for (int t = 0; t < p->ntrees; ++t)
-      if (cb.tree_off[t] >= 0) cand.push_back(t);
+      if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
     if (p->gjit_allowed && gjit_wanted((int)cand.size())) {
       std::stable_sort(cand.begin(), cand.end(), [&](int32_t x, int32_t y) {
         return cb.cost[x] != cb.cost[y] ? cb.cost[x] > cb.cost[y] : x < y;
@@ -905,7 +912,7 @@ void build_grad_program(srhip_program* p) {
   } else {  // Float64: the gradient tree code of jit64.cpp (L2)
     std::vector<int32_t> cand;
     for (int t = 0; t < p->ntrees; ++t)
-      if (cb.tree_off[t] >= 0) cand.push_back(t);
+      if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
     if (p->gjit_allowed && gjit_wanted((int)cand.size()) && jit::available64()) {
       std::stable_sort(cand.begin(), cand.end(), [&](int32_t x, int32_t y) {
         return cb.cost[x] != cb.cost[y] ? cb.cost[x] > cb.cost[y] : x < y;
@@ -939,7 +946,7 @@ void build_grad_program(srhip_program* p) {
       const int ngroups = std::max(1, (nc + kGradG - 1) / kGradG);
       for (int gi = 0; gi < ngroups; ++gi) {
         const int ntan = std::min(kGradG, nc - gi * kGradG);
-        const int k = cb.need[t] > 4 ? 3 : ntan <= 1 ? 0 : ntan <= 2 ? 1 : 2;
+        const int k = (cb.need[t] > 4 || cb.expr[t]) ? 3 : ntan <= 1 ? 0 : ntan <= 2 ? 1 : 2;
         cls[k].push_back({cb.cost[t], (int32_t)(t | (gi << 24))});
       }
     }
@@ -1098,6 +1105,7 @@ void build_program(srhip_program* p) {
   p->opset = OPSET_BASIC;
   for (const Ins<T>& ins : cb.code) {
     const int opc = (int)(ins.code & 0xffu);
+    if (opc >= kNumOpcodes) continue;  // an expression operator's micro-instruction (deep list only)
     if (opc >= OP_BIN0 ? !opset_has_bop(OPSET_BASIC, (opc - OP_BIN0) % SRHIP_NUM_BOPS)
                        : opc >= OP_UN0 && !opset_has_uop(OPSET_BASIC, opc - OP_UN0))
       p->opset = OPSET_FULL;
@@ -1106,8 +1114,10 @@ void build_program(srhip_program* p) {
   std::vector<int32_t> a, b;
   for (int t = 0; t < p->ntrees; ++t) {
     if (cb.tree_off[t] < 0) continue;
-    (cb.need[t] <= kShallowSlots && cb.len[t] <= kVProgMax ? a : b).push_back(t);
+    // (a tree with expression-operator code: the deep list whatever its need)
+    (cb.need[t] <= kShallowSlots && cb.len[t] <= kVProgMax && !cb.expr[t] ? a : b).push_back(t);
   }
+  p->has_expr = std::find(cb.expr.begin(), cb.expr.end(), (uint8_t)1) != cb.expr.end();
   auto by_cost = [&](int32_t x, int32_t y) {
     return cb.cost[x] != cb.cost[y] ? cb.cost[x] > cb.cost[y] : x < y;
   };
@@ -1845,7 +1855,8 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
         throw Error(SRHIP_ERR_UNSUPPORTED, "row tile of " + std::to_string(nfeat) + " features does not fit in LDS");
       plan.threads = 64 * jw;
       tail_split(c, &plan, rows, jw);
-    } else if (!plan_eval(p->dtype, pass == 1, p->opset, mode, w != nullptr, nfeat, rows, nlist, &plan)) {
+    } else if (!plan_eval(p->dtype, pass == 1, (pass == 1 && p->has_expr) ? (int)OPSET_EXPR : p->opset, mode,
+                          w != nullptr, nfeat, rows, nlist, &plan)) {
       throw Error(SRHIP_ERR_UNSUPPORTED, "row tile of " + std::to_string(nfeat) + " features does not fit in LDS");
     }
     if (seg > 0) {
@@ -2402,7 +2413,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     a.lparam = lparam;
     if (mode == GRAD_LOSS && loss >= SRHIP_EXPR_LOSS_BEGIN) a.lprog = expr_loss_device<T>(c, loss);
     a.G = G;
-    a.opset = deep ? OPSET_FULL : p->g_opset;
+    a.opset = deep ? (p->g_has_expr ? (int)OPSET_EXPR : (int)OPSET_FULL) : p->g_opset;
     c->partial.ensure((size_t)plan.nrg * plan.ntg * plan.tpb * (2 + G) * sizeof(T));
     a.partial = static_cast<T*>(c->partial.p);
     a.out_value = out_value;
@@ -2709,6 +2720,12 @@ int32_t srhip_op_eval(int32_t dtype, int32_t arity, int32_t id, double a, double
   return guarded([&] {
     if (!out) throw Error(SRHIP_ERR_INVALID, "null out");
     if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
+    if (id >= SRHIP_EXPR_OP_BEGIN) {  // an expression operator: its body with the same routines
+      const std::shared_ptr<const ExprOp> e = expr_op_find(id, /*live=*/true);
+      if (e->arity != arity) throw Error(SRHIP_ERR_INVALID, "the expression operator has another arity");
+      *out = dtype == SRHIP_F32 ? (double)expr_op_eval<float>(*e, (float)a, (float)b) : expr_op_eval<double>(*e, a, b);
+      return SRHIP_OK;
+    }
     bool known = false;
     for (const auto& o : kOpNames) known = known || (o.arity == arity && o.id == id);
     if (!known) throw Error(SRHIP_ERR_UNSUPPORTED, "unknown operator id for this arity");
@@ -2718,6 +2735,22 @@ int32_t srhip_op_eval(int32_t dtype, int32_t arity, int32_t id, double a, double
     } else {
       *out = arity == 1 ? host::unop<double>(id, a) : host::binop<double>(id, a, b);
     }
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_op_expr_create(int32_t arity, const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
+                             const double* consts, int32_t nconsts, int32_t* out_op_id) {
+  return guarded([&] {
+    if (!out_op_id) throw Error(SRHIP_ERR_INVALID, "null out_op_id");
+    *out_op_id = expr_op_create(arity, kind, arg, nnodes, consts, nconsts);
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_op_expr_destroy(int32_t op_id) {
+  return guarded([&] {
+    expr_op_destroy(op_id);
     return SRHIP_OK;
   });
 }
@@ -2928,6 +2961,7 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
         const size_t cb = (size_t)nc * dtype_size(dtype);
         p->consts.resize(std::max<size_t>(cb, 1));
         if (cb) std::memcpy(p->consts.data(), trees->consts, cb);
+        p->xops = expr_ops_of(*trees);
       } else {
         p->node_off.assign(1, 0);
         p->const_off.assign(1, 0);
@@ -3264,6 +3298,8 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
     std::string text;
     std::vector<int32_t> offs;
     if (loss >= SRHIP_EXPR_LOSS_BEGIN) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for expression losses");
+    // expression operators: live handles only, and their trees have no tree code
+    const std::vector<std::shared_ptr<const ExprOp>> xops = expr_ops_of(*trees);
     if (loss < 0 || loss >= SRHIP_NUM_LOSSES) throw Error(SRHIP_ERR_INVALID, "unknown loss");
     uint64_t lbits;
     std::memcpy(&lbits, &lparam, 8);
@@ -3278,13 +3314,13 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
       CompiledBatch<double> cb = compile_batch<double>(*trees, /*grad=*/true);
       std::vector<int32_t> cand, coff(trees->const_off, trees->const_off + trees->ntrees + 1);
       for (int t = 0; t < cb.ntrees; ++t)
-        if (cb.tree_off[t] >= 0) cand.push_back(t);
+        if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
       jit::compile_grad_only64(cb, coff, cand, &bytes, &text, &offs, loss, lbits);
     } else if (mode == 5) {  // Float64 tree code (jit64.cpp): L2, another loss's tail, or per-row outputs
       CompiledBatch<double> cb = compile_batch<double>(*trees);
       std::vector<int32_t> cand;
       for (int t = 0; t < cb.ntrees; ++t)
-        if (cb.tree_off[t] >= 0 && cb.need[t] <= kShallowSlots) cand.push_back(t);
+        if (cb.tree_off[t] >= 0 && cb.need[t] <= kShallowSlots && !cb.expr[t]) cand.push_back(t);
       jit::Opts64 o;
       o.out = out_mode;
       o.loss = out_mode ? SRHIP_LOSS_L2 : loss;
@@ -3294,13 +3330,13 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
       CompiledBatch<float> cb = compile_batch<float>(*trees, /*grad=*/true);
       std::vector<int32_t> cand, coff(trees->const_off, trees->const_off + trees->ntrees + 1);
       for (int t = 0; t < cb.ntrees; ++t)
-        if (cb.tree_off[t] >= 0) cand.push_back(t);
+        if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
       jit::compile_grad_only(cb, coff, cand, &bytes, &text, &offs, nullptr, loss, lbits);
     } else {
       CompiledBatch<float> cb = compile_batch<float>(*trees);
       std::vector<int32_t> cand;
       for (int t = 0; t < cb.ntrees; ++t)
-        if (cb.tree_off[t] >= 0 && cb.need[t] <= kShallowSlots) cand.push_back(t);
+        if (cb.tree_off[t] >= 0 && cb.need[t] <= kShallowSlots && !cb.expr[t]) cand.push_back(t);
       jit::Options jo;
       jo.fast = mode == 1 || mode == 4;
       jo.memc = mode == 3 || mode == 4;
@@ -3412,6 +3448,7 @@ int32_t srhip_debug_constant_map(const srhip_trees* trees, int32_t dtype, int32_
     *out_recompiled = 0;
     *out_relayout = 0;
     const bool g = (grad & 1) != 0, keep = (grad & 2) != 0;
+    const std::vector<std::shared_ptr<const ExprOp>> xops = expr_ops_of(*trees);  // live handles, held for the call
     if (dtype == SRHIP_F32) constant_map_check<float>(trees, g, keep, new_consts, out_mismatch, out_recompiled, out_relayout);
     else if (dtype == SRHIP_F64) constant_map_check<double>(trees, g, keep, new_consts, out_mismatch, out_recompiled, out_relayout);
     else throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");

@@ -1,6 +1,7 @@
 // compile.h — host compiler from postfix node streams (include/srhip.h) to
 // the device accumulator-machine programs of srhip_internal.h.
 #pragma once
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -13,6 +14,37 @@ struct Error : std::runtime_error {
   int code;
   Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
+
+// ---- expression operators (srhip.h "expression operators") -------------------------
+// A registered operator body: its postfix stream parsed into nodes (children by
+// index, the root last) with the stack slots each subtree's temporaries need.
+// Entries are immutable. The registry is process-wide and hands out operator ids
+// from SRHIP_EXPR_OP_BEGIN on, never twice; a destroyed entry lives on for as
+// long as a program holds it.
+struct ExprOp {
+  struct N {
+    int deg;     // 0, 1, 2
+    int op;      // operator id (deg >= 1)
+    int feat;    // argument index (deg 0; -1: a constant)
+    double val;  // constant value (deg 0, feat < 0)
+    int l, r;
+    int need;    // slots of the subtree's own temporaries
+  };
+  int arity = 1;
+  std::vector<N> nd;
+  int cost = 0;  // VALU cost estimate per row
+};
+int32_t expr_op_create(int32_t arity, const uint8_t* kind, const uint16_t* arg, int32_t nnodes, const double* consts,
+                       int32_t nconsts);
+void expr_op_destroy(int32_t id);
+// live = true: a registered, not destroyed handle (what a new program may use);
+// false: also a destroyed one that a program still holds. Throws INVALID.
+std::shared_ptr<const ExprOp> expr_op_find(int32_t id, bool live);
+// The registered operators of `trees`, each checked to be live and of its node's arity.
+std::vector<std::shared_ptr<const ExprOp>> expr_ops_of(const srhip_trees& trees);
+// f(a, b) on the host in T: the body with host_ops.h, its constants rounded to T
+template <typename T>
+T expr_op_eval(const ExprOp& e, T a, T b);
 
 // a folded feature-free subtree (CompiledBatch::folds)
 // operand stack of eval_fold: a deeper fold is recompiled instead
@@ -34,6 +66,7 @@ struct CompiledBatch {
   std::vector<int32_t> need;         // stack slots used
   std::vector<int32_t> len;          // program length in instructions (END included)
   std::vector<int32_t> cost;         // VALU cost estimate per row
+  std::vector<uint8_t> expr;         // the program holds expression-operator code: the deep OPSET_EXPR pass only
   int max_feature = -1;              // largest feature index referenced
   int64_t total_nodes = 0;
   // constant map (srhip_program_set_constants without a recompile): per

@@ -10,7 +10,12 @@ bool ti_compiled() { return SR_TI != 0; }
 
 template <>
 hipError_t launch_eval<float>(const EvalPlan& plan, const EvalArgs<float>& a, int mode, hipStream_t stream) {
-  if (plan.D == kMaxSlots) return launch_rd<float, 4, kMaxSlots, OPSET_FULL>(plan, a, mode, stream);
+  if (plan.D == kMaxSlots) {
+    // deep trees; a list that holds expression operators runs the variant that
+    // dispatches their micro-instructions
+    if (plan.opset == OPSET_EXPR) return launch_rd<float, 4, kMaxSlots, OPSET_EXPR>(plan, a, mode, stream);
+    return launch_rd<float, 4, kMaxSlots, OPSET_FULL>(plan, a, mode, stream);
+  }
   if (plan.opset == OPSET_BASIC) return launch_rd<float, SR_R32, kShallowSlots, OPSET_BASIC>(plan, a, mode, stream);
   return launch_rd<float, SR_R32, kShallowSlots, OPSET_FULL>(plan, a, mode, stream);
 }

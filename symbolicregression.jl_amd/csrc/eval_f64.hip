@@ -7,7 +7,12 @@ namespace srhip {
 
 template <>
 hipError_t launch_eval<double>(const EvalPlan& plan, const EvalArgs<double>& a, int mode, hipStream_t stream) {
-  if (plan.D == kMaxSlots) return launch_rd<double, 2, kMaxSlots, OPSET_FULL>(plan, a, mode, stream);
+  if (plan.D == kMaxSlots) {
+    // deep trees; a list that holds expression operators runs the variant that
+    // dispatches their micro-instructions
+    if (plan.opset == OPSET_EXPR) return launch_rd<double, 2, kMaxSlots, OPSET_EXPR>(plan, a, mode, stream);
+    return launch_rd<double, 2, kMaxSlots, OPSET_FULL>(plan, a, mode, stream);
+  }
   if (plan.opset == OPSET_BASIC) return launch_rd<double, 4, kShallowSlots, OPSET_BASIC>(plan, a, mode, stream);
   return launch_rd<double, 4, kShallowSlots, OPSET_FULL>(plan, a, mode, stream);
 }

@@ -413,7 +413,8 @@ hipError_t launch_one(const EvalPlan& plan, const EvalArgs<T>& a, hipStream_t st
 template <typename T, int R, int D, int SET>
 hipError_t launch_rd(const EvalPlan& plan, const EvalArgs<T>& a, int mode, hipStream_t stream) {
   if (mode == MODE_OUT) return launch_one<T, R, D, SET, MODE_OUT, false>(plan, a, stream);
-  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_one<T, R, D, OPSET_FULL, kModeLossExpr, false>(plan, a, stream);
+  constexpr int LSET = SET == OPSET_EXPR ? OPSET_EXPR : OPSET_FULL;  // (expression losses: no basic-set variant)
+  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_one<T, R, D, LSET, kModeLossExpr, false>(plan, a, stream);
   if (a.loss == SRHIP_LOSS_L2) {
     if (a.w) return launch_one<T, R, D, SET, kModeLossL2, true>(plan, a, stream);
     return launch_one<T, R, D, SET, kModeLossL2, false>(plan, a, stream);

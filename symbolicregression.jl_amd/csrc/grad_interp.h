@@ -92,6 +92,10 @@ __device__ __forceinline__ void bin_grad(Dual<T, R, G>& a, const Dual<T, R, G>& 
   case OP_POP0 + K:                                                      \
     if constexpr (K < D) t = slot[K];                                    \
     break;
+#define SRG_LDS(K)                                                       \
+  case OP_LDS0 + K:                                                      \
+    if constexpr (K < D) a = slot[K];                                    \
+    break;
 #define SRG_UN(U) \
   case OP_UN0 + U: if constexpr (opset_has_uop(SET, U)) un_grad<U, T, R, G>(a, chk); break;
 #define SRG_BV(V, B) \
@@ -119,8 +123,31 @@ __device__ __forceinline__ void run_program_grad(CIns<T>* __restrict__ p,
     const Ins<T> nxt = fetch<T>(p + 1);
     const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.code);
     const T imm = uni(cur.imm);
-    const int f = (int)(code >> 16);
-    const int jc = (int)((code >> 8) & 0xffu) - g0;  // tangent seeded by a constant operand
+    int f = (int)(code >> 16);
+    int jc = (int)((code >> 8) & 0xffu) - g0;  // tangent seeded by a constant operand
+    T held = T(0);
+    if constexpr (SET == OPSET_EXPR) {
+      // expression operators: the no-mark flag shares the feature field, a body
+      // constant seeds no tangent, and the body's marks are undone below
+      f &= 0x7fff;
+      if (((code >> 8) & 0xffu) == (uint32_t)kBodyConst) jc = -1;
+      held = chk;
+      const uint32_t opc = code & 0xffu;
+      if (opc >= (uint32_t)OP_LDS0) {
+        if (opc == (uint32_t)OP_MARK) {
+          SR_UNROLL for (int r = 0; r < R; ++r) chk = mark(a.v[r], chk);
+        } else {
+          switch (opc) {
+            SRG_LDS(0) SRG_LDS(1) SRG_LDS(2) SRG_LDS(3) SRG_LDS(4) SRG_LDS(5) SRG_LDS(6) SRG_LDS(7)
+            SRG_LDS(8) SRG_LDS(9) SRG_LDS(10) SRG_LDS(11) SRG_LDS(12) SRG_LDS(13) SRG_LDS(14) SRG_LDS(15)
+            default: break;
+          }
+        }
+        cur = nxt;
+        ++p;
+        continue;
+      }
+    }
     switch (code & 0xffu) {
       case OP_END: return;
       case OP_LDX:
@@ -149,6 +176,9 @@ __device__ __forceinline__ void run_program_grad(CIns<T>* __restrict__ p,
       SRG_BIN(0) SRG_BIN(1) SRG_BIN(2) SRG_BIN(3) SRG_BIN(4) SRG_BIN(5) SRG_BIN(6) SRG_BIN(7)
       SRG_BIN(8) SRG_BIN(9) SRG_BIN(10)
       default: break;
+    }
+    if constexpr (SET == OPSET_EXPR) {
+      if (code & kNoMarkGrad) chk = held;  // nothing inside a body is checked
     }
     cur = nxt;
     ++p;

@@ -200,7 +200,8 @@ hipError_t launch_grad_one(const EvalPlan& plan, const GradArgs<T>& a, hipStream
 template <typename T, int R, int D, int G, int SET>
 hipError_t launch_grad_rd(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
   if (mode == GRAD_OUT) return launch_grad_one<T, R, D, GRAD_OUT, false, G, SET>(plan, a, stream);
-  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_grad_one<T, R, D, kGradLossExpr, false, G, OPSET_FULL>(plan, a, stream);
+  constexpr int LSET = SET == OPSET_EXPR ? OPSET_EXPR : OPSET_FULL;  // (expression losses: no basic-set variant)
+  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_grad_one<T, R, D, kGradLossExpr, false, G, LSET>(plan, a, stream);
   if (a.w) return launch_grad_one<T, R, D, GRAD_LOSS, true, G, SET>(plan, a, stream);
   return launch_grad_one<T, R, D, GRAD_LOSS, false, G, SET>(plan, a, stream);
 }
@@ -219,6 +220,9 @@ hipError_t launch_grad_g(const EvalPlan& plan, const GradArgs<T>& a, int mode, h
     if (a.opset == OPSET_BASIC) return launch_grad_rd<T, RS, 4, G, OPSET_BASIC>(plan, a, mode, stream);
     return launch_grad_rd<T, RS, 4, G, OPSET_FULL>(plan, a, mode, stream);
   }
+  // deep programs; with expression operators among them, the variant that
+  // dispatches their micro-instructions
+  if (a.opset == OPSET_EXPR) return launch_grad_rd<T, 1, kMaxSlots, G, OPSET_EXPR>(plan, a, mode, stream);
   return launch_grad_rd<T, 1, kMaxSlots, G, OPSET_FULL>(plan, a, mode, stream);
 }
 

@@ -246,6 +246,10 @@ __device__ __forceinline__ void bin_apply(T (&acc)[R], const T (&tmp)[R], const 
   case OP_POP0 + K:                                                  \
     if constexpr (K < D) { SR_UNROLL for (int r = 0; r < R; ++r) tmp[r] = slot[K][r]; } \
     break;
+#define SR_LDS(K)                                                    \
+  case OP_LDS0 + K:                                                  \
+    if constexpr (K < D) { SR_UNROLL for (int r = 0; r < R; ++r) acc[r] = slot[K][r]; } \
+    break;
 #define SR_UN(U) \
   case OP_UN0 + U: if constexpr (opset_has_uop(SET, U)) un_apply<U, T, R>(acc, chk); break;
 #define SR_BV(V, B) \
@@ -253,26 +257,55 @@ __device__ __forceinline__ void bin_apply(T (&acc)[R], const T (&tmp)[R], const 
 #define SR_BIN(B) SR_BV(V_AX, B) SR_BV(V_XA, B) SR_BV(V_AC, B) SR_BV(V_CA, B) \
   SR_BV(V_AT, B) SR_BV(V_TA, B) SR_BV(V_XX, B) SR_BV(V_XC, B) SR_BV(V_CX, B)
 
+// the opcode switch's cases of every operator set
+#define SR_CASES                                                                                    \
+    case OP_END: return false;                                                                      \
+    case OP_LDX: SR_UNROLL for (int r = 0; r < R; ++r) acc[r] = x[r]; break;                        \
+    case OP_LDC: SR_UNROLL for (int r = 0; r < R; ++r) acc[r] = imm; break;                         \
+    SR_PUSH(0) SR_PUSH(1) SR_PUSH(2) SR_PUSH(3) SR_PUSH(4) SR_PUSH(5) SR_PUSH(6) SR_PUSH(7)         \
+    SR_PUSH(8) SR_PUSH(9) SR_PUSH(10) SR_PUSH(11) SR_PUSH(12) SR_PUSH(13) SR_PUSH(14) SR_PUSH(15)   \
+    SR_POP(0) SR_POP(1) SR_POP(2) SR_POP(3) SR_POP(4) SR_POP(5) SR_POP(6) SR_POP(7)                 \
+    SR_POP(8) SR_POP(9) SR_POP(10) SR_POP(11) SR_POP(12) SR_POP(13) SR_POP(14) SR_POP(15)           \
+    SR_UN(0) SR_UN(1) SR_UN(2) SR_UN(3) SR_UN(4) SR_UN(5) SR_UN(6) SR_UN(7) SR_UN(8) SR_UN(9)       \
+    SR_UN(10) SR_UN(11) SR_UN(12) SR_UN(13) SR_UN(14) SR_UN(15) SR_UN(16) SR_UN(17) SR_UN(18)       \
+    SR_UN(19) SR_UN(20) SR_UN(21) SR_UN(22) SR_UN(23) SR_UN(24) SR_UN(25) SR_UN(26) SR_UN(27)       \
+    SR_UN(28)                                                                                       \
+    SR_BIN(0) SR_BIN(1) SR_BIN(2) SR_BIN(3) SR_BIN(4) SR_BIN(5) SR_BIN(6) SR_BIN(7) SR_BIN(8)       \
+    SR_BIN(9) SR_BIN(10)
+
+__device__ __forceinline__ float keep_if(uint32_t m, float held, float v) {
+  return __uint_as_float((__float_as_uint(held) & m) | (__float_as_uint(v) & ~m));
+}
+__device__ __forceinline__ double keep_if(uint32_t m, double held, double v) {
+  const uint64_t mm = ((uint64_t)m << 32) | m;
+  return __longlong_as_double((long long)(((uint64_t)__double_as_longlong(held) & mm) |
+                                          ((uint64_t)__double_as_longlong(v) & ~mm)));
+}
+
 // Execute one instruction (wave-uniform `code`, `imm`); returns false at END.
 template <typename T, int R, int D, int SET>
 __device__ __forceinline__ bool exec_ins(uint32_t code, T imm, T (&acc)[R], T (&tmp)[R],
                                          T (&slot)[D][R], const T (&x)[R],
                                          const T* __restrict__ sXt, int rs, int lane, T& chk) {
-  switch (code & 0xffu) {
-    case OP_END: return false;
-    case OP_LDX: SR_UNROLL for (int r = 0; r < R; ++r) acc[r] = x[r]; break;
-    case OP_LDC: SR_UNROLL for (int r = 0; r < R; ++r) acc[r] = imm; break;
-    SR_PUSH(0) SR_PUSH(1) SR_PUSH(2) SR_PUSH(3) SR_PUSH(4) SR_PUSH(5) SR_PUSH(6) SR_PUSH(7)
-    SR_PUSH(8) SR_PUSH(9) SR_PUSH(10) SR_PUSH(11) SR_PUSH(12) SR_PUSH(13) SR_PUSH(14) SR_PUSH(15)
-    SR_POP(0) SR_POP(1) SR_POP(2) SR_POP(3) SR_POP(4) SR_POP(5) SR_POP(6) SR_POP(7)
-    SR_POP(8) SR_POP(9) SR_POP(10) SR_POP(11) SR_POP(12) SR_POP(13) SR_POP(14) SR_POP(15)
-    SR_UN(0) SR_UN(1) SR_UN(2) SR_UN(3) SR_UN(4) SR_UN(5) SR_UN(6) SR_UN(7) SR_UN(8) SR_UN(9)
-    SR_UN(10) SR_UN(11) SR_UN(12) SR_UN(13) SR_UN(14) SR_UN(15) SR_UN(16) SR_UN(17) SR_UN(18)
-    SR_UN(19) SR_UN(20) SR_UN(21) SR_UN(22) SR_UN(23) SR_UN(24) SR_UN(25) SR_UN(26) SR_UN(27)
-    SR_UN(28)
-    SR_BIN(0) SR_BIN(1) SR_BIN(2) SR_BIN(3) SR_BIN(4) SR_BIN(5) SR_BIN(6) SR_BIN(7) SR_BIN(8)
-    SR_BIN(9) SR_BIN(10)
-    default: break;
+  if constexpr (SET == OPSET_EXPR) {
+    // Expression operators: their micro-instructions among the cases, and the
+    // no-mark flag of body instructions: after a flagged instruction the marker
+    // gets back the value it had (nothing inside a body is checked). The
+    // restore is a bit select under a wave-uniform mask, not a branch.
+    const T held = chk;
+    switch (code & 0xffu) {
+      SR_CASES
+      SR_LDS(0) SR_LDS(1) SR_LDS(2) SR_LDS(3) SR_LDS(4) SR_LDS(5) SR_LDS(6) SR_LDS(7)
+      SR_LDS(8) SR_LDS(9) SR_LDS(10) SR_LDS(11) SR_LDS(12) SR_LDS(13) SR_LDS(14) SR_LDS(15)
+      case OP_MARK: SR_UNROLL for (int r = 0; r < R; ++r) chk = mark(acc[r], chk); break;
+      default: break;
+    }
+    chk = keep_if((code & kNoMark) ? 0xffffffffu : 0u, held, chk);
+  } else {
+    switch (code & 0xffu) {
+      SR_CASES
+      default: break;
+    }
   }
   return true;
 }

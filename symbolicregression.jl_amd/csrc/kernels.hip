@@ -300,7 +300,9 @@ bool plan_eval(int dtype, bool deep, int opset, int mode, bool weighted, int nfe
   const int R = variant_R(dtype, deep);
   const bool ok = plan_geometry(esz, R, deep ? kMaxSlots : kShallowSlots, narr,
                                 2 * esz, n, nlist, p);
-  p->opset = deep ? OPSET_FULL : opset;  // the deep variant is built for the full set only
+  // the deep variant is built for the full set, and for the full set with
+  // expression operators
+  p->opset = deep ? (opset == OPSET_EXPR ? OPSET_EXPR : OPSET_FULL) : opset;
   return ok;
 }
 

@@ -51,12 +51,30 @@ constexpr int bin_opcode(int variant, int bop) {
   return OP_BIN0 + variant * SRHIP_NUM_BOPS + bop;
 }
 
+// Micro-instructions of expression operators (srhip.h "expression operators"),
+// dispatched by the OPSET_EXPR kernel variants only: the body of such an
+// operator is expanded in line, its computed arguments held in reserved slots.
+enum : int {
+  OP_LDS0 = kNumOpcodes,           // acc = slot[k] (an argument read by the body)
+  OP_MARK = OP_LDS0 + kMaxSlots,   // chk = mark(acc): a computed argument is checked
+  kNumOpcodesExpr = OP_MARK + 1,
+};
+static_assert(kNumOpcodesExpr <= 256, "opcode must fit in 8 bits");
+
 // code word: [7:0] opcode, [15:8] slot index, [31:16] feature index.
 // Evaluation programs set bit 15 (kNeedX) on instructions with an X[f]
 // operand (LDX and the AX/XA/XX/XC/CX variants): the kernel reads X[f] from
 // LDS ahead of the dispatch. Gradient programs use all 8 slot bits for
 // constant indices and never set it.
 constexpr uint32_t kNeedX = 1u << 15;
+// Body instructions of an expression operator carry a no-mark flag: the marks
+// of their lossy operands go to a throw-away marker (nothing inside a body is
+// checked). Evaluation programs: bit 14 (slot indices stay below 16).
+// Gradient programs: bit 31 (their feature index stays below 2^15), and a body
+// constant carries kBodyConst in the slot field: the index of no tangent.
+constexpr uint32_t kNoMark = 1u << 14;
+constexpr uint32_t kNoMarkGrad = 1u << 31;
+constexpr int kBodyConst = 255;
 constexpr uint32_t make_code(int opc, int slot, int feat) {
   return (uint32_t)opc | ((uint32_t)slot << 8) | ((uint32_t)feat << 16);
 }
@@ -108,14 +126,16 @@ constexpr bool uop_lossy(int op) {
 // A kernel variant compiled only with the dispatch cases of a small operator
 // set has a shallower dispatch branch tree. The host picks the smallest set
 // that contains every operator of the batch.
-enum OpSet : int { OPSET_BASIC = 0, OPSET_FULL = 1 };
+// OPSET_EXPR: the full set plus the expression operators' micro-instructions
+// and no-mark flag; deep kernel variants only.
+enum OpSet : int { OPSET_BASIC = 0, OPSET_FULL = 1, OPSET_EXPR = 2 };
 constexpr uint32_t kBasicBops = (1u << SRHIP_BOP_ADD) | (1u << SRHIP_BOP_SUB) | (1u << SRHIP_BOP_MUL) |
                                 (1u << SRHIP_BOP_DIV);
 constexpr uint32_t kBasicUops = (1u << SRHIP_UOP_NEG) | (1u << SRHIP_UOP_SQUARE) | (1u << SRHIP_UOP_CUBE) |
                                 (1u << SRHIP_UOP_EXP) | (1u << SRHIP_UOP_ABS) | (1u << SRHIP_UOP_LOG) |
                                 (1u << SRHIP_UOP_SQRT) | (1u << SRHIP_UOP_SIN) | (1u << SRHIP_UOP_COS);
-constexpr bool opset_has_bop(int set, int op) { return set == OPSET_FULL || ((kBasicBops >> op) & 1u); }
-constexpr bool opset_has_uop(int set, int op) { return set == OPSET_FULL || ((kBasicUops >> op) & 1u); }
+constexpr bool opset_has_bop(int set, int op) { return set != OPSET_BASIC || ((kBasicBops >> op) & 1u); }
+constexpr bool opset_has_uop(int set, int op) { return set != OPSET_BASIC || ((kBasicUops >> op) & 1u); }
 
 // Stack slots of the ordinary kernel variant; trees needing more (rare:
 // < 0.01 % of random trees at maxsize 30) run in the 16-slot variant.
@@ -162,6 +182,10 @@ constexpr uint32_t make_loss_code(int opc, int leaf) { return (uint32_t)opc | ((
 // instructions of the longest program: one per node, a PUSH and a POP per binary
 // node with two computed operands, END
 constexpr int kLossMaxIns = kLossMaxNodes + 2 * (kLossMaxNodes / 2) + 1;
+
+// ---- expression operators (srhip_op_expr_create) ----------------------------------
+constexpr int kExprOpMaxNodes = 64;
+constexpr int kExprOpMaxDepth = 4;
 
 // The name of the main (evaluation) kernel the calling thread launched last:
 // set at each launch site, read by srhip_last_kernel_name (bench.py ties a

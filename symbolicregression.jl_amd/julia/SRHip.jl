@@ -122,7 +122,23 @@ function device_available()
 end
 
 # ---- operator ids (srhip_op_lookup applies binopmap/unaopmap names) ------------
+# Expression operators (srhip.h "expression operators"): Julia functions that
+# register_operator! gave a body tree; flatten maps them to their handles.
+const SRHIP_EXPR_OP_BEGIN = Int32(1024)  # operator ids from here on are handles of expression operators
+mutable struct ExprOpHandle
+    id::Int32
+    arity::Int
+end
+const EXPR_OPS = IdDict{Any,ExprOpHandle}()
+
 function op_id(op, arity)
+    h = lock(CTX_LOCK) do
+        get(EXPR_OPS, op, nothing)
+    end
+    if h !== nothing
+        h.arity == arity || throw(Unsupported("operator $(op) has arity $(h.arity)"))
+        return UInt16(h.id)
+    end
     a = Ref{Int32}(0); i = Ref{Int32}(0)
     check(ccall((:srhip_op_lookup, libsrhip), Int32, (Cstring, Ptr{Int32}, Ptr{Int32}),
                 string(nameof(op)), a, i))
@@ -134,6 +150,52 @@ operator_ids(options::Options) = lock(CTX_LOCK) do
     get!(OPS_CACHE, options) do
         ([op_id(op, 2) for op in options.operators.binops], [op_id(op, 1) for op in options.operators.unaops])
     end
+end
+
+"""
+    register_operator!(f, tree::Node{T}, operators; arity)
+
+Give the custom operator `f` (a Julia function in `binary_operators` /
+`unary_operators`) its definition as a tree over x1 = the first argument and
+x2 = the second, built with `operators` (an `OperatorEnum` of engine
+primitives). The engine registers the body once; `flatten` then maps `f` to the
+handle (>= SRHIP_EXPR_OP_BEGIN) instead of asking `srhip_op_lookup`, so a
+search whose operator list holds `f` runs on the engine. The handle is destroyed
+by the finaliser of the returned object, which the registry keeps alive.
+Nothing inside the body is checked for non-finite values, as for an opaque
+Julia function; `f` itself stays the CPU path's definition.
+"""
+function register_operator!(f, tree::Node{T}, operators; arity::Int) where {T}
+    bin = [op_id(op, 2) for op in operators.binops]
+    una = [op_id(op, 1) for op in operators.unaops]
+    kind = UInt8[]; arg = UInt16[]; consts = Float64[]
+    function visit(t::Node{T})
+        if t.degree == 0
+            if t.constant
+                push!(kind, NODE_CONST); push!(arg, 0); push!(consts, Float64(t.val::T))
+            else
+                push!(kind, NODE_FEATURE); push!(arg, UInt16(t.feature - 1))
+            end
+        elseif t.degree == 1
+            visit(t.l); push!(kind, NODE_UNARY); push!(arg, una[t.op])
+        else
+            visit(t.l); visit(t.r); push!(kind, NODE_BINARY); push!(arg, bin[t.op])
+        end
+    end
+    visit(tree)
+    h = Ref{Int32}(0)
+    check(ccall((:srhip_op_expr_create, libsrhip), Int32,
+                (Int32, Ptr{UInt8}, Ptr{UInt16}, Int32, Ptr{Float64}, Int32, Ptr{Int32}),
+                Int32(arity), kind, arg, Int32(length(kind)), consts, Int32(length(consts)), h))
+    x = ExprOpHandle(h[], arity)
+    finalizer(x) do y
+        ccall((:srhip_op_expr_destroy, libsrhip), Int32, (Int32,), y.id)
+    end
+    lock(CTX_LOCK) do
+        EXPR_OPS[f] = x
+        empty!(OPS_CACHE)  # operator ids resolved before the registration are stale
+    end
+    return x
 end
 
 """

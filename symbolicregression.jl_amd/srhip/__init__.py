@@ -16,7 +16,7 @@ from .interface import (compile_trees, compute_complexity, eval_diff_tree_array,
                         update_baseline_loss_)
 from .node import (FlatTrees, Node, count_nodes, flatten, get_constants, has_constants, set_constants,
                    string_tree)
-from .options import (DWDMarginLoss, ExpLoss, ExprLoss, HingeLoss, HuberLoss, L1DistLoss, L1EpsilonInsLoss, L1HingeLoss,
+from .options import (DWDMarginLoss, ExpLoss, ExprLoss, ExprOp, HingeLoss, HuberLoss, L1DistLoss, L1EpsilonInsLoss, L1HingeLoss,
                       L2DistLoss, L2EpsilonInsLoss, L2HingeLoss, L2MarginLoss, LogCoshLoss, LogitDistLoss,
                       LogitMarginLoss, LPDistLoss, ModifiedHuberLoss, Options, PerceptronLoss, PeriodicLoss,
                       QuantileLoss, SigmoidLoss, SmoothedL1HingeLoss, SupervisedLoss, ZeroOneLoss,

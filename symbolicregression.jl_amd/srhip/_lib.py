@@ -75,6 +75,9 @@ SIGNATURES = {
     "srhip_loss_expr_create": [C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_double),
                                C.c_int32, C.POINTER(C.c_int32)],
     "srhip_loss_expr_destroy": [C.c_int32],
+    "srhip_op_expr_create": [C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_double),
+                             C.c_int32, C.POINTER(C.c_int32)],
+    "srhip_op_expr_destroy": [C.c_int32],
     "srhip_loss_expr_eval": [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "srhip_dataset_create": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)],

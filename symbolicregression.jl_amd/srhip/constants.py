@@ -23,6 +23,8 @@ LOSS = {n: i for i, n in enumerate(LOSSES)}
 MARGIN_LOSS_BEGIN = LOSS["ZEROONE"]
 # loss kinds from here on are handles of expression losses (srhip_loss_expr_create)
 EXPR_LOSS_BEGIN = 1024
+# operator ids from here on are handles of expression operators (srhip_op_expr_create)
+EXPR_OP_BEGIN = 1024
 
 # Julia operator names → (arity, id), applying binopmap / unaopmap
 # (src/Options.jl:86-120). Mirrors srhip_op_lookup.

@@ -206,6 +206,74 @@ def _destroy_expr_loss(kind: int) -> None:
         pass
 
 
+# ---- expression operators: a custom operator as an engine tree (srhip.h) ----
+class ExprOp:
+    """A custom unary or binary operator written as a tree: `tree` is a `Node`
+    built under `options`' primitive operators with x1 = the first argument and
+    x2 = the second (the reference takes any Julia function in its operator
+    lists, test/test_custom_operators.jl). It is registered with the engine
+    once; the handle (`.op_id`, >= constants.EXPR_OP_BEGIN) is the operator's
+    engine id, and is destroyed when the object is finalised. Give the object to
+    `Options(binary_operators=[..., op])` / `unary_operators` like a name; the
+    Options keeps it alive. srhip.h lists the semantics (nothing inside the body
+    is checked, the arguments and the result are) and the limits."""
+
+    def __init__(self, name: str, tree, options, arity: int):
+        import ctypes as C
+        import weakref
+
+        import numpy as np
+
+        from ._lib import check, lib
+        from .node import flatten
+
+        if arity not in (1, 2):
+            raise ValueError("arity must be 1 or 2")
+        flat = flatten([tree], options, dtype=np.float64)
+        kind = np.ascontiguousarray(flat.kind, dtype=np.uint8)
+        arg = np.ascontiguousarray(flat.arg, dtype=np.uint16)
+        consts = np.ascontiguousarray(flat.consts, dtype=np.float64)
+        out = C.c_int32(0)
+        check(lib().srhip_op_expr_create(int(arity), kind.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         arg.ctypes.data_as(C.POINTER(C.c_uint16)), int(len(kind)),
+                                         consts.ctypes.data_as(C.POINTER(C.c_double)), int(len(consts)),
+                                         C.byref(out)))
+        self.op_id = int(out.value)
+        self.__name__ = str(name)
+        self.arity = int(arity)
+        self.tree = tree
+        self._finalizer = weakref.finalize(self, _destroy_expr_op, self.op_id)
+
+    def destroy(self):
+        """Destroy the handle now: programs that exist keep working, new ones are refused."""
+        self._finalizer()
+
+    def value(self, a, b=0.0, dtype=None):
+        """f(a, b) on the host with the engine's semantics (srhip_op_eval)."""
+        import ctypes as C
+
+        import numpy as np
+
+        from ._lib import check, lib
+
+        out = C.c_double(0.0)
+        check(lib().srhip_op_eval(K.F64 if dtype in (None, np.float64) else K.F32, self.arity, self.op_id, float(a),
+                                  float(b), C.byref(out)))
+        return out.value
+
+    def __repr__(self):
+        return f"ExprOp({self.__name__!r}, op_id={self.op_id}, arity={self.arity})"
+
+
+def _destroy_expr_op(op_id: int) -> None:
+    from ._lib import lib
+
+    try:
+        lib().srhip_op_expr_destroy(op_id)
+    except Exception:  # interpreter shutdown: the library may be gone
+        pass
+
+
 # Keywords of the reference's Options (src/Options.jl:315-379) that steer only
 # its search control plane (mutation/crossover schedule, constraints, output,
 # recorder, stopping rules): accepted, stored, not used by this engine.
@@ -346,6 +414,8 @@ class Options:
         if kws:
             warnings.warn("Options: keyword(s) " + ", ".join(sorted(kws)) + " only affect the reference's "
                           "search control plane and are ignored here", stacklevel=2)
+        # expression operators by name (the objects are kept alive with the Options)
+        self.expr_operators = {_opname(o): o for o in (*binary_operators, *unary_operators) if isinstance(o, ExprOp)}
         self.binary_operators: Tuple[str, ...] = tuple(_opname(o) for o in binary_operators)
         self.unary_operators: Tuple[str, ...] = tuple(_opname(o) for o in unary_operators)
         if set(self.binary_operators) & set(self.unary_operators):
@@ -447,13 +517,20 @@ class Options:
         for operators outside the engine's table)."""
         if self._ids is None:
             b, u = [], []
+            xo = self.__dict__.get("expr_operators", {})
+
+            def lookup(name):
+                if name in xo:
+                    return xo[name].arity, xo[name].op_id
+                return K.OP_NAMES.get(name, (0, -1))
+
             for name in self.binary_operators:
-                ar, i = K.OP_NAMES.get(name, (0, -1))
+                ar, i = lookup(name)
                 if ar != 2:
                     raise Unsupported(-2, f"binary operator {name!r} is not supported by the engine")
                 b.append(i)
             for name in self.unary_operators:
-                ar, i = K.OP_NAMES.get(name, (0, -1))
+                ar, i = lookup(name)
                 if ar != 1:
                     raise Unsupported(-2, f"unary operator {name!r} is not supported by the engine")
                 u.append(i)
