@@ -28,6 +28,17 @@
  *    Constants are listed separately, in the order of the constant leaves in
  *    that stream, which is DynamicExpressions' get_constants order (leaf
  *    order, left to right; test/test_derivatives.jl:126-150).
+ *  - Feature counts: a feature index must fit srhip_trees.arg, so a dataset
+ *    has at most 65536 features, and 32768 for trees with expression
+ *    operators. The kernels keep a row tile of every feature in LDS; a dataset
+ *    whose tile does not fit (from 79 features for the ordinary interpreter
+ *    kernels, from 159 for every kernel) runs in the wide interpreter
+ *    kernels, which read their feature operands from device memory, with no
+ *    tree code. SRHIP_WIDE (environment, read per call; for tests and
+ *    measurements): 1 runs every interpreter pass in the wide kernels and
+ *    uses no tree code, 0 answers SRHIP_ERR_UNSUPPORTED for such a dataset
+ *    ("row tile of N features does not fit in LDS") as the engine did before
+ *    it had them. srhip_last_kernel_name then holds "wide".
  */
 #ifndef SRHIP_H
 #define SRHIP_H
@@ -491,7 +502,8 @@ int32_t srhip_optimize_constants_cb(const srhip_trees* trees, int32_t dtype, con
 /* ---- tree compiler ---------------------------------------------------------
  * Large programs are compiled to machine code, one block per tree
  * (symbolicregression.jl_amd/csrc/jit.cpp for Float32, jit64.cpp for
- * Float64; SRHIP_JIT=0 turns it off, =1 on for every size). Tree code
+ * Float64; SRHIP_JIT=0 turns it off, =1 on for every size; SRHIP_WIDE and
+ * wide datasets, which run without tree code: the conventions above). Tree code
  * computes exactly what the interpreter computes: eval_loss with L2 and with
  * every elementwise loss (Float32 Periodic: a tile whose |r·2π/c| leaves
  * its routine's Cody-Waite range hands the tree back to the interpreter),

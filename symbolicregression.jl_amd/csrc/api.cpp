@@ -1290,6 +1290,31 @@ static bool ti_enabled() {
   return ti_compiled() && !(e && e[0] == '0');
 }
 
+// Wide datasets: an interpreter pass whose row tile of all
+// nfeat features does not fit in LDS runs the wide kernel variant, which reads
+// its feature operands from global memory. SRHIP_WIDE (read per call): unset:
+// wide only where the LDS plan fails; 1: every interpreter pass wide and no
+// tree code (tests, A/B runs); 0: no wide kernels, UNSUPPORTED as before them.
+static int wide_mode() {
+  const char* e = std::getenv("SRHIP_WIDE");
+  return (!e || !e[0]) ? -1 : (e[0] == '0' ? 0 : 1);
+}
+[[noreturn]] static void throw_lds(int nfeat) {
+  throw Error(SRHIP_ERR_UNSUPPORTED, "row tile of " + std::to_string(nfeat) + " features does not fit in LDS");
+}
+// The plan of an interpreter evaluation pass: the LDS plan where it fits, else the wide one.
+static void plan_interp(int dtype, bool deep, int opset, int mode, bool weighted, int nfeat, int64_t rows, int nlist,
+                        EvalPlan* plan) {
+  const int wm = wide_mode();
+  if (wm != 1 && plan_eval(dtype, deep, opset, mode, weighted, nfeat, rows, nlist, plan)) return;
+  if (wm != 0 && plan_eval_wide(dtype, mode, weighted, rows, nlist, plan)) return;
+  throw_lds(nfeat);
+}
+static const char* interp_name(size_t esz, bool wide) {
+  return wide ? (esz == 4 ? "eval_kernel_wide<float>" : "eval_kernel_wide<double>")
+              : (esz == 4 ? "eval_kernel<float>" : "eval_kernel<double>");
+}
+
 // Row-group rotation of the tree order, off by default (SRHIP_ROT=1 enables
 // it): measured 4.09 -> 4.15 ms on config #2.
 // The interpreter kernels' waves take their trees from an LDS counter
@@ -1343,8 +1368,7 @@ void rerun_bailed(srhip_ctx* c, const srhip_program* p, jit::Module* jm, const E
     HIP_CHECK(hipMemcpyAsync(c->bail_list.p, bl.data(), bl.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(c->bail_fail.p, 0, (size_t)nb * sizeof(uint32_t), s));
     EvalPlan plan;
-    if (!plan_eval(p->dtype, false, OPSET_FULL, MODE_LOSS, ja.w != nullptr, nfeat, rows, nb, &plan))
-      throw Error(SRHIP_ERR_UNSUPPORTED, "row tile does not fit in LDS");
+    plan_interp(p->dtype, false, OPSET_FULL, MODE_LOSS, ja.w != nullptr, nfeat, rows, nb, &plan);
     EvalArgs<T> a = ja;
     a.contig = 0;  // the interpreter kernel deals its slots in snake order
     a.rotate = 0;
@@ -1353,7 +1377,7 @@ void rerun_bailed(srhip_ctx* c, const srhip_program* p, jit::Module* jm, const E
     a.fail = static_cast<uint32_t*>(c->bail_fail.p);
     a.nlist = nb;
     a.ti_rec = nullptr;
-    if (ti_enabled()) {
+    if (ti_enabled() && !plan.wide) {
       c->ti_rec.ensure((size_t)nb * 64 * sizeof(uint4));
       HIP_CHECK(launch_ti_records(reinterpret_cast<const Ins<float>*>(a.prog), a.list_off, nb,
                                   (uint32_t)(plan.ntiles * plan.tile * sizeof(T)), static_cast<uint4*>(c->ti_rec.p), s));
@@ -1368,7 +1392,7 @@ void rerun_bailed(srhip_ctx* c, const srhip_program* p, jit::Module* jm, const E
     c->partial.ensure((size_t)plan.nrg * plan.ntg * plan.tpb * sizeof(Part<T>));
     a.partial = static_cast<Part<T>*>(c->partial.p);
     const int tk = timed_begin(c, s);
-    note_kernel(sizeof(T) == 4 ? "eval_kernel<float>" : "eval_kernel<double>");
+    note_kernel(interp_name(sizeof(T), plan.wide));
     HIP_CHECK(launch_eval<T>(plan, a, MODE_LOSS, s));
     timed_end(c, s, tk);
     HIP_CHECK(launch_finalize<T>(a, c->res_sum, c->res_ok, s));
@@ -1703,8 +1727,7 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
     const int s0 = lists[pass][0], nlist = lists[pass][1];
     if (nlist == 0) continue;
     EvalPlan plan;
-    if (!plan_eval(SRHIP_F32, pass == 1, q->opset, MODE_OUT, false, nfeat, rows, nlist, &plan))
-      throw Error(SRHIP_ERR_UNSUPPORTED, "row tile of " + std::to_string(nfeat) + " features does not fit in LDS");
+    plan_interp(SRHIP_F32, pass == 1, q->opset, MODE_OUT, false, nfeat, rows, nlist, &plan);
     if (plan.tile % 256 != 0)  // the tree code reads whole 256-row tiles of the columns
       throw Error(SRHIP_ERR_INVALID, "shared-subtree derive pass: tile of " + std::to_string(plan.tile) + " rows");
     EvalArgs<float> a;
@@ -1714,7 +1737,7 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
     a.list_off = q->d_list + (q->nlist_a + q->nlist_b) + s0;
     a.fail = nullptr;
     a.ti_rec = nullptr;
-    if (ti_enabled() && pass == 0) {
+    if (ti_enabled() && pass == 0 && !plan.wide) {
       c->gti.ensure((size_t)nlist * 64 * sizeof(uint4));
       HIP_CHECK(launch_ti_records(a.prog, a.list_off, nlist, (uint32_t)(plan.ntiles * plan.tile * sizeof(float)),
                                   static_cast<uint4*>(c->gti.p), s));
@@ -1769,13 +1792,68 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
   const size_t nslots = (size_t)p->nlist_a + p->nlist_b;
   // slot ranges: [0, nj) tree code, [nj, nlist_a) shallow interpreter, then deep
   // (per-tree row sets, seg > 0: the interpreter, one tree per workgroup)
-  jit::Module* jm = (!std::is_same<T, float>::value || seg > 0) ? nullptr
-                    : mode == MODE_LOSS                          ? loss_module(p, loss, lparam)
-                                                                 : out_module(p);
+  const int wm = wide_mode();  // 1: no tree code for this call
+  jit::Module* jm = (!std::is_same<T, float>::value || seg > 0 || wm == 1) ? nullptr
+                    : mode == MODE_LOSS                                     ? loss_module(p, loss, lparam)
+                                                                            : out_module(p);
   // Float64 programs: their tree code (this loss, or per-row outputs)
   jit::Module64* jm64 = nullptr;
   if constexpr (std::is_same<T, double>::value)
-    if (p->jit64 && p->nlist_j > 0 && seg == 0) jm64 = module64(p, mode == MODE_LOSS ? loss : -2, lparam);
+    if (p->jit64 && p->nlist_j > 0 && seg == 0 && wm != 1) jm64 = module64(p, mode == MODE_LOSS ? loss : -2, lparam);
+  // the row tile of a tree-code part (LDS columns: y, the raw features the tree code reads, its
+  // derived columns, w); false: it does not fit in LDS
+  auto plan_tree_code = [&](int nlist, EvalPlan* plan) {
+    if (jm64) {
+      // Float64 tree code: 128-row tiles of y, the features it reads, w; 4 waves
+      const int narr = 1 + jit::nraw64(jm64) + (w ? 1 : 0);
+      if (jit::nraw64(jm64) > nfeat) throw Error(SRHIP_ERR_INVALID, "dataset has fewer features than the program reads");
+      if (!plan_geometry(8, 2, kShallowSlots, narr, 1, rows, nlist, plan, 52 * 1024, 52 * 1024, 16384, 64)) return false;
+      plan->threads = 256;
+      return true;
+    }
+    const jit::Columns& jc = jit::columns(jm);
+    if (jc.nraw > nfeat) throw Error(SRHIP_ERR_INVALID, "dataset has fewer features than the program reads");
+    const int narr = 1 + jc.nraw + jc.nder + (w ? 1 : 0);
+    // partials go to global memory: LDS holds the tiles (1 byte per slot keeps the slot bound away)
+    // 16384 workgroups of 4 waves, >= 64 trees per group (16 per wave): config #2 kernel
+    // 2.997 -> 2.867 ms at 4096 trees, 0.865 -> 0.828 at 1024, 512 unchanged
+    // (profiles/r02n_targetwg.txt); scaled by the waves per workgroup
+    const int jw = jc.waves;
+    const size_t lds_wg = jit::lds_per_workgroup(jw);
+    const size_t budget = std::max(jit_tile_budget() * jw / 4,
+                                   lds_wg - (jit::part_global() ? 0 : std::min<size_t>(lds_wg / 4, 8192)));
+    if (!plan_geometry(4, 4, kShallowSlots, narr, 1, rows, nlist, plan, budget, 52 * 1024 * jw / 4,
+                       16384 * 4 / jw, 64 * jw / 4))
+      return false;
+    plan->threads = 64 * jw;
+    tail_split(c, plan, rows, jw);
+    return true;
+  };
+  // A call with a pass whose row tile does not fit in LDS (the tree code's, or an interpreter
+  // pass's for the trees the tree code does not hold) was UNSUPPORTED before the wide kernels:
+  // it runs in the interpreter, with no tree code, wide where the tile does not fit
+  // (SRHIP_WIDE=0: UNSUPPORTED, as before them). The tree-code plans are kept for the launches.
+  std::vector<EvalPlan> tc_plans;
+  if ((jm || jm64) && rows > 0 && p->nlist_j > 0) {
+    EvalPlan ip;
+    bool fits = (p->nlist_a == p->nlist_j ||
+                 plan_eval(p->dtype, false, p->opset, mode, w != nullptr, nfeat, rows, p->nlist_a - p->nlist_j, &ip)) &&
+                (p->nlist_b == 0 || plan_eval(p->dtype, true, p->has_expr ? (int)OPSET_EXPR : (int)OPSET_FULL, mode,
+                                              w != nullptr, nfeat, rows, p->nlist_b, &ip));
+    const int np = jm ? jit::nparts(jm) : jit::nparts64(jm64);
+    for (int k = 0; k < np && fits; ++k) {
+      int s0, nsl;
+      if (jm) jit::part(jm, k, &s0, &nsl);
+      else jit::part64(jm64, k, &s0, &nsl);
+      tc_plans.emplace_back();
+      if (nsl > 0) fits = plan_tree_code(nsl, &tc_plans.back());
+    }
+    if (!fits) {
+      if (wm == 0) throw_lds(nfeat);
+      jm = nullptr;
+      jm64 = nullptr;
+    }
+  }
   const bool use_jit = jm != nullptr || jm64 != nullptr;
   c->last_jit_trees = (use_jit && rows > 0) ? p->nlist_j : 0;
   const int nj = use_jit ? p->nlist_j : 0;
@@ -1798,6 +1876,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
   }
   // launches: the tree-code parts (pass -1, one per code object), the shallow
   // interpreter (0), the deep interpreter (1)
+  bool any_wide = false;  // the call's kernel name says wide once an interpreter pass ran wide
   struct Launch { int pass, s0, nlist, part; };
   std::vector<Launch> launches;
   if (nj > 0) {
@@ -1830,34 +1909,11 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
       continue;
     }
     EvalPlan plan;
-    if (pass == -1 && jm64) {
-      // Float64 tree code: 128-row tiles of y, the features it reads, w; 4 waves
-      const int narr = 1 + jit::nraw64(jm64) + (w ? 1 : 0);
-      if (jit::nraw64(jm64) > nfeat) throw Error(SRHIP_ERR_INVALID, "dataset has fewer features than the program reads");
-      if (!plan_geometry(8, 2, kShallowSlots, narr, 1, rows, nlist, &plan, 52 * 1024, 52 * 1024, 16384, 64))
-        throw Error(SRHIP_ERR_UNSUPPORTED, "row tile of " + std::to_string(nfeat) + " features does not fit in LDS");
-      plan.threads = 256;
-    } else if (pass == -1) {
-      // LDS columns: y, the raw features the tree code reads, its derived columns, w
-      const jit::Columns& jc = jit::columns(jm);
-      if (jc.nraw > nfeat) throw Error(SRHIP_ERR_INVALID, "dataset has fewer features than the program reads");
-      const int narr = 1 + jc.nraw + jc.nder + (w ? 1 : 0);
-      // partials go to global memory: LDS holds the tiles (1 byte per slot keeps the slot bound away)
-      // 16384 workgroups of 4 waves, >= 64 trees per group (16 per wave): config #2 kernel
-      // 2.997 -> 2.867 ms at 4096 trees, 0.865 -> 0.828 at 1024, 512 unchanged
-      // (profiles/r02n_targetwg.txt); scaled by the waves per workgroup
-      const int jw = jc.waves;
-      const size_t lds_wg = jit::lds_per_workgroup(jw);
-      const size_t budget = std::max(jit_tile_budget() * jw / 4,
-                                     lds_wg - (jit::part_global() ? 0 : std::min<size_t>(lds_wg / 4, 8192)));
-      if (!plan_geometry(4, 4, kShallowSlots, narr, 1, rows, nlist, &plan, budget, 52 * 1024 * jw / 4,
-                         16384 * 4 / jw, 64 * jw / 4))
-        throw Error(SRHIP_ERR_UNSUPPORTED, "row tile of " + std::to_string(nfeat) + " features does not fit in LDS");
-      plan.threads = 64 * jw;
-      tail_split(c, &plan, rows, jw);
-    } else if (!plan_eval(p->dtype, pass == 1, (pass == 1 && p->has_expr) ? (int)OPSET_EXPR : p->opset, mode,
-                          w != nullptr, nfeat, rows, nlist, &plan)) {
-      throw Error(SRHIP_ERR_UNSUPPORTED, "row tile of " + std::to_string(nfeat) + " features does not fit in LDS");
+    if (pass == -1) {
+      plan = tc_plans[(size_t)launches[li].part];
+    } else {
+      plan_interp(p->dtype, pass == 1, (pass == 1 && p->has_expr) ? (int)OPSET_EXPR : p->opset, mode, w != nullptr,
+                  nfeat, rows, nlist, &plan);
     }
     if (seg > 0) {
       // per-tree row sets: one tree per workgroup of one wave, staging its
@@ -1874,7 +1930,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
     a.list_off = p->d_list + (p->nlist_a + p->nlist_b) + s0;
     a.fail = mode == MODE_LOSS ? static_cast<uint32_t*>(c->fail.p) + s0 : nullptr;
     a.ti_rec = nullptr;
-    if (ti_enabled() && std::is_same<T, float>::value && pass == 0) {
+    if (ti_enabled() && std::is_same<T, float>::value && pass == 0 && !plan.wide) {
       c->ti_rec.ensure((size_t)nlist * 64 * sizeof(uint4));
       HIP_CHECK(launch_ti_records(reinterpret_cast<const Ins<float>*>(a.prog), a.list_off, nlist,
                                   (uint32_t)(plan.ntiles * plan.tile * sizeof(T)),
@@ -1930,7 +1986,8 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
     } else {
       // the interpreter's pass after a tree-code pass runs the few trees left
       // over: the call's main kernel stays the tree code
-      if (nj == 0) note_kernel(sizeof(T) == 4 ? "eval_kernel<float>" : "eval_kernel<double>");
+      any_wide = any_wide || plan.wide;
+      if (nj == 0) note_kernel(interp_name(sizeof(T), any_wide));
       HIP_CHECK(launch_eval<T>(plan, a, mode, s));
     }
     timed_end(c, s, tk);
@@ -1945,9 +2002,9 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
       HIP_CHECK(hipStreamSynchronize(s));
       float ms = 0.f;
       HIP_CHECK(hipEventElapsedTime(&ms, c->tev[2 * (size_t)tk], c->tev[2 * (size_t)tk + 1]));
-      std::fprintf(stderr, "srhip pass %s: %d trees, %.3f ms (grid %d x %d, %d tiles/wg)\n",
-                   pass == -1 ? "tree-code" : pass == 0 ? "shallow" : "deep", nlist, ms, plan.nrg, plan.ntg,
-                   plan.ntiles);
+      std::fprintf(stderr, "srhip pass %s%s: %d trees, %.3f ms (grid %d x %d, %d tiles/wg)\n",
+                   pass == -1 ? "tree-code" : pass == 0 ? "shallow" : "deep", plan.wide ? " (wide)" : "", nlist, ms,
+                   plan.nrg, plan.ntg, plan.ntiles);
     }
     if (last_jit) rerun_bailed<T>(c, p, jm, a, plan, nfeat, rows, loss, lparam);
   }
@@ -2250,7 +2307,9 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
   // interpreter items of the other trees follow
   bool use_gjit = false;
   if constexpr (std::is_same<T, float>::value) {
-    jit::GradModule* gm = (p->gjit && mode == GRAD_LOSS && ds->rows > 0) ? grad_module(p, loss, lparam) : nullptr;
+    jit::GradModule* gm = (p->gjit && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
+                              ? grad_module(p, loss, lparam)
+                              : nullptr;
     if (gm) {
       const int nparts = jit::grad_nparts(gm);
       const int narr = 1 + ds->nfeat + (ds->w ? 1 : 0);
@@ -2322,8 +2381,9 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
                                          p->d_gjit_cidx, p->ngjit_cidx, static_cast<double*>(c->dloss.p), s));
       }
     }
-  } else if (jit::GradModule64* gm = (p->gjit64 && mode == GRAD_LOSS && ds->rows > 0) ? grad_module64(p, loss, lparam)
-                                                                                      : nullptr) {
+  } else if (jit::GradModule64* gm = (p->gjit64 && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
+                                         ? grad_module64(p, loss, lparam)
+                                         : nullptr) {
     // Float64 gradient tree code: 128-row tiles of y, the features it reads, w
     const int nparts = jit::grad64_nparts(gm);
     const int narr = 1 + jit::grad64_nraw(gm) + (ds->w ? 1 : 0);
@@ -2388,10 +2448,14 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     first += nitems;
     if (nitems == 0 || ds->rows == 0) continue;
     const bool deep = pass == 3;
-    const int G = pass == 0 ? 1 : pass == 1 ? 2 : kGradG;
+    int G = pass == 0 ? 1 : pass == 1 ? 2 : kGradG;
     EvalPlan plan;
-    if (!plan_grad(p->dtype, deep, G, mode, ds->w != nullptr, ds->nfeat, ds->rows, nitems, &plan))
-      throw Error(SRHIP_ERR_UNSUPPORTED, "row tile of " + std::to_string(ds->nfeat) + " features does not fit in LDS");
+    const int wm = wide_mode();
+    if (wm == 1 || !plan_grad(p->dtype, deep, G, mode, ds->w != nullptr, ds->nfeat, ds->rows, nitems, &plan)) {
+      // the wide variant: one configuration, kGradG tangents (a tree's tangents past its constants stay 0)
+      G = kGradG;
+      if (wm == 0 || !plan_grad_wide(p->dtype, mode, ds->w != nullptr, ds->rows, nitems, &plan)) throw_lds(ds->nfeat);
+    }
     GradArgs<T> a;
     a.prog = static_cast<const Ins<T>*>(p->d_gcode);
     a.tree_off = p->d_gtree_off;
@@ -2413,14 +2477,15 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     a.lparam = lparam;
     if (mode == GRAD_LOSS && loss >= SRHIP_EXPR_LOSS_BEGIN) a.lprog = expr_loss_device<T>(c, loss);
     a.G = G;
-    a.opset = deep ? (p->g_has_expr ? (int)OPSET_EXPR : (int)OPSET_FULL) : p->g_opset;
+    a.opset = (deep || plan.wide) ? (p->g_has_expr ? (int)OPSET_EXPR : (int)OPSET_FULL) : p->g_opset;
     c->partial.ensure((size_t)plan.nrg * plan.ntg * plan.tpb * (2 + G) * sizeof(T));
     a.partial = static_cast<T*>(c->partial.p);
     a.out_value = out_value;
     a.out_grad = out_grad;
     a.out_stride = out_stride;
     const int tk = timed_begin(c, s);
-    note_kernel(sizeof(T) == 4 ? "grad_kernel<float>" : "grad_kernel<double>");
+    note_kernel(plan.wide ? (sizeof(T) == 4 ? "grad_kernel_wide<float>" : "grad_kernel_wide<double>")
+                          : (sizeof(T) == 4 ? "grad_kernel<float>" : "grad_kernel<double>"));
     HIP_CHECK(launch_grad<T>(plan, a, mode, s));
     timed_end(c, s, tk);
     HIP_CHECK(launch_grad_finalize<T>(a, static_cast<double*>(c->sums.p), static_cast<uint8_t*>(c->oks.p),

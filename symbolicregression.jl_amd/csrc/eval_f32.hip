@@ -10,6 +10,7 @@ bool ti_compiled() { return SR_TI != 0; }
 
 template <>
 hipError_t launch_eval<float>(const EvalPlan& plan, const EvalArgs<float>& a, int mode, hipStream_t stream) {
+  if (plan.wide) return launch_eval_wide<float>(plan, a, mode, stream);  // eval_wide_f32.hip
   if (plan.D == kMaxSlots) {
     // deep trees; a list that holds expression operators runs the variant that
     // dispatches their micro-instructions

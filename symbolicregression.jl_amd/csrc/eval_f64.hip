@@ -7,6 +7,7 @@ namespace srhip {
 
 template <>
 hipError_t launch_eval<double>(const EvalPlan& plan, const EvalArgs<double>& a, int mode, hipStream_t stream) {
+  if (plan.wide) return launch_eval_wide<double>(plan, a, mode, stream);  // eval_wide_f64.hip
   if (plan.D == kMaxSlots) {
     // deep trees; a list that holds expression operators runs the variant that
     // dispatches their micro-instructions

@@ -176,7 +176,9 @@ constexpr int kWavesPerEUm =
 // One tree of a workgroup's group on its row tiles: the loss (or the per-row
 // outputs) of tree slot s into sPart[i], its failure flag set when a row fails
 // (the body of the interpreter's tree loop, static or dynamic deal).
-template <typename T, int R, int D, int SET, int MODE, bool W, bool VP, bool TI>
+// XG (the wide kernels): sX is the feature-major array in global memory at the
+// row group's first row, n_pad rows apart per feature, not the LDS row tile.
+template <typename T, int R, int D, int SET, int MODE, bool W, bool VP, bool TI, bool XG = false>
 __device__ __forceinline__ void eval_tree_in_group(const EvalArgs<T>& a, int i, int s, bool skip, const VProg<T>& vp,
                                                    const Ins<T>* prog, const T* sX, const T* sY, const T* sW,
                                                    Part<T>* sPart, int rows, int lane, int64_t row0, int nt_valid,
@@ -199,7 +201,8 @@ __device__ __forceinline__ void eval_tree_in_group(const EvalArgs<T>& a, int i, 
       }
     }
     if (done) {
-    } else if constexpr (VP && SR_VP == 2) run_program_v2<T, R, D, SET>(vp, sXt, rows, lane, acc, chk);
+    } else if constexpr (XG) run_program<T, R, D, SET>(p, sXt, a.n_pad, lane, acc, chk);
+    else if constexpr (VP && SR_VP == 2) run_program_v2<T, R, D, SET>(vp, sXt, rows, lane, acc, chk);
     else if constexpr (VP) run_program_v<T, R, D, SET>(vp, sXt, rows, lane, acc, chk);
     else run_program<T, R, D, SET>(p, sXt, rows, lane, acc, chk);
 #pragma unroll
@@ -238,7 +241,11 @@ __device__ __forceinline__ void eval_tree_in_group(const EvalArgs<T>& a, int i, 
   }
 }
 
-template <typename T, int R, int D, int SET, int MODE, bool W>
+// XG: the wide variant, for datasets whose row tile of every feature does not
+// fit in LDS. Step 1 stages y and w only; the programs read their feature
+// operands from a.X in global memory (interp.h run_program), so LDS use
+// does not depend on a.nfeat. Everything else is the LDS variant's.
+template <typename T, int R, int D, int SET, int MODE, bool W, bool XG = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWavesPerEUm<T, R, D, MODE>)))
 eval_kernel(EvalArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -246,9 +253,10 @@ eval_kernel(EvalArgs<T> a) {
   using V = typename V16<T>::type;
   constexpr int N = V16<T>::N;
   const int rows = a.ntiles * TILE;
-  const int narr = a.nfeat + (MODE != MODE_OUT ? ((W || (MODE == kModeLossExpr && a.w)) ? 2 : 1) : 0);
+  const int nx = XG ? 0 : a.nfeat;  // feature arrays staged in LDS
+  const int narr = nx + (MODE != MODE_OUT ? ((W || (MODE == kModeLossExpr && a.w)) ? 2 : 1) : 0);
   T* sX = reinterpret_cast<T*>(smem);
-  T* sY = sX + (size_t)a.nfeat * rows;
+  T* sY = sX + (size_t)nx * rows;
   T* sW = sY + rows;
   Part<T>* sPart = reinterpret_cast<Part<T>*>(sX + (size_t)narr * rows);
 
@@ -265,7 +273,7 @@ eval_kernel(EvalArgs<T> a) {
     for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
       const int arr = idx / vper;
       const int v = idx - arr * vper;
-      const T* src = arr < a.nfeat ? a.X + (size_t)arr * a.n_pad : (arr == a.nfeat ? a.y : a.w);
+      const T* src = arr < nx ? a.X + (size_t)arr * a.n_pad : (arr == nx ? a.y : a.w);
       reinterpret_cast<V*>(sX + (size_t)arr * rows)[v] = reinterpret_cast<const V*>(src + seg0 + row0)[v];
     }
     for (int i = threadIdx.x; i < a.tpb; i += blockDim.x) sPart[i] = Part<T>{T(0), T(0)};
@@ -286,8 +294,8 @@ eval_kernel(EvalArgs<T> a) {
   const int nwaves = (int)(blockDim.x >> 6);
   // The shallow variant keeps each tree's program in VGPRs (run_program_v);
   // the next tree's program is loaded while the current one runs.
-  constexpr bool VP = SR_VP != 0 && D == kShallowSlots;
-  constexpr bool TI = SR_TI != 0 && std::is_same<T, float>::value && R == SR_R32 && D == kShallowSlots;
+  constexpr bool VP = !XG && SR_VP != 0 && D == kShallowSlots;
+  constexpr bool TI = !XG && SR_TI != 0 && std::is_same<T, float>::value && R == SR_R32 && D == kShallowSlots;
   auto slot_of = [&](int i) { return i * a.ntg + ((i & 1) ? (a.ntg - 1 - g) : g); };
   // list_off is read through the constant address space: scalar loads (the
   // early-exit flag stores would otherwise make the compiler use vector loads)
@@ -295,6 +303,8 @@ eval_kernel(EvalArgs<T> a) {
     return a.prog + __builtin_amdgcn_readfirstlane(
                         ((const __attribute__((address_space(4))) int32_t*)(a.list_off))[s]);
   };
+  const T* pX = sX;  // the programs' feature operands
+  if constexpr (XG) pX = a.X + seg0 + row0;
   VProg<T> vnext;
   // TI: the program in VGPRs (lane j = instruction j; shallow programs have at
   // most kVProgMax instructions and the code buffer is padded by 64), loaded
@@ -354,7 +364,7 @@ eval_kernel(EvalArgs<T> a) {
       if constexpr (EE) {
         if (more) fnext = ld_flag(s2);
       }
-      eval_tree_in_group<T, R, D, SET, MODE, W, VP, TI>(a, i, s, skip, vp, prog_of(s), sX, sY, sW, sPart, rows, lane,
+      eval_tree_in_group<T, R, D, SET, MODE, W, VP, TI, XG>(a, i, s, skip, vp, prog_of(s), pX, sY, sW, sPart, rows, lane,
                                                         row0, nt_valid, last_valid, lp);
     }
   } else {
@@ -387,7 +397,7 @@ eval_kernel(EvalArgs<T> a) {
     if constexpr (EE) {
       if (more) fnext = ld_flag(s2);
     }
-    eval_tree_in_group<T, R, D, SET, MODE, W, VP, TI>(a, i, s, skip, vp, prog_of(s), sX, sY, sW, sPart, rows, lane,
+    eval_tree_in_group<T, R, D, SET, MODE, W, VP, TI, XG>(a, i, s, skip, vp, prog_of(s), pX, sY, sW, sPart, rows, lane,
                                                       row0, nt_valid, last_valid, lp);
   }
   }  // static deal
@@ -397,30 +407,30 @@ eval_kernel(EvalArgs<T> a) {
   for (int i = threadIdx.x; i < a.tpb; i += blockDim.x) dst[i] = sPart[i];
 }
 
-template <typename T, int R, int D, int SET, int MODE, bool W>
+template <typename T, int R, int D, int SET, int MODE, bool W, bool XG = false>
 hipError_t launch_one(const EvalPlan& plan, const EvalArgs<T>& a, hipStream_t stream) {
   // raise the dynamic-LDS ceiling once per kernel instantiation: a function-
   // local static is initialised exactly once even with concurrent callers
   static const hipError_t attr_err = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&eval_kernel<T, R, D, SET, MODE, W>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      reinterpret_cast<const void*>(&eval_kernel<T, R, D, SET, MODE, W, XG>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (attr_err != hipSuccess) return attr_err;
   const unsigned grid = (unsigned)a.nrg * (unsigned)a.ntg;
-  hipLaunchKernelGGL((eval_kernel<T, R, D, SET, MODE, W>), dim3(grid), dim3(plan.threads),
+  hipLaunchKernelGGL((eval_kernel<T, R, D, SET, MODE, W, XG>), dim3(grid), dim3(plan.threads),
                      plan.lds_bytes, stream, a);  // (plan_geometry: + 16 bytes after the partials, the tree counter)
   return hipGetLastError();
 }
 
-template <typename T, int R, int D, int SET>
+template <typename T, int R, int D, int SET, bool XG = false>
 hipError_t launch_rd(const EvalPlan& plan, const EvalArgs<T>& a, int mode, hipStream_t stream) {
-  if (mode == MODE_OUT) return launch_one<T, R, D, SET, MODE_OUT, false>(plan, a, stream);
+  if (mode == MODE_OUT) return launch_one<T, R, D, SET, MODE_OUT, false, XG>(plan, a, stream);
   constexpr int LSET = SET == OPSET_EXPR ? OPSET_EXPR : OPSET_FULL;  // (expression losses: no basic-set variant)
-  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_one<T, R, D, LSET, kModeLossExpr, false>(plan, a, stream);
+  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_one<T, R, D, LSET, kModeLossExpr, false, XG>(plan, a, stream);
   if (a.loss == SRHIP_LOSS_L2) {
-    if (a.w) return launch_one<T, R, D, SET, kModeLossL2, true>(plan, a, stream);
-    return launch_one<T, R, D, SET, kModeLossL2, false>(plan, a, stream);
+    if (a.w) return launch_one<T, R, D, SET, kModeLossL2, true, XG>(plan, a, stream);
+    return launch_one<T, R, D, SET, kModeLossL2, false, XG>(plan, a, stream);
   }
-  if (a.w) return launch_one<T, R, D, SET, MODE_LOSS, true>(plan, a, stream);
-  return launch_one<T, R, D, SET, MODE_LOSS, false>(plan, a, stream);
+  if (a.w) return launch_one<T, R, D, SET, MODE_LOSS, true, XG>(plan, a, stream);
+  return launch_one<T, R, D, SET, MODE_LOSS, false, XG>(plan, a, stream);
 }
 
 }  // namespace

@@ -44,15 +44,16 @@ __device__ __forceinline__ void un_grad(Dual<T, R, G>& a, T& chk) {
   }
 }
 
-template <int V, int B, typename T, int R, int G>
+// RS: int for the LDS row tile, int64_t for the wide kernels' global array (interp.h)
+template <int V, int B, typename T, int R, int G, typename RS = int>
 __device__ __forceinline__ void bin_grad(Dual<T, R, G>& a, const Dual<T, R, G>& t,
-                                         const T* __restrict__ sXt, int rs, int lane, int f,
+                                         const T* __restrict__ sXt, RS rs, int lane, int f,
                                          T imm, int jc, T& chk) {
   constexpr int SL = src_l(V), SR = src_r(V);
   constexpr bool LL = bop_lossy_lhs(B), LR = bop_lossy_rhs(B);
   T xa[R], xb[R];
-  if constexpr (SL == S_X || SR == S_X) lds_rows<T, R>(sXt + f * rs, lane, xa);
-  if constexpr (SR == S_X2) lds_rows<T, R>(sXt + imm_int(imm) * rs, lane, xb);
+  if constexpr (SL == S_X || SR == S_X) lds_rows<T, R>(sXt + (RS)f * rs, lane, xa);
+  if constexpr (SR == S_X2) lds_rows<T, R>(sXt + (RS)imm_int(imm) * rs, lane, xb);
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     T lv, rv;
@@ -105,9 +106,9 @@ __device__ __forceinline__ void bin_grad(Dual<T, R, G>& a, const Dual<T, R, G>& 
 
 // Run one tree's program over one row tile with tangents for constants
 // g0 .. g0+G-1; the result is left in a.
-template <typename T, int R, int D, int G, int SET>
+template <typename T, int R, int D, int G, int SET, typename RS = int>
 __device__ __forceinline__ void run_program_grad(CIns<T>* __restrict__ p,
-                                                 const T* __restrict__ sXt, int rs, int lane,
+                                                 const T* __restrict__ sXt, RS rs, int lane,
                                                  int g0, Dual<T, R, G>& a, T& chk) {
   Dual<T, R, G> t;
   Dual<T, R, G> slot[D];
@@ -151,7 +152,7 @@ __device__ __forceinline__ void run_program_grad(CIns<T>* __restrict__ p,
     switch (code & 0xffu) {
       case OP_END: return;
       case OP_LDX:
-        lds_rows<T, R>(sXt + f * rs, lane, a.v);
+        lds_rows<T, R>(sXt + (RS)f * rs, lane, a.v);
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll

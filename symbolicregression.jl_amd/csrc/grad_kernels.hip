@@ -25,7 +25,9 @@ using namespace interp;
 // column is the run-time a.w): the others keep their code.
 constexpr int kGradLossExpr = 2;
 
-template <typename T, int R, int D, int MODE, bool W, int G, int SET>
+// XG: the wide variant (eval_kernel.h): y and w staged in LDS only, the programs'
+// feature operands read from a.X in global memory.
+template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = false>
 __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
   constexpr int S = 2 + G;
   constexpr int TILE = 64 * R;
@@ -33,9 +35,10 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
   constexpr int N = V16<T>::N;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int rows = a.ntiles * TILE;
-  const int narr = a.nfeat + (MODE == GRAD_LOSS ? (W ? 2 : 1) : MODE == kGradLossExpr ? (a.w ? 2 : 1) : 0);
+  const int nx = XG ? 0 : a.nfeat;  // feature arrays staged in LDS
+  const int narr = nx + (MODE == GRAD_LOSS ? (W ? 2 : 1) : MODE == kGradLossExpr ? (a.w ? 2 : 1) : 0);
   T* sX = reinterpret_cast<T*>(smem);
-  T* sY = sX + (size_t)a.nfeat * rows;
+  T* sY = sX + (size_t)nx * rows;
   T* sW = sY + rows;
   T* sPart = sX + (size_t)narr * rows;
 
@@ -48,7 +51,7 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
     for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
       const int arr = idx / vper;
       const int v = idx - arr * vper;
-      const T* src = arr < a.nfeat ? a.X + (size_t)arr * a.n_pad : (arr == a.nfeat ? a.y : a.w);
+      const T* src = arr < nx ? a.X + (size_t)arr * a.n_pad : (arr == nx ? a.y : a.w);
       reinterpret_cast<V*>(sX + (size_t)arr * rows)[v] = reinterpret_cast<const V*>(src + row0)[v];
     }
     for (int i = threadIdx.x; i < a.tpb * S; i += blockDim.x) sPart[i] = T(0);
@@ -85,9 +88,13 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
 #pragma unroll
     for (int k = 0; k < S; ++k) acc[k] = T(0);  // [0] Σ w·ℓ, [1] marker, [2+j] Σ w·ℓ'·∂ŷ/∂c
     for (int tl = 0; tl < nt_valid; ++tl) {
-      const T* sXt = sX + tl * TILE;
       Dual<T, R, G> d;
-      run_program_grad<T, R, D, G, SET>(p, sXt, rows, lane, g0, d, acc[1]);
+      if constexpr (XG) {
+        run_program_grad<T, R, D, G, SET>(p, a.X + row0 + tl * TILE, a.n_pad, lane, g0, d, acc[1]);
+      } else {
+        const T* sXt = sX + tl * TILE;
+        run_program_grad<T, R, D, G, SET>(p, sXt, rows, lane, g0, d, acc[1]);
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) acc[1] = mark(d.v[r], acc[1]);
       if constexpr (MODE == GRAD_OUT) {
@@ -183,27 +190,27 @@ __global__ void __launch_bounds__(256) grad_finalize_kernel(GradArgs<T> a, doubl
   }
 }
 
-template <typename T, int R, int D, int MODE, bool W, int G, int SET>
+template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = false>
 hipError_t launch_grad_one(const EvalPlan& plan, const GradArgs<T>& a, hipStream_t stream) {
   // raise the dynamic-LDS ceiling once per kernel instantiation: a function-
   // local static is initialised exactly once even with concurrent callers
   static const hipError_t attr_err = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&grad_kernel<T, R, D, MODE, W, G, SET>), hipFuncAttributeMaxDynamicSharedMemorySize,
+      reinterpret_cast<const void*>(&grad_kernel<T, R, D, MODE, W, G, SET, XG>), hipFuncAttributeMaxDynamicSharedMemorySize,
       160 * 1024);
   if (attr_err != hipSuccess) return attr_err;
   const unsigned grid = (unsigned)a.nrg * (unsigned)a.ntg;
-  hipLaunchKernelGGL((grad_kernel<T, R, D, MODE, W, G, SET>), dim3(grid), dim3(plan.threads), plan.lds_bytes,
+  hipLaunchKernelGGL((grad_kernel<T, R, D, MODE, W, G, SET, XG>), dim3(grid), dim3(plan.threads), plan.lds_bytes,
                      stream, a);
   return hipGetLastError();
 }
 
-template <typename T, int R, int D, int G, int SET>
+template <typename T, int R, int D, int G, int SET, bool XG = false>
 hipError_t launch_grad_rd(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
-  if (mode == GRAD_OUT) return launch_grad_one<T, R, D, GRAD_OUT, false, G, SET>(plan, a, stream);
+  if (mode == GRAD_OUT) return launch_grad_one<T, R, D, GRAD_OUT, false, G, SET, XG>(plan, a, stream);
   constexpr int LSET = SET == OPSET_EXPR ? OPSET_EXPR : OPSET_FULL;  // (expression losses: no basic-set variant)
-  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_grad_one<T, R, D, kGradLossExpr, false, G, LSET>(plan, a, stream);
-  if (a.w) return launch_grad_one<T, R, D, GRAD_LOSS, true, G, SET>(plan, a, stream);
-  return launch_grad_one<T, R, D, GRAD_LOSS, false, G, SET>(plan, a, stream);
+  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_grad_one<T, R, D, kGradLossExpr, false, G, LSET, XG>(plan, a, stream);
+  if (a.w) return launch_grad_one<T, R, D, GRAD_LOSS, true, G, SET, XG>(plan, a, stream);
+  return launch_grad_one<T, R, D, GRAD_LOSS, false, G, SET, XG>(plan, a, stream);
 }
 
 // gradient variants: rows per lane R (fewer tangents leave room for more
@@ -235,8 +242,22 @@ bool plan_grad(int dtype, bool deep, int G, int mode, bool weighted, int nfeat, 
   return plan_geometry(esz, grad_R(dtype, deep, G), deep ? kMaxSlots : 4, narr, (2 + G) * esz, n, nitems, p);
 }
 
+bool plan_grad_wide(int dtype, int mode, bool weighted, int64_t n, int nitems, EvalPlan* p) {
+  const size_t esz = dtype == SRHIP_F32 ? 4 : 8;
+  const int narr = mode == GRAD_LOSS ? (weighted ? 2 : 1) : 0;  // y, w: no feature array
+  const bool ok = plan_geometry(esz, grad_R(dtype, true, kGradG), kMaxSlots, narr, (2 + kGradG) * esz, n, nitems, p);
+  p->wide = true;
+  return ok;
+}
+
 template <typename T>
 hipError_t launch_grad(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
+  if (plan.wide) {
+    // the wide variants: the deep configuration, a.G = kGradG. Both operator sets: a gradient
+    // program's feature index has 16 bits without expression operators, 15 with them
+    if (a.opset == OPSET_EXPR) return launch_grad_rd<T, 1, kMaxSlots, kGradG, OPSET_EXPR, true>(plan, a, mode, stream);
+    return launch_grad_rd<T, 1, kMaxSlots, kGradG, OPSET_FULL, true>(plan, a, mode, stream);
+  }
   if (plan.D != 4) return launch_grad_g<T, kGradG>(plan, a, mode, stream);  // deep programs: one variant
   if (a.G == 1) return launch_grad_g<T, 1>(plan, a, mode, stream);
   if (a.G == 2) return launch_grad_g<T, 2>(plan, a, mode, stream);

@@ -194,15 +194,17 @@ __device__ __forceinline__ void un_apply(T (&acc)[R], T& chk) {
 
 // x: the instruction's X operand (feature f), already in registers — loaded
 // by the driver (prefetched one instruction ahead by run_program_v).
-template <int V, int B, typename T, int R>
+// RS: the type of the row stride between features: int for the LDS row tile,
+// int64_t for the wide kernels' feature-major array in global memory.
+template <int V, int B, typename T, int R, typename RS = int>
 __device__ __forceinline__ void bin_apply(T (&acc)[R], const T (&tmp)[R], const T (&x)[R],
-                                          const T* __restrict__ sXt, int rs,
+                                          const T* __restrict__ sXt, RS rs,
                                           int lane, T imm, T& chk) {
   constexpr bool LL = bop_lossy_lhs(B);
   constexpr bool LR = bop_lossy_rhs(B);
   if constexpr (V == V_XX) {
     T x2[R];
-    lds_rows<T, R>(sXt + imm_int(imm) * rs, lane, x2);
+    lds_rows<T, R>(sXt + (RS)imm_int(imm) * rs, lane, x2);
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = bop<B>(x[r], x2[r]);
   } else {
@@ -283,10 +285,10 @@ __device__ __forceinline__ double keep_if(uint32_t m, double held, double v) {
 }
 
 // Execute one instruction (wave-uniform `code`, `imm`); returns false at END.
-template <typename T, int R, int D, int SET>
+template <typename T, int R, int D, int SET, typename RS = int>
 __device__ __forceinline__ bool exec_ins(uint32_t code, T imm, T (&acc)[R], T (&tmp)[R],
                                          T (&slot)[D][R], const T (&x)[R],
-                                         const T* __restrict__ sXt, int rs, int lane, T& chk) {
+                                         const T* __restrict__ sXt, RS rs, int lane, T& chk) {
   if constexpr (SET == OPSET_EXPR) {
     // Expression operators: their micro-instructions among the cases, and the
     // no-mark flag of body instructions: after a flagged instruction the marker
@@ -312,9 +314,15 @@ __device__ __forceinline__ bool exec_ins(uint32_t code, T imm, T (&acc)[R], T (&
 
 // Driver 1 (any program length): instructions fetched with scalar loads, one
 // ahead; the X operand is read from LDS right before the instruction.
-template <typename T, int R, int D, int SET>
+// The wide kernels (eval_kernel.h XG) run it on the feature-major array in
+// global memory: sXt = X + the tile's first row, rs = n_pad as int64_t (feature
+// × n_pad needs 64 bits). A lane's rows are lds_rows' own layout, so a wave
+// reads one contiguous, 16-byte-aligned run of 64·R elements per operand.
+// (Loading the next instruction's operand into a second buffer under the
+// current instruction measured slower, DESIGN.md §3.14: it is not done.)
+template <typename T, int R, int D, int SET, typename RS = int>
 __device__ __forceinline__ void run_program(CIns<T>* __restrict__ p,
-                                            const T* __restrict__ sXt, int rs,
+                                            const T* __restrict__ sXt, RS rs,
                                             int lane, T (&acc)[R], T& chk) {
   T tmp[R], x[R];
   T slot[D][R];
@@ -325,7 +333,7 @@ __device__ __forceinline__ void run_program(CIns<T>* __restrict__ p,
     const Ins<T> nxt = fetch<T>(p + 1);  // prefetch; every program ends with OP_END + slack
     const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.code);
     const T imm = uni(cur.imm);
-    if (code & kNeedX) lds_rows<T, R>(sXt + (int)(code >> 16) * rs, lane, x);
+    if (code & kNeedX) lds_rows<T, R>(sXt + (RS)(code >> 16) * rs, lane, x);
     if (!exec_ins<T, R, D, SET>(code, imm, acc, tmp, slot, x, sXt, rs, lane, chk)) return;
     cur = nxt;
     ++p;

@@ -69,10 +69,14 @@ struct EvalPlan {
   // tree code only: row groups [0, nbig) of ntiles tiles, then row groups of
   // ts tiles (the last round of workgroups in smaller pieces); nbig < 0: all full
   int nbig = -1, ts = 0;
+  // the wide kernel variant (eval_kernel.h / grad_kernels.hip XG): X is read from
+  // global memory, LDS holds y, w and the partial slots only
+  bool wide = false;
 };
 
 // Choose the geometry for `nlist` trees over `n` rows; returns false when the
-// row tile of this feature count does not fit in LDS.
+// row tile of this feature count does not fit in LDS (the caller then plans
+// the wide variant, plan_eval_wide).
 // Threaded-interpreter instruction records of every list slot (f32 shallow
 // programs; eval_kernel.h / gen_asm_interp.py): [nlist][64] uint4.
 bool ti_compiled();  // eval kernels built with the threaded interpreter (SR_TI)
@@ -81,6 +85,9 @@ hipError_t launch_ti_records(const Ins<float>* prog, const int32_t* list_off, in
 
 bool plan_eval(int dtype, bool deep, int opset, int mode, bool weighted, int nfeat,
                int64_t n, int nlist, EvalPlan* plan);
+// The wide plan of the same launch: the deep configuration with no feature
+// array in LDS. False only when y, w and the partial slots do not fit.
+bool plan_eval_wide(int dtype, int mode, bool weighted, int64_t n, int nlist, EvalPlan* plan);
 // Same, for explicit R / D / LDS arrays / partial bytes per tree slot.
 // target_wg: workgroups the tree groups aim at; min_per_group: trees a group
 // keeps at least (the loss tree code: 16384 / 64, measured on config #2)
@@ -119,6 +126,8 @@ struct GradArgs {
 
 bool plan_grad(int dtype, bool deep, int G, int mode, bool weighted, int nfeat, int64_t n,
                int nitems, EvalPlan* plan);
+// The wide plan: the deep configuration, kGradG tangents, no feature array in LDS.
+bool plan_grad_wide(int dtype, int mode, bool weighted, int64_t n, int nitems, EvalPlan* plan);
 template <typename T>
 hipError_t launch_grad(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream);
 template <typename T>
@@ -141,6 +150,9 @@ hipError_t launch_gconst_finalize(const double* gpart, int nrg, int nconst, cons
 template <typename T>
 hipError_t launch_eval(const EvalPlan& plan, const EvalArgs<T>& a, int mode,
                        hipStream_t stream);
+// the wide variants (plan.wide; launch_eval forwards to them)
+template <typename T>
+hipError_t launch_eval_wide(const EvalPlan& plan, const EvalArgs<T>& a, int mode, hipStream_t stream);
 
 // Σ over row groups of the partials → per-tree fp64 sum and ok flag; clears
 // the failure flags it read (a.fail) and, given cnt, copies the two tree-code

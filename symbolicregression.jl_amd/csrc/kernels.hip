@@ -220,6 +220,7 @@ bool plan_geometry(size_t esz, int R, int D, int narr, size_t part_bytes, int64_
   p->opset = OPSET_FULL;
   p->tile = 64 * R;
   p->threads = 256;
+  p->wide = false;
   const size_t per_tile = (size_t)narr * p->tile * esz;
   const size_t budget = tile_budget;
 #ifndef SR_NTMAX
@@ -303,6 +304,15 @@ bool plan_eval(int dtype, bool deep, int opset, int mode, bool weighted, int nfe
   // the deep variant is built for the full set, and for the full set with
   // expression operators
   p->opset = deep ? (opset == OPSET_EXPR ? OPSET_EXPR : OPSET_FULL) : opset;
+  return ok;
+}
+
+bool plan_eval_wide(int dtype, int mode, bool weighted, int64_t n, int nlist, EvalPlan* p) {
+  const size_t esz = dtype == SRHIP_F32 ? 4 : 8;
+  const int narr = mode == MODE_LOSS ? (weighted ? 2 : 1) : 0;  // y, w: no feature array
+  const bool ok = plan_geometry(esz, variant_R(dtype, true), kMaxSlots, narr, 2 * esz, n, nlist, p);
+  p->opset = OPSET_EXPR;  // the one operator set the wide variants are built for
+  p->wide = true;
   return ok;
 }
 
