@@ -499,6 +499,99 @@ int32_t srhip_optimize_constants_cb(const srhip_trees* trees, int32_t dtype, con
                                     srhip_constopt_eval_fn fn, void* user, void* out_consts, double* out_loss,
                                     uint8_t* out_converged, double* out_num_evals);
 
+/* ---- device groups: one process, row shards over several GPUs ---------------
+ * The reference spreads a search over its workers from one Julia process
+ * (src/SymbolicRegression.jl:539-630 the per-island dispatch, :717-778 the main
+ * loop that collects and migrates; src/SearchUtils.jl:33-45 one task per
+ * island) and optimises constants against the whole dataset
+ * (src/ConstantOptimization.jl:12-65). A group owns `ndev` members; member k
+ * is a context of its own on devices[k] (what srhip_open makes) with one
+ * persistent driver thread that does the member's hipSetDevice, host planning
+ * and enqueues. The same device may be listed more than once: each entry is a
+ * full member, which is also how a one-GPU machine runs every path. A group
+ * dataset holds row shard k = srhip_group_shard_range(n, ndev, k) on member k;
+ * a group program is one identical program per member. A group call
+ *  - hands the call to every member; each evaluates its shard on its own stream
+ *    and leaves its packed partials (the srhip_eval_loss_packed layout; for
+ *    gradients [Σw·ℓ, failed] per tree, Σw·∂ℓ/∂c per constant, Σw) in slot k of
+ *    a pinned host buffer that every device maps; an empty shard launches nothing;
+ *  - member 0's stream waits for the other members' events and one combine
+ *    kernel adds the slots elementwise in fp64 IN MEMBER ORDER k = 0 … ndev-1 —
+ *    the result is the left-to-right sum of the shards' single-context results,
+ *    bit for bit, whatever the timing — and finishes them: a tree that failed
+ *    on ANY shard has a NaN sum, NaN for each of its constants and ok = 0;
+ *  - returns after every member has finished its part, with one host wait on
+ *    member 0's stream; reports the first error in member order (the message
+ *    names the member) and then writes nothing into the caller's arrays.
+ * No peer access is used. Group calls on one group are serialised (one mutex);
+ * a context lent by srhip_group_ctx may be used with the single-device entry
+ * points from any thread at any time: its own mutex serialises those calls with
+ * the member's part of a group call. Destroy the group's datasets and programs
+ * before srhip_group_close, and call neither while a call on them is running.
+ * Not in this version: row_idx, per-tree row sets and per-row outputs over a
+ * group (use the member contexts), tree shards (islands use srhip_group_ctx). */
+typedef struct srhip_group srhip_group;
+typedef struct srhip_group_dataset srhip_group_dataset;
+typedef struct srhip_group_program srhip_group_program;
+
+/* 1 <= ndev <= 16, devices non-NULL and non-negative (else SRHIP_ERR_INVALID);
+ * an index beyond srhip_device_count is SRHIP_ERR_DEVICE, answered before any
+ * context is made (so also on a machine without a device). */
+int32_t srhip_group_open(const int32_t* devices, int32_t ndev, srhip_group** out_group);
+int32_t srhip_group_close(srhip_group* group);
+/* devices_out: [ndev] or NULL */
+int32_t srhip_group_info(const srhip_group* group, int32_t* out_ndev, int32_t* devices_out);
+/* Member k's context, lent: an island assigned to device k scores through the
+ * single-device entry points (srhip_eval_loss_batch_ctx and the rest,
+ * SearchUtils.jl:33-45). It stays the group's: do not srhip_close it. */
+int32_t srhip_group_ctx(srhip_group* group, int32_t k, srhip_ctx** out_ctx);
+/* Rows [begin, end) of member k of ndev over n rows: contiguous, sizes differ by
+ * at most one, the first n % ndev shards the longer ones; a shard may be empty.
+ * Host arithmetic only. n < 0, ndev outside 1..16 or k outside 0..ndev-1:
+ * SRHIP_ERR_INVALID. */
+int32_t srhip_group_shard_range(int64_t n, int32_t ndev, int32_t k, int64_t* begin, int64_t* end);
+
+/* Dataset(X, y; weights) (src/Dataset.jl:43-64) with the rows sharded: every
+ * member uploads its shard (srhip_dataset_create's arguments and checks), all
+ * members at once. */
+int32_t srhip_group_dataset_create(srhip_group* group, int32_t dtype, int32_t x_layout, const void* X,
+                                   const void* y, const void* w, int64_t n, int32_t nfeat,
+                                   srhip_group_dataset** out_gds);
+int32_t srhip_group_dataset_destroy(srhip_group_dataset* gds);
+/* all rows, nfeat, Σw and Σ y·w added over the members in member order, and
+ * whether every shard's X is finite */
+int32_t srhip_group_dataset_info(const srhip_group_dataset* gds, int64_t* out_rows, int32_t* out_nfeat,
+                                 double* out_sum_w, double* out_sum_yw, int32_t* out_x_finite);
+
+/* srhip_program_create_ex on every member with the same trees and flags, built
+ * at once; the builds share the host threads one build would use (8 / ndev
+ * each, so together they stay within 16). */
+int32_t srhip_group_program_create(srhip_group* group, int32_t dtype, const srhip_trees* trees, uint32_t flags,
+                                   srhip_group_program** out_gp);
+int32_t srhip_group_program_destroy(srhip_group_program* gp);
+/* srhip_program_set_constants on every member (ConstantOptimization.jl:12-19) */
+int32_t srhip_group_program_set_constants(srhip_group_program* gp, const void* consts);
+
+/* srhip_eval_loss over all rows of all shards (src/LossFunctions.jl:34-67):
+ * the same outputs with the same meaning, every loss kind (margin losses and
+ * expression-loss handles included). A program of another group than the
+ * dataset's is SRHIP_ERR_INVALID. */
+int32_t srhip_group_eval_loss(srhip_group_dataset* gds, srhip_group_program* gp, int32_t loss_kind,
+                              const double* loss_params, double* out_loss_sum, double* out_weight_sum,
+                              uint8_t* out_ok);
+/* srhip_eval_loss_grad over all rows of all shards
+ * (src/ConstantOptimization.jl:12-19, :43 with the rows split over GPUs). */
+int32_t srhip_group_eval_loss_grad(srhip_group_dataset* gds, srhip_group_program* gp, int32_t loss_kind,
+                                   const double* loss_params, double* out_loss_sum, double* out_dloss,
+                                   double* out_weight_sum, uint8_t* out_ok);
+/* srhip_optimize_constants_batch with the rows sharded
+ * (src/ConstantOptimization.jl:22-65): the same optimiser, its evaluation sets
+ * group programs (SRHIP_PROGRAM_VARYING_CONSTANTS) scored by the two calls
+ * above. Outputs as srhip_optimize_constants_batch. */
+int32_t srhip_group_optimize_constants(srhip_group_dataset* gds, const srhip_trees* trees,
+                                       const srhip_constopt_options* opts, void* out_consts, double* out_loss,
+                                       uint8_t* out_converged, double* out_num_evals);
+
 /* ---- tree compiler ---------------------------------------------------------
  * Large programs are compiled to machine code, one block per tree
  * (symbolicregression.jl_amd/csrc/jit.cpp for Float32, jit64.cpp for

@@ -37,6 +37,10 @@ thread_local const char* t_last_kernel = "";
 }
 void note_kernel(const char* name) { t_last_kernel = name ? name : ""; }
 const char* last_kernel() { return t_last_kernel; }
+int& host_thread_cap() {
+  thread_local int cap = 0;
+  return cap;
+}
 }  // namespace srhip
 
 using namespace srhip;
@@ -3593,22 +3597,16 @@ double secs_since(std::chrono::steady_clock::time_point t0) {
 // The candidates of one evaluation set as a program on the engine (memory-
 // constant tree code: constant updates never recompile); loss and ∂L/∂c of
 // every member in one call each, finished as the reference's loss (:12-19).
-struct EngineSet : copt::Set {
-  srhip_ctx* ctx;
-  srhip_dataset* ds;
-  int dtype, loss;
-  const double* params;
-  srhip_program* prog = nullptr;
-  std::vector<int32_t> coff;  // members' constant offsets
-  EngineSet(srhip_ctx* c, srhip_dataset* d, const srhip_trees* trees, int dt, int ls, const double* pr,
-            const std::vector<int32_t>& members)
-      : ctx(c), ds(d), dtype(dt), loss(ls), params(pr) {
+// The members of an evaluation set (input tree indices, with repetition) as a
+// batch of their own: the trees' streams and constants copied in member order.
+struct MemberTrees {
+  std::vector<int32_t> noff{0}, coff{0};
+  std::vector<uint8_t> kind;
+  std::vector<uint16_t> arg;
+  std::vector<unsigned char> cst;
+  srhip_trees tr;
+  MemberTrees(const srhip_trees* trees, int dt, const std::vector<int32_t>& members) {
     const size_t es = dt == SRHIP_F32 ? 4 : 8;
-    std::vector<int32_t> noff{0};
-    std::vector<uint8_t> kind;
-    std::vector<uint16_t> arg;
-    std::vector<unsigned char> cst;
-    coff.push_back(0);
     for (int32_t t : members) {
       if (t < 0 || t >= trees->ntrees) throw Error(SRHIP_ERR_INVALID, "member out of range");
       const int32_t a = trees->node_off[t], b = trees->node_off[t + 1];
@@ -3620,13 +3618,28 @@ struct EngineSet : copt::Set {
       cst.insert(cst.end(), src + (size_t)ca * es, src + (size_t)cb * es);
       coff.push_back(coff.back() + (cb - ca));
     }
-    srhip_trees tr;
     tr.ntrees = (int32_t)members.size();
     tr.node_off = noff.data();
     tr.kind = kind.data();
     tr.arg = arg.data();
     tr.const_off = coff.data();
     tr.consts = cst.data();
+  }
+};
+
+struct EngineSet : copt::Set {
+  srhip_ctx* ctx;
+  srhip_dataset* ds;
+  int dtype, loss;
+  const double* params;
+  srhip_program* prog = nullptr;
+  std::vector<int32_t> coff;  // members' constant offsets
+  EngineSet(srhip_ctx* c, srhip_dataset* d, const srhip_trees* trees, int dt, int ls, const double* pr,
+            const std::vector<int32_t>& members)
+      : ctx(c), ds(d), dtype(dt), loss(ls), params(pr) {
+    MemberTrees mt(trees, dt, members);
+    coff = mt.coff;
+    const srhip_trees& tr = mt.tr;
     const auto t0 = std::chrono::steady_clock::now();
     check_rc(srhip_program_create_ex(ctx, dtype, &tr, SRHIP_PROGRAM_VARYING_CONSTANTS, &prog));
     t_copt.create += secs_since(t0);
@@ -3782,3 +3795,673 @@ int32_t srhip_optimize_constants_cb(const srhip_trees* trees, int32_t dtype, con
     return SRHIP_OK;
   });
 }
+
+// ---- device groups (srhip.h "device groups") ----------------------------------------
+// One process, several contexts: member k is a context on devices[k] with a
+// persistent driver thread that does the member's hipSetDevice, host planning
+// and enqueues. A group call is handed to every driver; each member leaves its
+// row shard's packed partials in slot k of a pinned host buffer every device
+// maps, member 0's stream waits for the others' events and one combine kernel
+// adds the slots in member order. DESIGN.md §5 "Device groups".
+namespace {
+
+constexpr int kMaxGroup = 16;
+
+// The driver thread of one member: runs the jobs posted to it, one at a time.
+class Driver {
+ public:
+  Driver() : th_([this] { loop(); }) {}
+  ~Driver() {
+    {
+      std::lock_guard<std::mutex> lk(m_);
+      stop_ = true;
+    }
+    cv_.notify_all();
+    th_.join();
+  }
+  void post(std::function<void()> f) {
+    {
+      std::lock_guard<std::mutex> lk(m_);
+      job_ = std::move(f);
+      has_ = true;
+    }
+    cv_.notify_all();
+  }
+  void wait() {
+    std::unique_lock<std::mutex> lk(m_);
+    cv_done_.wait(lk, [&] { return !has_; });
+  }
+
+ private:
+  void loop() {
+    std::unique_lock<std::mutex> lk(m_);
+    for (;;) {
+      cv_.wait(lk, [&] { return stop_ || has_; });
+      if (!has_) return;  // stop_
+      std::function<void()> f = std::move(job_);
+      lk.unlock();
+      f();
+      lk.lock();
+      has_ = false;
+      cv_done_.notify_all();
+    }
+  }
+  std::mutex m_;
+  std::condition_variable cv_, cv_done_;
+  std::function<void()> job_;
+  bool has_ = false, stop_ = false;
+  std::thread th_;  // last: the loop uses the members above
+};
+
+struct MemberStatus {
+  int rc = SRHIP_OK;
+  std::string msg;
+};
+
+}  // namespace
+
+struct srhip_group {
+  int ndev = 0;
+  std::vector<int32_t> devices;
+  std::vector<srhip_ctx*> ctx;
+  std::vector<std::unique_ptr<Driver>> drv;
+  std::vector<hipEvent_t> done;  // member k records it after its partials are enqueued
+  std::mutex mu;                 // one group call at a time
+  // pinned, mapped, portable host memory (coherent): the members' packed
+  // partials [ndev][slot_len], the gradient programs' static verdicts
+  // [ndev][verd_len], and the combined results — sums [nt], ∂L/∂c [nconst], Σw
+  // in res, ok [nt] in res_ok — with their addresses on each member's device
+  double* slots = nullptr;
+  uint8_t* verd = nullptr;
+  double* res = nullptr;
+  uint8_t* res_ok = nullptr;
+  size_t slot_len = 0, verd_len = 0;
+  std::vector<double*> d_slot;   // slot k as member k's device sees it
+  std::vector<uint8_t*> d_verd;
+  double* d_slots0 = nullptr;    // all slots, the results: member 0's device
+  double* d_res = nullptr;
+  uint8_t* d_res_ok = nullptr;
+};
+
+struct srhip_group_dataset {
+  srhip_group* g = nullptr;
+  int dtype = SRHIP_F32;
+  int64_t n = 0;
+  int nfeat = 0;
+  bool weighted = false;
+  std::vector<srhip_dataset*> ds;
+};
+
+struct srhip_group_program {
+  srhip_group* g = nullptr;
+  int dtype = SRHIP_F32;
+  int ntrees = 0, nconst = 0;
+  std::vector<srhip_program*> prog;
+  std::vector<int32_t> const_off;
+  std::vector<int32_t*> d_const_off;  // on each member's device (pack and combine kernels)
+};
+
+namespace {
+
+// fn(k) on every member's driver thread, all at once; returns when all are done
+template <typename F>
+std::vector<MemberStatus> run_members(srhip_group* g, F&& fn) {
+  std::vector<MemberStatus> st((size_t)g->ndev);
+  for (int k = 0; k < g->ndev; ++k)
+    g->drv[k]->post([&, k] {
+      st[k].rc = guarded([&] {
+        fn(k);
+        return SRHIP_OK;
+      });
+      if (st[k].rc != SRHIP_OK) st[k].msg = g_last_error;
+    });
+  for (int k = 0; k < g->ndev; ++k) g->drv[k]->wait();
+  return st;
+}
+
+// the first error in member order, as an Error on the calling thread
+void throw_first(const srhip_group* g, const std::vector<MemberStatus>& st) {
+  for (int k = 0; k < g->ndev; ++k)
+    if (st[k].rc != SRHIP_OK)
+      throw Error(st[k].rc, "group member " + std::to_string(k) + " (device " + std::to_string(g->devices[k]) +
+                                "): " + st[k].msg);
+}
+
+void free_group_pinned(srhip_group* g) {
+  for (void* h : {(void*)g->slots, (void*)g->verd, (void*)g->res, (void*)g->res_ok})
+    if (h) (void)hipHostFree(h);
+  g->slots = g->res = nullptr;
+  g->verd = g->res_ok = nullptr;
+  g->slot_len = g->verd_len = 0;
+}
+
+// the pinned buffers for partials of len doubles and nt trees (grow only)
+void ensure_group_buffers(srhip_group* g, size_t len, size_t nt) {
+  if (len <= g->slot_len && nt <= g->verd_len) return;
+  const size_t nl = std::max<size_t>(std::max(len, g->slot_len), 1024);
+  const size_t nv = std::max<size_t>(std::max(nt, g->verd_len), 512);
+  const unsigned flags = hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent;
+  auto st = run_members(g, [&](int k) {
+    if (k != 0) return;
+    HIP_CHECK(hipSetDevice(g->ctx[0]->device));
+    free_group_pinned(g);
+    HIP_CHECK(hipHostMalloc((void**)&g->slots, (size_t)g->ndev * nl * sizeof(double), flags));
+    HIP_CHECK(hipHostMalloc((void**)&g->verd, (size_t)g->ndev * nv, flags));
+    HIP_CHECK(hipHostMalloc((void**)&g->res, nl * sizeof(double), flags));
+    HIP_CHECK(hipHostMalloc((void**)&g->res_ok, nv, flags));
+    g->slot_len = nl;
+    g->verd_len = nv;
+  });
+  throw_first(g, st);
+  st = run_members(g, [&](int k) {
+    HIP_CHECK(hipSetDevice(g->ctx[k]->device));
+    void* d = nullptr;
+    HIP_CHECK(hipHostGetDevicePointer(&d, g->slots, 0));
+    g->d_slot[k] = static_cast<double*>(d) + (size_t)k * nl;
+    if (k == 0) g->d_slots0 = static_cast<double*>(d);
+    HIP_CHECK(hipHostGetDevicePointer(&d, g->verd, 0));
+    g->d_verd[k] = static_cast<uint8_t*>(d) + (size_t)k * nv;
+    if (k == 0) {
+      HIP_CHECK(hipHostGetDevicePointer(&d, g->res, 0));
+      g->d_res = static_cast<double*>(d);
+      HIP_CHECK(hipHostGetDevicePointer(&d, g->res_ok, 0));
+      g->d_res_ok = static_cast<uint8_t*>(d);
+    }
+  });
+  throw_first(g, st);
+}
+
+void shard_range(int64_t n, int32_t ndev, int32_t k, int64_t* begin, int64_t* end) {
+  const int64_t base = n / ndev, extra = n % ndev;
+  *begin = k * base + std::min<int64_t>(k, extra);
+  *end = *begin + base + (k < extra ? 1 : 0);
+}
+
+void destroy_group_program(srhip_group_program* gp) {
+  srhip_group* g = gp->g;
+  (void)run_members(g, [&](int k) {
+    if (gp->d_const_off[k]) {
+      (void)hipSetDevice(g->ctx[k]->device);
+      (void)hipFree(gp->d_const_off[k]);
+    }
+    if (gp->prog[k]) (void)srhip_program_destroy(gp->prog[k]);
+  });
+  delete gp;
+}
+
+srhip_group_program* create_group_program(srhip_group* g, int32_t dtype, const srhip_trees* trees, uint32_t flags) {
+  if (!g || !trees) throw Error(SRHIP_ERR_INVALID, "null argument");
+  std::unique_ptr<srhip_group_program> gp(new srhip_group_program());
+  gp->g = g;
+  gp->dtype = dtype;
+  gp->prog.assign((size_t)g->ndev, nullptr);
+  gp->d_const_off.assign((size_t)g->ndev, nullptr);
+  // the members build at once: the builders' host threads (8 for one program)
+  // are divided between them
+  const int cap = std::max(1, 8 / g->ndev);
+  std::lock_guard<std::mutex> lk(g->mu);
+  auto st = run_members(g, [&](int k) {
+    host_thread_cap() = cap;
+    const int32_t rc = srhip_program_create_ex(g->ctx[k], dtype, trees, flags, &gp->prog[k]);
+    host_thread_cap() = 0;
+    check_rc(rc);
+    const srhip_program* p = gp->prog[k];
+    HIP_CHECK(hipSetDevice(g->ctx[k]->device));
+    HIP_CHECK(hipMalloc((void**)&gp->d_const_off[k], p->const_off.size() * sizeof(int32_t)));
+    HIP_CHECK(hipMemcpy(gp->d_const_off[k], p->const_off.data(), p->const_off.size() * sizeof(int32_t),
+                        hipMemcpyHostToDevice));
+  });
+  for (int k = 0; k < g->ndev; ++k)
+    if (st[k].rc != SRHIP_OK) {
+      destroy_group_program(gp.release());
+      throw_first(g, st);
+    }
+  gp->ntrees = gp->prog[0]->ntrees;
+  gp->const_off = gp->prog[0]->const_off;
+  gp->nconst = gp->const_off.back();
+  return gp.release();
+}
+
+void set_group_constants(srhip_group_program* gp, const void* consts) {
+  if (!gp) throw Error(SRHIP_ERR_INVALID, "null group program");
+  srhip_group* g = gp->g;
+  std::lock_guard<std::mutex> lk(g->mu);
+  auto st = run_members(g, [&](int k) { check_rc(srhip_program_set_constants(gp->prog[k], consts)); });
+  throw_first(g, st);
+}
+
+// Member k's part of a group evaluation: its shard's packed partials into slot k
+// (enqueued on the member's stream, then its event recorded; *recorded false: the
+// host wrote the slot, nothing is in flight).
+template <typename T>
+void member_enqueue(srhip_group* g, int k, srhip_dataset* ds, srhip_program* p, const int32_t* d_const_off, bool grad,
+                    int loss, const double* params, bool* recorded) {
+  srhip_ctx* c = g->ctx[k];
+  check_program_vs_dataset(ds, p);
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_CHECK(hipSetDevice(c->device));
+  const int nt = p->ntrees;
+  const double wsum = ds->w ? ds->sum_w : (double)ds->rows;
+  double* slot = g->slots + (size_t)k * g->slot_len;  // host address
+  *recorded = false;
+  if (!grad) {
+    if (ds->rows == 0) {  // an empty shard launches nothing: the static verdicts, written here
+      timing_reset(c);
+      c->last_jit_trees = 0;
+      for (int t = 0; t < nt; ++t) {
+        slot[2 * (size_t)t] = 0.0;
+        slot[2 * (size_t)t + 1] = p->static_fail[t] ? 1.0 : 0.0;
+      }
+      slot[2 * (size_t)nt] = wsum;
+      return;
+    }
+    eval_loss_packed_impl<T>(ds, p, loss, params, g->d_slot[k]);
+  } else {
+    const int nconst = p->const_off.back();
+    build_grad_program<T>(p);
+    if (std::is_same<T, float>::value && loss == SRHIP_LOSS_PERIODIC && p->gjit) {
+      // Float32 Periodic with gradient tree code: the trees a tile of it failed are evaluated
+      // again by the forward-mode interpreter, which needs the host (eval_loss_grad_impl); the
+      // member packs the finished results here
+      std::vector<double> sum((size_t)std::max(nt, 1)), dl((size_t)std::max(nconst, 1));
+      std::vector<uint8_t> ok((size_t)std::max(nt, 1));
+      eval_loss_grad_impl<T>(ds, p, loss, params, sum.data(), dl.data(), nullptr, ok.data());
+      for (int t = 0; t < nt; ++t) {
+        slot[2 * (size_t)t] = ok[t] ? sum[t] : 0.0;
+        slot[2 * (size_t)t + 1] = ok[t] ? 0.0 : 1.0;
+        for (int32_t j = p->const_off[t]; j < p->const_off[t + 1]; ++j) slot[2 * (size_t)nt + j] = ok[t] ? dl[j] : 0.0;
+      }
+      slot[2 * (size_t)nt + nconst] = wsum;
+      return;
+    }
+    run_grad<T>(c, p, GRAD_LOSS, ds, loss, params ? params[0] : 0.0, nullptr, nullptr, 0);
+    const bool have = ds->rows > 0 && nt > 0 && (p->ngitems[0] + p->ngitems[1] + p->ngitems[2] + p->ngitems[3]) > 0;
+    if (ds->rows == 0) {
+      for (int t = 0; t < nt; ++t) {
+        slot[2 * (size_t)t] = 0.0;
+        slot[2 * (size_t)t + 1] = p->g_static_fail[t] ? 1.0 : 0.0;
+      }
+      for (int j = 0; j < nconst; ++j) slot[2 * (size_t)nt + j] = 0.0;
+      slot[2 * (size_t)nt + nconst] = wsum;
+      return;
+    }
+    uint8_t* verd = g->verd + (size_t)k * g->verd_len;
+    for (int t = 0; t < nt; ++t) verd[t] = p->g_static_fail[t] ? 1 : 0;
+    HIP_CHECK(launch_pack_grad_partials(static_cast<const double*>(c->sums.p), static_cast<const uint8_t*>(c->oks.p),
+                                        static_cast<const double*>(c->dloss.p), g->d_verd[k], d_const_off, nt, nconst,
+                                        have, wsum, g->d_slot[k], c->stream));
+  }
+  HIP_CHECK(hipEventRecord(g->done[k], c->stream));
+  *recorded = true;
+}
+
+// One group evaluation (loss, or loss and ∂L/∂c): every member enqueues its
+// shard and its partials; member 0 then makes its stream wait for the other
+// members' events, launches the combine kernel over the slots and waits for
+// its own stream — the call's one host wait on a device. The results reach the
+// caller's arrays only when every member succeeded.
+template <typename T>
+void group_eval(srhip_group_dataset* gds, srhip_group_program* gp, bool grad, int loss, const double* params,
+                double* out_sum, double* out_dloss, double* out_wsum, uint8_t* out_ok) {
+  srhip_group* g = gds->g;
+  const int ndev = g->ndev, nt = gp->ntrees, nconst = grad ? gp->nconst : 0;
+  const size_t len = 2 * (size_t)nt + nconst + 1;
+  std::lock_guard<std::mutex> call(g->mu);
+  ensure_group_buffers(g, len, (size_t)std::max(nt, 1));
+  std::mutex m;
+  std::condition_variable cv;
+  int left = ndev - 1;  // members other than 0 still enqueueing
+  bool failed = false;
+  std::vector<uint8_t> recorded((size_t)ndev, 0);
+  auto st = run_members(g, [&](int k) {
+    srhip_ctx* c = g->ctx[k];
+    auto arrive = [&](bool ok) {
+      std::lock_guard<std::mutex> lk(m);
+      if (!ok) failed = true;
+      if (k != 0) --left;
+      cv.notify_all();
+    };
+    try {
+      bool rec = false;
+      member_enqueue<T>(g, k, gds->ds[k], gp->prog[k], gp->d_const_off[k], grad, loss, params, &rec);
+      recorded[k] = rec ? 1 : 0;
+    } catch (...) {
+      (void)hipSetDevice(c->device);
+      (void)hipStreamSynchronize(c->stream);
+      arrive(false);
+      throw;
+    }
+    arrive(true);
+    if (k != 0) return;
+    {
+      std::unique_lock<std::mutex> lk(m);
+      cv.wait(lk, [&] { return left == 0; });
+      if (failed) return;  // the caller drains every stream and reports the member's error
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_CHECK(hipSetDevice(c->device));
+    for (int j = 1; j < ndev; ++j)
+      if (recorded[j]) HIP_CHECK(hipStreamWaitEvent(c->stream, g->done[j], 0));
+    HIP_CHECK(launch_combine_partials(g->d_slots0, g->slot_len, ndev, nt, nconst, grad ? gp->d_const_off[0] : nullptr,
+                                      g->d_res, g->d_res_ok, grad ? g->d_res + nt : nullptr, g->d_res + nt + nconst,
+                                      c->stream));
+    wait_stream(c->stream);
+    timing_finish(c);
+  });
+  bool bad = false;
+  for (const auto& s : st) bad = bad || s.rc != SRHIP_OK;
+  if (bad) {
+    (void)run_members(g, [&](int k) {
+      (void)hipSetDevice(g->ctx[k]->device);
+      (void)hipStreamSynchronize(g->ctx[k]->stream);
+    });
+    throw_first(g, st);
+  }
+  if (out_sum) std::copy(g->res, g->res + nt, out_sum);
+  if (out_ok) std::copy(g->res_ok, g->res_ok + nt, out_ok);
+  if (grad && out_dloss) std::copy(g->res + nt, g->res + nt + nconst, out_dloss);
+  if (out_wsum) *out_wsum = g->res[nt + nconst];
+}
+
+void group_eval_checked(srhip_group_dataset* gds, srhip_group_program* gp, bool grad, int32_t loss_kind,
+                        const double* loss_params, double* out_sum, double* out_dloss, double* out_wsum,
+                        uint8_t* out_ok) {
+  if (!gds || !gp) throw Error(SRHIP_ERR_INVALID, "null group dataset or program");
+  if (gds->g != gp->g) throw Error(SRHIP_ERR_INVALID, "the group program belongs to another group than the dataset");
+  if (gds->dtype != gp->dtype) throw Error(SRHIP_ERR_INVALID, "dataset and program dtypes differ");
+  check_loss(loss_kind, loss_params);
+  check_expr_loss_weights(loss_kind, gds->weighted);
+  if (gds->dtype == SRHIP_F32)
+    group_eval<float>(gds, gp, grad, loss_kind, loss_params, out_sum, out_dloss, out_wsum, out_ok);
+  else
+    group_eval<double>(gds, gp, grad, loss_kind, loss_params, out_sum, out_dloss, out_wsum, out_ok);
+}
+
+// The candidates of one evaluation set as a group program (EngineSet with the
+// rows sharded): the two group evaluations, finished as the reference's loss.
+struct GroupSet : copt::Set {
+  srhip_group_dataset* gds;
+  int dtype, loss;
+  const double* params;
+  srhip_group_program* gp = nullptr;
+  std::vector<int32_t> coff;
+  GroupSet(srhip_group_dataset* d, const srhip_trees* trees, int ls, const double* pr,
+           const std::vector<int32_t>& members)
+      : gds(d), dtype(d->dtype), loss(ls), params(pr) {
+    MemberTrees mt(trees, dtype, members);
+    coff = mt.coff;
+    gp = create_group_program(gds->g, dtype, &mt.tr, SRHIP_PROGRAM_VARYING_CONSTANTS);
+  }
+  ~GroupSet() override {
+    if (!gp) return;
+    std::lock_guard<std::mutex> lk(gds->g->mu);
+    destroy_group_program(gp);
+  }
+  void eval(const std::vector<double>& X, bool grad, std::vector<double>& f, std::vector<double>& g) override {
+    const int n = (int)coff.size() - 1;
+    const size_t nc = (size_t)coff.back();
+    if (X.size() != nc) throw Error(SRHIP_ERR_INVALID, "constant count mismatch");
+    if (dtype == SRHIP_F32) {
+      std::vector<float> c(nc);
+      for (size_t j = 0; j < nc; ++j) c[j] = (float)X[j];
+      set_group_constants(gp, c.data());
+    } else {
+      set_group_constants(gp, X.data());
+    }
+    std::vector<double> sums(std::max(n, 1)), dl(std::max<size_t>(nc, 1));
+    std::vector<uint8_t> ok(std::max(n, 1));
+    double wsum = 0.0;
+    group_eval_checked(gds, gp, grad, loss, params, sums.data(), grad ? dl.data() : nullptr, &wsum, ok.data());
+    f.assign(n, 0.0);
+    for (int t = 0; t < n; ++t) {
+      const double v = sums[t] / wsum;
+      f[t] = (ok[t] && std::isfinite(v)) ? v : INFINITY;
+    }
+    if (grad) {
+      g.assign(nc, 0.0);
+      for (int t = 0; t < n; ++t)
+        for (int32_t j = coff[t]; j < coff[t + 1]; ++j) g[j] = ok[t] ? dl[j] / wsum : NAN;
+    }
+  }
+};
+struct GroupFactory : copt::Factory {
+  srhip_group_dataset* gds;
+  const srhip_trees* trees;
+  int loss;
+  const double* params;
+  std::unique_ptr<copt::Set> make(const std::vector<int32_t>& members) override {
+    return std::unique_ptr<copt::Set>(new GroupSet(gds, trees, loss, params, members));
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int32_t srhip_group_shard_range(int64_t n, int32_t ndev, int32_t k, int64_t* begin, int64_t* end) {
+  return guarded([&] {
+    if (n < 0 || ndev < 1 || ndev > kMaxGroup || k < 0 || k >= ndev)
+      throw Error(SRHIP_ERR_INVALID, "shard range: need n >= 0, 1 <= ndev <= 16 and 0 <= k < ndev");
+    if (!begin || !end) throw Error(SRHIP_ERR_INVALID, "null output");
+    shard_range(n, ndev, k, begin, end);
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_open(const int32_t* devices, int32_t ndev, srhip_group** out) {
+  return guarded([&] {
+    if (!out) throw Error(SRHIP_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!devices) throw Error(SRHIP_ERR_INVALID, "null device list");
+    if (ndev < 1 || ndev > kMaxGroup) throw Error(SRHIP_ERR_INVALID, "a group has 1 to 16 members");
+    for (int k = 0; k < ndev; ++k)
+      if (devices[k] < 0) throw Error(SRHIP_ERR_INVALID, "negative device index");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) n = 0;
+    for (int k = 0; k < ndev; ++k)
+      if (devices[k] >= n)
+        throw Error(SRHIP_ERR_DEVICE, n == 0 ? std::string("no HIP device available")
+                                             : "group member " + std::to_string(k) + ": device " +
+                                                   std::to_string(devices[k]) + " of " + std::to_string(n));
+    std::unique_ptr<srhip_group> g(new srhip_group());
+    g->ndev = ndev;
+    g->devices.assign(devices, devices + ndev);
+    g->ctx.assign((size_t)ndev, nullptr);
+    g->done.assign((size_t)ndev, nullptr);
+    g->d_slot.assign((size_t)ndev, nullptr);
+    g->d_verd.assign((size_t)ndev, nullptr);
+    for (int k = 0; k < ndev; ++k) g->drv.emplace_back(new Driver());
+    auto st = run_members(g.get(), [&](int k) {
+      check_rc(srhip_open(g->devices[k], &g->ctx[k]));
+      // no timing; a system-scope release, so that what the member wrote to the
+      // pinned slots is visible to another device once the event has completed
+      HIP_CHECK(hipEventCreateWithFlags(&g->done[k], hipEventDisableTiming | hipEventReleaseToSystem));
+    });
+    for (int k = 0; k < ndev; ++k)
+      if (st[k].rc != SRHIP_OK) {
+        srhip_group* raw = g.release();
+        std::string msg;
+        try {
+          throw_first(raw, st);
+        } catch (const Error& e) {
+          msg = e.what();
+        }
+        (void)srhip_group_close(raw);
+        throw Error(st[k].rc, msg);
+      }
+    *out = g.release();
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_close(srhip_group* group) {
+  return guarded([&] {
+    if (!group) return SRHIP_OK;
+    {
+      std::lock_guard<std::mutex> lk(group->mu);
+      (void)run_members(group, [&](int k) {
+        if (!group->ctx[k]) return;
+        (void)hipSetDevice(group->ctx[k]->device);
+        (void)hipStreamSynchronize(group->ctx[k]->stream);
+        if (group->done[k]) (void)hipEventDestroy(group->done[k]);
+        if (k == 0) free_group_pinned(group);
+        (void)srhip_close(group->ctx[k]);
+        group->ctx[k] = nullptr;
+      });
+      group->drv.clear();  // joins the driver threads
+    }
+    delete group;
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_info(const srhip_group* group, int32_t* out_ndev, int32_t* devices_out) {
+  return guarded([&] {
+    if (!group) throw Error(SRHIP_ERR_INVALID, "null group");
+    if (out_ndev) *out_ndev = group->ndev;
+    if (devices_out) std::copy(group->devices.begin(), group->devices.end(), devices_out);
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_ctx(srhip_group* group, int32_t k, srhip_ctx** out) {
+  return guarded([&] {
+    if (!group || !out) throw Error(SRHIP_ERR_INVALID, "null group or out");
+    *out = nullptr;
+    if (k < 0 || k >= group->ndev) throw Error(SRHIP_ERR_INVALID, "member index out of range");
+    *out = group->ctx[k];
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_dataset_destroy(srhip_group_dataset* gds) {
+  return guarded([&] {
+    if (!gds) return SRHIP_OK;
+    {
+      std::lock_guard<std::mutex> lk(gds->g->mu);
+      (void)run_members(gds->g, [&](int k) {
+        if (gds->ds[k]) (void)srhip_dataset_destroy(gds->ds[k]);
+      });
+    }
+    delete gds;
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_dataset_create(srhip_group* group, int32_t dtype, int32_t x_layout, const void* X, const void* y,
+                                   const void* w, int64_t n, int32_t nfeat, srhip_group_dataset** out) {
+  return guarded([&] {
+    if (!group || !out) throw Error(SRHIP_ERR_INVALID, "null group or out");
+    *out = nullptr;
+    if (n < 0) throw Error(SRHIP_ERR_INVALID, "bad shape");
+    std::unique_ptr<srhip_group_dataset> gds(new srhip_group_dataset());
+    gds->g = group;
+    gds->dtype = dtype;
+    gds->n = n;
+    gds->nfeat = nfeat;
+    gds->weighted = w != nullptr;
+    gds->ds.assign((size_t)group->ndev, nullptr);
+    std::vector<MemberStatus> st;
+    {
+      std::lock_guard<std::mutex> lk(group->mu);
+      st = run_members(group, [&](int k) {
+        int64_t b, e;
+        shard_range(n, group->ndev, k, &b, &e);
+        check_rc(srhip_dataset_create(group->ctx[k], dtype, x_layout, X, y, w, n, nfeat, b, e, &gds->ds[k]));
+      });
+    }
+    for (int k = 0; k < group->ndev; ++k)
+      if (st[k].rc != SRHIP_OK) {
+        (void)srhip_group_dataset_destroy(gds.release());
+        throw_first(group, st);
+      }
+    *out = gds.release();
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_dataset_info(const srhip_group_dataset* gds, int64_t* out_rows, int32_t* out_nfeat,
+                                 double* out_sum_w, double* out_sum_yw, int32_t* out_x_finite) {
+  return guarded([&] {
+    if (!gds) throw Error(SRHIP_ERR_INVALID, "null group dataset");
+    double sw = 0.0, syw = 0.0;
+    bool fin = true;
+    for (const srhip_dataset* d : gds->ds) {  // member order
+      sw += d->sum_w;
+      syw += d->sum_yw;
+      fin = fin && d->x_finite;
+    }
+    if (out_rows) *out_rows = gds->n;
+    if (out_nfeat) *out_nfeat = gds->nfeat;
+    if (out_sum_w) *out_sum_w = sw;
+    if (out_sum_yw) *out_sum_yw = syw;
+    if (out_x_finite) *out_x_finite = fin ? 1 : 0;
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_program_create(srhip_group* group, int32_t dtype, const srhip_trees* trees, uint32_t flags,
+                                   srhip_group_program** out) {
+  return guarded([&] {
+    if (!out) throw Error(SRHIP_ERR_INVALID, "out is null");
+    *out = nullptr;
+    *out = create_group_program(group, dtype, trees, flags);
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_program_destroy(srhip_group_program* gp) {
+  return guarded([&] {
+    if (!gp) return SRHIP_OK;
+    std::lock_guard<std::mutex> lk(gp->g->mu);
+    destroy_group_program(gp);
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_program_set_constants(srhip_group_program* gp, const void* consts) {
+  return guarded([&] {
+    set_group_constants(gp, consts);
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_eval_loss(srhip_group_dataset* gds, srhip_group_program* gp, int32_t loss_kind,
+                              const double* loss_params, double* out_loss_sum, double* out_weight_sum,
+                              uint8_t* out_ok) {
+  return guarded([&] {
+    group_eval_checked(gds, gp, false, loss_kind, loss_params, out_loss_sum, nullptr, out_weight_sum, out_ok);
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_eval_loss_grad(srhip_group_dataset* gds, srhip_group_program* gp, int32_t loss_kind,
+                                   const double* loss_params, double* out_loss_sum, double* out_dloss,
+                                   double* out_weight_sum, uint8_t* out_ok) {
+  return guarded([&] {
+    group_eval_checked(gds, gp, true, loss_kind, loss_params, out_loss_sum, out_dloss, out_weight_sum, out_ok);
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_group_optimize_constants(srhip_group_dataset* gds, const srhip_trees* trees,
+                                       const srhip_constopt_options* opts, void* out_consts, double* out_loss,
+                                       uint8_t* out_converged, double* out_num_evals) {
+  return guarded([&] {
+    if (!gds) throw Error(SRHIP_ERR_INVALID, "null group dataset");
+    if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
+    check_loss(opts->loss_kind, opts->loss_params);
+    check_expr_loss_weights(opts->loss_kind, gds->weighted);
+    copt::Problem pb = make_problem(trees, gds->dtype);
+    GroupFactory fac;
+    fac.gds = gds;
+    fac.trees = trees;
+    fac.loss = opts->loss_kind;
+    fac.params = opts->loss_params;
+    const copt::Result r = copt::optimize(pb, make_copt_options(opts), fac);
+    write_result(r, gds->dtype, out_consts, out_loss, out_converged, out_num_evals, true);
+    return SRHIP_OK;
+  });
+}
+
+}  // extern "C"

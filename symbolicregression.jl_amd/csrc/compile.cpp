@@ -673,7 +673,8 @@ template <typename T>
 CompiledBatch<T> compile_batch_par(const srhip_trees& trees, bool grad, bool keep_layout) {
   const int nt = trees.ntrees;
   const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  const int nthr = (int)std::min<unsigned>(8u, hw);
+  const int cap = host_thread_cap();  // a device group's members share the 8
+  const int nthr = (int)std::min<unsigned>(cap > 0 ? (unsigned)std::min(cap, 8) : 8u, hw);
   if (nt < 2048 || nthr < 2) return compile_batch<T>(trees, grad, keep_layout);
   const int nchunk = nthr;
   std::vector<CompiledBatch<T>> part(nchunk);

@@ -1486,7 +1486,8 @@ static int codegen_threads() {
     const int hw = (int)std::max(1u, std::thread::hardware_concurrency());
     return e ? std::max(1, std::atoi(e)) : std::min(16, hw);
   }();
-  return n;
+  const int cap = host_thread_cap();  // a device group's members build concurrently
+  return cap > 0 ? std::min(n, cap) : n;
 }
 template <typename F>
 static void parallel_for(size_t n, F&& body) {

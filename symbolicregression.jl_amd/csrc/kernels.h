@@ -141,6 +141,17 @@ hipError_t launch_zero_words(uint32_t* a, int64_t na, uint32_t* b, int64_t nb, h
 // [Σ w·ℓ, failed] per tree + Σ w into device memory (srhip_eval_loss_packed)
 hipError_t launch_pack_partials(const double* sum, const uint8_t* ok, const uint8_t* verdict, int nt, int64_t rows,
                                 double wsum, double* out, hipStream_t stream);
+// the gradient's partials: [Σ w·ℓ, failed] per tree, Σ w·∂ℓ/∂c per constant, Σ w
+// (2·nt + nconst + 1 doubles; have: sum / ok / dloss hold this call's results)
+hipError_t launch_pack_grad_partials(const double* sum, const uint8_t* ok, const double* dloss,
+                                     const uint8_t* static_fail, const int32_t* const_off, int nt, int nconst,
+                                     bool have, double wsum, double* out, hipStream_t stream);
+// device groups: ndev packed partials (stride doubles apart) added in member
+// order and finished (NaN / ok = 0 for a tree that failed on any shard);
+// out_dloss null: the loss layout (nconst = 0)
+hipError_t launch_combine_partials(const double* slots, size_t stride, int ndev, int nt, int nconst,
+                                   const int32_t* const_off, double* out_sum, uint8_t* out_ok, double* out_dloss,
+                                   double* out_wsum, hipStream_t stream);
 hipError_t launch_gconst_finalize(const float* gpart, int nrg, int nconst, const int32_t* cidx, int ncidx,
                                   double* out, hipStream_t stream);
 // the same over Float64 partials (jit64.cpp's gradient tree code)

@@ -357,6 +357,83 @@ hipError_t launch_pack_partials(const double* sum, const uint8_t* ok, const uint
   return hipGetLastError();
 }
 
+namespace {
+// The gradient's row-shard partials (srhip/distributed.py pack_grad_partials):
+// [Σ w·ℓ (0 when failed), failed (1/0)] per tree, Σ w·∂ℓ/∂c per constant (0 for
+// a failed tree), then Σ w. One thread per tree writes the tree's pair and its
+// constants. static_fail: the gradient programs' static verdicts; have == 0:
+// nothing was launched (no rows, or no work items) and sum / ok / dloss are not
+// read — every value is 0 and a tree fails only statically.
+__global__ void pack_grad_partials_kernel(const double* __restrict__ sum, const uint8_t* __restrict__ ok,
+                                          const double* __restrict__ dloss, const uint8_t* __restrict__ static_fail,
+                                          const int32_t* __restrict__ const_off, int nt, int nconst, int have,
+                                          double wsum, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < nt) {
+    const bool fail = static_fail[t] != 0 || (have && ok[t] == 0);
+    out[2 * (size_t)t] = (fail || !have) ? 0.0 : sum[t];
+    out[2 * (size_t)t + 1] = fail ? 1.0 : 0.0;
+    for (int32_t k = const_off[t]; k < const_off[t + 1]; ++k)
+      out[2 * (size_t)nt + k] = (fail || !have) ? 0.0 : dloss[k];
+  }
+  if (t == 0) out[2 * (size_t)nt + nconst] = wsum;
+}
+
+// Device groups (srhip_group_eval_loss / _grad): the packed partials of the
+// members, slots[k] = slots + k·stride, added elementwise in member order
+// k = 0 … ndev-1 (fp64, starting from member 0's value), then finished as
+// unpack_partials / unpack_grad_partials do: a tree with a non-zero failure count
+// gets a NaN sum, ok = 0 and NaN for each of its constants. nconst == 0 with a
+// null out_dloss: the loss layout (no gradient block). One thread per tree.
+__global__ void combine_partials_kernel(const double* __restrict__ slots, size_t stride, int ndev, int nt, int nconst,
+                                        const int32_t* __restrict__ const_off, double* __restrict__ out_sum,
+                                        uint8_t* __restrict__ out_ok, double* __restrict__ out_dloss,
+                                        double* __restrict__ out_wsum) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < nt) {
+    double s = slots[2 * (size_t)t], f = slots[2 * (size_t)t + 1];
+    for (int k = 1; k < ndev; ++k) {
+      s += slots[k * stride + 2 * (size_t)t];
+      f += slots[k * stride + 2 * (size_t)t + 1];
+    }
+    const bool good = f == 0.0;
+    out_sum[t] = good ? s : __builtin_nan("");
+    out_ok[t] = good ? 1 : 0;
+    if (out_dloss)
+      for (int32_t c = const_off[t]; c < const_off[t + 1]; ++c) {
+        const size_t j = 2 * (size_t)nt + c;
+        double g = slots[j];
+        for (int k = 1; k < ndev; ++k) g += slots[k * stride + j];
+        out_dloss[c] = good ? g : __builtin_nan("");
+      }
+  }
+  if (t == 0) {
+    const size_t j = 2 * (size_t)nt + nconst;
+    double w = slots[j];
+    for (int k = 1; k < ndev; ++k) w += slots[k * stride + j];
+    *out_wsum = w;
+  }
+}
+}  // namespace
+
+hipError_t launch_pack_grad_partials(const double* sum, const uint8_t* ok, const double* dloss,
+                                     const uint8_t* static_fail, const int32_t* const_off, int nt, int nconst,
+                                     bool have, double wsum, double* out, hipStream_t stream) {
+  const unsigned grid = (unsigned)std::max(1, (nt + 255) / 256);
+  hipLaunchKernelGGL(pack_grad_partials_kernel, dim3(grid), dim3(256), 0, stream, sum, ok, dloss, static_fail,
+                     const_off, nt, nconst, have ? 1 : 0, wsum, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_combine_partials(const double* slots, size_t stride, int ndev, int nt, int nconst,
+                                   const int32_t* const_off, double* out_sum, uint8_t* out_ok, double* out_dloss,
+                                   double* out_wsum, hipStream_t stream) {
+  const unsigned grid = (unsigned)std::max(1, (nt + 255) / 256);
+  hipLaunchKernelGGL(combine_partials_kernel, dim3(grid), dim3(256), 0, stream, slots, stride, ndev, nt, nconst,
+                     const_off, out_sum, out_ok, out_dloss, out_wsum);
+  return hipGetLastError();
+}
+
 hipError_t launch_zero_words(uint32_t* a, int64_t na, uint32_t* b, int64_t nb, hipStream_t stream) {
   if (na + nb <= 0) return hipSuccess;
   const unsigned grid = (unsigned)std::min<int64_t>(1024, (na + nb + 255) / 256);

@@ -193,4 +193,9 @@ constexpr int kExprOpMaxDepth = 4;
 void note_kernel(const char* name);
 const char* last_kernel();
 
+// The most host threads a program build on the calling thread may start
+// (0: no cap beyond each builder's own). The members of a device group build
+// concurrently and share the builders' budget between them.
+int& host_thread_cap();
+
 }  // namespace srhip

@@ -25,6 +25,9 @@
 #   * `optimize_and_simplify_population_batched` — optimize_and_simplify_population
 #     (src/SingleIteration.jl:63-123): the members drawn for optimisation go
 #     through one batched optimiser call instead of one Optim run each.
+#   * every function above that ends in an SRHip call takes `device::Int=0` and passes
+#     it down; `s_r_cycle_devices` runs the islands with (k - 1) % ndev == d on the
+#     d-th device of an SRHip.DeviceGroup, one task per device (INTEGRATION.md §4).
 #
 # next_generation is split into `propose` (mutation choice, attempts,
 # check_constraints — everything before score_func, calling the reference's
@@ -65,10 +68,11 @@ import ..SRHip
 score_func (src/LossFunctions.jl:86-92) for every tree: one SRHip launch when
 the engine covers the options, else the reference, tree by tree.
 """
-function score_batch(dataset::Dataset{T}, trees::AbstractVector{Node{T}}, options::Options) where {T}
+function score_batch(dataset::Dataset{T}, trees::AbstractVector{Node{T}}, options::Options;
+                     device::Int=0) where {T}
     if !isempty(trees) && SRHip.enabled(options)
         try
-            losses = SRHip.eval_loss_batch(trees, dataset, options)
+            losses = SRHip.eval_loss_batch(trees, dataset, options; device=device)
             scores = [loss_to_score(l, dataset.baseline_loss, t, options) for (l, t) in zip(losses, trees)]
             return scores, losses
         catch e
@@ -88,11 +92,12 @@ draws one per call (:98), all trees in one launch
 (SRHip.eval_loss_batch_rowsets); a failed evaluation scores (0, Inf) as in
 the reference.
 """
-function score_batch_minibatch(dataset::Dataset{T}, trees::AbstractVector{Node{T}}, options::Options) where {T}
+function score_batch_minibatch(dataset::Dataset{T}, trees::AbstractVector{Node{T}}, options::Options;
+                               device::Int=0) where {T}
     if !isempty(trees) && SRHip.enabled(options)
         try
             idx = rand(1:(dataset.n), options.batch_size, length(trees))  # column t: tree t's sample
-            losses = SRHip.eval_loss_batch_rowsets(trees, dataset, options, idx)
+            losses = SRHip.eval_loss_batch_rowsets(trees, dataset, options, idx; device=device)
             scores = [isfinite(l) ? loss_to_score(l, dataset.baseline_loss, t, options) : zero(T)
                       for (l, t) in zip(losses, trees)]
             return scores, losses
@@ -108,9 +113,9 @@ end
 
 """Population(dataset; npop, nlength, options, nfeatures) with one launch."""
 function population_batched(dataset::Dataset{T}; npop::Int, nlength::Int=3, options::Options,
-                            nfeatures::Int) where {T}
+                            nfeatures::Int, device::Int=0) where {T}
     trees = [gen_random_tree(nlength, options, nfeatures, T) for _ in 1:npop]
-    scores, losses = score_batch(dataset, trees, options)
+    scores, losses = score_batch(dataset, trees, options; device=device)
     members = [PopMember(trees[i], scores[i], losses[i]; parent=-1, deterministic=options.deterministic)
                for i in 1:npop]
     return Population{T}(members, npop)
@@ -118,9 +123,10 @@ end
 
 """finalize_scores (src/Population.jl:134-148): with batching, every member is
 re-scored on the full dataset — one launch for the population."""
-function finalize_scores_batched(dataset::Dataset{T}, pop::Population, options::Options) where {T}
+function finalize_scores_batched(dataset::Dataset{T}, pop::Population, options::Options;
+                                 device::Int=0) where {T}
     options.batching || return (pop, 0.0)
-    scores, losses = score_batch(dataset, [m.tree for m in pop.members], options)
+    scores, losses = score_batch(dataset, [m.tree for m in pop.members], options; device=device)
     for (m, s, l) in zip(pop.members, scores, losses)
         m.score = s
         m.loss = l
@@ -140,12 +146,12 @@ One SRHip call when the engine covers the options, else the reference member
 by member.
 """
 function optimize_constants_batched(dataset::Dataset{T}, members::AbstractVector{<:PopMember{T}},
-                                    options::Options) where {T}
+                                    options::Options; device::Int=0) where {T}
     isempty(members) && return Float64[]
     if SRHip.enabled(options)
         try
             trees = Node{T}[m.tree for m in members]
-            losses, converged, num_evals = SRHip.optimize_constants_batch!(trees, dataset, options)
+            losses, converged, num_evals = SRHip.optimize_constants_batch!(trees, dataset, options; device=device)
             for (m, l, c) in zip(members, losses, converged)
                 c || continue
                 m.score = loss_to_score(l, dataset.baseline_loss, m.tree, options)
@@ -173,15 +179,15 @@ optimised in one batched call and finalize_scores as one launch; the
 simplification, the new references and the record are the reference's.
 """
 function optimize_and_simplify_population_batched(dataset::Dataset{T}, pop::Population, options::Options,
-                                                  curmaxsize::Int, record::RecordType) where {T}
+                                                  curmaxsize::Int, record::RecordType; device::Int=0) where {T}
     do_optimization = rand(pop.n) .< options.optimizer_probability
     for j in 1:(pop.n)
         pop.members[j].tree = simplify_tree(pop.members[j].tree, options.operators)
         pop.members[j].tree = combine_operators(pop.members[j].tree, options.operators)
     end
     chosen = options.should_optimize_constants ? findall(do_optimization) : Int[]
-    num_evals = sum(optimize_constants_batched(dataset, pop.members[chosen], options); init=0.0)
-    pop, tmp_num_evals = finalize_scores_batched(dataset, pop, options)
+    num_evals = sum(optimize_constants_batched(dataset, pop.members[chosen], options; device=device); init=0.0)
+    pop, tmp_num_evals = finalize_scores_batched(dataset, pop, options; device=device)
     num_evals += tmp_num_evals
     for j in 1:(pop.n)
         old_ref = pop.members[j].ref
@@ -306,7 +312,11 @@ per island, in the reference's order.
 """
 function reg_evol_cycle_batched(dataset::Dataset{T}, pops::AbstractVector{<:Population}, temperature,
                                 curmaxsize::Int, stats::AbstractVector{RunningSearchStatistics},
-                                options::Options) where {T}
+                                options::Options; device::Int=0) where {T}
+    # this cycle's scoring and optimiser calls, on its device
+    score_batch(ds, ts, o) = BatchedCallers.score_batch(ds, ts, o; device=device)
+    score_batch_minibatch(ds, ts, o) = BatchedCallers.score_batch_minibatch(ds, ts, o; device=device)
+    optimize_constants_batched(ds, ms, o) = BatchedCallers.optimize_constants_batched(ds, ms, o; device=device)
     proposals = Vector{Vector{Proposal{T}}}(undef, length(pops))
     allstars = Vector{Vector{PopMember{T}}}(undef, length(pops))
     for (k, pop) in enumerate(pops)
@@ -412,7 +422,11 @@ exactly the serial per-island result.
 """
 function reg_evol_cycle_lockstep(dataset::Dataset{T}, pops::AbstractVector{<:Population}, temperature,
                                  curmaxsize::Int, stats::AbstractVector{RunningSearchStatistics},
-                                 options::Options) where {T}
+                                 options::Options; device::Int=0) where {T}
+    # this cycle's scoring and optimiser calls, on its device
+    score_batch(ds, ts, o) = BatchedCallers.score_batch(ds, ts, o; device=device)
+    score_batch_minibatch(ds, ts, o) = BatchedCallers.score_batch_minibatch(ds, ts, o; device=device)
+    optimize_constants_batched(ds, ms, o) = BatchedCallers.optimize_constants_batched(ds, ms, o; device=device)
     num_evals = 0.0
     nsteps = round(Int, pops[1].n / options.tournament_selection_n)
     for _ in 1:nsteps
@@ -511,7 +525,7 @@ island runs the reference's own s_r_cycle instead, recording into records[k].
 """
 function s_r_cycle_lockstep(dataset::Dataset{T}, pops::AbstractVector{<:Population}, ncycles::Int,
                             curmaxsize::Int, stats::AbstractVector{RunningSearchStatistics},
-                            options::Options; records=nothing) where {T}
+                            options::Options; records=nothing, device::Int=0) where {T}
     if options.recorder
         best_seen = Vector{HallOfFame{T}}(undef, length(pops))
         num_evals = 0.0
@@ -529,8 +543,8 @@ function s_r_cycle_lockstep(dataset::Dataset{T}, pops::AbstractVector{<:Populati
     num_evals = 0.0
     for temperature in LinRange(max_temp, min_temp, ncycles)
         _, ev = options.fast_cycle ?
-                reg_evol_cycle_batched(dataset, pops, temperature, curmaxsize, stats, options) :
-                reg_evol_cycle_lockstep(dataset, pops, temperature, curmaxsize, stats, options)
+                reg_evol_cycle_batched(dataset, pops, temperature, curmaxsize, stats, options; device=device) :
+                reg_evol_cycle_lockstep(dataset, pops, temperature, curmaxsize, stats, options; device=device)
         num_evals += ev
         for (k, pop) in enumerate(pops), member in pop.members
             size = compute_complexity(member.tree, options)
@@ -540,6 +554,49 @@ function s_r_cycle_lockstep(dataset::Dataset{T}, pops::AbstractVector{<:Populati
                 best_seen[k].members[size] = copy_pop_member(member)
             end
         end
+    end
+    return pops, best_seen, num_evals
+end
+
+"""
+    s_r_cycle_devices(dataset, pops, ncycles, curmaxsize, stats, options, group) -> (pops, best_seen, num_evals)
+
+s_r_cycle_lockstep spread over the devices of `group` (an SRHip.DeviceGroup):
+island k (1-based) belongs to member d = (k - 1) % ndev, the islands of one
+member run their lockstep cycles together on that member's device
+(`device = group.devices[d + 1]`), and the members run at once, one task per
+member (src/SearchUtils.jl:33-45 spawns one per island; here one per device,
+each scoring its islands' candidates in one launch). Every task scores through
+the single-device calls on its device's full copy of the dataset, so an island
+computes what it computes alone. Migration, the hall of fame and the
+statistics stay on the host with the caller, between rounds, as in the
+reference (src/SymbolicRegression.jl:717-778). The results come back in
+island order.
+"""
+function s_r_cycle_devices(dataset::Dataset{T}, pops::AbstractVector{<:Population}, ncycles::Int,
+                           curmaxsize::Int, stats::AbstractVector{RunningSearchStatistics},
+                           options::Options, group::SRHip.DeviceGroup; records=nothing) where {T}
+    ndev = SRHip.ndevices(group)
+    parts = [collect(d:ndev:length(pops)) for d in 1:ndev]   # islands of member d - 1
+    tasks = map(1:ndev) do d
+        ks = parts[d]
+        Threads.@spawn begin
+            isempty(ks) && return (ks, nothing, nothing, 0.0)
+            p, b, ev = s_r_cycle_lockstep(dataset, pops[ks], ncycles, curmaxsize, stats[ks], options;
+                                          records=(records === nothing ? nothing : records[ks]),
+                                          device=Int(group.devices[d]))
+            (ks, p, b, ev)
+        end
+    end
+    best_seen = Vector{HallOfFame{T}}(undef, length(pops))
+    num_evals = 0.0
+    for t in tasks
+        ks, p, b, ev = fetch(t)
+        for (i, k) in enumerate(ks)
+            pops[k] = p[i]
+            best_seen[k] = b[i]
+        end
+        num_evals += ev
     end
     return pops, best_seen, num_evals
 end

@@ -666,4 +666,220 @@ function _const_grads(tree::Node{T}, X::AbstractMatrix{T}, options::Options, dev
     return value, G, ok[] == 1
 end
 
+# ---- device groups (srhip.h "device groups"): one process, row shards over several GPUs ----
+# A group owns one context and one driver thread per entry of `devices` (a device
+# may be listed more than once). Its datasets hold one row shard per member, its
+# programs one identical program per member, and an evaluation combines the
+# shards on the device in member order. The search's islands do not go through
+# the group calls: island k runs on device devices[k % ndev] through the
+# single-device functions above (`device=`), see BatchedCallers.s_r_cycle_devices.
+"""
+    DeviceGroup(devices)
+
+Open a device group (srhip_group_open) on `devices` (0-based device indices, 1
+to 16 of them). Closed by `close!` or by the finaliser; the group datasets and
+programs made through it are destroyed first.
+"""
+mutable struct DeviceGroup
+    h::Ptr{Cvoid}
+    devices::Vector{Int32}
+    children::Vector{WeakRef}   # live GroupCopy / GroupProgram objects, destroyed before the group
+end
+function DeviceGroup(devices::AbstractVector{<:Integer})
+    devs = Vector{Int32}(devices)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve devs check(ccall((:srhip_group_open, libsrhip), Int32, (Ptr{Int32}, Int32, Ptr{Ptr{Cvoid}}),
+                                  devs, Int32(length(devs)), h))
+    g = DeviceGroup(h[], devs, WeakRef[])
+    finalizer(close!, g)
+    return g
+end
+function close!(g::DeviceGroup)
+    g.h == C_NULL && return nothing
+    for r in g.children
+        r.value === nothing || free!(r.value)
+    end
+    empty!(g.children)
+    ccall((:srhip_group_close, libsrhip), Int32, (Ptr{Cvoid},), g.h)
+    g.h = C_NULL
+    return nothing
+end
+ndevices(g::DeviceGroup) = length(g.devices)
+
+"""Member k's (0-based) context, lent (srhip_group_ctx): the group owns it."""
+function group_context(g::DeviceGroup, k::Int)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:srhip_group_ctx, libsrhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}), g.h, Int32(k), h))
+    return h[]
+end
+
+"""Rows (0-based, half-open) of member k of ndev over n rows (srhip_group_shard_range)."""
+function shard_range(n::Integer, ndev::Integer, k::Integer)
+    b = Ref{Int64}(0); e = Ref{Int64}(0)
+    check(ccall((:srhip_group_shard_range, libsrhip), Int32, (Int64, Int32, Int32, Ptr{Int64}, Ptr{Int64}),
+                Int64(n), Int32(ndev), Int32(k), b, e))
+    return b[], e[]
+end
+
+# one sharded copy per (Dataset, group), uploaded once; held weakly like DEVICE_DATASETS
+mutable struct GroupCopy
+    h::Ptr{Cvoid}
+    group::DeviceGroup
+end
+function free!(d::GroupCopy)
+    (d.h == C_NULL || d.group.h == C_NULL) && (d.h = C_NULL; return nothing)
+    ccall((:srhip_group_dataset_destroy, libsrhip), Int32, (Ptr{Cvoid},), d.h)
+    d.h = C_NULL
+    return nothing
+end
+const GROUP_DATASETS = WeakKeyDict{Dataset,IdDict{DeviceGroup,GroupCopy}}()
+function group_dataset(dataset::Dataset{T}, group::DeviceGroup) where {T}
+    lock(CTX_LOCK) do
+        copies = get!(() -> IdDict{DeviceGroup,GroupCopy}(), GROUP_DATASETS, dataset)
+        d = get(copies, group, nothing)
+        d !== nothing && d.h != C_NULL && return d.h
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        Xc = Matrix{T}(dataset.X); yc = Vector{T}(dataset.y)
+        wc = dataset.weighted ? Vector{T}(dataset.weights) : nothing
+        nfeat, n = size(Xc)
+        GC.@preserve Xc yc wc begin
+            check(ccall((:srhip_group_dataset_create, libsrhip), Int32,
+                        (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Int64, Int32, Ptr{Ptr{Cvoid}}),
+                        group.h, dtype_code(T), X_JULIA, Xc, yc, wc === nothing ? Ptr{T}(C_NULL) : wc, n, nfeat, h))
+        end
+        d = GroupCopy(h[], group)
+        finalizer(free!, d)
+        push!(group.children, WeakRef(d))
+        copies[group] = d
+        return d.h
+    end
+end
+
+# one identical program per member (srhip_group_program_create)
+mutable struct GroupProgram
+    h::Ptr{Cvoid}
+    ntrees::Int
+    const_off::Vector{Int32}
+    group::DeviceGroup
+end
+function free!(p::GroupProgram)
+    (p.h == C_NULL || p.group.h == C_NULL) && (p.h = C_NULL; return nothing)
+    ccall((:srhip_group_program_destroy, libsrhip), Int32, (Ptr{Cvoid},), p.h)
+    p.h = C_NULL
+    return nothing
+end
+destroy(p::GroupProgram) = free!(p)
+function GroupProgram(trees::AbstractVector{Node{T}}, options::Options, group::DeviceGroup;
+                      varying_constants::Bool=false) where {T}
+    node_off, kind, arg, const_off, consts = flatten(trees, options)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    flags = varying_constants ? PROGRAM_VARYING_CONSTANTS : UInt32(0)
+    GC.@preserve node_off kind arg const_off consts begin
+        tr = Ref(SrhipTrees(Int32(length(trees)), pointer(node_off), pointer(kind), pointer(arg),
+                            pointer(const_off), Ptr{Cvoid}(pointer(consts))))
+        check(ccall((:srhip_group_program_create, libsrhip), Int32,
+                    (Ptr{Cvoid}, Int32, Ref{SrhipTrees}, UInt32, Ptr{Ptr{Cvoid}}),
+                    group.h, dtype_code(T), tr, flags, h))
+    end
+    p = GroupProgram(h[], length(trees), const_off, group)
+    finalizer(free!, p)
+    lock(() -> push!(group.children, WeakRef(p)), CTX_LOCK)
+    return p
+end
+function set_constants!(p::GroupProgram, consts::Vector{T}) where {T}
+    length(consts) == p.const_off[end] || throw(ArgumentError("expected $(p.const_off[end]) constants"))
+    GC.@preserve consts check(ccall((:srhip_group_program_set_constants, libsrhip), Int32,
+                                    (Ptr{Cvoid}, Ptr{Cvoid}), p.h, consts))
+    return p
+end
+
+"""
+    eval_loss_batch(trees, dataset, options, group::DeviceGroup) -> Vector{T}
+
+`eval_loss_batch` with the dataset's rows sharded over `group` (all rows: no `idx`).
+"""
+function eval_loss_batch(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, options::Options,
+                         group::DeviceGroup) where {T}
+    nt = length(trees)
+    p = GroupProgram(trees, options, group)
+    sums = Vector{Float64}(undef, nt); ok = Vector{UInt8}(undef, nt); wsum = Ref{Float64}(0)
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    try
+        GC.@preserve sums ok params check(ccall((:srhip_group_eval_loss, libsrhip), Int32,
+                                                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64},
+                                                 Ref{Float64}, Ptr{UInt8}),
+                                                group_dataset(dataset, group), p.h, kindcode, params, sums, wsum, ok))
+    finally
+        destroy(p)
+    end
+    return [ok[i] == 1 ? T(sums[i] / wsum[]) : T(Inf) for i in 1:nt]
+end
+
+"""
+    eval_loss_grad(p::GroupProgram, dataset, options) -> (losses, grads, ok)
+
+`eval_loss_grad_batch` over the group of `p` (srhip_group_eval_loss_grad).
+"""
+function eval_loss_grad(p::GroupProgram, dataset::Dataset{T}, options::Options) where {T}
+    nt = p.ntrees
+    ncon = Int(p.const_off[end])
+    sums = Vector{Float64}(undef, nt); ok = Vector{UInt8}(undef, nt); wsum = Ref{Float64}(0)
+    dloss = Vector{Float64}(undef, ncon)
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    GC.@preserve sums ok dloss params begin
+        check(ccall((:srhip_group_eval_loss_grad, libsrhip), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
+                     Ptr{UInt8}),
+                    group_dataset(dataset, p.group), p.h, kindcode, params, sums, dloss, wsum, ok))
+    end
+    losses = [ok[i] == 1 ? T(sums[i] / wsum[]) : T(Inf) for i in 1:nt]
+    grads = [dloss[(p.const_off[i] + 1):p.const_off[i + 1]] ./ wsum[] for i in 1:nt]
+    return losses, grads, ok .== 1
+end
+
+"""
+    optimize_constants_batch!(trees, dataset, options, group::DeviceGroup) -> (losses, converged, num_evals)
+
+`optimize_constants_batch!` with the dataset's rows sharded over `group`
+(srhip_group_optimize_constants): the same optimiser and start noise.
+"""
+function optimize_constants_batch!(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, options::Options,
+                                   group::DeviceGroup) where {T}
+    algo = options.optimizer_algorithm == "BFGS" ? OPT_BFGS :
+           options.optimizer_algorithm == "NelderMead" ? OPT_NELDERMEAD :
+           error("Optimization function not implemented.")
+    node_off, kind, arg, const_off, consts = flatten(trees, options)
+    nt = length(trees)
+    nr = options.optimizer_nrestarts
+    noise = Float64[]
+    for i in 1:nt
+        nc = Int(const_off[i + 1] - const_off[i])
+        nc == 0 && continue
+        for _ in 1:nr
+            append!(noise, Float64.(randn(T, nc)))
+        end
+    end
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    out_c = similar(consts); out_l = Vector{Float64}(undef, nt)
+    out_k = Vector{UInt8}(undef, nt); out_n = Vector{Float64}(undef, nt)
+    GC.@preserve node_off kind arg const_off consts noise params out_c out_l out_k out_n begin
+        tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
+                            Ptr{Cvoid}(pointer(consts))))
+        opts = Ref(ConstOptOptions(algo, Int32(options.optimizer_options.iterations), Int32(nr), kindcode,
+                                   pointer(params), pointer(noise), UInt64(0)))
+        check(ccall((:srhip_group_optimize_constants, libsrhip), Int32,
+                    (Ptr{Cvoid}, Ref{SrhipTrees}, Ref{ConstOptOptions}, Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8},
+                     Ptr{Float64}),
+                    group_dataset(dataset, group), tr, opts, out_c, out_l, out_k, out_n))
+    end
+    converged = out_k .== 1
+    for i in 1:nt
+        converged[i] && set_constants(trees[i], out_c[(const_off[i] + 1):const_off[i + 1]])
+    end
+    return T.(out_l), converged, out_n
+end
+
 end # module

@@ -129,6 +129,26 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "srhip_debug_constant_map": [C.POINTER(Trees), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
+    # device groups
+    "srhip_group_open": [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)],
+    "srhip_group_close": [C.c_void_p],
+    "srhip_group_info": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "srhip_group_ctx": [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)],
+    "srhip_group_shard_range": [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "srhip_group_dataset_create": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_int32, C.POINTER(C.c_void_p)],
+    "srhip_group_dataset_destroy": [C.c_void_p],
+    "srhip_group_dataset_info": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_int32)],
+    "srhip_group_program_create": [C.c_void_p, C.c_int32, C.POINTER(Trees), C.c_uint32, C.POINTER(C.c_void_p)],
+    "srhip_group_program_destroy": [C.c_void_p],
+    "srhip_group_program_set_constants": [C.c_void_p, C.c_void_p],
+    "srhip_group_eval_loss": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                              C.c_void_p],
+    "srhip_group_eval_loss_grad": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_double), C.c_void_p],
+    "srhip_group_optimize_constants": [C.c_void_p, C.POINTER(Trees), C.POINTER(ConstOptOptions), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p],
 }
 
 

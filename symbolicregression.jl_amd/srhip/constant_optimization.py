@@ -33,7 +33,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from ._lib import CONSTOPT_EVAL_FN, ConstOptOptions, check, lib
-from .dataset import Dataset
+from .dataset import Dataset, GroupDataset
 from .engine import _trees_struct
 from .node import Node, flatten, set_constants
 from .options import Options
@@ -112,7 +112,10 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
     out_k = np.zeros(max(nt, 1), dtype=np.uint8)
     out_n = np.zeros(max(nt, 1))
     ptrs = [a.ctypes.data_as(C.c_void_p) for a in (out_c, out_l, out_k, out_n)]
-    if evaluator_factory is None:
+    if evaluator_factory is None and isinstance(dataset, GroupDataset):
+        # the rows sharded over a device group (srhip_group_optimize_constants)
+        check(lib().srhip_group_optimize_constants(dataset.handle, C.byref(tr), C.byref(opts), *ptrs))
+    elif evaluator_factory is None:
         dev = dataset.device(device)
         check(lib().srhip_optimize_constants_batch(dev.ctx.handle, dev.handle, C.byref(tr), C.byref(opts), *ptrs))
     else:

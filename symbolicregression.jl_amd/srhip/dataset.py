@@ -46,3 +46,67 @@ class Dataset:
             d = DeviceDataset(ctx, self.X, self.y, self.weights, rb, re)
             self._dev[ctx.device] = d
         return d
+
+
+class GroupDataset(Dataset):
+    """A Dataset whose rows are sharded over the members of a DeviceGroup
+    (srhip_group_dataset), uploaded when it is made. eval_loss_batch_ok,
+    eval_loss_grad_batch and optimize_constants_batch take it where they take
+    a Dataset and then run over the whole group."""
+
+    def __init__(self, group, X: np.ndarray, y: np.ndarray, weights: Optional[np.ndarray] = None,
+                 varMap: Optional[Sequence[str]] = None):
+        import ctypes as C
+
+        from . import constants as K
+        from ._lib import check, lib
+        from .engine import DeviceGroup, dtype_code
+
+        if not isinstance(group, DeviceGroup):
+            raise TypeError("group must be a DeviceGroup")
+        self.handle = None
+        super().__init__(X, y, weights, varMap)
+        self.group = group
+        dt = np.dtype(self.T)
+        if self.X.flags.c_contiguous:
+            layout, Xa = K.X_FEATURE_MAJOR, np.ascontiguousarray(self.X, dtype=dt)
+        else:  # Fortran order = Julia's column-major (nfeatures, n)
+            layout, Xa = K.X_JULIA, np.asfortranarray(self.X, dtype=dt)
+        ya = np.ascontiguousarray(self.y, dtype=dt)
+        wa = None if self.weights is None else np.ascontiguousarray(self.weights, dtype=dt)
+        if ya.shape != (self.n,) or (wa is not None and wa.shape != (self.n,)):
+            raise AssertionError("Dataset dimensions are invalid")  # Configure.jl:53-60
+        h = C.c_void_p()
+        check(lib().srhip_group_dataset_create(group._live(), dtype_code(dt), layout, Xa.ctypes.data, ya.ctypes.data,
+                                               None if wa is None else wa.ctypes.data, self.n, self.nfeatures,
+                                               C.byref(h)))
+        self.handle = h
+
+    def device(self, device: Optional[int] = None):
+        raise TypeError("a GroupDataset lives on its group's members; use group.context(k) with a Dataset for one device")
+
+    def info(self):
+        import ctypes as C
+
+        from ._lib import check, lib
+
+        if not self.handle:
+            raise ValueError("the group dataset is closed")
+        rows, nf, fin = C.c_int64(), C.c_int32(), C.c_int32()
+        sw, syw = C.c_double(), C.c_double()
+        check(lib().srhip_group_dataset_info(self.handle, C.byref(rows), C.byref(nf), C.byref(sw), C.byref(syw),
+                                             C.byref(fin)))
+        return dict(rows=rows.value, nfeat=nf.value, sum_w=sw.value, sum_yw=syw.value, x_finite=bool(fin.value))
+
+    def close(self):
+        from ._lib import lib
+
+        if self.handle and self.group.handle:
+            lib().srhip_group_dataset_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

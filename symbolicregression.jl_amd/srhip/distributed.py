@@ -21,6 +21,19 @@ Trees of one batch are split over ranks by `shard_trees` (strided, so every
 rank gets a similar cost mix) and put back in order by `merge_tree_shards`
 (bench.py's strong-scaling run).
 
+A third way needs no process group at all: one process, one device group
+(`srhip.DeviceGroup`, include/srhip.h "device groups"). The group holds one
+context and one driver thread per GPU, `group.dataset(X, y)` shards the rows
+with the same `shard_range`, and `GroupProgram.eval_loss` / `eval_loss_grad`
+leave each shard's packed partials (the `pack_partials` /
+`pack_grad_partials` layouts below) in pinned host memory, where one kernel on
+the first member adds them in member order and applies `unpack_partials` /
+`unpack_grad_partials` — the functions of this module are its specification
+(tests/test_group_gpu.py compares bit for bit). `eval_loss_batch_ok`,
+`eval_loss_grad_batch` and `optimize_constants_batch` take the `GroupDataset`
+directly. This is the way a single Julia process uses several GPUs; the two
+ways above remain for multi-process runs (bench.py).
+
 The combine steps are plain host logic on top of any all-reduce, so they are
 tested with the gloo backend on CPU (tests/test_distributed.py) and on the
 engine with both ranks on one GPU (tests/test_distributed_gpu.py).

@@ -302,6 +302,181 @@ class Program:
             pass
 
 
+class _MemberContext(Context):
+    """Member k's context of a DeviceGroup, lent (srhip_group_ctx): the group
+    owns it, so close() leaves it open."""
+
+    def __init__(self, handle, device: int):
+        self.handle = handle
+        self.device = int(device)
+
+    def close(self):
+        self.handle = None
+
+
+def group_shard_range(n: int, ndev: int, k: int):
+    """srhip_group_shard_range: rows [begin, end) of member k of ndev."""
+    b, e = C.c_int64(0), C.c_int64(0)
+    check(lib().srhip_group_shard_range(int(n), int(ndev), int(k), C.byref(b), C.byref(e)))
+    return b.value, e.value
+
+
+class DeviceGroup:
+    """srhip_group: one process, one member (context + driver thread) per entry
+    of `devices`; the same device may be listed more than once. Datasets are
+    row-sharded over the members, programs are built on every member, and one
+    evaluation call combines the shards on the device in member order.
+    A context manager; closing it first destroys the datasets and programs
+    made through it that are still alive."""
+
+    def __init__(self, devices):
+        try:
+            devs = [int(d) for d in devices]
+        except TypeError:
+            raise TypeError("devices must be a sequence of device indices") from None
+        if not 1 <= len(devs) <= 16:
+            raise ValueError("a device group has 1 to 16 members")
+        if any(d < 0 for d in devs):
+            raise ValueError("device indices are non-negative")
+        self.handle = None
+        self._children = []
+        arr = (C.c_int32 * len(devs))(*devs)
+        h = C.c_void_p()
+        check(lib().srhip_group_open(arr, len(devs), C.byref(h)))
+        self.handle = h
+        self.devices = tuple(devs)
+        self.ndev = len(devs)
+
+    def _live(self):
+        if not self.handle:
+            raise ValueError("the device group is closed")
+        return self.handle
+
+    def _adopt(self, child):
+        import weakref
+
+        self._children = [r for r in self._children if r() is not None]
+        self._children.append(weakref.ref(child))
+        return child
+
+    def dataset(self, X, y, weights=None):
+        """A GroupDataset: rows of (X (nfeatures, n), y, weights) sharded over the members."""
+        from .dataset import GroupDataset
+
+        return self._adopt(GroupDataset(self, X, y, weights))
+
+    def program(self, flat: FlatTrees, dtype, flags: int = 0):
+        """A GroupProgram: the trees compiled on every member (flags: PROGRAM_*)."""
+        return self._adopt(GroupProgram(self, flat, dtype, flags))
+
+    def context(self, k: int) -> Context:
+        """Member k's context, for the single-device calls of an island on device k."""
+        h = C.c_void_p()
+        check(lib().srhip_group_ctx(self._live(), int(k), C.byref(h)))
+        return _MemberContext(h, self.devices[int(k)])
+
+    def info(self):
+        n = C.c_int32(0)
+        devs = (C.c_int32 * 16)()
+        check(lib().srhip_group_info(self._live(), C.byref(n), devs))
+        return tuple(devs[: n.value])
+
+    def close(self):
+        if not self.handle:
+            return
+        for r in self._children:
+            c = r()
+            if c is not None:
+                c.close()
+        self._children = []
+        lib().srhip_group_close(self.handle)
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GroupProgram:
+    """srhip_group_program: one identical program per member of a DeviceGroup."""
+
+    def __init__(self, group: DeviceGroup, flat: FlatTrees, dtype, flags: int = 0):
+        if not isinstance(group, DeviceGroup):
+            raise TypeError("group must be a DeviceGroup")
+        if not isinstance(flat, FlatTrees):
+            raise TypeError("flat must be FlatTrees (srhip.flatten)")
+        self.handle = None
+        self.group = group
+        self.dtype = np.dtype(dtype)
+        self.flat = flat
+        consts = np.ascontiguousarray(flat.consts, dtype=self.dtype)
+        tr = _trees_struct(flat, consts)
+        h = C.c_void_p()
+        check(lib().srhip_group_program_create(group._live(), dtype_code(self.dtype), C.byref(tr), int(flags),
+                                               C.byref(h)))
+        self.handle = h
+        self.ntrees = flat.ntrees
+
+    def _gds(self, gds):
+        if not hasattr(gds, "group") or not getattr(gds, "handle", None):
+            raise TypeError("a GroupProgram is evaluated on a live GroupDataset")
+        if not self.handle:
+            raise ValueError("the group program is closed")
+        return gds.handle
+
+    def set_constants(self, consts: np.ndarray):
+        c = np.ascontiguousarray(consts, dtype=self.dtype)
+        if c.shape != (int(self.flat.const_off[-1]),):
+            raise ValueError("constant vector has the wrong length")
+        if not self.handle:
+            raise ValueError("the group program is closed")
+        check(lib().srhip_group_program_set_constants(self.handle, _p(c)))
+
+    def eval_loss(self, gds, loss_kind: int, params=None):
+        """(Σ w·ℓ per tree, Σw, ok) over all rows of all shards."""
+        nt = self.ntrees
+        sums = np.empty(max(nt, 1), dtype=np.float64)
+        ok = np.empty(max(nt, 1), dtype=np.uint8)
+        wsum = C.c_double(0)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_group_eval_loss(self._gds(gds), self.handle, int(loss_kind), _p(par), _p(sums),
+                                          C.byref(wsum), _p(ok)))
+        return sums[:nt], wsum.value, ok[:nt].view(bool)
+
+    def eval_loss_grad(self, gds, loss_kind: int, params=None):
+        """(Σ w·ℓ per tree, Σ w·∂ℓ/∂c per constant [const_off order], Σw, ok)."""
+        nt = self.ntrees
+        nc = int(self.flat.const_off[-1])
+        sums = np.zeros(max(nt, 1), dtype=np.float64)
+        grads = np.zeros(max(nc, 1), dtype=np.float64)
+        ok = np.zeros(max(nt, 1), dtype=np.uint8)
+        wsum = C.c_double(0)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_group_eval_loss_grad(self._gds(gds), self.handle, int(loss_kind), _p(par), _p(sums),
+                                               _p(grads), C.byref(wsum), _p(ok)))
+        return sums[:nt], grads[:nc], wsum.value, ok[:nt].astype(bool)
+
+    def close(self):
+        if self.handle and self.group.handle:
+            lib().srhip_group_program_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _trees_struct(flat: FlatTrees, consts: np.ndarray) -> Trees:
     return Trees(
         flat.ntrees,
@@ -376,4 +551,4 @@ def debug_constant_map(flat: FlatTrees, new_consts, dtype, grad: bool = False, k
 
 
 __all__ = ["Context", "DeviceDataset", "Program", "get_context", "device_count", "SrhipError", "jit_compile",
-           "debug_constant_map"]
+           "debug_constant_map", "DeviceGroup", "GroupProgram", "group_shard_range"]

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .dataset import Dataset
+from .dataset import Dataset, GroupDataset
 from .engine import DeviceDataset, Program, get_context
 from .node import Node, count_nodes, flatten
 from .options import Options
@@ -168,11 +168,17 @@ def eval_loss_grad_batch(trees: Sequence[Node], dataset: Dataset, options: Optio
                          device: Optional[int] = None):
     """Batched loss + constant gradients for ConstantOptimization
     (src/ConstantOptimization.jl:12-65): per tree (loss in T, ∂loss/∂c as a
-    float64 vector in get_constants order, did_succeed)."""
-    dev = dataset.device(device)
-    prog = compile_trees(trees, options, dataset.T, dev.ctx.device)
+    float64 vector in get_constants order, did_succeed). A GroupDataset runs
+    over its device group (`device` is then unused)."""
     loss = options.elementwise_loss
-    sums, grads, wsum, ok = prog.eval_loss_grad(dev, loss.kind, loss.params)
+    if isinstance(dataset, GroupDataset):
+        prog = dataset.group.program(flatten(trees, options, dtype=dataset.T), dataset.T)
+        sums, grads, wsum, ok = prog.eval_loss_grad(dataset, loss.kind, loss.params)
+        prog.close()
+    else:
+        dev = dataset.device(device)
+        prog = compile_trees(trees, options, dataset.T, dev.ctx.device)
+        sums, grads, wsum, ok = prog.eval_loss_grad(dev, loss.kind, loss.params)
     T = dataset.T
     with np.errstate(invalid="ignore", divide="ignore"):
         losses = (sums / wsum).astype(T)
@@ -194,15 +200,26 @@ def eval_loss_batch(trees: Sequence[Node], dataset: Dataset, options: Options,
 def eval_loss_batch_ok(trees: Sequence[Node], dataset: Dataset, options: Options,
                        row_idx: Optional[np.ndarray] = None, device: Optional[int] = None,
                        program: Optional[Program] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """(losses in T, did_succeed per tree)."""
+    """(losses in T, did_succeed per tree). A GroupDataset runs over its
+    device group (all rows: no row_idx there; `program`, if given, a
+    GroupProgram of that group; `device` unused)."""
     if options.loss_function is not None:
         f = options.loss_function
         vals = np.asarray([f(t, dataset, options) for t in trees], dtype=dataset.T)
         return vals, np.isfinite(vals)
-    dev = dataset.device(device)
-    prog = program if program is not None else compile_trees(trees, options, dataset.T, dev.ctx.device)
     loss = options.elementwise_loss
-    sums, wsum, ok = prog.eval_loss(dev, loss.kind, loss.params, row_idx)
+    if isinstance(dataset, GroupDataset):
+        if row_idx is not None:
+            raise ValueError("row_idx is not supported on a GroupDataset")
+        prog = program if program is not None else dataset.group.program(
+            flatten(trees, options, dtype=dataset.T), dataset.T)
+        sums, wsum, ok = prog.eval_loss(dataset, loss.kind, loss.params)
+        if program is None:
+            prog.close()
+    else:
+        dev = dataset.device(device)
+        prog = program if program is not None else compile_trees(trees, options, dataset.T, dev.ctx.device)
+        sums, wsum, ok = prog.eval_loss(dev, loss.kind, loss.params, row_idx)
     T = dataset.T
     with np.errstate(invalid="ignore", divide="ignore"):
         out = (sums / wsum).astype(T)
