@@ -418,6 +418,67 @@ int32_t srhip_eval_loss_batch_rowsets_ctx(srhip_ctx* ctx, srhip_dataset* ds, con
                                           double* out_loss_sum, double* out_weight_sum,
                                           uint8_t* out_ok);
 
+/* ---- multi-output datasets: one X, a target per tree --------------------------
+ * EquationSearch(X, y::AbstractMatrix) builds nout Datasets over the same X
+ * (src/SymbolicRegression.jl:304-315) and scores the candidates of all outputs
+ * in one loop (:459-494). A multi-target dataset holds X once with ntargets
+ * target columns, each with its own optional weight column. It is scored in two
+ * ways:
+ *   views      srhip_dataset_view(ds, k): target k as an ordinary single-target
+ *              dataset on the parent's device memory (no copy). Every entry point
+ *              takes a view and runs the kernels it runs on a dataset made of
+ *              (X, Y[k], W[k]) by srhip_dataset_create, with the same results.
+ *   fused      srhip_eval_loss_targets and its forms: the trees of one program each
+ *              carry a target index and one launch scores every tree against its
+ *              own column.
+ * Rules:
+ *   - ntargets outside 1..SRHIP_MAX_TARGETS, or a null Y, is SRHIP_ERR_INVALID,
+ *     answered before any device work (and before ctx is looked at).
+ *   - a target[t] outside 0..ntargets-1 is SRHIP_ERR_INVALID; nothing is written.
+ *   - a dataset with ntargets > 1 passed to a single-target entry point (every
+ *     entry point above and below that takes a srhip_dataset, the constant
+ *     optimiser included) is SRHIP_ERR_INVALID; the message says to take a view.
+ *   - with ntargets == 1 the dataset is an ordinary dataset everywhere.
+ *   - the fused calls accept every table loss, distance and margin; an
+ *     expression-loss handle is SRHIP_ERR_UNSUPPORTED there in this version
+ *     (views take it).
+ *   - out_ok and out_loss_sum mean what they mean for srhip_eval_loss with
+ *     (y, w) = (Y[target[t]], W[target[t]]); a failed tree has a NaN sum.
+ *   - srhip_dataset_info's x_finite, rows and nfeat refer to the shared X; the Σw
+ *     and Σ y·w of target k come from srhip_dataset_target_info.
+ *   - the fused calls always run in the interpreter kernels (variants of their
+ *     own whose row tile holds every column; the wide variant when that tile does
+ *     not fit in LDS): srhip_last_tree_code gives 0. Callers with large batches
+ *     per target score them on views, which run tree code.
+ * Not in this version: fused gradients and fused constant optimisation
+ * (srhip_eval_loss_grad, srhip_optimize_constants_batch take views); expression
+ * losses in the fused calls; multi-target group datasets (a device group takes
+ * one srhip_group_dataset per target). */
+#define SRHIP_MAX_TARGETS 16
+/* Y: [ntargets][n] (target-major); W: NULL or [ntargets][n]. Rows [row_begin,row_end) as srhip_dataset_create. */
+int32_t srhip_dataset_create_multi(srhip_ctx* ctx, int32_t dtype, int32_t x_layout, const void* X, const void* Y,
+                                   const void* W, int64_t n, int32_t nfeat, int32_t ntargets,
+                                   int64_t row_begin, int64_t row_end, srhip_dataset** out_ds);
+int32_t srhip_dataset_targets(const srhip_dataset* ds, int32_t* out_ntargets); /* 1 for every other dataset */
+int32_t srhip_dataset_target_info(const srhip_dataset* ds, int32_t k, double* out_sum_w, double* out_sum_yw);
+/* single-target dataset on the parent's X / Y[k] / W[k]; no copy. Parent and views may be destroyed
+ * (srhip_dataset_destroy) in any order: device memory goes with the last of them. */
+int32_t srhip_dataset_view(srhip_dataset* ds, int32_t k, srhip_dataset** out_view);
+/* srhip_eval_loss with tree t scored against column target[t]; out_weight_sum is [ntargets]. */
+int32_t srhip_eval_loss_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                const double* loss_params, const int32_t* target, double* out_loss_sum,
+                                double* out_weight_sum, uint8_t* out_ok);
+/* srhip_program_create_ex(SRHIP_PROGRAM_INTERPRETED) + srhip_eval_loss_targets + destroy, the program in ctx
+ * (NULL: the dataset's context). */
+int32_t srhip_eval_loss_batch_targets_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                          int32_t loss_kind, const double* loss_params, const int32_t* target,
+                                          double* out_loss_sum, double* out_weight_sum, uint8_t* out_ok);
+/* srhip_eval_loss_rowsets with a target per tree (row_idx [ntrees][batch_size]; out_weight_sum [ntrees]). */
+int32_t srhip_eval_loss_rowsets_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                        const double* loss_params, const int32_t* target, const int64_t* row_idx,
+                                        int64_t batch_size, double* out_loss_sum, double* out_weight_sum,
+                                        uint8_t* out_ok);
+
 /* ---- per-row outputs: eval_tree_array src/InterfaceDynamicExpressions.jl:50-52
  * out is [ntrees][rows] of the dataset dtype (row-major per tree); rows of a
  * failed tree are unspecified (the reference returns an undef array). */

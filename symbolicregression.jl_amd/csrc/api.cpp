@@ -207,6 +207,7 @@ struct srhip_ctx {
   DevBuf partial, sums, oks, dloss, scratch_idx, gather, derived;
   DevBuf gderived;  // [ngcol][n_pad] shared-subtree columns of the tree code (jit.h Columns)
   DevBuf gpartial, gsum, gok, gti;  // their derive pass's partials, per-column results, threaded records
+  DevBuf tgt;  // [ntrees] the target of each tree (srhip_eval_loss_targets, _rowsets_targets)
   DevBuf fail;  // [list slots] early-exit flags of the eval kernel (MODE_LOSS)
   bool fail_clean = false;  // all of `fail` is zero: the finalize kernels clear the flags they read
   DevBuf ti_rec;  // threaded-interpreter records of the shallow f32 list
@@ -221,6 +222,22 @@ struct srhip_ctx {
   std::vector<LossProg> lprogs;
 };
 
+// Device memory of a multi-target dataset (srhip_dataset_create_multi): one X,
+// the target columns Y and weight columns W ([ntargets][n_pad] each), owned
+// jointly by the parent and its views and freed with the last of them.
+struct MultiMem {
+  int device = 0;
+  void* X = nullptr;
+  void* Y = nullptr;
+  void* W = nullptr;
+  ~MultiMem() {
+    (void)hipSetDevice(device);
+    if (X) (void)hipFree(X);
+    if (Y) (void)hipFree(Y);
+    if (W) (void)hipFree(W);
+  }
+};
+
 struct srhip_dataset {
   srhip_ctx* ctx = nullptr;
   int dtype = SRHIP_F32;
@@ -233,6 +250,13 @@ struct srhip_dataset {
   double sum_w = 0.0, sum_yw = 0.0;
   bool x_finite = true;
   std::vector<double> h_w;  // host copy of the shard weights (Σw of row samples)
+  // multi-target datasets and their views: X / y / w point into mem and are not
+  // freed by the dataset. ntargets > 1 (the parent): y / w are the first of
+  // ntargets columns n_pad rows apart, t_* the per-target Σw, Σy·w and weights.
+  int ntargets = 1;
+  std::shared_ptr<MultiMem> mem;
+  std::vector<double> t_sum_w, t_sum_yw;
+  std::vector<std::vector<double>> t_h_w;
 };
 
 struct srhip_program {
@@ -1270,8 +1294,11 @@ void update_constants(srhip_program* p) {
   ++p->n_inplace;
 }
 
-void check_program_vs_dataset(const srhip_dataset* ds, const srhip_program* p) {
+void check_program_vs_dataset(const srhip_dataset* ds, const srhip_program* p, bool multi_ok = false) {
   if (!ds || !p) throw Error(SRHIP_ERR_INVALID, "null dataset or program");
+  if (ds->ntargets > 1 && !multi_ok)
+    throw Error(SRHIP_ERR_INVALID, "dataset has " + std::to_string(ds->ntargets) +
+                                       " targets: take a view of one (srhip_dataset_view) or use srhip_eval_loss_targets");
   // a dataset is read-only device memory once created: any context of its
   // device may evaluate a program on it (the program's context runs the call)
   if (ds->ctx->device != p->ctx->device)
@@ -1308,10 +1335,10 @@ static int wide_mode() {
 }
 // The plan of an interpreter evaluation pass: the LDS plan where it fits, else the wide one.
 static void plan_interp(int dtype, bool deep, int opset, int mode, bool weighted, int nfeat, int64_t rows, int nlist,
-                        EvalPlan* plan) {
+                        EvalPlan* plan, int ntgt = 0) {
   const int wm = wide_mode();
-  if (wm != 1 && plan_eval(dtype, deep, opset, mode, weighted, nfeat, rows, nlist, plan)) return;
-  if (wm != 0 && plan_eval_wide(dtype, mode, weighted, rows, nlist, plan)) return;
+  if (wm != 1 && plan_eval(dtype, deep, opset, mode, weighted, nfeat, rows, nlist, plan, ntgt)) return;
+  if (wm != 0 && plan_eval_wide(dtype, mode, weighted, rows, nlist, plan, ntgt)) return;
   throw_lds(nfeat);
 }
 static const char* interp_name(size_t esz, bool wide) {
@@ -1777,7 +1804,9 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
 template <typename T>
 void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const T* y,
               const T* w, int64_t rows, int64_t n_pad, int nfeat, int loss, double lparam,
-              T* out, int64_t out_stride, int64_t seg = 0) {
+              T* out, int64_t out_stride, int64_t seg = 0, const int32_t* tgt = nullptr, int ntgt = 0) {
+  // tgt (device memory, per tree id): a target per tree; y / w are then ntgt columns
+  // n_pad rows apart and every pass runs the interpreter's per-tree-targets variants
   hipStream_t s = c->stream;
   timing_reset(c);
   c->sums.ensure(std::max<size_t>(p->ntrees, 1) * sizeof(double));
@@ -1797,13 +1826,13 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
   // slot ranges: [0, nj) tree code, [nj, nlist_a) shallow interpreter, then deep
   // (per-tree row sets, seg > 0: the interpreter, one tree per workgroup)
   const int wm = wide_mode();  // 1: no tree code for this call
-  jit::Module* jm = (!std::is_same<T, float>::value || seg > 0 || wm == 1) ? nullptr
+  jit::Module* jm = (!std::is_same<T, float>::value || seg > 0 || wm == 1 || tgt) ? nullptr
                     : mode == MODE_LOSS                                     ? loss_module(p, loss, lparam)
                                                                             : out_module(p);
   // Float64 programs: their tree code (this loss, or per-row outputs)
   jit::Module64* jm64 = nullptr;
   if constexpr (std::is_same<T, double>::value)
-    if (p->jit64 && p->nlist_j > 0 && seg == 0 && wm != 1) jm64 = module64(p, mode == MODE_LOSS ? loss : -2, lparam);
+    if (p->jit64 && p->nlist_j > 0 && seg == 0 && wm != 1 && !tgt) jm64 = module64(p, mode == MODE_LOSS ? loss : -2, lparam);
   // the row tile of a tree-code part (LDS columns: y, the raw features the tree code reads, its
   // derived columns, w); false: it does not fit in LDS
   auto plan_tree_code = [&](int nlist, EvalPlan* plan) {
@@ -1917,7 +1946,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
       plan = tc_plans[(size_t)launches[li].part];
     } else {
       plan_interp(p->dtype, pass == 1, (pass == 1 && p->has_expr) ? (int)OPSET_EXPR : p->opset, mode, w != nullptr,
-                  nfeat, rows, nlist, &plan);
+                  nfeat, rows, nlist, &plan, tgt ? ntgt : 0);
     }
     if (seg > 0) {
       // per-tree row sets: one tree per workgroup of one wave, staging its
@@ -1964,6 +1993,8 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
     a.out = out;
     a.out_stride = out_stride;
     a.seg = seg;
+    a.tgt = tgt;
+    a.ntgt = tgt ? ntgt : 0;
     const int tk = timed_begin(c, s);
     if (pass == -1) {
       if constexpr (std::is_same<T, float>::value) {
@@ -2120,7 +2151,9 @@ int eval_loss_impl(srhip_dataset* ds, const srhip_program* p, int loss, const do
 template <typename T>
 int eval_loss_rowsets_impl(srhip_dataset* ds, const srhip_program* p, int loss, const double* params,
                            const int64_t* row_idx, int64_t bs, double* out_sum, double* out_wsum,
-                           uint8_t* out_ok) {
+                           uint8_t* out_ok, const int32_t* target = nullptr) {
+  // target (srhip_eval_loss_rowsets_targets, checked by the caller): tree t's sample takes its
+  // y and w from column target[t] of the dataset's target-major y / w
   srhip_ctx* c = p->ctx;
   const int nt = p->ntrees;
   if (bs < 0) throw Error(SRHIP_ERR_INVALID, "negative batch size");
@@ -2143,9 +2176,18 @@ int eval_loss_rowsets_impl(srhip_dataset* ds, const srhip_program* p, int loss, 
   T* wg = yg + gp;
   if (nidx > 0) {
     HIP_CHECK(hipMemcpyAsync(c->scratch_idx.p, row_idx, nidx * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(launch_gather_rows<T>(static_cast<const T*>(ds->X), static_cast<const T*>(ds->y), w, ds->nfeat,
-                                    ds->n_pad, static_cast<const int64_t*>(c->scratch_idx.p), bs, seg, gp, Xg, yg,
-                                    w ? wg : nullptr, c->stream));
+    if (target) {
+      c->tgt.ensure((size_t)nt * sizeof(int32_t));
+      HIP_CHECK(hipMemcpyAsync(c->tgt.p, target, (size_t)nt * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+      HIP_CHECK(launch_gather_rows_targets<T>(static_cast<const T*>(ds->X), static_cast<const T*>(ds->y), w,
+                                              static_cast<const int32_t*>(c->tgt.p), ds->nfeat, ds->n_pad,
+                                              static_cast<const int64_t*>(c->scratch_idx.p), bs, seg, gp, Xg, yg,
+                                              w ? wg : nullptr, c->stream));
+    } else {
+      HIP_CHECK(launch_gather_rows<T>(static_cast<const T*>(ds->X), static_cast<const T*>(ds->y), w, ds->nfeat,
+                                      ds->n_pad, static_cast<const int64_t*>(c->scratch_idx.p), bs, seg, gp, Xg, yg,
+                                      w ? wg : nullptr, c->stream));
+    }
   }
   run_eval<T>(c, p, MODE_LOSS, Xg, yg, w ? wg : nullptr, bs, gp, ds->nfeat, loss, params ? params[0] : 0.0, nullptr,
               0, seg);
@@ -2153,12 +2195,34 @@ int eval_loss_rowsets_impl(srhip_dataset* ds, const srhip_program* p, int loss, 
   if (out_wsum)
     for (int t = 0; t < nt; ++t) {  // Σ w over tree t's (repeated) sample
       double s = 0.0;
+      const std::vector<double>& hw = (target && ds->ntargets > 1) ? ds->t_h_w[(size_t)target[t]] : ds->h_w;
       if (w)
-        for (int64_t k = 0; k < bs; ++k) s += ds->h_w[row_idx[(size_t)t * bs + k]];
+        for (int64_t k = 0; k < bs; ++k) s += hw[row_idx[(size_t)t * bs + k]];
       else
         s = (double)bs;
       out_wsum[t] = s;
     }
+  return SRHIP_OK;
+}
+
+// srhip_eval_loss with tree t scored against column target[t] (checked by the
+// caller) of a multi-target dataset: one interpreter pass per tree list whose row
+// tile holds every column (run_eval tgt). A single-target dataset has one column.
+template <typename T>
+int eval_loss_targets_impl(srhip_dataset* ds, const srhip_program* p, int loss, const double* params,
+                           const int32_t* target, double* out_sum, double* out_wsum, uint8_t* out_ok) {
+  srhip_ctx* c = p->ctx;
+  const int nt = p->ntrees;
+  c->tgt.ensure((size_t)std::max(nt, 1) * sizeof(int32_t));
+  if (nt > 0)
+    HIP_CHECK(hipMemcpyAsync(c->tgt.p, target, (size_t)nt * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  run_eval<T>(c, p, MODE_LOSS, static_cast<const T*>(ds->X), static_cast<const T*>(ds->y),
+              static_cast<const T*>(ds->w), ds->rows, ds->n_pad, ds->nfeat, loss, params ? params[0] : 0.0, nullptr, 0,
+              0, static_cast<const int32_t*>(c->tgt.p), ds->ntargets);
+  collect_results(c, p, ds->rows, out_sum, out_ok);
+  if (out_wsum)
+    for (int k = 0; k < ds->ntargets; ++k)
+      out_wsum[k] = !ds->w ? (double)ds->rows : (ds->ntargets > 1 ? ds->t_sum_w[(size_t)k] : ds->sum_w);
   return SRHIP_OK;
 }
 
@@ -2969,9 +3033,13 @@ int32_t srhip_dataset_destroy(srhip_dataset* ds) {
     std::lock_guard<std::mutex> lk(ds->ctx->mu);
     (void)hipSetDevice(ds->ctx->device);
     (void)hipStreamSynchronize(ds->ctx->stream);
-    if (ds->X) (void)hipFree(ds->X);
-    if (ds->y) (void)hipFree(ds->y);
-    if (ds->w) (void)hipFree(ds->w);
+    if (ds->mem) {
+      ds->mem.reset();  // the last of a multi-target dataset and its views frees the memory
+    } else {
+      if (ds->X) (void)hipFree(ds->X);
+      if (ds->y) (void)hipFree(ds->y);
+      if (ds->w) (void)hipFree(ds->w);
+    }
     delete ds;
     return SRHIP_OK;
   });
@@ -2986,6 +3054,164 @@ int32_t srhip_dataset_info(const srhip_dataset* ds, int64_t* out_rows, int32_t* 
     if (out_sum_w) *out_sum_w = ds->sum_w;
     if (out_sum_yw) *out_sum_yw = ds->sum_yw;
     if (out_x_finite) *out_x_finite = ds->x_finite ? 1 : 0;
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_dataset_create_multi(srhip_ctx* ctx, int32_t dtype, int32_t x_layout, const void* X, const void* Y,
+                                   const void* W, int64_t n, int32_t nfeat, int32_t ntargets, int64_t row_begin,
+                                   int64_t row_end, srhip_dataset** out_ds) {
+  return guarded([&] {
+    // the target count and Y are answered first: no context, no device work
+    if (ntargets < 1 || ntargets > SRHIP_MAX_TARGETS)
+      throw Error(SRHIP_ERR_INVALID, "ntargets must be 1.." + std::to_string(SRHIP_MAX_TARGETS));
+    if (!Y) throw Error(SRHIP_ERR_INVALID, "null Y");
+    if (!ctx || !out_ds) throw Error(SRHIP_ERR_INVALID, "null ctx or out_ds");
+    *out_ds = nullptr;
+    if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
+    if (x_layout != SRHIP_X_JULIA && x_layout != SRHIP_X_FEATURE_MAJOR) throw Error(SRHIP_ERR_INVALID, "bad X layout");
+    if (n < 0 || nfeat <= 0 || nfeat > 65535) throw Error(SRHIP_ERR_INVALID, "bad shape");
+    if (row_begin < 0 || row_end < row_begin || row_end > n) throw Error(SRHIP_ERR_INVALID, "bad row range");
+    if (row_end > row_begin && !X) throw Error(SRHIP_ERR_INVALID, "null X");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t es = dtype_size(dtype);
+    const int64_t rows = row_end - row_begin;
+    const int64_t n_pad = pad_rows(rows);
+    const size_t K = (size_t)ntargets;
+    std::unique_ptr<srhip_dataset> ds(new srhip_dataset());  // (mem frees the device memory on every path)
+    ds->ctx = ctx;
+    ds->dtype = dtype;
+    ds->rows = rows;
+    ds->nfeat = nfeat;
+    ds->n_pad = n_pad;
+    ds->ntargets = ntargets;
+    ds->mem = std::make_shared<MultiMem>();
+    MultiMem* m = ds->mem.get();
+    m->device = ctx->device;
+    HIP_CHECK(hipMalloc(&m->X, (size_t)n_pad * nfeat * es));
+    HIP_CHECK(hipMalloc(&m->Y, K * (size_t)n_pad * es));
+    if (W) HIP_CHECK(hipMalloc(&m->W, K * (size_t)n_pad * es));
+    HIP_CHECK(hipMemsetAsync(m->X, 0, (size_t)n_pad * nfeat * es, ctx->stream));
+    HIP_CHECK(hipMemsetAsync(m->Y, 0, K * (size_t)n_pad * es, ctx->stream));
+    if (W) HIP_CHECK(hipMemsetAsync(m->W, 0, K * (size_t)n_pad * es, ctx->stream));
+    if (rows > 0) {
+      ScopedBuf raw_b, rawv_b, bad_b;
+      raw_b.ensure((size_t)rows * nfeat * es);
+      rawv_b.ensure((size_t)rows * es);
+      bad_b.ensure(sizeof(int));
+      void* raw = raw_b.p;
+      void* rawv = rawv_b.p;
+      int* bad = static_cast<int*>(bad_b.p);
+      HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+      if (x_layout == SRHIP_X_JULIA) {
+        HIP_CHECK(hipMemcpyAsync(raw, static_cast<const char*>(X) + (size_t)row_begin * nfeat * es,
+                                 (size_t)rows * nfeat * es, hipMemcpyHostToDevice, ctx->stream));
+      } else {
+        HIP_CHECK(hipMemcpy2DAsync(raw, rows * es, static_cast<const char*>(X) + row_begin * es, n * es, rows * es,
+                                   nfeat, hipMemcpyHostToDevice, ctx->stream));
+      }
+      if (dtype == SRHIP_F32)
+        HIP_CHECK(launch_pack_x<float>((const float*)raw, x_layout, rows, rows, nfeat, n_pad, (float*)m->X, bad, ctx->stream));
+      else
+        HIP_CHECK(launch_pack_x<double>((const double*)raw, x_layout, rows, rows, nfeat, n_pad, (double*)m->X, bad, ctx->stream));
+      // column k of Y / W: rows [row_begin, row_end) of the host's row k, padded as a single y is
+      const void* blocks[2] = {Y, W};
+      void* dsts[2] = {m->Y, m->W};
+      for (int b = 0; b < 2; ++b) {
+        if (!blocks[b]) continue;
+        for (size_t k = 0; k < K; ++k) {
+          HIP_CHECK(hipMemcpyAsync(rawv, static_cast<const char*>(blocks[b]) + (k * (size_t)n + (size_t)row_begin) * es,
+                                   (size_t)rows * es, hipMemcpyHostToDevice, ctx->stream));
+          void* dst = static_cast<char*>(dsts[b]) + k * (size_t)n_pad * es;
+          if (dtype == SRHIP_F32)
+            HIP_CHECK(launch_pack_vec<float>((const float*)rawv, rows, n_pad, (float*)dst, ctx->stream));
+          else
+            HIP_CHECK(launch_pack_vec<double>((const double*)rawv, rows, n_pad, (double*)dst, ctx->stream));
+        }
+      }
+      int hbad = 0;
+      HIP_CHECK(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      ds->x_finite = hbad == 0;
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // Σw and Σ y·w of every target over the shard, in double (src/Dataset.jl:56-60)
+    ds->t_sum_w.assign(K, 0.0);
+    ds->t_sum_yw.assign(K, 0.0);
+    ds->t_h_w.assign(K, std::vector<double>());
+    auto at = [&](const void* base, size_t k, int64_t i) {
+      const size_t j = k * (size_t)n + (size_t)i;
+      return dtype == SRHIP_F32 ? (double)static_cast<const float*>(base)[j] : static_cast<const double*>(base)[j];
+    };
+    for (size_t k = 0; k < K; ++k) {
+      double sw = 0.0, syw = 0.0;
+      if (W) ds->t_h_w[k].reserve((size_t)rows);
+      for (int64_t i = row_begin; i < row_end; ++i) {
+        double wi = 1.0;
+        if (W) {
+          wi = at(W, k, i);
+          ds->t_h_w[k].push_back(wi);
+        }
+        sw += wi;
+        syw += at(Y, k, i) * wi;
+      }
+      ds->t_sum_w[k] = sw;
+      ds->t_sum_yw[k] = syw;
+    }
+    ds->X = m->X;
+    ds->y = m->Y;
+    ds->w = m->W;
+    ds->sum_w = ds->t_sum_w[0];
+    ds->sum_yw = ds->t_sum_yw[0];
+    if (ntargets == 1) ds->h_w = ds->t_h_w[0];  // an ordinary dataset everywhere
+    *out_ds = ds.release();
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_dataset_targets(const srhip_dataset* ds, int32_t* out_ntargets) {
+  return guarded([&] {
+    if (!ds || !out_ntargets) throw Error(SRHIP_ERR_INVALID, "null dataset or output");
+    *out_ntargets = ds->ntargets;
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_dataset_target_info(const srhip_dataset* ds, int32_t k, double* out_sum_w, double* out_sum_yw) {
+  return guarded([&] {
+    if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
+    if (k < 0 || k >= ds->ntargets) throw Error(SRHIP_ERR_INVALID, "target index out of range");
+    const bool multi = ds->ntargets > 1;
+    if (out_sum_w) *out_sum_w = multi ? ds->t_sum_w[(size_t)k] : ds->sum_w;
+    if (out_sum_yw) *out_sum_yw = multi ? ds->t_sum_yw[(size_t)k] : ds->sum_yw;
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_dataset_view(srhip_dataset* ds, int32_t k, srhip_dataset** out_view) {
+  return guarded([&] {
+    if (!ds || !out_view) throw Error(SRHIP_ERR_INVALID, "null dataset or out_view");
+    *out_view = nullptr;
+    if (!ds->mem) throw Error(SRHIP_ERR_INVALID, "views are taken of datasets made by srhip_dataset_create_multi");
+    if (k < 0 || k >= ds->ntargets) throw Error(SRHIP_ERR_INVALID, "target index out of range");
+    const size_t col = (size_t)k * (size_t)ds->n_pad * dtype_size(ds->dtype);
+    std::unique_ptr<srhip_dataset> v(new srhip_dataset());
+    v->ctx = ds->ctx;
+    v->dtype = ds->dtype;
+    v->rows = ds->rows;
+    v->nfeat = ds->nfeat;
+    v->n_pad = ds->n_pad;
+    v->x_finite = ds->x_finite;
+    v->mem = ds->mem;
+    v->X = ds->X;
+    v->y = static_cast<char*>(ds->y) + col;  // (a view's own column when ds is a view: k = 0)
+    v->w = ds->w ? static_cast<char*>(ds->w) + col : nullptr;
+    const bool multi = ds->ntargets > 1;
+    v->sum_w = multi ? ds->t_sum_w[(size_t)k] : ds->sum_w;
+    v->sum_yw = multi ? ds->t_sum_yw[(size_t)k] : ds->sum_yw;
+    v->h_w = multi ? ds->t_h_w[(size_t)k] : ds->h_w;
+    *out_view = v.release();
     return SRHIP_OK;
   });
 }
@@ -3207,6 +3433,66 @@ int32_t srhip_eval_loss_batch_rowsets_ctx(srhip_ctx* ctx, srhip_dataset* ds, con
   srhip_program_destroy(p);
   g_last_error = err;
   return rc;
+}
+
+// the fused calls' own checks: table losses only, every target within the dataset's columns
+static void check_targets(const srhip_dataset* ds, const srhip_program* p, int32_t loss_kind, const int32_t* target) {
+  if (loss_kind >= SRHIP_EXPR_LOSS_BEGIN)
+    throw Error(SRHIP_ERR_UNSUPPORTED, "expression losses are not scored per target in this version: take views");
+  if (p->ntrees > 0 && !target) throw Error(SRHIP_ERR_INVALID, "target is NULL");
+  for (int t = 0; t < p->ntrees; ++t)
+    if (target[t] < 0 || target[t] >= ds->ntargets)
+      throw Error(SRHIP_ERR_INVALID, "target " + std::to_string(target[t]) + " of tree " + std::to_string(t) +
+                                         " is outside 0.." + std::to_string(ds->ntargets - 1));
+}
+
+int32_t srhip_eval_loss_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                const double* loss_params, const int32_t* target, double* out_loss_sum,
+                                double* out_weight_sum, uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog, true);
+    check_loss(loss_kind, loss_params);
+    check_targets(ds, prog, loss_kind, target);
+    std::lock_guard<std::mutex> lk(prog->ctx->mu);
+    HIP_CHECK(hipSetDevice(prog->ctx->device));
+    if (ds->dtype == SRHIP_F32)
+      return eval_loss_targets_impl<float>(ds, prog, loss_kind, loss_params, target, out_loss_sum, out_weight_sum, out_ok);
+    return eval_loss_targets_impl<double>(ds, prog, loss_kind, loss_params, target, out_loss_sum, out_weight_sum, out_ok);
+  });
+}
+
+int32_t srhip_eval_loss_batch_targets_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                          int32_t loss_kind, const double* loss_params, const int32_t* target,
+                                          double* out_loss_sum, double* out_weight_sum, uint8_t* out_ok) {
+  if (!ds) return set_error(SRHIP_ERR_INVALID, "null dataset");
+  if (!ctx) ctx = ds->ctx;
+  srhip_program* p = nullptr;
+  // the fused call runs in the interpreter: no tree code to build
+  int32_t rc = srhip_program_create_ex(ctx, ds->dtype, trees, SRHIP_PROGRAM_INTERPRETED, &p);
+  if (rc != SRHIP_OK) return rc;
+  rc = srhip_eval_loss_targets(ds, p, loss_kind, loss_params, target, out_loss_sum, out_weight_sum, out_ok);
+  std::string err = g_last_error;
+  srhip_program_destroy(p);
+  g_last_error = err;
+  return rc;
+}
+
+int32_t srhip_eval_loss_rowsets_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                        const double* loss_params, const int32_t* target, const int64_t* row_idx,
+                                        int64_t batch_size, double* out_loss_sum, double* out_weight_sum,
+                                        uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog, true);
+    check_loss(loss_kind, loss_params);
+    check_targets(ds, prog, loss_kind, target);
+    std::lock_guard<std::mutex> lk(prog->ctx->mu);
+    HIP_CHECK(hipSetDevice(prog->ctx->device));
+    if (ds->dtype == SRHIP_F32)
+      return eval_loss_rowsets_impl<float>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
+                                           out_weight_sum, out_ok, target);
+    return eval_loss_rowsets_impl<double>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
+                                          out_weight_sum, out_ok, target);
+  });
 }
 
 int32_t srhip_eval_tree_array(srhip_dataset* ds, const srhip_program* prog, void* out, uint8_t* out_ok) {
@@ -3749,6 +4035,8 @@ int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const 
   return guarded([&] {
     if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
     if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
+    if (ds->ntargets > 1)
+      throw Error(SRHIP_ERR_INVALID, "dataset has several targets: take a view of one (srhip_dataset_view)");
     check_loss(opts->loss_kind, opts->loss_params);
     check_expr_loss_weights(opts->loss_kind, ds->w != nullptr);
     t_copt = CoptProfile();

@@ -93,6 +93,12 @@ constexpr int kModeLossL2 = 2;
 // only: every other instantiation keeps its code. The weight column is a
 // run-time property of these (a.w), so there is one per (T, R, D).
 constexpr int kModeLossExpr = 3;
+// Kernel mode of a MODE_LOSS launch with a target per tree (a.tgt set,
+// srhip_eval_loss_targets): a.y / a.w are a.ntgt columns, n_pad rows apart; step 1
+// stages all of them and tree id t reads column a.tgt[t]. The loss kind stays a
+// run-time value (tile_loss_any). Instantiations of their own, for the full
+// operator set only (eval_targets_*.hip): every other instantiation keeps its code.
+constexpr int kModeLossTargets = 4;
 
 // Σ over this lane's rows of the tile of ℓ(ŷ, y, w), ℓ the loss program: no
 // implicit weight (srhip.h); masked rows (past n) add 0.
@@ -212,8 +218,16 @@ __device__ __forceinline__ void eval_tree_in_group(const EvalArgs<T>& a, int i, 
       store_rows<T, R>(a.out + (size_t)t * a.out_stride + row0 + tl * TILE, lane, acc);
     } else {
       T yv[R], wv[R];
-      lds_rows<T, R>(sY + tl * TILE, lane, yv);
-      if constexpr (W) lds_rows<T, R>(sW + tl * TILE, lane, wv);
+      if constexpr (MODE == kModeLossTargets) {
+        // this tree's column of the staged y (and w): wave-uniform, scalar loads
+        const int t = __builtin_amdgcn_readfirstlane(a.list[s]);
+        const int col = __builtin_amdgcn_readfirstlane(a.tgt[t]) * rows;
+        lds_rows<T, R>(sY + col + tl * TILE, lane, yv);
+        if constexpr (W) lds_rows<T, R>(sW + col + tl * TILE, lane, wv);
+      } else {
+        lds_rows<T, R>(sY + tl * TILE, lane, yv);
+        if constexpr (W) lds_rows<T, R>(sW + tl * TILE, lane, wv);
+      }
       if constexpr (MODE == kModeLossExpr) {
         if (a.w) lds_rows<T, R>(sW + tl * TILE, lane, wv);
         else SR_UNROLL for (int r = 0; r < R; ++r) wv[r] = T(0);  // (a loss reading w is refused without weights)
@@ -254,10 +268,11 @@ eval_kernel(EvalArgs<T> a) {
   constexpr int N = V16<T>::N;
   const int rows = a.ntiles * TILE;
   const int nx = XG ? 0 : a.nfeat;  // feature arrays staged in LDS
-  const int narr = nx + (MODE != MODE_OUT ? ((W || (MODE == kModeLossExpr && a.w)) ? 2 : 1) : 0);
+  const int ncol = MODE == kModeLossTargets ? a.ntgt : 1;  // columns of y (and of w)
+  const int narr = nx + (MODE != MODE_OUT ? ncol * ((W || (MODE == kModeLossExpr && a.w)) ? 2 : 1) : 0);
   T* sX = reinterpret_cast<T*>(smem);
   T* sY = sX + (size_t)nx * rows;
-  T* sW = sY + rows;
+  T* sW = sY + (size_t)ncol * rows;
   Part<T>* sPart = reinterpret_cast<Part<T>*>(sX + (size_t)narr * rows);
 
   const int rg = blockIdx.x / a.ntg;
@@ -274,6 +289,9 @@ eval_kernel(EvalArgs<T> a) {
       const int arr = idx / vper;
       const int v = idx - arr * vper;
       const T* src = arr < nx ? a.X + (size_t)arr * a.n_pad : (arr == nx ? a.y : a.w);
+      if constexpr (MODE == kModeLossTargets) {  // columns of y, then of w, n_pad rows apart
+        if (arr >= nx) src = arr < nx + ncol ? a.y + (size_t)(arr - nx) * a.n_pad : a.w + (size_t)(arr - nx - ncol) * a.n_pad;
+      }
       reinterpret_cast<V*>(sX + (size_t)arr * rows)[v] = reinterpret_cast<const V*>(src + seg0 + row0)[v];
     }
     for (int i = threadIdx.x; i < a.tpb; i += blockDim.x) sPart[i] = Part<T>{T(0), T(0)};
@@ -423,6 +441,7 @@ hipError_t launch_one(const EvalPlan& plan, const EvalArgs<T>& a, hipStream_t st
 template <typename T, int R, int D, int SET, bool XG = false>
 hipError_t launch_rd(const EvalPlan& plan, const EvalArgs<T>& a, int mode, hipStream_t stream) {
   if (mode == MODE_OUT) return launch_one<T, R, D, SET, MODE_OUT, false, XG>(plan, a, stream);
+  if (a.tgt) return launch_eval_targets<T>(plan, a, stream);  // a target per tree: eval_targets_*.hip
   constexpr int LSET = SET == OPSET_EXPR ? OPSET_EXPR : OPSET_FULL;  // (expression losses: no basic-set variant)
   if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_one<T, R, D, LSET, kModeLossExpr, false, XG>(plan, a, stream);
   if (a.loss == SRHIP_LOSS_L2) {
@@ -431,6 +450,13 @@ hipError_t launch_rd(const EvalPlan& plan, const EvalArgs<T>& a, int mode, hipSt
   }
   if (a.w) return launch_one<T, R, D, SET, MODE_LOSS, true, XG>(plan, a, stream);
   return launch_one<T, R, D, SET, MODE_LOSS, false, XG>(plan, a, stream);
+}
+
+// The per-tree-targets instantiation of one (T, R, D, SET, XG): weighted or not.
+template <typename T, int R, int D, int SET, bool XG = false>
+hipError_t launch_targets_rd(const EvalPlan& plan, const EvalArgs<T>& a, hipStream_t stream) {
+  if (a.w) return launch_one<T, R, D, SET, kModeLossTargets, true, XG>(plan, a, stream);
+  return launch_one<T, R, D, SET, kModeLossTargets, false, XG>(plan, a, stream);
 }
 
 }  // namespace

@@ -53,6 +53,11 @@ struct EvalArgs {
   int part4 = 0;
   // the loss program of an expression loss (loss >= SRHIP_EXPR_LOSS_BEGIN), device memory
   const Ins<T>* lprog = nullptr;
+  // per-tree targets (srhip_eval_loss_targets; the kModeLossTargets variants of
+  // eval_targets_*.hip): tree id t is scored against column tgt[t] of y / w, which
+  // are then [ntgt][n_pad] (target-major); nullptr / 0: one y, one w
+  const int32_t* tgt = nullptr;
+  int ntgt = 0;
 };
 
 // Geometry of one evaluation launch, chosen by plan_eval().
@@ -83,11 +88,12 @@ bool ti_compiled();  // eval kernels built with the threaded interpreter (SR_TI)
 hipError_t launch_ti_records(const Ins<float>* prog, const int32_t* list_off, int nlist,
                              uint32_t rs_bytes, uint4* rec, hipStream_t stream);
 
+// ntgt > 0 (a per-tree-targets launch): the tile holds ntgt columns of y (and of w).
 bool plan_eval(int dtype, bool deep, int opset, int mode, bool weighted, int nfeat,
-               int64_t n, int nlist, EvalPlan* plan);
+               int64_t n, int nlist, EvalPlan* plan, int ntgt = 0);
 // The wide plan of the same launch: the deep configuration with no feature
 // array in LDS. False only when y, w and the partial slots do not fit.
-bool plan_eval_wide(int dtype, int mode, bool weighted, int64_t n, int nlist, EvalPlan* plan);
+bool plan_eval_wide(int dtype, int mode, bool weighted, int64_t n, int nlist, EvalPlan* plan, int ntgt = 0);
 // Same, for explicit R / D / LDS arrays / partial bytes per tree slot.
 // target_wg: workgroups the tree groups aim at; min_per_group: trees a group
 // keeps at least (the loss tree code: 16384 / 64, measured on config #2)
@@ -164,6 +170,9 @@ hipError_t launch_eval(const EvalPlan& plan, const EvalArgs<T>& a, int mode,
 // the wide variants (plan.wide; launch_eval forwards to them)
 template <typename T>
 hipError_t launch_eval_wide(const EvalPlan& plan, const EvalArgs<T>& a, int mode, hipStream_t stream);
+// the per-tree-targets variants (a.tgt set, MODE_LOSS; eval_targets_*.hip): LDS or wide by plan.wide
+template <typename T>
+hipError_t launch_eval_targets(const EvalPlan& plan, const EvalArgs<T>& a, hipStream_t stream);
 
 // Σ over row groups of the partials → per-tree fp64 sum and ok flag; clears
 // the failure flags it read (a.fail) and, given cnt, copies the two tree-code
@@ -195,5 +204,12 @@ hipError_t launch_gather_rows(const T* X, const T* y, const T* w, int nfeat,
                               int64_t src_pad, const int64_t* idx, int64_t nidx, int64_t seg,
                               int64_t dst_pad, T* Xd, T* yd, T* wd,
                               hipStream_t stream);
+// The per-tree samples of a multi-target dataset (srhip_eval_loss_rowsets_targets):
+// Y / W are [ntargets][src_pad]; segment t takes its y (and w) rows from column
+// tgt[t]. seg > 0, idx = [dst_pad / seg][nidx], tgt = [dst_pad / seg].
+template <typename T>
+hipError_t launch_gather_rows_targets(const T* X, const T* Y, const T* W, const int32_t* tgt, int nfeat,
+                                      int64_t src_pad, const int64_t* idx, int64_t nidx, int64_t seg,
+                                      int64_t dst_pad, T* Xd, T* yd, T* wd, hipStream_t stream);
 
 }  // namespace srhip

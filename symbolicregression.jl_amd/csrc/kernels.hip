@@ -145,6 +145,28 @@ __global__ void gather_rows_kernel(const T* __restrict__ X, const T* __restrict_
   }
 }
 
+// gather_rows_kernel for per-tree samples of a multi-target dataset: segment t
+// reads its y (and w) rows from column tgt[t] of Y / W ([ntargets][src_pad]).
+template <typename T>
+__global__ void gather_rows_targets_kernel(const T* __restrict__ X, const T* __restrict__ Y,
+                                           const T* __restrict__ W, const int32_t* __restrict__ tgt, int nfeat,
+                                           int64_t src_pad, const int64_t* __restrict__ idx, int64_t nidx,
+                                           int64_t seg, int64_t dst_pad, T* __restrict__ Xd, T* __restrict__ yd,
+                                           T* __restrict__ wd) {
+  const int64_t total = dst_pad * (nfeat + 2);
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < total;
+       k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t f = k / dst_pad;
+    const int64_t j = k - f * dst_pad;
+    const int64_t t = j / seg;
+    const int64_t jj = j - t * seg;
+    const int64_t r = idx[t * nidx + (jj < nidx ? jj : nidx - 1)];
+    if (f < nfeat) Xd[f * dst_pad + j] = X[f * src_pad + r];
+    else if (f == nfeat) yd[j] = Y[(int64_t)tgt[t] * src_pad + r];
+    else if (W) wd[j] = W[(int64_t)tgt[t] * src_pad + r];
+  }
+}
+
 // Columns of shared subtrees (jit.h Columns) whose subtree failed somewhere
 // (ok[g] == 0: a node non-finite on some row) become NaN on every row, so
 // every tree reading the column fails, as DynamicExpressions fails a tree
@@ -295,9 +317,10 @@ bool plan_geometry(size_t esz, int R, int D, int narr, size_t part_bytes, int64_
 }
 
 bool plan_eval(int dtype, bool deep, int opset, int mode, bool weighted, int nfeat, int64_t n,
-               int nlist, EvalPlan* p) {
+               int nlist, EvalPlan* p, int ntgt) {
   const size_t esz = dtype == SRHIP_F32 ? 4 : 8;
-  const int narr = nfeat + (mode == MODE_LOSS ? (weighted ? 2 : 1) : 0);
+  const int ncol = ntgt > 0 ? ntgt : 1;  // columns of y (and of w) in the tile
+  const int narr = nfeat + (mode == MODE_LOSS ? ncol * (weighted ? 2 : 1) : 0);
   const int R = variant_R(dtype, deep);
   const bool ok = plan_geometry(esz, R, deep ? kMaxSlots : kShallowSlots, narr,
                                 2 * esz, n, nlist, p);
@@ -307,9 +330,10 @@ bool plan_eval(int dtype, bool deep, int opset, int mode, bool weighted, int nfe
   return ok;
 }
 
-bool plan_eval_wide(int dtype, int mode, bool weighted, int64_t n, int nlist, EvalPlan* p) {
+bool plan_eval_wide(int dtype, int mode, bool weighted, int64_t n, int nlist, EvalPlan* p, int ntgt) {
   const size_t esz = dtype == SRHIP_F32 ? 4 : 8;
-  const int narr = mode == MODE_LOSS ? (weighted ? 2 : 1) : 0;  // y, w: no feature array
+  const int ncol = ntgt > 0 ? ntgt : 1;
+  const int narr = mode == MODE_LOSS ? ncol * (weighted ? 2 : 1) : 0;  // y, w: no feature array
   const bool ok = plan_geometry(esz, variant_R(dtype, true), kMaxSlots, narr, 2 * esz, n, nlist, p);
   p->opset = OPSET_EXPR;  // the one operator set the wide variants are built for
   p->wide = true;
@@ -507,6 +531,18 @@ hipError_t launch_gather_rows(const T* X, const T* y, const T* w, int nfeat, int
   return hipGetLastError();
 }
 
+template <typename T>
+hipError_t launch_gather_rows_targets(const T* X, const T* Y, const T* W, const int32_t* tgt, int nfeat,
+                                      int64_t src_pad, const int64_t* idx, int64_t nidx, int64_t seg,
+                                      int64_t dst_pad, T* Xd, T* yd, T* wd, hipStream_t stream) {
+  const int64_t total = dst_pad * (nfeat + 2);
+  unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+  if (grid == 0) grid = 1;
+  hipLaunchKernelGGL((gather_rows_targets_kernel<T>), dim3(grid), dim3(256), 0, stream, X, Y, W, tgt, nfeat,
+                     src_pad, idx, nidx, seg, dst_pad, Xd, yd, wd);
+  return hipGetLastError();
+}
+
 #define SR_INST(T)                                                                             \
   template hipError_t launch_finalize<T>(const EvalArgs<T>&, double*, uint8_t*, hipStream_t, uint32_t*, uint32_t*); \
   template hipError_t launch_pack_x<T>(const T*, int, int64_t, int64_t, int, int64_t, T*,     \
@@ -514,7 +550,10 @@ hipError_t launch_gather_rows(const T* X, const T* y, const T* w, int nfeat, int
   template hipError_t launch_pack_vec<T>(const T*, int64_t, int64_t, T*, hipStream_t);         \
   template hipError_t launch_gather_rows<T>(const T*, const T*, const T*, int, int64_t,        \
                                             const int64_t*, int64_t, int64_t, int64_t, T*, T*, \
-                                            T*, hipStream_t);
+                                            T*, hipStream_t);                                  \
+  template hipError_t launch_gather_rows_targets<T>(const T*, const T*, const T*, const int32_t*, int, int64_t, \
+                                                    const int64_t*, int64_t, int64_t, int64_t, T*, T*, T*,      \
+                                                    hipStream_t);
 SR_INST(float)
 SR_INST(double)
 

@@ -109,6 +109,49 @@ function score_batch_minibatch(dataset::Dataset{T}, trees::AbstractVector{Node{T
     return T[p[1] for p in pairs], T[p[2] for p in pairs]
 end
 
+"""
+    score_batch_multi(datasets, js, trees, options) -> (scores, losses)
+
+One step's candidates from several outputs of a multi-output search in ONE call:
+`trees[i]` belongs to output `js[i]` and is scored against `datasets[js[i]]`, the
+Datasets EquationSearch builds over one shared `X` (src/SymbolicRegression.jl:304-315),
+uploaded once (SRHip.MultiCopy). With `options.batching` every tree gets its own row
+sample, as score_batch_minibatch. Outside the engine's coverage (`Unsupported`, or
+datasets that do not share their X): score_batch / score_batch_minibatch per output.
+"""
+function score_batch_multi(datasets::AbstractVector{<:Dataset{T}}, js::AbstractVector{<:Integer},
+                           trees::AbstractVector{Node{T}}, options::Options; device::Int=0) where {T}
+    length(js) == length(trees) || throw(ArgumentError("one output index per tree"))
+    shared = all(d -> d.X === datasets[1].X && d.weighted == datasets[1].weighted, datasets)
+    if !isempty(trees) && shared && SRHip.enabled(options)
+        try
+            if options.batching
+                idx = rand(1:(datasets[1].n), options.batch_size, length(trees))  # column t: tree t's sample
+                losses = SRHip.eval_loss_batch_targets_rowsets(trees, js, datasets, options, idx; device=device)
+                scores = [isfinite(l) ? loss_to_score(l, datasets[j].baseline_loss, t, options) : zero(T)
+                          for (l, t, j) in zip(losses, trees, js)]
+            else
+                losses = SRHip.eval_loss_batch_targets(trees, js, datasets, options; device=device)
+                scores = [loss_to_score(l, datasets[j].baseline_loss, t, options)
+                          for (l, t, j) in zip(losses, trees, js)]
+            end
+            return scores, losses
+        catch e
+            e isa SRHip.Unsupported || rethrow()
+        end
+    end
+    scores = Vector{T}(undef, length(trees)); losses = Vector{T}(undef, length(trees))
+    for j in unique(js)   # regroup by output, score, scatter back
+        sel = findall(==(j), js)
+        sub = Node{T}[trees[i] for i in sel]
+        sc, lo = options.batching ? score_batch_minibatch(datasets[j], sub, options; device=device) :
+                 score_batch(datasets[j], sub, options; device=device)
+        scores[sel] .= sc
+        losses[sel] .= lo
+    end
+    return scores, losses
+end
+
 # ---- Population / finalize_scores ---------------------------------------------------
 
 """Population(dataset; npop, nlength, options, nfeatures) with one launch."""

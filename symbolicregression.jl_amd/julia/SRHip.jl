@@ -325,6 +325,7 @@ end
 # optimize_constants), so Float32 tree code reads its constants from memory
 # from the start (SRHIP_PROGRAM_VARYING_CONSTANTS: no recompile on a new set)
 const PROGRAM_VARYING_CONSTANTS = UInt32(1)
+const PROGRAM_INTERPRETED = UInt32(2)  # no loss / output tree code (per-tree row sets, per-tree targets)
 function Program(trees::AbstractVector{Node{T}}, options::Options, device::Int=0;
                  varying_constants::Bool=false) where {T}
     node_off, kind, arg, const_off, consts = flatten(trees, options)
@@ -383,6 +384,9 @@ end
 const DEVICE_DATASETS = WeakKeyDict{Dataset,Dict{Int,DeviceCopy}}()
 function device_dataset(dataset::Dataset{T}, device::Int=0) where {T}
     lock(CTX_LOCK) do
+        # an output of a multi-output search (MultiCopy below): its view of the shared upload
+        e = covering(dataset, device)
+        e !== nothing && e[1].h != C_NULL && return e[1].views[e[2]]
         copies = get!(() -> Dict{Int,DeviceCopy}(), DEVICE_DATASETS, dataset)
         d = get(copies, device, nothing)
         d !== nothing && d.h != C_NULL && return d.h
@@ -400,6 +404,155 @@ function release_dataset!(dataset::Dataset)
         copies === nothing || foreach(free!, values(copies))
     end
     return nothing
+end
+
+# ---- multi-output datasets (srhip.h "multi-output datasets") ------------------------
+# EquationSearch(X, y::AbstractMatrix) builds nout Datasets over the SAME X object
+# (src/SymbolicRegression.jl:304-315). A MultiCopy is one upload for all of them:
+# X once, the targets and weights as columns (srhip_dataset_create_multi), and one
+# view per output (srhip_dataset_view), which device_dataset(datasets[j]) then
+# returns, so an nout-output search holds one X on the device. Each covered
+# Dataset is held weakly (MULTI_DATASETS); the MultiCopy is freed by its finaliser
+# once no Dataset refers to it, or at once by free!. Guarded by CTX_LOCK.
+const SRHIP_MAX_TARGETS = Int32(16)
+mutable struct MultiCopy
+    h::Ptr{Cvoid}               # the multi-target dataset
+    views::Vector{Ptr{Cvoid}}   # views[j]: output j as a single-target dataset
+    device::Int
+end
+function free!(m::MultiCopy)
+    m.h == C_NULL && return nothing
+    foreach(destroy_dataset, m.views)   # parent and views in any order: memory goes with the last
+    destroy_dataset(m.h)
+    empty!(m.views)
+    m.h = C_NULL
+    return nothing
+end
+const MULTI_DATASETS = WeakKeyDict{Dataset,Dict{Int,Tuple{MultiCopy,Int}}}()
+# the (MultiCopy, output index) that covers `dataset` on `device`, or nothing (under CTX_LOCK)
+function covering(dataset::Dataset, device::Int)
+    mv = get(MULTI_DATASETS, dataset, nothing)
+    return mv === nothing ? nothing : get(mv, device, nothing)
+end
+"""
+    MultiCopy(datasets, device=0) -> MultiCopy
+
+One device upload for the `nout` Datasets of a multi-output search, whose `X` must be the
+same object (`datasets[j].X === datasets[1].X`) and which are all weighted or all
+unweighted. Returns the existing one when these Datasets are already covered.
+"""
+function MultiCopy(datasets::AbstractVector{<:Dataset{T}}, device::Int=0) where {T}
+    K = length(datasets)
+    1 <= K <= SRHIP_MAX_TARGETS || throw(ArgumentError("1 to $(SRHIP_MAX_TARGETS) outputs"))
+    d1 = datasets[1]
+    for d in datasets
+        d.X === d1.X || throw(ArgumentError("the datasets of a MultiCopy share one X object"))
+        d.weighted == d1.weighted || throw(ArgumentError("all outputs weighted, or none"))
+    end
+    lock(CTX_LOCK) do
+        m1 = covering(d1, device)
+        if m1 !== nothing && m1[1].h != C_NULL && length(m1[1].views) == K &&
+           all(j -> covering(datasets[j], device) == (m1[1], j), 1:K)
+            return m1[1]
+        end
+        nfeat, n = size(d1.X)
+        Xc = Matrix{T}(d1.X)
+        Yc = Matrix{T}(undef, n, K)          # column j = target j: [ntargets][n] in C
+        Wc = d1.weighted ? Matrix{T}(undef, n, K) : nothing
+        for j in 1:K
+            Yc[:, j] .= datasets[j].y
+            Wc === nothing || (Wc[:, j] .= datasets[j].weights)
+        end
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        GC.@preserve Xc Yc Wc begin
+            check(ccall((:srhip_dataset_create_multi, libsrhip), Int32,
+                        (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Int64, Int32, Int32, Int64, Int64,
+                         Ptr{Ptr{Cvoid}}),
+                        context(device), dtype_code(T), X_JULIA, Xc, Yc,
+                        Wc === nothing ? Ptr{T}(C_NULL) : Wc, n, nfeat, K, 0, n, h))
+        end
+        m = MultiCopy(h[], Ptr{Cvoid}[], device)
+        finalizer(free!, m)
+        for j in 1:K
+            v = Ref{Ptr{Cvoid}}(C_NULL)
+            check(ccall((:srhip_dataset_view, libsrhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                        m.h, j - 1, v))
+            push!(m.views, v[])
+        end
+        for j in 1:K
+            get!(() -> Dict{Int,Tuple{MultiCopy,Int}}(), MULTI_DATASETS, datasets[j])[device] = (m, j)
+        end
+        return m
+    end
+end
+
+"""
+    eval_loss_batch_targets(trees, js, datasets, options; device=0) -> Vector{T}
+
+`eval_loss` of `trees[i]` against `datasets[js[i]]` (the outputs of one MultiCopy) for the
+candidates of several outputs in ONE launch (srhip_eval_loss_batch_targets_ctx); T(Inf)
+where evaluation fails. Expression losses are `Unsupported` here (the callers fall back).
+"""
+function eval_loss_batch_targets(trees::AbstractVector{Node{T}}, js::AbstractVector{<:Integer},
+                                 datasets::AbstractVector{<:Dataset{T}}, options::Options;
+                                 device::Int=0) where {T}
+    nt = length(trees)
+    length(js) == nt || throw(ArgumentError("one output index per tree"))
+    m = MultiCopy(datasets, device)
+    node_off, kind, arg, const_off, consts = flatten(trees, options)
+    sums = Vector{Float64}(undef, nt); ok = Vector{UInt8}(undef, nt)
+    wsum = Vector{Float64}(undef, length(datasets))
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    target = Int32.(js .- 1)
+    GC.@preserve node_off kind arg const_off consts sums ok wsum params target m datasets begin
+        tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
+                            Ptr{Cvoid}(pointer(consts))))
+        check(ccall((:srhip_eval_loss_batch_targets_ctx, libsrhip), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{UInt8}),
+                    context(device), m.h, tr, kindcode, params, target, sums, wsum, ok))
+    end
+    return [ok[i] == 1 ? T(sums[i] / wsum[js[i]]) : T(Inf) for i in 1:nt]
+end
+
+"""
+    eval_loss_batch_targets_rowsets(trees, js, datasets, options, idx) -> Vector{T}
+
+The per-tree minibatch form: `trees[i]` on its own row sample `idx[:, i]` (1-based, with
+repetition) against `datasets[js[i]]`, one launch (srhip_eval_loss_rowsets_targets).
+"""
+function eval_loss_batch_targets_rowsets(trees::AbstractVector{Node{T}}, js::AbstractVector{<:Integer},
+                                         datasets::AbstractVector{<:Dataset{T}}, options::Options,
+                                         idx::AbstractMatrix{<:Integer}; device::Int=0) where {T}
+    nt = length(trees)
+    length(js) == nt || throw(ArgumentError("one output index per tree"))
+    size(idx, 2) == nt || throw(ArgumentError("one row sample (column of idx) per tree"))
+    m = MultiCopy(datasets, device)
+    node_off, kind, arg, const_off, consts = flatten(trees, options)
+    sums = Vector{Float64}(undef, nt); ok = Vector{UInt8}(undef, nt); wsum = Vector{Float64}(undef, nt)
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    target = Int32.(js .- 1)
+    rows = Matrix{Int64}(idx .- 1)  # column-major: tree t's sample is contiguous ([ntrees][bs] in C)
+    prog = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve node_off kind arg const_off consts sums ok wsum params target rows m datasets begin
+        tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
+                            Ptr{Cvoid}(pointer(consts))))
+        # row sets run in the interpreter: no tree code to build
+        check(ccall((:srhip_program_create_ex, libsrhip), Int32,
+                    (Ptr{Cvoid}, Int32, Ref{SrhipTrees}, UInt32, Ptr{Ptr{Cvoid}}),
+                    context(device), dtype_code(T), tr, PROGRAM_INTERPRETED, prog))
+        try
+            check(ccall((:srhip_eval_loss_rowsets_targets, libsrhip), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Int64}, Int64, Ptr{Float64},
+                         Ptr{Float64}, Ptr{UInt8}),
+                        m.h, prog[], kindcode, params, target, rows, size(rows, 1), sums, wsum, ok))
+        finally
+            ccall((:srhip_program_destroy, libsrhip), Int32, (Ptr{Cvoid},), prog[])
+        end
+    end
+    return [ok[i] == 1 ? T(sums[i] / wsum[i]) : T(Inf) for i in 1:nt]
 end
 # ---- eval_loss (src/LossFunctions.jl:34-67), batched ------------------------------
 """

@@ -84,6 +84,18 @@ SIGNATURES = {
     "srhip_dataset_destroy": [C.c_void_p],
     "srhip_dataset_info": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)],
+    # multi-output datasets
+    "srhip_dataset_create_multi": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)],
+    "srhip_dataset_targets": [C.c_void_p, C.POINTER(C.c_int32)],
+    "srhip_dataset_target_info": [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "srhip_dataset_view": [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)],
+    "srhip_eval_loss_targets": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p],
+    "srhip_eval_loss_batch_targets_ctx": [C.c_void_p, C.c_void_p, C.POINTER(Trees), C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p],
+    "srhip_eval_loss_rowsets_targets": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "srhip_program_create": [C.c_void_p, C.c_int32, C.POINTER(Trees), C.POINTER(C.c_void_p)],
     "srhip_program_create_ex": [C.c_void_p, C.c_int32, C.POINTER(Trees), C.c_uint32, C.POINTER(C.c_void_p)],
     "srhip_program_destroy": [C.c_void_p],

@@ -11,7 +11,9 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .engine import DeviceDataset, get_context
+import weakref
+
+from .engine import DeviceDataset, MultiDeviceDataset, get_context
 
 
 class Dataset:
@@ -44,6 +46,75 @@ class Dataset:
         if d is None:
             rb, re = self.row_range if self.row_range is not None else (0, self.n)
             d = DeviceDataset(ctx, self.X, self.y, self.weights, rb, re)
+            self._dev[ctx.device] = d
+        return d
+
+
+class _TargetDataset(Dataset):
+    """Target k of a MultiDataset: a Dataset over (X, Y[k], weights[k]) whose
+    device copy is a view of the parent's (no second upload of X). It holds the
+    parent weakly: a view made while the parent lived keeps the device memory
+    alive on its own, and without one the target uploads like any Dataset."""
+
+    def __init__(self, parent, k: int):
+        super().__init__(parent.X, parent.Y[k], None if parent.weights is None else parent.weights[k],
+                         parent.varMap, parent.row_range)
+        self._parent = weakref.ref(parent)
+        self.target_index = k
+
+    def device(self, device: Optional[int] = None) -> DeviceDataset:
+        ctx = get_context(device)
+        d = self._dev.get(ctx.device)
+        if d is None:
+            parent = self._parent()
+            if parent is None:
+                return super().device(device)
+            d = parent.device(device).view(self.target_index)
+            self._dev[ctx.device] = d
+        return d
+
+
+class MultiDataset:
+    """One X (nfeatures, n) with K target rows Y (K, n) and optional per-target
+    weights (K, n): what EquationSearch(X, y::AbstractMatrix) builds as nout
+    Datasets over the same X (src/SymbolicRegression.jl:304-315), uploaded once.
+    target(k) is an ordinary Dataset for every single-target function;
+    eval_loss_batch_ok / eval_loss_batch_rowsets take the MultiDataset itself
+    with one target index per tree."""
+
+    def __init__(self, X: np.ndarray, Y: np.ndarray, weights: Optional[np.ndarray] = None,
+                 varMap: Optional[Sequence[str]] = None, row_range: Optional[tuple] = None):
+        X = np.asarray(X)
+        Y = np.asarray(Y)
+        if X.ndim != 2:
+            raise ValueError("X must be (nfeatures, n)")
+        W = None if weights is None else np.asarray(weights)
+        if Y.ndim != 2 or Y.shape[1] != X.shape[1] or Y.shape[0] < 1 or (W is not None and W.shape != Y.shape):
+            raise AssertionError("Dataset dimensions are invalid")  # Configure.jl:53-60
+        self.X = X
+        self.Y = Y
+        self.weights = W
+        self.weighted = W is not None
+        self.nfeatures, self.n = X.shape
+        self.ntargets = Y.shape[0]
+        self.varMap = list(varMap) if varMap is not None else [f"x{i + 1}" for i in range(self.nfeatures)]
+        self.row_range = row_range
+        self._targets = [_TargetDataset(self, k) for k in range(self.ntargets)]
+        self.T = self._targets[0].T
+        self.avg_y = np.asarray([t.avg_y for t in self._targets], dtype=self.T)
+        self._dev = {}
+
+    def target(self, k: int) -> Dataset:
+        if not 0 <= k < self.ntargets:
+            raise IndexError("target index out of range")
+        return self._targets[k]
+
+    def device(self, device: Optional[int] = None) -> MultiDeviceDataset:
+        ctx = get_context(device)
+        d = self._dev.get(ctx.device)
+        if d is None:
+            rb, re = self.row_range if self.row_range is not None else (0, self.n)
+            d = MultiDeviceDataset(ctx, self.X, self.Y, self.weights, rb, re)
             self._dev[ctx.device] = d
         return d
 

@@ -152,6 +152,65 @@ class DeviceDataset:
             pass
 
 
+class MultiDeviceDataset:
+    """srhip_dataset of several targets (srhip_dataset_create_multi): rows
+    [row_begin, row_end) of one X (nfeatures, n) with the target columns Y
+    (ntargets, n) and optional weight columns W (ntargets, n). view(k) is target
+    k as a DeviceDataset on the same device memory."""
+
+    def __init__(self, ctx: Context, X: np.ndarray, Y: np.ndarray, W: Optional[np.ndarray] = None,
+                 row_begin: int = 0, row_end: Optional[int] = None):
+        if X.ndim != 2:
+            raise ValueError("X must be (nfeatures, n)")
+        dt = np.result_type(X.dtype, Y.dtype)
+        code = dtype_code(dt)
+        nfeat, n = X.shape
+        if X.flags.c_contiguous:
+            layout, Xa = K.X_FEATURE_MAJOR, np.ascontiguousarray(X, dtype=dt)
+        else:  # Fortran order = Julia's column-major (nfeatures, n)
+            layout, Xa = K.X_JULIA, np.asfortranarray(X, dtype=dt)
+        Ya = np.ascontiguousarray(Y, dtype=dt)
+        Wa = None if W is None else np.ascontiguousarray(W, dtype=dt)
+        if Ya.ndim != 2 or Ya.shape[1] != n or (Wa is not None and Wa.shape != Ya.shape):
+            raise AssertionError("Dataset dimensions are invalid")  # Configure.jl:53-60
+        rb = int(row_begin)
+        re = n if row_end is None else int(row_end)
+        h = C.c_void_p()
+        check(lib().srhip_dataset_create_multi(ctx.handle, code, layout, _p(Xa), _p(Ya), _p(Wa), n, nfeat,
+                                               Ya.shape[0], rb, re, C.byref(h)))
+        self.handle = h
+        self.ctx = ctx
+        self.dtype = dt
+        self.nfeat = nfeat
+        self.ntargets = Ya.shape[0]
+        self.rows = re - rb
+        self.weighted = W is not None
+
+    info = DeviceDataset.info
+
+    def target_info(self, k: int):
+        """(Σw, Σ y·w) of target k over the shard (srhip_dataset_target_info)."""
+        sw, syw = C.c_double(), C.c_double()
+        check(lib().srhip_dataset_target_info(self.handle, int(k), C.byref(sw), C.byref(syw)))
+        return sw.value, syw.value
+
+    def view(self, k: int) -> DeviceDataset:
+        """Target k as a single-target DeviceDataset sharing this dataset's
+        device memory (srhip_dataset_view); it may outlive this object."""
+        h = C.c_void_p()
+        check(lib().srhip_dataset_view(self.handle, int(k), C.byref(h)))
+        v = DeviceDataset.__new__(DeviceDataset)
+        v.handle = h
+        v.ctx = self.ctx
+        v.dtype = self.dtype
+        v.nfeat = self.nfeat
+        v.rows = self.rows
+        v.weighted = self.weighted
+        return v
+
+    __del__ = DeviceDataset.__del__
+
+
 class Program:
     """srhip_program: a compiled, device-resident batch of trees.
     varying_constants (SRHIP_PROGRAM_VARYING_CONSTANTS): the caller will set
@@ -253,6 +312,40 @@ class Program:
         par = None if params is None else np.asarray(params, dtype=np.float64)
         check(lib().srhip_eval_loss_rowsets(ds.handle, self.handle, int(loss_kind), _p(par), _p(idx), idx.shape[1],
                                             _p(sums), _p(wsum), _p(ok)))
+        return sums[:nt], wsum[:nt], ok[:nt].view(bool)
+
+    def eval_loss_targets(self, ds, loss_kind: int, targets, params=None):
+        """srhip_eval_loss_targets: tree t against column targets[t] of a
+        MultiDeviceDataset in one launch: (Σ w·ℓ per tree, Σ w per target, ok)."""
+        nt = self.ntrees
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        if tg.shape != (nt,):
+            raise ValueError("targets must have one entry per tree")
+        ntg = getattr(ds, "ntargets", 1)
+        sums = np.empty(max(nt, 1), dtype=np.float64)
+        wsum = np.empty(ntg, dtype=np.float64)
+        ok = np.empty(max(nt, 1), dtype=np.uint8)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_eval_loss_targets(ds.handle, self.handle, int(loss_kind), _p(par), _p(tg), _p(sums),
+                                            _p(wsum), _p(ok)))
+        return sums[:nt], wsum, ok[:nt].view(bool)
+
+    def eval_loss_rowsets_targets(self, ds, loss_kind: int, targets, row_idx, params=None):
+        """srhip_eval_loss_rowsets_targets: tree t on its own rows row_idx[t]
+        against column targets[t]: (Σ w·ℓ per tree, Σ w per tree, ok)."""
+        nt = self.ntrees
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        if tg.shape != (nt,):
+            raise ValueError("targets must have one entry per tree")
+        idx = np.ascontiguousarray(row_idx, dtype=np.int64)
+        if idx.ndim != 2 or idx.shape[0] != nt:
+            raise ValueError("row_idx must be (ntrees, batch_size)")
+        sums = np.empty(max(nt, 1), dtype=np.float64)
+        wsum = np.empty(max(nt, 1), dtype=np.float64)
+        ok = np.empty(max(nt, 1), dtype=np.uint8)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_eval_loss_rowsets_targets(ds.handle, self.handle, int(loss_kind), _p(par), _p(tg), _p(idx),
+                                                    idx.shape[1], _p(sums), _p(wsum), _p(ok)))
         return sums[:nt], wsum[:nt], ok[:nt].view(bool)
 
     def eval_loss_packed(self, ds: DeviceDataset, loss_kind: int, d_out: int, params=None):

@@ -17,7 +17,8 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .dataset import Dataset, GroupDataset
+from . import constants as K
+from .dataset import Dataset, GroupDataset, MultiDataset
 from .engine import DeviceDataset, Program, get_context
 from .node import Node, count_nodes, flatten
 from .options import Options
@@ -197,12 +198,87 @@ def eval_loss_batch(trees: Sequence[Node], dataset: Dataset, options: Options,
     return eval_loss_batch_ok(trees, dataset, options, row_idx, device, program)[0]
 
 
+# Trees per call up to which a MultiDataset's candidates are scored by the fused
+# call; larger batches go to per-target views (regroup, score, scatter back).
+# The fused call always runs in the interpreter and a view call runs tree code from
+# 256 shallow trees on (api.cpp jit_wanted, SRHIP_JIT), so the expected switch was
+# 256. Measured (tools/bench_targets.py, profiles/targets_timing.json; Float32, L2,
+# 5 features, K = 4; one step = a program built, scored and destroyed per call, as
+# these functions do): 4 x 66 trees on 100k rows: fused 0.37 ms, four view calls
+# 0.58 ms; 4 x 1024 trees on 1M rows: fused 8.8 ms (kernels 7.4), four view calls
+# 52-58 ms (kernels 17.9, the rest building and loading tree code for one use). No
+# crossover up to 4096 trees, the largest batch measured: the fused call is used up
+# to there and the views beyond it. A caller that keeps its programs (srhip.Program on
+# mds.target(k).device()) pays for the tree code once and is not covered by this.
+FUSED_TARGETS_MAX_TREES = 4096
+
+
+def _check_targets(trees, dataset: MultiDataset, targets) -> np.ndarray:
+    if targets is None:
+        if dataset.ntargets > 1:
+            raise ValueError("a MultiDataset with several targets needs targets= (one target index per tree), "
+                             "or score dataset.target(k)")
+        targets = np.zeros(len(trees), dtype=np.int32)
+    tg = np.asarray(targets)
+    if tg.shape != (len(trees),):
+        raise ValueError("targets must have one entry per tree")
+    if len(tg) and (tg.min() < 0 or tg.max() >= dataset.ntargets):
+        raise ValueError("target index out of range")
+    return tg.astype(np.int32)
+
+
+def _scatter_by_target(trees, dataset: MultiDataset, tg: np.ndarray, fn):
+    """Regroup the trees by target, score each group with fn(subtrees, dataset.target(k), positions),
+    scatter the (losses, ok) back."""
+    losses = np.zeros(len(trees), dtype=dataset.T)
+    ok = np.zeros(len(trees), dtype=bool)
+    for k in np.unique(tg):
+        idx = np.flatnonzero(tg == k)
+        lv, kv = fn([trees[t] for t in idx], dataset.target(int(k)), idx)
+        losses[idx] = lv
+        ok[idx] = kv
+    return losses, ok
+
+
+def _eval_loss_targets(trees, dataset: MultiDataset, options: Options, row_idx, device, targets, fused):
+    tg = _check_targets(trees, dataset, targets)
+    if options.loss_function is not None:
+        return _scatter_by_target(trees, dataset, tg,
+                                  lambda sub, ds, idx: eval_loss_batch_ok(sub, ds, options, row_idx, device))
+    loss = options.elementwise_loss
+    if fused is None:
+        fused = len(trees) <= FUSED_TARGETS_MAX_TREES
+    # the fused call covers all rows and the table losses; everything else goes through views
+    if not fused or row_idx is not None or loss.kind >= K.EXPR_LOSS_BEGIN:
+        return _scatter_by_target(trees, dataset, tg,
+                                  lambda sub, ds, idx: eval_loss_batch_ok(sub, ds, options, row_idx, device))
+    T = dataset.T
+    dev = dataset.device(device)
+    prog = Program(dev.ctx, flatten(trees, options, dtype=T), T, interpreted=True)
+    sums, wsum, ok = prog.eval_loss_targets(dev, loss.kind, tg, loss.params)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = (sums / wsum[tg]).astype(T)
+    out[~ok] = T(np.inf)
+    return out, ok
+
+
 def eval_loss_batch_ok(trees: Sequence[Node], dataset: Dataset, options: Options,
                        row_idx: Optional[np.ndarray] = None, device: Optional[int] = None,
-                       program: Optional[Program] = None) -> Tuple[np.ndarray, np.ndarray]:
+                       program: Optional[Program] = None, targets: Optional[Sequence[int]] = None,
+                       fused: Optional[bool] = None) -> Tuple[np.ndarray, np.ndarray]:
     """(losses in T, did_succeed per tree). A GroupDataset runs over its
     device group (all rows: no row_idx there; `program`, if given, a
-    GroupProgram of that group; `device` unused)."""
+    GroupProgram of that group; `device` unused). A MultiDataset takes
+    targets (one target index per tree) and scores tree t against target
+    targets[t]: in one fused launch up to FUSED_TARGETS_MAX_TREES trees, on
+    per-target views (regroup, score, scatter back) beyond; `fused` forces
+    either."""
+    if isinstance(dataset, MultiDataset):
+        if program is not None:
+            raise ValueError("program= is not supported with a MultiDataset")
+        return _eval_loss_targets(list(trees), dataset, options, row_idx, device, targets, fused)
+    if targets is not None:
+        raise ValueError("targets= needs a MultiDataset")
     if options.loss_function is not None:
         f = options.loss_function
         vals = np.asarray([f(t, dataset, options) for t in trees], dtype=dataset.T)
@@ -228,26 +304,37 @@ def eval_loss_batch_ok(trees: Sequence[Node], dataset: Dataset, options: Options
 
 
 def eval_loss_batch_rowsets(trees: Sequence[Node], dataset: Dataset, options: Options,
-                            rows: Sequence[np.ndarray], device: Optional[int] = None
-                            ) -> Tuple[np.ndarray, np.ndarray]:
+                            rows: Sequence[np.ndarray], device: Optional[int] = None,
+                            targets: Optional[Sequence[int]] = None) -> Tuple[np.ndarray, np.ndarray]:
     """score_func_batch's evaluation for many trees, tree t on its OWN row
     sample rows[t] (with replacement, LossFunctions.jl:95-115; the reference
     draws one sample per call, :98): (losses in T, did_succeed). One engine
     launch for all trees (srhip_eval_loss_rowsets) when the samples have one
     length (the reference's batch_size); one per distinct length otherwise.
     score_func_batch uses options.elementwise_loss even when loss_function is
-    set (:101-111), and so does this."""
+    set (:101-111), and so does this. A MultiDataset takes targets (one target
+    index per tree): tree t's sample is scored against target targets[t], still
+    in one launch (srhip_eval_loss_rowsets_targets)."""
     T = dataset.T
     n = len(trees)
     losses = np.zeros(n, dtype=T)
     ok = np.zeros(n, dtype=bool)
+    multi = isinstance(dataset, MultiDataset)
+    if multi:
+        tg = _check_targets(trees, dataset, targets)
+    elif targets is not None:
+        raise ValueError("targets= needs a MultiDataset")
     if n == 0:
         return losses, ok
     rows = [np.asarray(r, dtype=np.int64) for r in rows]
     if len(rows) != n:
         raise ValueError("one row sample per tree")
-    dev = dataset.device(device)
     loss = options.elementwise_loss
+    if multi and loss.kind >= K.EXPR_LOSS_BEGIN:  # expression losses: views
+        return _scatter_by_target(list(trees), dataset, tg,
+                                  lambda sub, ds, idx: eval_loss_batch_rowsets(sub, ds, options,
+                                                                               [rows[t] for t in idx], device))
+    dev = dataset.device(device)
     by_len = {}
     for t, r in enumerate(rows):
         by_len.setdefault(len(r), []).append(t)
@@ -255,7 +342,10 @@ def eval_loss_batch_rowsets(trees: Sequence[Node], dataset: Dataset, options: Op
         sub = [trees[t] for t in idx]
         prog = Program(dev.ctx, flatten(sub, options, dtype=T), T, interpreted=True)
         R = np.stack([rows[t] for t in idx]) if bs else np.zeros((len(idx), 0), dtype=np.int64)
-        sums, wsum, k = prog.eval_loss_rowsets(dev, loss.kind, R, loss.params)
+        if multi:
+            sums, wsum, k = prog.eval_loss_rowsets_targets(dev, loss.kind, tg[idx], R, loss.params)
+        else:
+            sums, wsum, k = prog.eval_loss_rowsets(dev, loss.kind, R, loss.params)
         with np.errstate(invalid="ignore", divide="ignore"):
             lv = (sums / wsum).astype(T)
         lv[~k] = T(np.inf)
