@@ -495,6 +495,28 @@ int32_t srhip_eval_loss_grad(srhip_dataset* ds, const srhip_program* prog,
                              double* out_loss_sum, double* out_dloss,
                              double* out_weight_sum, uint8_t* out_ok);
 
+/* ---- constant gradients on per-tree minibatches ------------------------------
+ * srhip_eval_loss_grad with tree t on its own sample: row_idx [ntrees][batch_size], 0-based within the
+ * shard, repetition allowed. out_weight_sum is [ntrees]. Rules as srhip_eval_loss_rowsets:
+ *   out_loss_sum[t]   = Σ_k w_{idx[t][k]} · ℓ(ŷ_t, y) over tree t's sample (NaN if !ok)
+ *   out_dloss[c]      = Σ_k w_{idx[t][k]} · ∂ℓ/∂c for every constant c of tree t (NaN if !ok)
+ *   out_weight_sum[t] = Σ_k w_{idx[t][k]} (batch_size when unweighted)
+ *   out_ok[t]         = did_succeed on that sample
+ * Every loss kind srhip_eval_loss_grad takes is accepted, with the same rule for
+ * expression losses that read w. Answered before any launch with
+ * SRHIP_ERR_INVALID: a null row_idx with ntrees·batch_size > 0, an index outside
+ * [0, rows), a negative batch_size, a dataset with several targets (take a view).
+ * Runs in the forward-mode interpreter, one (tree, tangent group) per workgroup
+ * over the tree's gathered sample, with the tiles, lane sums and row-group sum of
+ * a dataset made of that sample: the results equal srhip_eval_loss_grad's on such
+ * a dataset bit for bit. Gradient tree code is never used (srhip_last_tree_code
+ * gives 0) and none is built for such a call; srhip_last_kernel_name gives
+ * "grad_kernel_seg<float>" and its kin. */
+int32_t srhip_eval_loss_grad_rowsets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                     const double* loss_params, const int64_t* row_idx, int64_t batch_size,
+                                     double* out_loss_sum, double* out_dloss, double* out_weight_sum,
+                                     uint8_t* out_ok);
+
 /* Per-row constant gradients for few trees: out_grad is
  * [total consts][rows] (∂ŷ_i/∂c), out_value [ntrees][rows]. */
 int32_t srhip_eval_grad_tree_array(srhip_dataset* ds, const srhip_program* prog,
@@ -539,13 +561,33 @@ typedef struct srhip_constopt_options {
 int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
                                        const srhip_constopt_options* opts, void* out_consts, double* out_loss,
                                        uint8_t* out_converged, double* out_num_evals);
+/* srhip_optimize_constants_batch with input tree t optimised on its own sample, the same rows for
+ * all of its starts, iterations and the final evaluation. Outputs as srhip_optimize_constants_batch;
+ * out_loss is the loss on the sample. row_idx is [ntrees][batch_size] as for
+ * srhip_eval_loss_grad_rowsets, with the same rules, and batch_size < 1 is
+ * SRHIP_ERR_INVALID. Every candidate is scored on the sample of its input tree:
+ * loss-only phases as srhip_eval_loss_rowsets, gradient phases as
+ * srhip_eval_loss_grad_rowsets; the samples of an evaluation set's candidates are
+ * gathered once when the set is made. out_num_evals counts evaluations as
+ * srhip_optimize_constants_batch does: a caller that follows the reference's
+ * convention (src/Mutate.jl:43) scales it by batch_size / n.
+ * Not in this version: group datasets (srhip_group_optimize_constants); a
+ * target per tree (take a view); one gather shared among all sets through a
+ * segment indirection; row sets in srhip_optimize_constants_cb, whose evaluator
+ * owns the rows. */
+int32_t srhip_optimize_constants_rowsets(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                         const srhip_constopt_options* opts, const int64_t* row_idx,
+                                         int64_t batch_size, void* out_consts, double* out_loss,
+                                         uint8_t* out_converged, double* out_num_evals);
 /* Where the last srhip_optimize_constants_batch call of this thread spent
  * its time: out[0..8] = total, program builds, set_constants, loss calls,
  * gradient calls, the kernels inside those calls (HIP events) — seconds —
  * then the number of builds, loss calls, gradient calls and full program
  * rebuilds inside set_constants, then the builds' tree-code generation and
- * code-object load times (s) (the first n of these 12 written). The rest of
- * the total is the host optimiser's own algebra. */
+ * code-object load times (s), then (srhip_optimize_constants_rowsets) the
+ * sets' sample gathers (s) and the number of evaluations run on row segments
+ * (the first n of these 14 written). The rest of the total is the host
+ * optimiser's own algebra. */
 int32_t srhip_constopt_profile(double* out, int32_t n);
 /* The same optimiser over any evaluator (row-sharded datasets whose partials
  * the caller all-reduces, custom losses on the CPU, tests): fn scores

@@ -309,6 +309,8 @@ struct srhip_program {
   bool jit_forced = false;
   // gradient tree code allowed (the rerun of Periodic's handed-back trees: none)
   bool gjit_allowed = true;
+  // the gradient programs were built by a call on per-tree row sets, without tree code
+  bool gjit_skipped = false;
   // tree code reads its constants from the device programs (jit::Options::memc):
   // built at the first new constant set, after which set_constants only
   // updates the programs in place
@@ -877,10 +879,15 @@ void patch_grad_constants(srhip_program* p) {
 
 // Gradient programs: compiled without folding, one work item per (tree,
 // tangent group of kGradG constants), cost-sorted.
+// tree_code false (a call on per-tree row sets, which never runs it): no gradient
+// tree code is built; the first later call that could run it builds the programs
+// again with it.
 template <typename T>
-void build_grad_program(srhip_program* p) {
+void build_grad_program(srhip_program* p, bool tree_code = true) {
+  if (p->grad_built && tree_code && p->gjit_skipped) p->grad_built = false;
   if (p->grad_built && p->grad_stale) patch_grad_constants<T>(p);
   if (p->grad_built) return;
+  p->gjit_skipped = !tree_code && p->gjit_allowed && gjit_wanted(p->ntrees);
   srhip_trees tr;
   tr.ntrees = p->ntrees;
   tr.node_off = p->node_off.data();
@@ -918,7 +925,7 @@ void build_grad_program(srhip_program* p) {
     std::vector<int32_t> cand;
     for (int t = 0; t < p->ntrees; ++t)
       if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
-    if (p->gjit_allowed && gjit_wanted((int)cand.size())) {
+    if (tree_code && p->gjit_allowed && gjit_wanted((int)cand.size())) {
       std::stable_sort(cand.begin(), cand.end(), [&](int32_t x, int32_t y) {
         return cb.cost[x] != cb.cost[y] ? cb.cost[x] > cb.cost[y] : x < y;
       });
@@ -941,7 +948,7 @@ void build_grad_program(srhip_program* p) {
     std::vector<int32_t> cand;
     for (int t = 0; t < p->ntrees; ++t)
       if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
-    if (p->gjit_allowed && gjit_wanted((int)cand.size()) && jit::available64()) {
+    if (tree_code && p->gjit_allowed && gjit_wanted((int)cand.size()) && jit::available64()) {
       std::stable_sort(cand.begin(), cand.end(), [&](int32_t x, int32_t y) {
         return cb.cost[x] != cb.cost[y] ? cb.cost[x] > cb.cost[y] : x < y;
       });
@@ -2142,25 +2149,36 @@ int eval_loss_impl(srhip_dataset* ds, const srhip_program* p, int loss, const do
   return SRHIP_OK;
 }
 
-// score_func_batch for every tree of the program on its OWN row sample
-// (src/LossFunctions.jl:95-115 draws `batch_size` rows with replacement per
-// call): the samples are gathered into one segment per tree — seg rows,
-// row set t in [t·seg, t·seg + bs), padded with its last row — and the
-// interpreter runs one tree per workgroup over its segment (run_eval seg).
-// One gather, one evaluation launch and one finalize for all trees.
+// Per-tree row samples (src/LossFunctions.jl:95-115 draws `batch_size` rows with
+// replacement per call) gathered into one segment per tree: seg rows, row set t
+// in [t·seg, t·seg + bs), padded with its last row. One gathered buffer serves the
+// loss (run_eval seg) and the gradient (run_grad) launches.
 template <typename T>
-int eval_loss_rowsets_impl(srhip_dataset* ds, const srhip_program* p, int loss, const double* params,
-                           const int64_t* row_idx, int64_t bs, double* out_sum, double* out_wsum,
-                           uint8_t* out_ok, const int32_t* target = nullptr) {
-  // target (srhip_eval_loss_rowsets_targets, checked by the caller): tree t's sample takes its
-  // y and w from column target[t] of the dataset's target-major y / w
-  srhip_ctx* c = p->ctx;
-  const int nt = p->ntrees;
+struct RowSegs {
+  const T* X = nullptr;  // [nfeat][n_pad]
+  const T* y = nullptr;  // [n_pad]
+  const T* w = nullptr;  // [n_pad] or nullptr
+  int64_t seg = 0, n_pad = 0, bs = 0;
+};
+
+// the rules of a [nt][bs] row-set argument, answered before any launch
+void check_row_sets(const srhip_dataset* ds, int nt, const int64_t* row_idx, int64_t bs) {
   if (bs < 0) throw Error(SRHIP_ERR_INVALID, "negative batch size");
   if (bs > 0 && nt > 0 && !row_idx) throw Error(SRHIP_ERR_INVALID, "row_idx is NULL");
   const int64_t nidx = (int64_t)nt * bs;
   for (int64_t k = 0; k < nidx; ++k)
     if (row_idx[k] < 0 || row_idx[k] >= ds->rows) throw Error(SRHIP_ERR_INVALID, "row index out of range");
+}
+
+// Check, upload and gather nt row sets of bs rows into `out` (index scratch
+// `idx`; both the context's, or a buffer of the caller's that outlives the call).
+// target (srhip_eval_loss_rowsets_targets, checked by the caller): tree t's sample
+// takes its y and w from column target[t] of the dataset's target-major y / w
+template <typename T>
+RowSegs<T> gather_row_sets(srhip_ctx* c, const srhip_dataset* ds, int nt, const int64_t* row_idx, int64_t bs,
+                           const int32_t* target, DevBuf& idx, DevBuf& out) {
+  check_row_sets(ds, nt, row_idx, bs);
+  const int64_t nidx = (int64_t)nt * bs;
   // segment: a power of two >= the row group of any interpreter variant
   // (rows_wg = tiles · 64R is a power of two < 2·bs, or one 512-row tile)
   int64_t seg = 512;
@@ -2169,39 +2187,63 @@ int eval_loss_rowsets_impl(srhip_dataset* ds, const srhip_program* p, int loss, 
   const T* w = static_cast<const T*>(ds->w);
   const int64_t gp = seg * std::max(nt, 1);
   const size_t es = sizeof(T);
-  c->scratch_idx.ensure((size_t)std::max<int64_t>(nidx, 1) * sizeof(int64_t));
-  c->gather.ensure((size_t)gp * (ds->nfeat + 2) * es);
-  T* Xg = static_cast<T*>(c->gather.p);
+  idx.ensure((size_t)std::max<int64_t>(nidx, 1) * sizeof(int64_t));
+  out.ensure((size_t)gp * (ds->nfeat + 2) * es);
+  T* Xg = static_cast<T*>(out.p);
   T* yg = Xg + (size_t)gp * ds->nfeat;
   T* wg = yg + gp;
   if (nidx > 0) {
-    HIP_CHECK(hipMemcpyAsync(c->scratch_idx.p, row_idx, nidx * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(idx.p, row_idx, nidx * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     if (target) {
       c->tgt.ensure((size_t)nt * sizeof(int32_t));
       HIP_CHECK(hipMemcpyAsync(c->tgt.p, target, (size_t)nt * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
       HIP_CHECK(launch_gather_rows_targets<T>(static_cast<const T*>(ds->X), static_cast<const T*>(ds->y), w,
                                               static_cast<const int32_t*>(c->tgt.p), ds->nfeat, ds->n_pad,
-                                              static_cast<const int64_t*>(c->scratch_idx.p), bs, seg, gp, Xg, yg,
+                                              static_cast<const int64_t*>(idx.p), bs, seg, gp, Xg, yg,
                                               w ? wg : nullptr, c->stream));
     } else {
       HIP_CHECK(launch_gather_rows<T>(static_cast<const T*>(ds->X), static_cast<const T*>(ds->y), w, ds->nfeat,
-                                      ds->n_pad, static_cast<const int64_t*>(c->scratch_idx.p), bs, seg, gp, Xg, yg,
+                                      ds->n_pad, static_cast<const int64_t*>(idx.p), bs, seg, gp, Xg, yg,
                                       w ? wg : nullptr, c->stream));
     }
   }
-  run_eval<T>(c, p, MODE_LOSS, Xg, yg, w ? wg : nullptr, bs, gp, ds->nfeat, loss, params ? params[0] : 0.0, nullptr,
-              0, seg);
+  RowSegs<T> rs;
+  rs.X = Xg;
+  rs.y = yg;
+  rs.w = w ? wg : nullptr;
+  rs.seg = seg;
+  rs.n_pad = gp;
+  rs.bs = bs;
+  return rs;
+}
+
+// Σ w over tree t's (repeated) sample, on the host
+void row_set_weight_sums(const srhip_dataset* ds, int nt, const int64_t* row_idx, int64_t bs, const int32_t* target,
+                         double* out_wsum) {
+  for (int t = 0; t < nt; ++t) {
+    double s = 0.0;
+    const std::vector<double>& hw = (target && ds->ntargets > 1) ? ds->t_h_w[(size_t)target[t]] : ds->h_w;
+    if (ds->w)
+      for (int64_t k = 0; k < bs; ++k) s += hw[row_idx[(size_t)t * bs + k]];
+    else
+      s = (double)bs;
+    out_wsum[t] = s;
+  }
+}
+
+// score_func_batch for every tree of the program on its OWN row sample: the
+// interpreter runs one tree per workgroup over its segment (run_eval seg).
+// One gather, one evaluation launch and one finalize for all trees.
+template <typename T>
+int eval_loss_rowsets_impl(srhip_dataset* ds, const srhip_program* p, int loss, const double* params,
+                           const int64_t* row_idx, int64_t bs, double* out_sum, double* out_wsum,
+                           uint8_t* out_ok, const int32_t* target = nullptr) {
+  srhip_ctx* c = p->ctx;
+  const RowSegs<T> rs = gather_row_sets<T>(c, ds, p->ntrees, row_idx, bs, target, c->scratch_idx, c->gather);
+  run_eval<T>(c, p, MODE_LOSS, rs.X, rs.y, rs.w, bs, rs.n_pad, ds->nfeat, loss, params ? params[0] : 0.0, nullptr, 0,
+              rs.seg);
   collect_results(c, p, bs, out_sum, out_ok);  // (the copy of row_idx is ordered before these waits)
-  if (out_wsum)
-    for (int t = 0; t < nt; ++t) {  // Σ w over tree t's (repeated) sample
-      double s = 0.0;
-      const std::vector<double>& hw = (target && ds->ntargets > 1) ? ds->t_h_w[(size_t)target[t]] : ds->h_w;
-      if (w)
-        for (int64_t k = 0; k < bs; ++k) s += hw[row_idx[(size_t)t * bs + k]];
-      else
-        s = (double)bs;
-      out_wsum[t] = s;
-    }
+  if (out_wsum) row_set_weight_sums(ds, p->ntrees, row_idx, bs, target, out_wsum);
   return SRHIP_OK;
 }
 
@@ -2362,8 +2404,16 @@ int eval_tree_array_impl(srhip_dataset* ds, const srhip_program* p, void* out, u
 
 template <typename T>
 void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds, int loss, double lparam,
-              T* out_value, T* out_grad, int64_t out_stride) {
-  build_grad_program<T>(p);
+              T* out_value, T* out_grad, int64_t out_stride, const RowSegs<T>* rs = nullptr) {
+  // rs (GRAD_LOSS): tree t on its own gathered sample, segment t of rs; the
+  // interpreter, one work item per workgroup of one wave, no tree code
+  build_grad_program<T>(p, rs == nullptr);
+  const T* const vX = rs ? rs->X : static_cast<const T*>(ds->X);
+  const T* const vy = rs ? rs->y : static_cast<const T*>(ds->y);
+  const T* const vw = rs ? rs->w : static_cast<const T*>(ds->w);
+  const int64_t vrows = rs ? rs->bs : ds->rows;
+  const int64_t vpad = rs ? rs->n_pad : ds->n_pad;
+  const int64_t seg = rs ? rs->seg : 0;
   hipStream_t s = c->stream;
   timing_reset(c);
   const int nt = p->ntrees;
@@ -2375,7 +2425,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
   // interpreter items of the other trees follow
   bool use_gjit = false;
   if constexpr (std::is_same<T, float>::value) {
-    jit::GradModule* gm = (p->gjit && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
+    jit::GradModule* gm = (p->gjit && !rs && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
                               ? grad_module(p, loss, lparam)
                               : nullptr;
     if (gm) {
@@ -2449,7 +2499,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
                                          p->d_gjit_cidx, p->ngjit_cidx, static_cast<double*>(c->dloss.p), s));
       }
     }
-  } else if (jit::GradModule64* gm = (p->gjit64 && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
+  } else if (jit::GradModule64* gm = (p->gjit64 && !rs && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
                                          ? grad_module64(p, loss, lparam)
                                          : nullptr) {
     // Float64 gradient tree code: 128-row tiles of y, the features it reads, w
@@ -2514,15 +2564,25 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     const int nitems = ngi[pass];
     const int item0 = first;
     first += nitems;
-    if (nitems == 0 || ds->rows == 0) continue;
+    if (nitems == 0 || vrows == 0) continue;
     const bool deep = pass == 3;
     int G = pass == 0 ? 1 : pass == 1 ? 2 : kGradG;
     EvalPlan plan;
     const int wm = wide_mode();
-    if (wm == 1 || !plan_grad(p->dtype, deep, G, mode, ds->w != nullptr, ds->nfeat, ds->rows, nitems, &plan)) {
+    if (wm == 1 || !plan_grad(p->dtype, deep, G, mode, vw != nullptr, ds->nfeat, vrows, nitems, &plan)) {
       // the wide variant: one configuration, kGradG tangents (a tree's tangents past its constants stay 0)
       G = kGradG;
-      if (wm == 0 || !plan_grad_wide(p->dtype, mode, ds->w != nullptr, ds->rows, nitems, &plan)) throw_lds(ds->nfeat);
+      if (wm == 0 || !plan_grad_wide(p->dtype, mode, vw != nullptr, vrows, nitems, &plan)) throw_lds(ds->nfeat);
+    }
+    if (seg > 0) {
+      // per-tree row sets: the tiles and row groups of a dataset of vrows rows (the
+      // per-item arithmetic is that dataset's), one item per workgroup of one wave
+      // staging its tree's segment (grad_kernels.hip seg0); the segment holds the row groups
+      plan.lds_bytes -= (size_t)(plan.tpb - 1) * (2 + G) * sizeof(T);
+      plan.tpb = 1;
+      plan.ntg = nitems;
+      plan.threads = 64;
+      if ((int64_t)plan.nrg * plan.rows_wg > seg) throw Error(SRHIP_ERR_INVALID, "row set segment too short");
     }
     GradArgs<T> a;
     a.prog = static_cast<const Ins<T>*>(p->d_gcode);
@@ -2531,11 +2591,12 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     a.nitems = nitems;
     a.dyn = interp_dyn() ? 1 : 0;
     a.const_off = p->d_const_off;
-    a.X = static_cast<const T*>(ds->X);
-    a.y = static_cast<const T*>(ds->y);
-    a.w = static_cast<const T*>(ds->w);
-    a.n = ds->rows;
-    a.n_pad = ds->n_pad;
+    a.X = vX;
+    a.y = vy;
+    a.w = vw;
+    a.n = vrows;
+    a.n_pad = vpad;
+    a.seg = seg;
     a.nfeat = ds->nfeat;
     a.ntiles = plan.ntiles;
     a.ntg = plan.ntg;
@@ -2552,8 +2613,12 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     a.out_grad = out_grad;
     a.out_stride = out_stride;
     const int tk = timed_begin(c, s);
-    note_kernel(plan.wide ? (sizeof(T) == 4 ? "grad_kernel_wide<float>" : "grad_kernel_wide<double>")
-                          : (sizeof(T) == 4 ? "grad_kernel<float>" : "grad_kernel<double>"));
+    if (seg > 0)
+      note_kernel(plan.wide ? (sizeof(T) == 4 ? "grad_kernel_wide_seg<float>" : "grad_kernel_wide_seg<double>")
+                            : (sizeof(T) == 4 ? "grad_kernel_seg<float>" : "grad_kernel_seg<double>"));
+    else
+      note_kernel(plan.wide ? (sizeof(T) == 4 ? "grad_kernel_wide<float>" : "grad_kernel_wide<double>")
+                            : (sizeof(T) == 4 ? "grad_kernel<float>" : "grad_kernel<double>"));
     HIP_CHECK(launch_grad<T>(plan, a, mode, s));
     timed_end(c, s, tk);
     HIP_CHECK(launch_grad_finalize<T>(a, static_cast<double*>(c->sums.p), static_cast<uint8_t*>(c->oks.p),
@@ -2674,6 +2739,21 @@ int eval_loss_grad_impl(srhip_dataset* ds, srhip_program* p, int loss, const dou
   if (out_sum) std::copy(sum.begin(), sum.end(), out_sum);
   if (out_dloss && nconst > 0) std::copy(dl.begin(), dl.begin() + nconst, out_dloss);
   if (out_ok) std::copy(ok.begin(), ok.end(), out_ok);
+  return SRHIP_OK;
+}
+
+// srhip_eval_loss_grad with tree t on its own row sample: the samples gathered as
+// for srhip_eval_loss_rowsets, then the forward-mode interpreter with one work
+// item per workgroup over its tree's segment (run_grad rs). No tree code.
+template <typename T>
+int eval_loss_grad_rowsets_impl(srhip_dataset* ds, srhip_program* p, int loss, const double* params,
+                                const int64_t* row_idx, int64_t bs, double* out_sum, double* out_dloss,
+                                double* out_wsum, uint8_t* out_ok) {
+  srhip_ctx* c = p->ctx;
+  const RowSegs<T> rs = gather_row_sets<T>(c, ds, p->ntrees, row_idx, bs, nullptr, c->scratch_idx, c->gather);
+  run_grad<T>(c, p, GRAD_LOSS, ds, loss, params ? params[0] : 0.0, nullptr, nullptr, 0, &rs);
+  collect_grad_results(c, p, bs, out_sum, out_dloss, out_ok);
+  if (out_wsum) row_set_weight_sums(ds, p->ntrees, row_idx, bs, nullptr, out_wsum);
   return SRHIP_OK;
 }
 
@@ -3521,6 +3601,26 @@ int32_t srhip_eval_loss_grad(srhip_dataset* ds, const srhip_program* prog, int32
   });
 }
 
+int32_t srhip_eval_loss_grad_rowsets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                     const double* loss_params, const int64_t* row_idx, int64_t batch_size,
+                                     double* out_loss_sum, double* out_dloss, double* out_weight_sum,
+                                     uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog);
+    check_loss(loss_kind, loss_params);
+    check_expr_loss_weights(loss_kind, ds->w != nullptr);
+    check_row_sets(ds, prog->ntrees, row_idx, batch_size);  // before the gradient programs are built
+    std::lock_guard<std::mutex> lk(prog->ctx->mu);
+    HIP_CHECK(hipSetDevice(prog->ctx->device));
+    auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
+    if (ds->dtype == SRHIP_F32)
+      return eval_loss_grad_rowsets_impl<float>(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
+                                                out_dloss, out_weight_sum, out_ok);
+    return eval_loss_grad_rowsets_impl<double>(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
+                                               out_dloss, out_weight_sum, out_ok);
+  });
+}
+
 int32_t srhip_eval_grad_tree_array(srhip_dataset* ds, const srhip_program* prog, void* out_value,
                                    void* out_grad, uint8_t* out_ok) {
   return guarded([&] {
@@ -3874,6 +3974,9 @@ struct CoptProfile {
   double total = 0, create = 0, set = 0, loss = 0, grad = 0, kernel_ms = 0;
   int64_t ncreate = 0, nloss = 0, ngrad = 0, nrebuilt = 0;
   double jit_codegen_ms = 0, jit_load_ms = 0;  // of the builds (tree code)
+  // srhip_optimize_constants_rowsets: the sets' gathers (wall), evaluations run on row segments
+  double gather = 0;
+  int64_t nseg = 0;
 };
 thread_local CoptProfile t_copt;
 double secs_since(std::chrono::steady_clock::time_point t0) {
@@ -3920,16 +4023,35 @@ struct EngineSet : copt::Set {
   const double* params;
   srhip_program* prog = nullptr;
   std::vector<int32_t> coff;  // members' constant offsets
+  // row sets (srhip_optimize_constants_rowsets): member m is evaluated on the sample
+  // of its input tree in every evaluation. The members are fixed for the set's
+  // lifetime, so their segments are gathered once, into buffers of the set (the
+  // context's scratch belongs to whichever set evaluates next).
+  int64_t bs = 0;
+  DevBuf seg_idx, seg_rows;
+  RowSegs<float> rs32;
+  RowSegs<double> rs64;
+  std::vector<double> wsums;  // Σ w over each member's sample
   EngineSet(srhip_ctx* c, srhip_dataset* d, const srhip_trees* trees, int dt, int ls, const double* pr,
-            const std::vector<int32_t>& members)
-      : ctx(c), ds(d), dtype(dt), loss(ls), params(pr) {
+            const std::vector<int32_t>& members, const int64_t* row_idx = nullptr, int64_t batch = 0)
+      : ctx(c), ds(d), dtype(dt), loss(ls), params(pr), bs(row_idx ? batch : 0) {
     MemberTrees mt(trees, dt, members);
     coff = mt.coff;
     const srhip_trees& tr = mt.tr;
     const auto t0 = std::chrono::steady_clock::now();
-    check_rc(srhip_program_create_ex(ctx, dtype, &tr, SRHIP_PROGRAM_VARYING_CONSTANTS, &prog));
+    // (row sets run in the interpreter: no tree code to build)
+    check_rc(srhip_program_create_ex(
+        ctx, dtype, &tr, SRHIP_PROGRAM_VARYING_CONSTANTS | (bs > 0 ? SRHIP_PROGRAM_INTERPRETED : 0u), &prog));
     t_copt.create += secs_since(t0);
     t_copt.ncreate += 1;
+    if (bs > 0) {
+      try {
+        gather_members(members, row_idx);
+      } catch (...) {
+        release();
+        throw;
+      }
+    }
     {
       int32_t nt = 0, nf = 0;
       int64_t nb = 0;
@@ -3940,10 +4062,54 @@ struct EngineSet : copt::Set {
       }
     }
   }
+  void release() {
+    if (prog) (void)srhip_program_destroy(prog);  // (waits for the stream: nothing reads the segments after it)
+    prog = nullptr;
+    if (seg_idx.p || seg_rows.p) {
+      (void)hipSetDevice(ctx->device);
+      seg_idx.release();
+      seg_rows.release();
+    }
+  }
   ~EngineSet() override {
     int64_t inplace = 0, rebuilt = 0;
     if (prog && srhip_program_update_stats(prog, &inplace, &rebuilt) == SRHIP_OK) t_copt.nrebuilt += rebuilt;
-    if (prog) (void)srhip_program_destroy(prog);
+    release();
+  }
+  // the members' row sets (row_idx[members[m]], checked by the caller) gathered into the set's buffers
+  void gather_members(const std::vector<int32_t>& members, const int64_t* row_idx) {
+    const int n = (int)members.size();
+    std::vector<int64_t> idx((size_t)n * bs);
+    for (int m = 0; m < n; ++m)
+      std::copy(row_idx + (size_t)members[m] * bs, row_idx + (size_t)(members[m] + 1) * bs, idx.begin() + (size_t)m * bs);
+    wsums.assign(std::max(n, 1), 0.0);
+    const auto t0 = std::chrono::steady_clock::now();
+    check_program_vs_dataset(ds, prog);
+    {
+      std::lock_guard<std::mutex> lk(ctx->mu);
+      HIP_CHECK(hipSetDevice(ctx->device));
+      if (dtype == SRHIP_F32) rs32 = gather_row_sets<float>(ctx, ds, n, idx.data(), bs, nullptr, seg_idx, seg_rows);
+      else rs64 = gather_row_sets<double>(ctx, ds, n, idx.data(), bs, nullptr, seg_idx, seg_rows);
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));  // idx leaves scope
+    }
+    row_set_weight_sums(ds, n, idx.data(), bs, nullptr, wsums.data());
+    t_copt.gather += secs_since(t0);
+  }
+  // loss (and ∂L/∂c) of every member on its gathered sample
+  void eval_segments(bool grad, double* sums, double* dl, uint8_t* ok) {
+    check_program_vs_dataset(ds, prog);  // as the public entry points: device, dtype, feature count, finite X
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    const double lp = params ? params[0] : 0.0;
+    if (dtype == SRHIP_F32) {
+      if (grad) run_grad<float>(ctx, prog, GRAD_LOSS, ds, loss, lp, nullptr, nullptr, 0, &rs32);
+      else run_eval<float>(ctx, prog, MODE_LOSS, rs32.X, rs32.y, rs32.w, bs, rs32.n_pad, ds->nfeat, loss, lp, nullptr, 0, rs32.seg);
+    } else {
+      if (grad) run_grad<double>(ctx, prog, GRAD_LOSS, ds, loss, lp, nullptr, nullptr, 0, &rs64);
+      else run_eval<double>(ctx, prog, MODE_LOSS, rs64.X, rs64.y, rs64.w, bs, rs64.n_pad, ds->nfeat, loss, lp, nullptr, 0, rs64.seg);
+    }
+    if (grad) collect_grad_results(ctx, prog, bs, sums, dl, ok);
+    else collect_results(ctx, prog, bs, sums, ok);
   }
   void eval(const std::vector<double>& X, bool grad, std::vector<double>& f, std::vector<double>& g) override {
     const int n = (int)coff.size() - 1;
@@ -3962,8 +4128,14 @@ struct EngineSet : copt::Set {
     std::vector<uint8_t> ok(std::max(n, 1));
     double wsum = 0.0;
     t0 = std::chrono::steady_clock::now();
-    if (grad) check_rc(srhip_eval_loss_grad(ds, prog, loss, params, sums.data(), dl.data(), &wsum, ok.data()));
-    else check_rc(srhip_eval_loss(ds, prog, loss, params, nullptr, 0, sums.data(), &wsum, ok.data()));
+    if (bs > 0) {
+      eval_segments(grad, sums.data(), dl.data(), ok.data());
+      t_copt.nseg += 1;
+    } else if (grad) {
+      check_rc(srhip_eval_loss_grad(ds, prog, loss, params, sums.data(), dl.data(), &wsum, ok.data()));
+    } else {
+      check_rc(srhip_eval_loss(ds, prog, loss, params, nullptr, 0, sums.data(), &wsum, ok.data()));
+    }
     (grad ? t_copt.grad : t_copt.loss) += secs_since(t0);
     (grad ? t_copt.ngrad : t_copt.nloss) += 1;
     {
@@ -3972,13 +4144,16 @@ struct EngineSet : copt::Set {
     }
     f.assign(n, 0.0);
     for (int t = 0; t < n; ++t) {
-      const double v = sums[t] / wsum;
+      const double ws = bs > 0 ? wsums[t] : wsum;  // (row sets: Σ w of the member's own sample)
+      const double v = sums[t] / ws;
       f[t] = (ok[t] && std::isfinite(v)) ? v : INFINITY;
     }
     if (grad) {
       g.assign(nc, 0.0);
-      for (int t = 0; t < n; ++t)
-        for (int32_t j = coff[t]; j < coff[t + 1]; ++j) g[j] = ok[t] ? dl[j] / wsum : NAN;
+      for (int t = 0; t < n; ++t) {
+        const double ws = bs > 0 ? wsums[t] : wsum;
+        for (int32_t j = coff[t]; j < coff[t + 1]; ++j) g[j] = ok[t] ? dl[j] / ws : NAN;
+      }
     }
   }
 };
@@ -3988,8 +4163,12 @@ struct EngineFactory : copt::Factory {
   const srhip_trees* trees;
   int dtype, loss;
   const double* params;
+  // srhip_optimize_constants_rowsets: [ntrees][batch_size], input tree t's sample
+  const int64_t* row_idx = nullptr;
+  int64_t batch_size = 0;
   std::unique_ptr<copt::Set> make(const std::vector<int32_t>& members) override {
-    return std::unique_ptr<copt::Set>(new EngineSet(ctx, ds, trees, dtype, loss, params, members));
+    return std::unique_ptr<copt::Set>(
+        new EngineSet(ctx, ds, trees, dtype, loss, params, members, row_idx, batch_size));
   }
 };
 
@@ -4056,14 +4235,46 @@ int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const 
   });
 }
 
+int32_t srhip_optimize_constants_rowsets(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                         const srhip_constopt_options* opts, const int64_t* row_idx,
+                                         int64_t batch_size, void* out_consts, double* out_loss,
+                                         uint8_t* out_converged, double* out_num_evals) {
+  return guarded([&] {
+    if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
+    if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
+    if (ds->ntargets > 1)
+      throw Error(SRHIP_ERR_INVALID, "dataset has several targets: take a view of one (srhip_dataset_view)");
+    check_loss(opts->loss_kind, opts->loss_params);
+    check_expr_loss_weights(opts->loss_kind, ds->w != nullptr);
+    if (batch_size < 1) throw Error(SRHIP_ERR_INVALID, "batch_size must be at least 1");
+    t_copt = CoptProfile();
+    const auto t0 = std::chrono::steady_clock::now();
+    copt::Problem pb = make_problem(trees, ds->dtype);
+    check_row_sets(ds, trees->ntrees, row_idx, batch_size);
+    EngineFactory fac;
+    fac.ctx = ctx ? ctx : ds->ctx;
+    fac.ds = ds;
+    fac.trees = trees;
+    fac.dtype = ds->dtype;
+    fac.loss = opts->loss_kind;
+    fac.params = opts->loss_params;
+    fac.row_idx = row_idx;
+    fac.batch_size = batch_size;
+    const copt::Result r = copt::optimize(pb, make_copt_options(opts), fac);
+    write_result(r, ds->dtype, out_consts, out_loss, out_converged, out_num_evals, true);
+    t_copt.total = secs_since(t0);
+    return SRHIP_OK;
+  });
+}
+
 int32_t srhip_constopt_profile(double* out, int32_t n) {
   return guarded([&] {
     if (!out || n < 0) throw Error(SRHIP_ERR_INVALID, "null output");
     const CoptProfile& q = t_copt;
-    const double v[12] = {q.total, q.create, q.set, q.loss, q.grad, q.kernel_ms * 1e-3,
+    const double v[14] = {q.total, q.create, q.set, q.loss, q.grad, q.kernel_ms * 1e-3,
                           (double)q.ncreate, (double)q.nloss, (double)q.ngrad, (double)q.nrebuilt,
-                          q.jit_codegen_ms * 1e-3, q.jit_load_ms * 1e-3};
-    for (int32_t i = 0; i < n && i < 12; ++i) out[i] = v[i];
+                          q.jit_codegen_ms * 1e-3, q.jit_load_ms * 1e-3, q.gather, (double)q.nseg};
+    for (int32_t i = 0; i < n && i < 14; ++i) out[i] = v[i];
     return SRHIP_OK;
   });
 }

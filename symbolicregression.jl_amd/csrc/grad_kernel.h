@@ -1,0 +1,223 @@
+// grad_kernel.h — the constant-gradient kernel (forward mode, fused with the
+// loss) and its launch dispatch, shared by grad_kernels.hip (the variants over
+// shared rows) and grad_seg_f32.hip / grad_seg_f64.hip (per-tree row sets).
+//
+// Same workgroup structure as eval_kernel (row group staged in LDS, waves take
+// work items round-robin); a work item is (tree, tangent group of kGradG
+// constants). GRAD_LOSS returns Σ w·ℓ and Σ w·ℓ'(r)·∂ŷ/∂c_k per constant;
+// GRAD_OUT writes ŷ and ∂ŷ/∂c_k per row.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "grad_interp.h"
+#include "kernels.h"
+
+namespace srhip {
+namespace {
+
+using namespace interp;
+
+// Kernel mode of a GRAD_LOSS launch whose loss is an expression loss (a.loss >=
+// SRHIP_EXPR_LOSS_BEGIN): (ℓ, dℓ/dŷ) per row come from the loss program in dual
+// numbers (grad_interp.h run_loss_dual) in place of elem_loss / elem_dloss, with
+// no implicit weight. Instantiations of their own (full operator set; the weight
+// column is the run-time a.w): the others keep their code.
+constexpr int kGradLossExpr = 2;
+
+// XG: the wide variant (eval_kernel.h): y and w staged in LDS only, the programs'
+// feature operands read from a.X in global memory.
+//
+// SEG: per-tree row sets (srhip_eval_loss_grad_rowsets; GRAD_LOSS and kGradLossExpr
+// only). The launch has one work item per workgroup of one wave (a.tpb = 1, a.ntg =
+// a.nitems, slot g is item g), and the workgroup stages its tree's own segment: rows
+// [a.seg·t + row0, …) of the gathered X / y / w. a.ntiles and a.nrg are those of a
+// dataset of a.n rows, so an item's tiles, lane sums, shuffle tree and row-group
+// partials are the ones it has in a launch over such a dataset. A template
+// parameter: the instantiations without it keep their code.
+template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = false, bool SEG = false>
+__global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
+  constexpr int S = 2 + G;
+  constexpr int TILE = 64 * R;
+  using V = typename V16<T>::type;
+  constexpr int N = V16<T>::N;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int rows = a.ntiles * TILE;
+  const int nx = XG ? 0 : a.nfeat;  // feature arrays staged in LDS
+  const int narr = nx + (MODE == GRAD_LOSS ? (W ? 2 : 1) : MODE == kGradLossExpr ? (a.w ? 2 : 1) : 0);
+  T* sX = reinterpret_cast<T*>(smem);
+  T* sY = sX + (size_t)nx * rows;
+  T* sW = sY + rows;
+  T* sPart = sX + (size_t)narr * rows;
+
+  const int rg = blockIdx.x / a.ntg;
+  const int g = blockIdx.x - rg * a.ntg;
+  const int64_t row0 = (int64_t)rg * rows;
+  int64_t seg0 = 0;  // slot g's tree reads its own segment of X / y / w
+  if constexpr (SEG) seg0 = a.seg * (int64_t)(a.items[g] & 0xffffff);
+  {
+    const int vper = rows / N;
+    const int total = narr * vper;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+      const int arr = idx / vper;
+      const int v = idx - arr * vper;
+      const T* src = arr < nx ? a.X + (size_t)arr * a.n_pad : (arr == nx ? a.y : a.w);
+      reinterpret_cast<V*>(sX + (size_t)arr * rows)[v] = reinterpret_cast<const V*>(src + seg0 + row0)[v];
+    }
+    for (int i = threadIdx.x; i < a.tpb * S; i += blockDim.x) sPart[i] = T(0);
+    if (threadIdx.x == 0) *reinterpret_cast<uint32_t*>(sPart + a.tpb * S) = 0u;  // item counter (a.dyn)
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int64_t rem = a.n - row0;
+  const int nt_valid = (int)min((int64_t)a.ntiles, (rem + TILE - 1) / TILE);
+  const int last_valid = (int)(rem - (int64_t)(nt_valid - 1) * TILE);
+  const double lp = a.lparam;
+
+  // Waves take the group's (cost-sorted) items round-robin, or (a.dyn, the
+  // default) from an LDS counter, so a wave that drew cheap items takes more.
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nwaves = (int)(blockDim.x >> 6);
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(sPart + a.tpb * S);
+  auto claim = [&]() {
+    uint32_t v = 0;
+    if (lane == 0) v = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_amdgcn_readfirstlane((int)v);
+  };
+  for (int i = a.dyn ? claim() : wave; i < a.tpb; i = a.dyn ? claim() : i + nwaves) {
+    const int s = i * a.ntg + ((i & 1) ? (a.ntg - 1 - g) : g);
+    if (s >= a.nitems) continue;
+    const int item = __builtin_amdgcn_readfirstlane(a.items[s]);
+    const int t = item & 0xffffff;
+    const int g0 = (item >> 24) * kGradG;  // groups are kGradG constants; G of them carried
+    CIns<T>* p = const_prog(a.prog + __builtin_amdgcn_readfirstlane(a.tree_off[t]));
+    const int cbase = __builtin_amdgcn_readfirstlane(a.const_off[t]);
+    const int nc = __builtin_amdgcn_readfirstlane(a.const_off[t + 1]) - cbase;
+    T acc[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) acc[k] = T(0);  // [0] Σ w·ℓ, [1] marker, [2+j] Σ w·ℓ'·∂ŷ/∂c
+    for (int tl = 0; tl < nt_valid; ++tl) {
+      Dual<T, R, G> d;
+      if constexpr (XG) {
+        run_program_grad<T, R, D, G, SET>(p, a.X + seg0 + row0 + tl * TILE, a.n_pad, lane, g0, d, acc[1]);
+      } else {
+        const T* sXt = sX + tl * TILE;
+        run_program_grad<T, R, D, G, SET>(p, sXt, rows, lane, g0, d, acc[1]);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[1] = mark(d.v[r], acc[1]);
+      if constexpr (MODE == GRAD_OUT) {
+        const int64_t off = row0 + tl * TILE;
+        if (g0 == 0) store_rows<T, R>(a.out_value + (size_t)t * a.out_stride + off, lane, d.v);
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+          if (g0 + j < nc)
+            store_rows<T, R>(a.out_grad + (size_t)(cbase + g0 + j) * a.out_stride + off, lane, d.d[j]);
+      } else {
+        T yv[R], wv[R];
+        lds_rows<T, R>(sY + tl * TILE, lane, yv);
+        if constexpr (W) lds_rows<T, R>(sW + tl * TILE, lane, wv);
+        const int valid = (tl < nt_valid - 1) ? TILE : last_valid;
+        if constexpr (MODE == kGradLossExpr) {
+          if (a.w) lds_rows<T, R>(sW + tl * TILE, lane, wv);
+          else SR_UNROLL for (int e = 0; e < R; ++e) wv[e] = T(0);  // (a loss reading w is refused without weights)
+          Dual<T, R, 1> ld;
+          run_loss_dual<T, R>(const_prog(a.lprog), d.v, yv, wv, ld);
+#pragma unroll
+          for (int e = 0; e < R; ++e) {
+            const bool in = row_of<T, R>(e, lane) < valid;
+            acc[0] += in ? ld.v[e] : T(0);
+#pragma unroll
+            for (int j = 0; j < G; ++j) acc[2 + j] += in ? ld.d[0][e] * d.d[j][e] : T(0);
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < R; ++e) {
+            T l = dev::elem_loss<T>(a.loss, lp, d.v[e], yv[e]);
+            T dl = dev::elem_dloss<T>(a.loss, lp, d.v[e], yv[e]);
+            if constexpr (W) { l = wv[e] * l; dl = wv[e] * dl; }
+            const bool in = row_of<T, R>(e, lane) < valid;
+            acc[0] += in ? l : T(0);
+#pragma unroll
+            for (int j = 0; j < G; ++j) acc[2 + j] += in ? dl * d.d[j][e] : T(0);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+      for (int k = 0; k < S; ++k) acc[k] += __shfl_xor(acc[k], off);
+    if (lane == 0)
+#pragma unroll
+      for (int k = 0; k < S; ++k) sPart[i * S + k] = acc[k];
+  }
+  __syncthreads();
+  T* dst = a.partial + ((size_t)rg * ((size_t)a.ntg * a.tpb) + (size_t)g * a.tpb) * S;
+  for (int i = threadIdx.x; i < a.tpb * S; i += blockDim.x) dst[i] = sPart[i];
+}
+
+template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = false, bool SEG = false>
+hipError_t launch_grad_one(const EvalPlan& plan, const GradArgs<T>& a, hipStream_t stream) {
+  // raise the dynamic-LDS ceiling once per kernel instantiation: a function-
+  // local static is initialised exactly once even with concurrent callers
+  static const hipError_t attr_err = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&grad_kernel<T, R, D, MODE, W, G, SET, XG, SEG>), hipFuncAttributeMaxDynamicSharedMemorySize,
+      160 * 1024);
+  if (attr_err != hipSuccess) return attr_err;
+  const unsigned grid = (unsigned)a.nrg * (unsigned)a.ntg;
+  hipLaunchKernelGGL((grad_kernel<T, R, D, MODE, W, G, SET, XG, SEG>), dim3(grid), dim3(plan.threads), plan.lds_bytes,
+                     stream, a);
+  return hipGetLastError();
+}
+
+template <typename T, int R, int D, int G, int SET, bool XG = false, bool SEG = false>
+hipError_t launch_grad_rd(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
+  if constexpr (SEG) {
+    if (mode == GRAD_OUT) return hipErrorInvalidValue;  // row sets: losses only
+  } else {
+    if (mode == GRAD_OUT) return launch_grad_one<T, R, D, GRAD_OUT, false, G, SET, XG>(plan, a, stream);
+  }
+  constexpr int LSET = SET == OPSET_EXPR ? OPSET_EXPR : OPSET_FULL;  // (expression losses: no basic-set variant)
+  if (a.loss >= SRHIP_EXPR_LOSS_BEGIN) return launch_grad_one<T, R, D, kGradLossExpr, false, G, LSET, XG, SEG>(plan, a, stream);
+  if (a.w) return launch_grad_one<T, R, D, GRAD_LOSS, true, G, SET, XG, SEG>(plan, a, stream);
+  return launch_grad_one<T, R, D, GRAD_LOSS, false, G, SET, XG, SEG>(plan, a, stream);
+}
+
+// gradient variants: rows per lane R (fewer tangents leave room for more
+// rows) and stack slots D
+inline int grad_R(int dtype, bool deep, int G) {
+  if (dtype != SRHIP_F32 || deep) return 1;
+  return G <= 2 ? 4 : 2;
+}
+
+template <typename T, int G, bool SEG = false>
+hipError_t launch_grad_g(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
+  constexpr int RS = sizeof(T) == 4 ? (G <= 2 ? 4 : 2) : 1;  // grad_R, shallow
+  if (plan.D == 4) {
+    if (a.opset == OPSET_BASIC) return launch_grad_rd<T, RS, 4, G, OPSET_BASIC, false, SEG>(plan, a, mode, stream);
+    return launch_grad_rd<T, RS, 4, G, OPSET_FULL, false, SEG>(plan, a, mode, stream);
+  }
+  // deep programs; with expression operators among them, the variant that
+  // dispatches their micro-instructions
+  if (a.opset == OPSET_EXPR) return launch_grad_rd<T, 1, kMaxSlots, G, OPSET_EXPR, false, SEG>(plan, a, mode, stream);
+  return launch_grad_rd<T, 1, kMaxSlots, G, OPSET_FULL, false, SEG>(plan, a, mode, stream);
+}
+
+// every variant of one element type; SEG: the per-tree row-set instantiations
+template <typename T, bool SEG>
+hipError_t launch_grad_all(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
+  if (plan.wide) {
+    // the wide variants: the deep configuration, a.G = kGradG. Both operator sets: a gradient
+    // program's feature index has 16 bits without expression operators, 15 with them
+    if (a.opset == OPSET_EXPR) return launch_grad_rd<T, 1, kMaxSlots, kGradG, OPSET_EXPR, true, SEG>(plan, a, mode, stream);
+    return launch_grad_rd<T, 1, kMaxSlots, kGradG, OPSET_FULL, true, SEG>(plan, a, mode, stream);
+  }
+  if (plan.D != 4) return launch_grad_g<T, kGradG, SEG>(plan, a, mode, stream);  // deep programs: one variant
+  if (a.G == 1) return launch_grad_g<T, 1, SEG>(plan, a, mode, stream);
+  if (a.G == 2) return launch_grad_g<T, 2, SEG>(plan, a, mode, stream);
+  return launch_grad_g<T, kGradG, SEG>(plan, a, mode, stream);
+}
+
+}  // namespace
+}  // namespace srhip

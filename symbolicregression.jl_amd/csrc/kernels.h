@@ -128,6 +128,9 @@ struct GradArgs {
   int64_t out_stride;
   int dyn = 0;              // waves take their items from an LDS counter (SRHIP_INTERP_DYN)
   const Ins<T>* lprog = nullptr;  // the loss program of an expression loss (loss >= SRHIP_EXPR_LOSS_BEGIN)
+  // per-tree row sets (srhip_eval_loss_grad_rowsets; GRAD_LOSS, one item per workgroup: tpb = 1,
+  // ntg = nitems): tree t reads rows [t·seg, t·seg + n) of X / y / w; 0 = shared rows
+  int64_t seg = 0;
 };
 
 bool plan_grad(int dtype, bool deep, int G, int mode, bool weighted, int nfeat, int64_t n,
@@ -136,6 +139,9 @@ bool plan_grad(int dtype, bool deep, int G, int mode, bool weighted, int nfeat, 
 bool plan_grad_wide(int dtype, int mode, bool weighted, int64_t n, int nitems, EvalPlan* plan);
 template <typename T>
 hipError_t launch_grad(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream);
+// the per-tree row-set variants (a.seg > 0, GRAD_LOSS; launch_grad forwards to them)
+template <typename T>
+hipError_t launch_grad_seg(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream);
 template <typename T>
 hipError_t launch_grad_finalize(const GradArgs<T>& a, double* out_sum, uint8_t* out_ok,
                                 double* out_dloss, hipStream_t stream);

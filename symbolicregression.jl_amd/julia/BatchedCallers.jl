@@ -187,14 +187,28 @@ updated in place: a converged member gets the optimised constants, its
 score_func re-score (:58) and a new birth (:60); the others keep x0 (:62).
 One SRHip call when the engine covers the options, else the reference member
 by member.
+
+`minibatch` (default false: the reference's v0.15.0 behaviour, which optimises on
+the full dataset even with options.batching, src/ConstantOptimization.jl:16): with
+`minibatch && options.batching` every member is optimised on its own sample of
+options.batch_size rows drawn with replacement, where and how score_func_batch
+draws them (src/LossFunctions.jl:98), the same rows for all of its starts and
+iterations; a converged member's loss is the one on its sample, and num_evals is
+scaled by batch_size / dataset.n (src/Mutate.jl:43). The CPU fall-back is the
+reference's full-data optimiser either way.
 """
 function optimize_constants_batched(dataset::Dataset{T}, members::AbstractVector{<:PopMember{T}},
-                                    options::Options; device::Int=0) where {T}
+                                    options::Options; device::Int=0, minibatch::Bool=false) where {T}
     isempty(members) && return Float64[]
     if SRHip.enabled(options)
         try
             trees = Node{T}[m.tree for m in members]
-            losses, converged, num_evals = SRHip.optimize_constants_batch!(trees, dataset, options; device=device)
+            sampled = minibatch && options.batching
+            # column t: member t's sample
+            row_idx = sampled ? rand(1:(dataset.n), options.batch_size, length(trees)) : nothing
+            losses, converged, num_evals = SRHip.optimize_constants_batch!(trees, dataset, options; device=device,
+                                                                           row_idx=row_idx)
+            sampled && (num_evals = num_evals .* (options.batch_size / dataset.n))
             for (m, l, c) in zip(members, losses, converged)
                 c || continue
                 m.score = loss_to_score(l, dataset.baseline_loss, m.tree, options)
@@ -222,14 +236,16 @@ optimised in one batched call and finalize_scores as one launch; the
 simplification, the new references and the record are the reference's.
 """
 function optimize_and_simplify_population_batched(dataset::Dataset{T}, pop::Population, options::Options,
-                                                  curmaxsize::Int, record::RecordType; device::Int=0) where {T}
+                                                  curmaxsize::Int, record::RecordType; device::Int=0,
+                                                  minibatch::Bool=false) where {T}
     do_optimization = rand(pop.n) .< options.optimizer_probability
     for j in 1:(pop.n)
         pop.members[j].tree = simplify_tree(pop.members[j].tree, options.operators)
         pop.members[j].tree = combine_operators(pop.members[j].tree, options.operators)
     end
     chosen = options.should_optimize_constants ? findall(do_optimization) : Int[]
-    num_evals = sum(optimize_constants_batched(dataset, pop.members[chosen], options; device=device); init=0.0)
+    num_evals = sum(optimize_constants_batched(dataset, pop.members[chosen], options; device=device,
+                                               minibatch=minibatch); init=0.0)
     pop, tmp_num_evals = finalize_scores_batched(dataset, pop, options; device=device)
     num_evals += tmp_num_evals
     for j in 1:(pop.n)
@@ -355,11 +371,13 @@ per island, in the reference's order.
 """
 function reg_evol_cycle_batched(dataset::Dataset{T}, pops::AbstractVector{<:Population}, temperature,
                                 curmaxsize::Int, stats::AbstractVector{RunningSearchStatistics},
-                                options::Options; device::Int=0) where {T}
-    # this cycle's scoring and optimiser calls, on its device
+                                options::Options; device::Int=0, minibatch::Bool=false) where {T}
+    # this cycle's scoring and optimiser calls, on its device (minibatch: the :optimize mutations
+    # optimise on per-member row samples, optimize_constants_batched)
     score_batch(ds, ts, o) = BatchedCallers.score_batch(ds, ts, o; device=device)
     score_batch_minibatch(ds, ts, o) = BatchedCallers.score_batch_minibatch(ds, ts, o; device=device)
     optimize_constants_batched(ds, ms, o) = BatchedCallers.optimize_constants_batched(ds, ms, o; device=device)
+    optimize_sampled(ds, ms, o) = BatchedCallers.optimize_constants_batched(ds, ms, o; device=device, minibatch=true)
     proposals = Vector{Vector{Proposal{T}}}(undef, length(pops))
     allstars = Vector{Vector{PopMember{T}}}(undef, length(pops))
     for (k, pop) in enumerate(pops)
@@ -393,7 +411,9 @@ function reg_evol_cycle_batched(dataset::Dataset{T}, pops::AbstractVector{<:Popu
     end
     # every :optimize mutation of every island in one batched optimiser call
     to_opt = PopMember{T}[p.member for props in proposals for p in props if p.optimize]
-    num_evals += sum(optimize_constants_batched(dataset, to_opt, options); init=0.0)
+    opt_evals = minibatch ? optimize_sampled(dataset, to_opt, options) :
+                optimize_constants_batched(dataset, to_opt, options)
+    num_evals += sum(opt_evals; init=0.0)
     # one launch for every island's babies
     trees = Node{T}[p.tree for props in proposals for p in props if p.member === nothing]
     scores, losses = options.batching ? score_batch_minibatch(dataset, trees, options) :
@@ -465,11 +485,13 @@ exactly the serial per-island result.
 """
 function reg_evol_cycle_lockstep(dataset::Dataset{T}, pops::AbstractVector{<:Population}, temperature,
                                  curmaxsize::Int, stats::AbstractVector{RunningSearchStatistics},
-                                 options::Options; device::Int=0) where {T}
-    # this cycle's scoring and optimiser calls, on its device
+                                 options::Options; device::Int=0, minibatch::Bool=false) where {T}
+    # this cycle's scoring and optimiser calls, on its device (minibatch: the :optimize mutations
+    # optimise on per-member row samples, optimize_constants_batched)
     score_batch(ds, ts, o) = BatchedCallers.score_batch(ds, ts, o; device=device)
     score_batch_minibatch(ds, ts, o) = BatchedCallers.score_batch_minibatch(ds, ts, o; device=device)
     optimize_constants_batched(ds, ms, o) = BatchedCallers.optimize_constants_batched(ds, ms, o; device=device)
+    optimize_sampled(ds, ms, o) = BatchedCallers.optimize_constants_batched(ds, ms, o; device=device, minibatch=true)
     num_evals = 0.0
     nsteps = round(Int, pops[1].n / options.tournament_selection_n)
     for _ in 1:nsteps
@@ -503,7 +525,9 @@ function reg_evol_cycle_lockstep(dataset::Dataset{T}, pops::AbstractVector{<:Pop
         end
         # every :optimize proposal of this step, all islands, in one optimiser call
         to_opt = PopMember{T}[s.prop.member for s in steps if !s.crossover && s.prop.optimize]
-        num_evals += sum(optimize_constants_batched(dataset, to_opt, options); init=0.0)
+        opt_evals = minibatch ? optimize_sampled(dataset, to_opt, options) :
+                    optimize_constants_batched(dataset, to_opt, options)
+        num_evals += sum(opt_evals; init=0.0)
         # ONE launch: mutated trees and both crossover children of every island
         trees = Node{T}[]
         for s in steps
@@ -568,7 +592,8 @@ island runs the reference's own s_r_cycle instead, recording into records[k].
 """
 function s_r_cycle_lockstep(dataset::Dataset{T}, pops::AbstractVector{<:Population}, ncycles::Int,
                             curmaxsize::Int, stats::AbstractVector{RunningSearchStatistics},
-                            options::Options; records=nothing, device::Int=0) where {T}
+                            options::Options; records=nothing, device::Int=0,
+                            minibatch::Bool=false) where {T}
     if options.recorder
         best_seen = Vector{HallOfFame{T}}(undef, length(pops))
         num_evals = 0.0
@@ -586,8 +611,10 @@ function s_r_cycle_lockstep(dataset::Dataset{T}, pops::AbstractVector{<:Populati
     num_evals = 0.0
     for temperature in LinRange(max_temp, min_temp, ncycles)
         _, ev = options.fast_cycle ?
-                reg_evol_cycle_batched(dataset, pops, temperature, curmaxsize, stats, options; device=device) :
-                reg_evol_cycle_lockstep(dataset, pops, temperature, curmaxsize, stats, options; device=device)
+                reg_evol_cycle_batched(dataset, pops, temperature, curmaxsize, stats, options; device=device,
+                                       minibatch=minibatch) :
+                reg_evol_cycle_lockstep(dataset, pops, temperature, curmaxsize, stats, options; device=device,
+                                        minibatch=minibatch)
         num_evals += ev
         for (k, pop) in enumerate(pops), member in pop.members
             size = compute_complexity(member.tree, options)

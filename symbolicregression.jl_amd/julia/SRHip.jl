@@ -638,6 +638,35 @@ function eval_loss_grad_batch(p::Program, dataset::Dataset{T}, options::Options)
     return losses, grads, ok .== 1
 end
 
+"""
+    eval_loss_grad_rowsets(p::Program, dataset, options, idx::Matrix{Int}) -> (losses, grads, ok)
+
+eval_loss_grad_batch with every tree on its OWN row sample (`srhip_eval_loss_grad_rowsets`): idx is
+(batch_size, ntrees), column t the 1-based rows (with repetition) of tree t, as
+eval_loss_batch_rowsets takes them. Loss and gradient are divided by the sample's Σw.
+"""
+function eval_loss_grad_rowsets(p::Program, dataset::Dataset{T}, options::Options,
+                                idx::AbstractMatrix{<:Integer}) where {T}
+    nt = p.ntrees
+    size(idx, 2) == nt || throw(ArgumentError("one row sample (column of idx) per tree"))
+    ncon = Int(p.const_off[end])
+    sums = Vector{Float64}(undef, nt); ok = Vector{UInt8}(undef, nt); wsum = Vector{Float64}(undef, nt)
+    dloss = Vector{Float64}(undef, ncon)
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    rows = Matrix{Int64}(idx .- 1)  # column-major: tree t's sample is contiguous ([ntrees][bs] in C)
+    GC.@preserve sums ok dloss wsum params rows begin
+        check(ccall((:srhip_eval_loss_grad_rowsets, libsrhip), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{UInt8}),
+                    device_dataset(dataset, p.device), p.h, kindcode, params, rows, size(rows, 1), sums, dloss,
+                    wsum, ok))
+    end
+    losses = [ok[i] == 1 ? T(sums[i] / wsum[i]) : T(Inf) for i in 1:nt]
+    grads = [dloss[(p.const_off[i] + 1):p.const_off[i + 1]] ./ wsum[i] for i in 1:nt]
+    return losses, grads, ok .== 1
+end
+
 # ---- batched constant optimisation (src/ConstantOptimization.jl:22-65) ----------------
 struct ConstOptOptions         # include/srhip.h: srhip_constopt_options
     algorithm::Int32
@@ -661,9 +690,15 @@ converged get the best start's constants (set_constants); the others keep
 x0 (:56-63). losses[i] is the loss of trees[i] at its final constants;
 num_evals[i] counts its loss evaluations (+1 for the re-score of a converged
 member, :58-59).
+
+`row_idx` (batch_size, ntrees), column t the 1-based rows (with repetition) of trees[t]: every tree
+is optimised on its own sample (srhip_optimize_constants_rowsets), the same rows for all of its
+starts, iterations and the final evaluation; losses are then those on the samples, and num_evals
+still counts evaluations (the caller scales by batch_size / n, src/Mutate.jl:43).
 """
 function optimize_constants_batch!(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, options::Options;
-                                   device::Int=0) where {T}
+                                   device::Int=0,
+                                   row_idx::Union{Nothing,AbstractMatrix{<:Integer}}=nothing) where {T}
     algo = options.optimizer_algorithm == "BFGS" ? OPT_BFGS :
            options.optimizer_algorithm == "NelderMead" ? OPT_NELDERMEAD :
            error("Optimization function not implemented.")
@@ -682,15 +717,28 @@ function optimize_constants_batch!(trees::AbstractVector{Node{T}}, dataset::Data
     params = Float64[param]
     out_c = similar(consts); out_l = Vector{Float64}(undef, nt)
     out_k = Vector{UInt8}(undef, nt); out_n = Vector{Float64}(undef, nt)
-    GC.@preserve node_off kind arg const_off consts noise params out_c out_l out_k out_n begin
+    if row_idx !== nothing
+        size(row_idx, 2) == nt || throw(ArgumentError("one row sample (column of row_idx) per tree"))
+    end
+    # column-major: tree t's sample is contiguous ([ntrees][bs] in C), 0-based
+    rows = row_idx === nothing ? Matrix{Int64}(undef, 0, 0) : Matrix{Int64}(row_idx .- 1)
+    GC.@preserve node_off kind arg const_off consts noise params out_c out_l out_k out_n rows begin
         tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
                             Ptr{Cvoid}(pointer(consts))))
         opts = Ref(ConstOptOptions(algo, Int32(options.optimizer_options.iterations), Int32(nr), kindcode,
                                    pointer(params), pointer(noise), UInt64(0)))
-        check(ccall((:srhip_optimize_constants_batch, libsrhip), Int32,
-                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Ref{ConstOptOptions}, Ptr{Cvoid}, Ptr{Float64},
-                     Ptr{UInt8}, Ptr{Float64}),
-                    context(device), device_dataset(dataset, device), tr, opts, out_c, out_l, out_k, out_n))
+        if row_idx === nothing
+            check(ccall((:srhip_optimize_constants_batch, libsrhip), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Ref{ConstOptOptions}, Ptr{Cvoid}, Ptr{Float64},
+                         Ptr{UInt8}, Ptr{Float64}),
+                        context(device), device_dataset(dataset, device), tr, opts, out_c, out_l, out_k, out_n))
+        else
+            check(ccall((:srhip_optimize_constants_rowsets, libsrhip), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Ref{ConstOptOptions}, Ptr{Int64}, Int64, Ptr{Cvoid},
+                         Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}),
+                        context(device), device_dataset(dataset, device), tr, opts, rows, size(rows, 1), out_c,
+                        out_l, out_k, out_n))
+        end
     end
     converged = out_k .== 1
     for i in 1:nt

@@ -27,6 +27,7 @@ checker.
 from __future__ import annotations
 
 import ctypes as C
+import inspect
 from dataclasses import dataclass
 from typing import Callable, Optional, Sequence
 
@@ -81,12 +82,26 @@ def start_noise(flat, nrestarts: int, rng: np.random.Generator) -> np.ndarray:
 def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: Options,
                              rng: Optional[np.random.Generator] = None, device: Optional[int] = None,
                              evaluator_factory: Optional[Callable] = None,
-                             noise: Optional[np.ndarray] = None) -> ConstOptResult:
+                             noise: Optional[np.ndarray] = None,
+                             row_idx: Optional[np.ndarray] = None) -> ConstOptResult:
     """`optimize_constants` for many trees at once. Trees are updated in place
     (constants of the best start when it converged, else left at x0).
     `noise` (default: drawn from `rng`) is the standard normal draws of the
     perturbed starts in start_noise's order, for callers that draw them
-    where the reference does (srhip.evolution: from each island's stream)."""
+    where the reference does (srhip.evolution: from each island's stream).
+    `row_idx`, an (ntrees, batch_size) integer array: tree t is optimised on its
+    own row sample row_idx[t], the same rows for all of its starts, iterations
+    and the final evaluation (srhip_optimize_constants_rowsets; the losses are
+    those on the samples, num_evals counts evaluations as without it). Not on a
+    GroupDataset. With `evaluator_factory` the evaluator owns the rows: a factory
+    whose signature accepts `members=` is given the input tree index of each
+    candidate and picks their samples itself."""
+    if row_idx is not None:
+        from .interface import _check_row_sets
+
+        if isinstance(dataset, GroupDataset):
+            raise ValueError("row_idx is not supported on a GroupDataset")
+        row_idx = _check_row_sets(row_idx, len(trees))
     algorithm = getattr(options, "optimizer_algorithm", "BFGS")
     if algorithm not in ALGORITHMS:
         raise ValueError("Optimization function not implemented.")  # :39-41
@@ -115,6 +130,10 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
     if evaluator_factory is None and isinstance(dataset, GroupDataset):
         # the rows sharded over a device group (srhip_group_optimize_constants)
         check(lib().srhip_group_optimize_constants(dataset.handle, C.byref(tr), C.byref(opts), *ptrs))
+    elif evaluator_factory is None and row_idx is not None:
+        dev = dataset.device(device)
+        check(lib().srhip_optimize_constants_rowsets(dev.ctx.handle, dev.handle, C.byref(tr), C.byref(opts),
+                                                     row_idx.ctypes.data_as(C.c_void_p), row_idx.shape[1], *ptrs))
     elif evaluator_factory is None:
         dev = dataset.device(device)
         check(lib().srhip_optimize_constants_batch(dev.ctx.handle, dev.handle, C.byref(tr), C.byref(opts), *ptrs))
@@ -139,6 +158,12 @@ class _Callback:
 
     def __init__(self, trees, factory):
         self.trees, self.factory = trees, factory
+        # a factory that accepts members= is told the input tree of each candidate
+        try:
+            params = inspect.signature(factory).parameters.values()
+            self.pass_members = any(p.name == "members" or p.kind is p.VAR_KEYWORD for p in params)
+        except (TypeError, ValueError):
+            self.pass_members = False
         self.cache = {}
         self.error = None
         self.fn = CONSTOPT_EVAL_FN(self._eval)
@@ -149,7 +174,8 @@ class _Callback:
             key = members.tobytes()
             ev = self.cache.get(key)
             if ev is None:
-                ev = self.factory([self.trees[int(i)].copy() for i in members])
+                cands = [self.trees[int(i)].copy() for i in members]
+                ev = self.factory(cands, members=members.copy()) if self.pass_members else self.factory(cands)
                 self.cache[key] = ev
             nconst = sum(len(_consts_of(self.trees[int(i)])) for i in members)
             x = np.ctypeslib.as_array(consts, shape=(nconst,)).copy() if nconst else np.zeros(0)
@@ -176,11 +202,12 @@ def _consts_of(tree: Node):
 def last_profile() -> dict:
     """Where the last optimize_constants_batch call of this thread spent its
     time (srhip_constopt_profile): seconds and call counts."""
-    out = (C.c_double * 12)()
-    check(lib().srhip_constopt_profile(out, 12))
+    out = (C.c_double * 14)()
+    check(lib().srhip_constopt_profile(out, 14))
     keys = ("total_s", "create_s", "set_constants_s", "loss_s", "grad_s", "kernel_s", "n_create", "n_loss", "n_grad",
-            "n_rebuilt", "jit_codegen_s", "jit_load_s")
+            "n_rebuilt", "jit_codegen_s", "jit_load_s", "gather_s", "n_segment_evals")
     d = dict(zip(keys, (float(v) for v in out)))
-    d["host_s"] = d["total_s"] - d["create_s"] - d["set_constants_s"] - d["loss_s"] - d["grad_s"]
+    d["host_s"] = (d["total_s"] - d["create_s"] - d["set_constants_s"] - d["loss_s"] - d["grad_s"]
+                   - d["gather_s"])
     return d
 

@@ -166,12 +166,29 @@ def eval_grad_tree_array(tree: TreeOrTrees, X: np.ndarray, options: Options, var
 
 
 def eval_loss_grad_batch(trees: Sequence[Node], dataset: Dataset, options: Options,
-                         device: Optional[int] = None):
+                         device: Optional[int] = None, row_idx: Optional[np.ndarray] = None):
     """Batched loss + constant gradients for ConstantOptimization
     (src/ConstantOptimization.jl:12-65): per tree (loss in T, ∂loss/∂c as a
     float64 vector in get_constants order, did_succeed). A GroupDataset runs
-    over its device group (`device` is then unused)."""
+    over its device group (`device` is then unused). row_idx, an
+    (ntrees, batch_size) integer array: tree t on its own row sample row_idx[t]
+    (srhip_eval_loss_grad_rowsets), loss and gradient divided by that sample's
+    Σw; not on a GroupDataset."""
     loss = options.elementwise_loss
+    if row_idx is not None:
+        if isinstance(dataset, GroupDataset):
+            raise ValueError("row_idx is not supported on a GroupDataset")
+        R = _check_row_sets(row_idx, len(trees))
+        dev = dataset.device(device)
+        T = dataset.T
+        prog = Program(dev.ctx, flatten(trees, options, dtype=T), T, interpreted=True)
+        sums, grads, wsums, ok = prog.eval_loss_grad_rowsets(dev, loss.kind, R, loss.params)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            losses = (sums / wsums).astype(T)
+            co = prog.flat.const_off
+            g = [grads[co[t]:co[t + 1]] / wsums[t] for t in range(len(trees))]
+        losses[~ok] = T(np.inf)
+        return losses, g, ok
     if isinstance(dataset, GroupDataset):
         prog = dataset.group.program(flatten(trees, options, dtype=dataset.T), dataset.T)
         sums, grads, wsum, ok = prog.eval_loss_grad(dataset, loss.kind, loss.params)
@@ -187,6 +204,16 @@ def eval_loss_grad_batch(trees: Sequence[Node], dataset: Dataset, options: Optio
     co = prog.flat.const_off
     g = [grads[co[t]:co[t + 1]] / wsum for t in range(len(trees))]
     return losses, g, ok
+
+
+def _check_row_sets(row_idx, ntrees: int) -> np.ndarray:
+    """An (ntrees, batch_size) integer array of row samples, one per tree."""
+    R = np.asarray(row_idx)
+    if R.ndim != 2 or R.shape[0] != ntrees:
+        raise ValueError(f"row_idx must be (ntrees, batch_size) = ({ntrees}, batch_size), not {R.shape}")
+    if R.size and not np.issubdtype(R.dtype, np.integer):
+        raise ValueError("row_idx must hold integers")
+    return np.ascontiguousarray(R, dtype=np.int64)
 
 
 # ---- losses -------------------------------------------------------------------------
