@@ -111,6 +111,26 @@ int64_t pad_rows(int64_t rows) { return ((std::max<int64_t>(rows, 1) + kRowPad -
 
 size_t dtype_size(int dtype) { return dtype == SRHIP_F32 ? 4 : 8; }
 
+// Environment knobs: 0 or 1 as the value starts, else -1 (unset, anything else);
+// on unless 0; on only if 1; an integer with a default. When a knob is read
+// (once, per build, per call or launch) is decided where it is used.
+int env_01(const char* name) {
+  const char* e = std::getenv(name);
+  return (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : -1;
+}
+bool env_on(const char* name) { return env_01(name) != 0; }
+bool env_is1(const char* name) { return env_01(name) == 1; }
+int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : dflt;
+}
+
+// f(T()) with T the element type of dtype (checked by the caller): float or double
+template <typename F>
+auto by_dtype(int dtype, F&& f) -> decltype(f(float())) {
+  return dtype == SRHIP_F32 ? f(float()) : f(double());
+}
+
 // Persistent host-copy workers of one context (copy_rows_to_host): created
 // at the first large per-row output, joined when the context closes. A job is
 // one function run by every worker with its index; the caller keeps issuing
@@ -384,6 +404,29 @@ struct srhip_program {
 
 namespace {
 
+// The scope of a call on a context: its mutex held, its device current.
+struct CallScope {
+  std::lock_guard<std::mutex> lk;
+  CallScope(srhip_ctx* c, const char* what) : lk(c->mu) {
+    const hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) throw Error(SRHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+  }
+};
+// (a failing hipSetDevice is reported with the caller's expression, as HIP_CHECK words it)
+#define CALL_SCOPE(ctx) CallScope scope((ctx), "hipSetDevice(" #ctx "->device)")
+
+// the program's own trees as the tree compilers take them, with the given constants
+srhip_trees trees_of(const srhip_program* p, const void* consts) {
+  srhip_trees tr;
+  tr.ntrees = p->ntrees;
+  tr.node_off = p->node_off.data();
+  tr.kind = p->kind.data();
+  tr.arg = p->arg.data();
+  tr.const_off = p->const_off.data();
+  tr.consts = consts;
+  return tr;
+}
+
 // ---- expression losses (srhip.h "expression losses") ----------------------------
 // A registered loss tree: its postfix stream (the host statement of the
 // semantics, srhip_loss_expr_eval) and its loss program for both element types
@@ -615,6 +658,14 @@ void timing_finish(srhip_ctx* c) {
     c->cnt_pending = false;
   }
 }
+// the timing and counters of a call that returned before its results were read
+// (srhip_eval_loss_packed): wait for it, under the context's lock, and read them
+void flush_pending(srhip_ctx* c) {
+  if (!c->timing_pending && !c->cnt_pending) return;
+  CALL_SCOPE(c);
+  HIP_CHECK(hipStreamSynchronize(c->stream));
+  timing_finish(c);
+}
 
 void free_grad_device(srhip_program* p) {
   for (void* q : {p->d_gcode, (void*)p->d_gtree_off, (void*)p->d_gitems, (void*)p->d_const_off,
@@ -645,19 +696,14 @@ void free_grad_device(srhip_program* p) {
 // costs about a millisecond).
 bool gjit_wanted(int ntrees) {
   if (!jit::available() || ntrees == 0) return false;
-  const char* e = std::getenv("SRHIP_GJIT");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  return ntrees >= 256;
+  const int k = env_01("SRHIP_GJIT");
+  return k >= 0 ? k == 1 : ntrees >= 256;
 }
 
 // LDS for the row tiles of a gradient tree-code workgroup (SRHIP_GJIT_LDS, KiB:
 // experiments); more tiles per workgroup amortise each tree's call over more rows
 size_t gjit_tile_budget() {
-  static const size_t b = [] {
-    const char* e = std::getenv("SRHIP_GJIT_LDS");
-    return (size_t)(e ? std::atoi(e) : 52) * 1024;
-  }();
+  static const size_t b = (size_t)env_int("SRHIP_GJIT_LDS", 52) * 1024;
   return b;
 }
 
@@ -737,13 +783,7 @@ bool patch_image(srhip_program* p, std::vector<unsigned char>& code, const std::
   Ins<T>* ins = reinterpret_cast<Ins<T>*>(code.data());
   const T* c = reinterpret_cast<const T*>(p->consts.data());
   const int32_t* co = p->const_off.data();
-  srhip_trees tr;  // the program's own trees with the new constants (eval_fold)
-  tr.ntrees = nt;
-  tr.node_off = p->node_off.data();
-  tr.kind = p->kind.data();
-  tr.arg = p->arg.data();
-  tr.const_off = co;
-  tr.consts = c;
+  const srhip_trees tr = trees_of(p, c);  // the program's own trees with the new constants (eval_fold)
   std::vector<int32_t> redo;
   const bool keep = p->jit_memc;  // compiled with keep_layout: every tree has its code
   const T* cp = cprev.size() == p->consts.size() ? reinterpret_cast<const T*>(cprev.data()) : nullptr;
@@ -888,14 +928,7 @@ void build_grad_program(srhip_program* p, bool tree_code = true) {
   if (p->grad_built && p->grad_stale) patch_grad_constants<T>(p);
   if (p->grad_built) return;
   p->gjit_skipped = !tree_code && p->gjit_allowed && gjit_wanted(p->ntrees);
-  srhip_trees tr;
-  tr.ntrees = p->ntrees;
-  tr.node_off = p->node_off.data();
-  tr.kind = p->kind.data();
-  tr.arg = p->arg.data();
-  tr.const_off = p->const_off.data();
-  tr.consts = p->consts.data();
-  CompiledBatch<T> cb = compile_batch_par<T>(tr, /*grad=*/true, p->jit_memc);
+  CompiledBatch<T> cb = compile_batch_par<T>(trees_of(p, p->consts.data()), /*grad=*/true, p->jit_memc);
   if (p->ntrees >= (1 << 24)) throw Error(SRHIP_ERR_UNSUPPORTED, "too many trees for gradient work items");
   p->g_static_fail = cb.static_fail;
   p->g_has_expr = std::find(cb.expr.begin(), cb.expr.end(), (uint8_t)1) != cb.expr.end();
@@ -1037,42 +1070,30 @@ void build_grad_program(srhip_program* p, bool tree_code = true) {
 // SRHIP_JIT_FAST=0 keeps the FAST path out.
 bool jit_wanted(int nshallow) {
   if (!jit::available() || nshallow == 0) return false;
-  const char* e = std::getenv("SRHIP_JIT");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  return nshallow >= 256;
+  const int k = env_01("SRHIP_JIT");
+  return k >= 0 ? k == 1 : nshallow >= 256;
 }
 // Tree code: SRHIP_JIT_CONTIG=1 gives tree group g the contiguous slots
 // [g*tpb, (g+1)*tpb) of the cost-sorted list (its code one contiguous range).
 // Measured slower than the snake deal (config #2 3.39 -> 3.63 ms, config #5
 // gradient 49.6 -> 60.9 ms: the expensive trees end up in a few groups;
 // profiles/r02i_evalknobs.txt), so off by default.
-bool jit_contig() {
-  const char* e = std::getenv("SRHIP_JIT_CONTIG");  // read per launch: A/B measurements
-  return e && e[0] == '1';
-}
+bool jit_contig() { return env_is1("SRHIP_JIT_CONTIG"); }  // read per launch: A/B measurements
 
 // Tree code: every tree group of a row group on one XCD, so that the row
 // group's X tile comes from HBM once and from that XCD's L2 for the other tree
 // groups (config #2: 110 -> 32 MB fetched per launch, 3.006 -> 2.982 ms);
 // SRHIP_RG_XCD=0: blocks in launch order
-bool rg_xcd() {
-  const char* e = std::getenv("SRHIP_RG_XCD");  // read per launch: A/B measurements
-  return !(e && e[0] == '0');
-}
+bool rg_xcd() { return env_on("SRHIP_RG_XCD"); }  // read per launch: A/B measurements
 // SRHIP_TG_MAJOR=1 (experiment, read per launch): within an XCD the blocks
 // run tree group by tree group (jit_template.hip block_of, rotate 3), so the
 // workgroups resident on a CU share their tree code in the instruction cache
 int rotate_mode() {
   if (!rg_xcd()) return 0;
-  const char* e = std::getenv("SRHIP_TG_MAJOR");
-  return (e && e[0] == '1') ? 3 : 2;
+  return env_is1("SRHIP_TG_MAJOR") ? 3 : 2;
 }
 
-bool zero_copy_enabled() {
-  const char* e = std::getenv("SRHIP_ZERO_COPY");  // read per call: A/B measurements
-  return !(e && e[0] == '0');
-}
+bool zero_copy_enabled() { return env_on("SRHIP_ZERO_COPY"); }  // read per call: A/B measurements
 void ensure_pinned(srhip_ctx* c, size_t nt);
 
 // Wait for a call's last launch by polling the stream instead of the runtime's
@@ -1084,8 +1105,7 @@ void ensure_pinned(srhip_ctx* c, size_t nt);
 // kernel (config #5's 48 ms gradients) does not hold a host core that the
 // caller's other threads need. SRHIP_SPIN=0: the blocking wait (A/B).
 void wait_stream(hipStream_t s) {
-  const char* e = std::getenv("SRHIP_SPIN");  // read per call: A/B measurements
-  if (e && e[0] == '0') {
+  if (!env_on("SRHIP_SPIN")) {  // read per call: A/B measurements
     HIP_CHECK(hipStreamSynchronize(s));
     return;
   }
@@ -1109,27 +1129,14 @@ void wait_stream(hipStream_t s) {
 
 // LDS for the row tiles of a tree-code workgroup (SRHIP_EVAL_LDS, KiB)
 size_t jit_tile_budget() {
-  static const size_t b = [] {
-    const char* e = std::getenv("SRHIP_EVAL_LDS");
-    return (size_t)(e ? std::atoi(e) : 40) * 1024;
-  }();
+  static const size_t b = (size_t)env_int("SRHIP_EVAL_LDS", 40) * 1024;
   return b;
 }
-bool jit_fast_enabled() {
-  const char* e = std::getenv("SRHIP_JIT_FAST");
-  return !(e && e[0] == '0');
-}
+bool jit_fast_enabled() { return env_on("SRHIP_JIT_FAST"); }
 
 template <typename T>
 void build_program(srhip_program* p) {
-  srhip_trees tr;
-  tr.ntrees = p->ntrees;
-  tr.node_off = p->node_off.data();
-  tr.kind = p->kind.data();
-  tr.arg = p->arg.data();
-  tr.const_off = p->const_off.data();
-  tr.consts = p->consts.data();
-  CompiledBatch<T> cb = compile_batch_par<T>(tr, /*grad=*/false, p->jit_memc);
+  CompiledBatch<T> cb = compile_batch_par<T>(trees_of(p, p->consts.data()), /*grad=*/false, p->jit_memc);
   p->nodes = cb.nodes;
   p->static_fail = cb.static_fail;
   p->fail_if_rows = cb.fail_if_rows;
@@ -1173,8 +1180,7 @@ void build_program(srhip_program* p) {
       std::vector<int32_t> jl, rest;
       jit::Options jo;
       jo.fast = jit_fast_enabled();
-      const char* me = std::getenv("SRHIP_JIT_MEMC");  // read per build: tests
-      jo.memc = p->jit_memc || (me && me[0] == '1');
+      jo.memc = p->jit_memc || env_is1("SRHIP_JIT_MEMC");  // read per build: tests
       p->jit = jit::build(cb, a, jl, rest, jo, &p->jit_stats);
       if (p->jit) {
         p->nlist_j = (int)jl.size();
@@ -1187,7 +1193,7 @@ void build_program(srhip_program* p) {
   } else {
     // Float64 tree code (jit64.cpp) for the shallow trees of large batches;
     // SRHIP_JIT64=0: interpreted
-    static const bool on64 = [] { const char* e = std::getenv("SRHIP_JIT64"); return !(e && e[0] == '0'); }();
+    static const bool on64 = env_on("SRHIP_JIT64");
     // Float64 tree code holds its constants as literals: a VARYING_CONSTANTS program (the
     // optimiser's candidates) would rebuild it interpreted at its first set_constants
     if (on64 && p->jit_allowed && !p->jit_memc && jit_wanted((int)a.size()) && jit::available64()) {
@@ -1323,10 +1329,7 @@ void check_program_vs_dataset(const srhip_dataset* ds, const srhip_program* p, b
 
 // Threaded interpreter on/off (SRHIP_TI=0 disables it; built only when the
 // kernels were compiled with SR_TI).
-static bool ti_enabled() {
-  const char* e = std::getenv("SRHIP_TI");  // read per launch: tests compare both paths
-  return ti_compiled() && !(e && e[0] == '0');
-}
+static bool ti_enabled() { return ti_compiled() && env_on("SRHIP_TI"); }  // read per launch: tests compare both paths
 
 // Wide datasets: an interpreter pass whose row tile of all
 // nfeat features does not fit in LDS runs the wide kernel variant, which reads
@@ -1360,14 +1363,8 @@ static const char* interp_name(size_t esz, bool wide) {
 // profiles/r04_interp_dyn_ab.jsonl) config #3 interpreted 0.511 → 0.469 ms,
 // a 300-tree batch 0.117 → 0.112, config #2 interpreted 5.95 → 5.90; sums bit
 // for bit. SRHIP_INTERP_DYN=0 (read per launch): round-robin.
-static bool interp_dyn() {
-  const char* e = std::getenv("SRHIP_INTERP_DYN");
-  return !(e && e[0] == '0');
-}
-static bool rotate_enabled() {
-  const char* e = std::getenv("SRHIP_ROT");  // read per launch: A/B measurements
-  return e && e[0] == '1';
-}
+static bool interp_dyn() { return env_on("SRHIP_INTERP_DYN"); }
+static bool rotate_enabled() { return env_is1("SRHIP_ROT"); }  // read per launch: A/B measurements
 
 // Trees whose tree code handed a tile back (a sin/cos argument beyond the
 // fast reduction, jit_template.hip) are evaluated again, whole, by the
@@ -1463,7 +1460,7 @@ int device_cus(const srhip_ctx* c) {
 // workgroup sized to match: jit::lds_per_workgroup). SRHIP_JIT_TAIL=0 keeps
 // every row group whole.
 void tail_split(const srhip_ctx* c, EvalPlan* plan, int64_t rows, int jw) {
-  static const bool on = [] { const char* e = std::getenv("SRHIP_JIT_TAIL"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("SRHIP_JIT_TAIL");
   if (!on || plan->ntiles < 2 || rows <= 0) return;
   const int64_t conc = (int64_t)device_cus(c) * std::max(1, 20 / jw);
   const int64_t W = (int64_t)plan->nrg * plan->ntg;
@@ -1482,6 +1479,33 @@ void tail_split(const srhip_ctx* c, EvalPlan* plan, int64_t rows, int jw) {
   plan->nrg = (int)(nbig + nsmall);
 }
 
+// The skeleton of the tree-code modules built at first use: the module cached
+// under (kind, bits), else the program's trees compiled again with the
+// constants of the first build (`consts`), `build` run on them, a module whose
+// slot layout is not that build's (`same_layout` false) destroyed, and the
+// result, null included, cached with the program.
+template <typename T, typename M, typename Cache, typename Build, typename Same, typename Destroy>
+M* lazy_module(const srhip_program* p, Cache& cache, int kind, uint64_t bits, const std::vector<unsigned char>& consts,
+               bool grad, Build build, Same same_layout, Destroy destroy) {
+  for (const auto& l : cache)
+    if (l.kind == kind && l.bits == bits) return l.m;
+  const CompiledBatch<T> cb = compile_batch_par<T>(trees_of(p, consts.data()), grad);
+  std::vector<int32_t> jl, rest;
+  M* m = build(cb, jl, rest);
+  if (m && !same_layout(jl, rest)) {
+    destroy(m);  // a different slot layout: interpreted
+    m = nullptr;
+  }
+  cache.push_back({kind, bits, m});
+  return m;
+}
+
+uint64_t bits_of(double lparam) {
+  uint64_t bits;
+  std::memcpy(&bits, &lparam, 8);
+  return bits;
+}
+
 // The tree code of a Float32 program for an elementwise loss: the L2 build
 // itself, or (other losses) the same trees compiled with that loss's tile
 // tail, built at the loss's first evaluation and kept with the program
@@ -1489,34 +1513,21 @@ void tail_split(const srhip_ctx* c, EvalPlan* plan, int64_t rows, int jw) {
 jit::Module* loss_module(const srhip_program* p, int loss, double lparam) {
   if (!p->jit || p->nlist_j == 0) return nullptr;
   if (loss == SRHIP_LOSS_L2) return p->jit;
-  static const bool on = [] { const char* e = std::getenv("SRHIP_JIT_LOSSES"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("SRHIP_JIT_LOSSES");
   if (!on || loss < 0 || loss >= SRHIP_NUM_LOSSES || !jit::has_loss_routine(loss)) return nullptr;
-  uint64_t bits;
-  std::memcpy(&bits, &lparam, 8);
-  for (const auto& l : p->jit_loss)
-    if (l.kind == loss && l.bits == bits) return l.m;
-  srhip_trees tr;
-  tr.ntrees = p->ntrees;
-  tr.node_off = p->node_off.data();
-  tr.kind = p->kind.data();
-  tr.arg = p->arg.data();
-  tr.const_off = p->const_off.data();
-  tr.consts = p->jit_consts.data();
-  CompiledBatch<float> cb = compile_batch_par<float>(tr);
   jit::Options jo;
   jo.fast = jit_fast_enabled();
   jo.memc = jit::memc(p->jit);
   jo.loss = loss;
-  jo.lparam = bits;
-  std::vector<int32_t> jl, rest;
-  jit::Stats st;
-  jit::Module* m = jit::build(cb, p->h_jit_list, jl, rest, jo, &st);
-  if (m && (jl != p->h_jit_list || !rest.empty())) {
-    jit::destroy(m);  // a different slot layout: this loss runs interpreted
-    m = nullptr;
-  }
-  p->jit_loss.push_back({loss, bits, m});
-  return m;
+  jo.lparam = bits_of(lparam);
+  return lazy_module<float, jit::Module>(
+      p, p->jit_loss, loss, jo.lparam, p->jit_consts, false,
+      [&](const CompiledBatch<float>& cb, std::vector<int32_t>& jl, std::vector<int32_t>& rest) {
+        jit::Stats st;
+        return jit::build(cb, p->h_jit_list, jl, rest, jo, &st);
+      },
+      [&](const std::vector<int32_t>& jl, const std::vector<int32_t>& rest) { return jl == p->h_jit_list && rest.empty(); },
+      jit::destroy);
 }
 
 // The Float64 tree code of a program for an elementwise loss (L2: the build
@@ -1529,33 +1540,20 @@ jit::Module* loss_module(const srhip_program* p, int loss, double lparam) {
 jit::Module64* module64(const srhip_program* p, int kind, double lparam) {
   if (!p->jit64 || p->nlist_j == 0) return nullptr;
   if (kind == SRHIP_LOSS_L2) return p->jit64;
-  static const bool on = [] { const char* e = std::getenv("SRHIP_JIT64_EXTRA"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("SRHIP_JIT64_EXTRA");
   if (!on || kind < -2 || kind >= SRHIP_NUM_LOSSES || (kind >= 0 && !jit::has_loss_routine64(kind))) return nullptr;
-  uint64_t bits = 0;
-  if (kind != -2) std::memcpy(&bits, &lparam, 8);
-  for (const auto& l : p->jit64_loss)
-    if (l.kind == kind && l.bits == bits) return l.m;
-  srhip_trees tr;
-  tr.ntrees = p->ntrees;
-  tr.node_off = p->node_off.data();
-  tr.kind = p->kind.data();
-  tr.arg = p->arg.data();
-  tr.const_off = p->const_off.data();
-  tr.consts = p->jit_consts.data();
-  CompiledBatch<double> cb = compile_batch_par<double>(tr);
   jit::Opts64 o;
   o.out = kind == -2;
   o.loss = kind == -2 ? SRHIP_LOSS_L2 : kind;
-  o.lparam = bits;
-  std::vector<int32_t> jl, rest;
-  jit::Stats st;
-  jit::Module64* m = jit::build64(cb, p->h_jit_list, jl, rest, &st, o);
-  if (m && (jl != p->h_jit_list || !rest.empty())) {
-    jit::destroy64(m);  // a different slot layout: interpreted
-    m = nullptr;
-  }
-  p->jit64_loss.push_back({kind, bits, m});
-  return m;
+  o.lparam = kind == -2 ? 0 : bits_of(lparam);
+  return lazy_module<double, jit::Module64>(
+      p, p->jit64_loss, kind, o.lparam, p->jit_consts, false,
+      [&](const CompiledBatch<double>& cb, std::vector<int32_t>& jl, std::vector<int32_t>& rest) {
+        jit::Stats st;
+        return jit::build64(cb, p->h_jit_list, jl, rest, &st, o);
+      },
+      [&](const std::vector<int32_t>& jl, const std::vector<int32_t>& rest) { return jl == p->h_jit_list && rest.empty(); },
+      jit::destroy64);
 }
 
 // The per-row output tree code of a Float32 program (srhip_eval_tree_array):
@@ -1564,31 +1562,20 @@ jit::Module64* module64(const srhip_program* p, int kind, double lparam) {
 // jit_loss); null (SRHIP_JIT_OUT=0, a different slot layout): interpreted.
 jit::Module* out_module(const srhip_program* p) {
   if (!p->jit || p->nlist_j == 0) return nullptr;
-  static const bool on = [] { const char* e = std::getenv("SRHIP_JIT_OUT"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("SRHIP_JIT_OUT");
   if (!on) return nullptr;
-  for (const auto& l : p->jit_loss)
-    if (l.kind == -2) return l.m;
-  srhip_trees tr;
-  tr.ntrees = p->ntrees;
-  tr.node_off = p->node_off.data();
-  tr.kind = p->kind.data();
-  tr.arg = p->arg.data();
-  tr.const_off = p->const_off.data();
-  tr.consts = p->jit_consts.data();
-  CompiledBatch<float> cb = compile_batch_par<float>(tr);
   jit::Options jo;
   jo.fast = false;
   jo.memc = jit::memc(p->jit);
   jo.out = true;
-  std::vector<int32_t> jl, rest;
-  jit::Stats st;
-  jit::Module* m = jit::build(cb, p->h_jit_list, jl, rest, jo, &st);
-  if (m && (jl != p->h_jit_list || !rest.empty())) {
-    jit::destroy(m);
-    m = nullptr;
-  }
-  p->jit_loss.push_back({-2, 0, m});
-  return m;
+  return lazy_module<float, jit::Module>(
+      p, p->jit_loss, -2, 0, p->jit_consts, false,
+      [&](const CompiledBatch<float>& cb, std::vector<int32_t>& jl, std::vector<int32_t>& rest) {
+        jit::Stats st;
+        return jit::build(cb, p->h_jit_list, jl, rest, jo, &st);
+      },
+      [&](const std::vector<int32_t>& jl, const std::vector<int32_t>& rest) { return jl == p->h_jit_list && rest.empty(); },
+      jit::destroy);
 }
 
 // The gradient tree code of a Float32 program for an elementwise loss: the
@@ -1599,29 +1586,16 @@ jit::Module* out_module(const srhip_program* p) {
 jit::GradModule* grad_module(srhip_program* p, int loss, double lparam) {
   if (!p->gjit) return nullptr;
   if (loss == SRHIP_LOSS_L2) return p->gjit;
-  static const bool on = [] { const char* e = std::getenv("SRHIP_JIT_LOSSES"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("SRHIP_JIT_LOSSES");
   if (!on || loss < 0 || loss >= SRHIP_NUM_LOSSES || !jit::has_dloss_routine(loss)) return nullptr;
-  uint64_t bits;
-  std::memcpy(&bits, &lparam, 8);
-  for (const auto& l : p->gjit_loss)
-    if (l.kind == loss && l.bits == bits) return l.m;
-  srhip_trees tr;
-  tr.ntrees = p->ntrees;
-  tr.node_off = p->node_off.data();
-  tr.kind = p->kind.data();
-  tr.arg = p->arg.data();
-  tr.const_off = p->const_off.data();
-  tr.consts = p->gjit_consts.data();
-  CompiledBatch<float> cb = compile_batch_par<float>(tr, /*grad=*/true);
-  std::vector<int32_t> gjl, rest;
-  jit::GradStats st;
-  jit::GradModule* m = jit::build_grad(cb, p->const_off, p->h_gcand, gjl, rest, &st, loss, bits);
-  if (m && gjl != p->h_gjl) {
-    jit::destroy_grad(m);
-    m = nullptr;
-  }
-  p->gjit_loss.push_back({loss, bits, m});
-  return m;
+  const uint64_t bits = bits_of(lparam);
+  return lazy_module<float, jit::GradModule>(
+      p, p->gjit_loss, loss, bits, p->gjit_consts, true,
+      [&](const CompiledBatch<float>& cb, std::vector<int32_t>& gjl, std::vector<int32_t>& rest) {
+        jit::GradStats st;
+        return jit::build_grad(cb, p->const_off, p->h_gcand, gjl, rest, &st, loss, bits);
+      },
+      [&](const std::vector<int32_t>& gjl, const std::vector<int32_t>&) { return gjl == p->h_gjl; }, jit::destroy_grad);
 }
 
 // The same for a Float64 program (jit64.cpp GradGen64): the L2 build, or the
@@ -1629,29 +1603,17 @@ jit::GradModule* grad_module(srhip_program* p, int loss, double lparam) {
 jit::GradModule64* grad_module64(srhip_program* p, int loss, double lparam) {
   if (!p->gjit64) return nullptr;
   if (loss == SRHIP_LOSS_L2) return p->gjit64;
-  static const bool on = [] { const char* e = std::getenv("SRHIP_JIT_LOSSES"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("SRHIP_JIT_LOSSES");
   if (!on || loss < 0 || loss >= SRHIP_NUM_LOSSES || !jit::has_dloss_routine64(loss)) return nullptr;
-  uint64_t bits;
-  std::memcpy(&bits, &lparam, 8);
-  for (const auto& l : p->gjit64_loss)
-    if (l.kind == loss && l.bits == bits) return l.m;
-  srhip_trees tr;
-  tr.ntrees = p->ntrees;
-  tr.node_off = p->node_off.data();
-  tr.kind = p->kind.data();
-  tr.arg = p->arg.data();
-  tr.const_off = p->const_off.data();
-  tr.consts = p->gjit_consts.data();
-  CompiledBatch<double> cb = compile_batch_par<double>(tr, /*grad=*/true);
-  std::vector<int32_t> gjl, rest;
-  jit::GradStats st;
-  jit::GradModule64* m = jit::build_grad64(cb, p->const_off, p->h_gcand, gjl, rest, &st, loss, bits);
-  if (m && gjl != p->h_gjl) {
-    jit::destroy_grad64(m);
-    m = nullptr;
-  }
-  p->gjit64_loss.push_back({loss, bits, m});
-  return m;
+  const uint64_t bits = bits_of(lparam);
+  return lazy_module<double, jit::GradModule64>(
+      p, p->gjit64_loss, loss, bits, p->gjit_consts, true,
+      [&](const CompiledBatch<double>& cb, std::vector<int32_t>& gjl, std::vector<int32_t>& rest) {
+        jit::GradStats st;
+        return jit::build_grad64(cb, p->const_off, p->h_gcand, gjl, rest, &st, loss, bits);
+      },
+      [&](const std::vector<int32_t>& gjl, const std::vector<int32_t>&) { return gjl == p->h_gjl; },
+      jit::destroy_grad64);
 }
 
 // The shared subtrees of a tree-code module (jit.h Columns), once per row of
@@ -1666,7 +1628,7 @@ jit::GradModule64* grad_module64(srhip_program* p, int loss, double lparam) {
 // slot / keys: the program's cache of the subtree program (p->shared for the
 // loss tree code, p->gshared for the gradient tree code).
 bool derive_jit_enabled() {
-  static const bool on = [] { const char* e = std::getenv("SRHIP_DERIVE_JIT"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("SRHIP_DERIVE_JIT");
   return on;
 }
 void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>& keys, const jit::Columns& jc,
@@ -2007,7 +1969,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
       if constexpr (std::is_same<T, float>::value) {
         // the derived columns of this call, once per row, before the first part
         const jit::Columns& jc = jit::columns(jm);
-        static const bool precompute = [] { const char* e = std::getenv("SRHIP_JIT_DERIVE_PRE"); return !(e && e[0] == '0'); }();
+        static const bool precompute = env_on("SRHIP_JIT_DERIVE_PRE");
         const float* dcols = nullptr;
         if (jc.nder > 0 && precompute) {
           c->derived.ensure((size_t)jc.nder * (size_t)n_pad * sizeof(float));
@@ -2325,8 +2287,7 @@ void copy_rows_to_host(srhip_ctx* c, unsigned char* dst, const unsigned char* sr
   // buffer are most of the cost: 0.82 GB in 43 ms on 16 threads, 63 ms on 8,
   // profiles/r03_hostcopy.txt)
   static const unsigned nthr = [] {
-    const char* e = std::getenv("SRHIP_COPY_THREADS");
-    const unsigned want = e ? (unsigned)std::max(1, std::atoi(e)) : 16u;
+    const unsigned want = (unsigned)std::max(1, env_int("SRHIP_COPY_THREADS", 16));
     return std::max(1u, std::min(want, std::max(1u, std::thread::hardware_concurrency())));
   }();
   if (!c->copy_pool) c->copy_pool.reset(new CopyPool());
@@ -2828,6 +2789,98 @@ const OpName kOpNames[] = {
     {"inv", 1, SRHIP_UOP_INV},
 };
 
+// `call` on a program of `trees` that lives for the call; the call's error survives the destroy
+template <typename Call>
+int32_t with_temp_program(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees, uint32_t flags, Call call) {
+  srhip_program* p = nullptr;
+  int32_t rc = srhip_program_create_ex(ctx, ds->dtype, trees, flags, &p);
+  if (rc != SRHIP_OK) return rc;
+  rc = call(p);
+  const std::string err = g_last_error;
+  srhip_program_destroy(p);
+  g_last_error = err;
+  return rc;
+}
+
+// ---- what the two dataset constructors share ----
+void check_dataset_shape(int32_t dtype, int32_t x_layout, int64_t n, int32_t nfeat, int64_t row_begin,
+                         int64_t row_end) {
+  if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
+  if (x_layout != SRHIP_X_JULIA && x_layout != SRHIP_X_FEATURE_MAJOR) throw Error(SRHIP_ERR_INVALID, "bad X layout");
+  if (n < 0 || nfeat <= 0 || nfeat > 65535) throw Error(SRHIP_ERR_INVALID, "bad shape");
+  if (row_begin < 0 || row_end < row_begin || row_end > n) throw Error(SRHIP_ERR_INVALID, "bad row range");
+}
+
+// Staging of one upload: the raw shard of X, one raw column, the count of
+// non-finite X values. Freed on every path (ScopedBuf), the error path included.
+struct UploadStage {
+  ScopedBuf raw, rawv, bad;
+  UploadStage(srhip_ctx* ctx, int64_t rows, int nfeat, size_t es) {
+    raw.ensure((size_t)rows * nfeat * es);
+    rawv.ensure((size_t)rows * es);
+    bad.ensure(sizeof(int));
+    HIP_CHECK(hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
+  }
+};
+
+// rows [row_begin, row_begin + rows) of the host's X: raw shard upload, then
+// packed / transposed on the device into dX ([nfeat][n_pad])
+void upload_x(srhip_ctx* ctx, UploadStage& st, int dtype, int x_layout, const void* X, int64_t n, int nfeat,
+              int64_t row_begin, int64_t rows, int64_t n_pad, void* dX) {
+  const size_t es = dtype_size(dtype);
+  if (x_layout == SRHIP_X_JULIA) {
+    HIP_CHECK(hipMemcpyAsync(st.raw.p, static_cast<const char*>(X) + (size_t)row_begin * nfeat * es,
+                             (size_t)rows * nfeat * es, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    HIP_CHECK(hipMemcpy2DAsync(st.raw.p, rows * es, static_cast<const char*>(X) + row_begin * es, n * es, rows * es,
+                               nfeat, hipMemcpyHostToDevice, ctx->stream));
+  }
+  by_dtype(dtype, [&](auto t) {  // (source stride rows: the packed feature-major shard)
+    using T = decltype(t);
+    HIP_CHECK(launch_pack_x<T>((const T*)st.raw.p, x_layout, rows, rows, nfeat, n_pad, (T*)dX,
+                               static_cast<int*>(st.bad.p), ctx->stream));
+  });
+}
+
+// `rows` values of a host column from src on, padded into dst ([n_pad])
+void upload_column(srhip_ctx* ctx, UploadStage& st, int dtype, const void* src, int64_t rows, int64_t n_pad,
+                   void* dst) {
+  HIP_CHECK(hipMemcpyAsync(st.rawv.p, src, (size_t)rows * dtype_size(dtype), hipMemcpyHostToDevice, ctx->stream));
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    HIP_CHECK(launch_pack_vec<T>((const T*)st.rawv.p, rows, n_pad, (T*)dst, ctx->stream));
+  });
+}
+
+// waits for the uploads; whether every X value was finite
+bool finish_upload(srhip_ctx* ctx, UploadStage& st) {
+  int hbad = 0;
+  HIP_CHECK(hipMemcpyAsync(&hbad, st.bad.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return hbad == 0;
+}
+
+// Σw and Σ y·w over elements [b, e) of the host columns y and w (w may be null),
+// in double (src/Dataset.jl:56-60); the weights are appended to hw
+void weight_sums(int dtype, const void* y, const void* w, size_t b, size_t e, double* sum_w, double* sum_yw,
+                 std::vector<double>& hw) {
+  auto at = [&](const void* base, size_t j) {
+    return dtype == SRHIP_F32 ? (double)static_cast<const float*>(base)[j] : static_cast<const double*>(base)[j];
+  };
+  double sw = 0.0, syw = 0.0;
+  for (size_t j = b; j < e; ++j) {
+    double wi = 1.0;
+    if (w) {
+      wi = at(w, j);
+      hw.push_back(wi);
+    }
+    sw += wi;
+    syw += at(y, j) * wi;
+  }
+  *sum_w = sw;
+  *sum_yw = syw;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3002,12 +3055,11 @@ int32_t srhip_loss_expr_eval(int32_t loss_kind, int32_t dtype, const void* yhat,
     if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
     if (n < 0 || (n > 0 && (!yhat || !y || !out))) throw Error(SRHIP_ERR_INVALID, "null array or negative length");
     if (e->uses_w && !w) throw Error(SRHIP_ERR_INVALID, "the expression loss reads the weight (feature 2) but w is NULL");
-    if (dtype == SRHIP_F32)
-      expr_loss_eval_host<float>(*e, static_cast<const float*>(yhat), static_cast<const float*>(y),
-                                 static_cast<const float*>(w), n, static_cast<float*>(out));
-    else
-      expr_loss_eval_host<double>(*e, static_cast<const double*>(yhat), static_cast<const double*>(y),
-                                  static_cast<const double*>(w), n, static_cast<double*>(out));
+    by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      expr_loss_eval_host<T>(*e, static_cast<const T*>(yhat), static_cast<const T*>(y), static_cast<const T*>(w), n,
+                             static_cast<T*>(out));
+    });
     return SRHIP_OK;
   });
 }
@@ -3018,13 +3070,9 @@ int32_t srhip_dataset_create(srhip_ctx* ctx, int32_t dtype, int32_t x_layout, co
   return guarded([&] {
     if (!ctx || !out_ds) throw Error(SRHIP_ERR_INVALID, "null ctx or out_ds");
     *out_ds = nullptr;
-    if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
-    if (x_layout != SRHIP_X_JULIA && x_layout != SRHIP_X_FEATURE_MAJOR) throw Error(SRHIP_ERR_INVALID, "bad X layout");
-    if (n < 0 || nfeat <= 0 || nfeat > 65535) throw Error(SRHIP_ERR_INVALID, "bad shape");
-    if (row_begin < 0 || row_end < row_begin || row_end > n) throw Error(SRHIP_ERR_INVALID, "bad row range");
+    check_dataset_shape(dtype, x_layout, n, nfeat, row_begin, row_end);
     if ((row_end > row_begin) && (!X || !y)) throw Error(SRHIP_ERR_INVALID, "null X or y");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIP_CHECK(hipSetDevice(ctx->device));
+    CALL_SCOPE(ctx);
     const size_t es = dtype_size(dtype);
     const int64_t rows = row_end - row_begin;
     const int64_t n_pad = pad_rows(rows);
@@ -3042,59 +3090,14 @@ int32_t srhip_dataset_create(srhip_ctx* ctx, int32_t dtype, int32_t x_layout, co
       HIP_CHECK(hipMemsetAsync(ds->y, 0, (size_t)n_pad * es, ctx->stream));
       if (w) HIP_CHECK(hipMemsetAsync(ds->w, 0, (size_t)n_pad * es, ctx->stream));
       if (rows > 0) {
-        // raw shard upload, then pack/transposes on the device; the staging
-        // buffers are freed on every path (ScopedBuf), the error path included
-        ScopedBuf raw_b, rawv_b, bad_b;
-        raw_b.ensure((size_t)rows * nfeat * es);
-        rawv_b.ensure((size_t)rows * es);
-        bad_b.ensure(sizeof(int));
-        void* raw = raw_b.p;
-        void* rawv = rawv_b.p;
-        int* bad = static_cast<int*>(bad_b.p);
-        HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-        if (x_layout == SRHIP_X_JULIA) {
-          HIP_CHECK(hipMemcpyAsync(raw, static_cast<const char*>(X) + (size_t)row_begin * nfeat * es,
-                                   (size_t)rows * nfeat * es, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-          HIP_CHECK(hipMemcpy2DAsync(raw, rows * es, static_cast<const char*>(X) + row_begin * es, n * es,
-                                     rows * es, nfeat, hipMemcpyHostToDevice, ctx->stream));
-        }
-        const int64_t src_stride = rows;  // packed feature-major shard
-        if (dtype == SRHIP_F32)
-          HIP_CHECK(launch_pack_x<float>((const float*)raw, x_layout, src_stride, rows, nfeat, n_pad, (float*)ds->X, bad, ctx->stream));
-        else
-          HIP_CHECK(launch_pack_x<double>((const double*)raw, x_layout, src_stride, rows, nfeat, n_pad, (double*)ds->X, bad, ctx->stream));
-        const void* vecs[2] = {y, w};
-        void* dsts[2] = {ds->y, ds->w};
-        for (int k = 0; k < 2; ++k) {
-          if (!vecs[k]) continue;
-          HIP_CHECK(hipMemcpyAsync(rawv, static_cast<const char*>(vecs[k]) + (size_t)row_begin * es, (size_t)rows * es,
-                                   hipMemcpyHostToDevice, ctx->stream));
-          if (dtype == SRHIP_F32)
-            HIP_CHECK(launch_pack_vec<float>((const float*)rawv, rows, n_pad, (float*)dsts[k], ctx->stream));
-          else
-            HIP_CHECK(launch_pack_vec<double>((const double*)rawv, rows, n_pad, (double*)dsts[k], ctx->stream));
-        }
-        int hbad = 0;
-        HIP_CHECK(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        ds->x_finite = hbad == 0;
+        UploadStage st(ctx, rows, nfeat, es);
+        upload_x(ctx, st, dtype, x_layout, X, n, nfeat, row_begin, rows, n_pad, ds->X);
+        upload_column(ctx, st, dtype, static_cast<const char*>(y) + (size_t)row_begin * es, rows, n_pad, ds->y);
+        if (w) upload_column(ctx, st, dtype, static_cast<const char*>(w) + (size_t)row_begin * es, rows, n_pad, ds->w);
+        ds->x_finite = finish_upload(ctx, st);
       }
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      // Σw and Σ y·w over the shard, in double (src/Dataset.jl:56-60)
-      double sw = 0.0, syw = 0.0;
-      for (int64_t i = row_begin; i < row_end; ++i) {
-        const double yi = dtype == SRHIP_F32 ? (double)static_cast<const float*>(y)[i] : static_cast<const double*>(y)[i];
-        double wi = 1.0;
-        if (w) {
-          wi = dtype == SRHIP_F32 ? (double)static_cast<const float*>(w)[i] : static_cast<const double*>(w)[i];
-          ds->h_w.push_back(wi);
-        }
-        sw += wi;
-        syw += yi * wi;
-      }
-      ds->sum_w = sw;
-      ds->sum_yw = syw;
+      weight_sums(dtype, y, w, (size_t)row_begin, (size_t)row_end, &ds->sum_w, &ds->sum_yw, ds->h_w);
     } catch (...) {
       if (ds->X) (void)hipFree(ds->X);
       if (ds->y) (void)hipFree(ds->y);
@@ -3148,13 +3151,9 @@ int32_t srhip_dataset_create_multi(srhip_ctx* ctx, int32_t dtype, int32_t x_layo
     if (!Y) throw Error(SRHIP_ERR_INVALID, "null Y");
     if (!ctx || !out_ds) throw Error(SRHIP_ERR_INVALID, "null ctx or out_ds");
     *out_ds = nullptr;
-    if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
-    if (x_layout != SRHIP_X_JULIA && x_layout != SRHIP_X_FEATURE_MAJOR) throw Error(SRHIP_ERR_INVALID, "bad X layout");
-    if (n < 0 || nfeat <= 0 || nfeat > 65535) throw Error(SRHIP_ERR_INVALID, "bad shape");
-    if (row_begin < 0 || row_end < row_begin || row_end > n) throw Error(SRHIP_ERR_INVALID, "bad row range");
+    check_dataset_shape(dtype, x_layout, n, nfeat, row_begin, row_end);
     if (row_end > row_begin && !X) throw Error(SRHIP_ERR_INVALID, "null X");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIP_CHECK(hipSetDevice(ctx->device));
+    CALL_SCOPE(ctx);
     const size_t es = dtype_size(dtype);
     const int64_t rows = row_end - row_begin;
     const int64_t n_pad = pad_rows(rows);
@@ -3176,68 +3175,28 @@ int32_t srhip_dataset_create_multi(srhip_ctx* ctx, int32_t dtype, int32_t x_layo
     HIP_CHECK(hipMemsetAsync(m->Y, 0, K * (size_t)n_pad * es, ctx->stream));
     if (W) HIP_CHECK(hipMemsetAsync(m->W, 0, K * (size_t)n_pad * es, ctx->stream));
     if (rows > 0) {
-      ScopedBuf raw_b, rawv_b, bad_b;
-      raw_b.ensure((size_t)rows * nfeat * es);
-      rawv_b.ensure((size_t)rows * es);
-      bad_b.ensure(sizeof(int));
-      void* raw = raw_b.p;
-      void* rawv = rawv_b.p;
-      int* bad = static_cast<int*>(bad_b.p);
-      HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-      if (x_layout == SRHIP_X_JULIA) {
-        HIP_CHECK(hipMemcpyAsync(raw, static_cast<const char*>(X) + (size_t)row_begin * nfeat * es,
-                                 (size_t)rows * nfeat * es, hipMemcpyHostToDevice, ctx->stream));
-      } else {
-        HIP_CHECK(hipMemcpy2DAsync(raw, rows * es, static_cast<const char*>(X) + row_begin * es, n * es, rows * es,
-                                   nfeat, hipMemcpyHostToDevice, ctx->stream));
-      }
-      if (dtype == SRHIP_F32)
-        HIP_CHECK(launch_pack_x<float>((const float*)raw, x_layout, rows, rows, nfeat, n_pad, (float*)m->X, bad, ctx->stream));
-      else
-        HIP_CHECK(launch_pack_x<double>((const double*)raw, x_layout, rows, rows, nfeat, n_pad, (double*)m->X, bad, ctx->stream));
+      UploadStage st(ctx, rows, nfeat, es);
+      upload_x(ctx, st, dtype, x_layout, X, n, nfeat, row_begin, rows, n_pad, m->X);
       // column k of Y / W: rows [row_begin, row_end) of the host's row k, padded as a single y is
       const void* blocks[2] = {Y, W};
       void* dsts[2] = {m->Y, m->W};
       for (int b = 0; b < 2; ++b) {
         if (!blocks[b]) continue;
-        for (size_t k = 0; k < K; ++k) {
-          HIP_CHECK(hipMemcpyAsync(rawv, static_cast<const char*>(blocks[b]) + (k * (size_t)n + (size_t)row_begin) * es,
-                                   (size_t)rows * es, hipMemcpyHostToDevice, ctx->stream));
-          void* dst = static_cast<char*>(dsts[b]) + k * (size_t)n_pad * es;
-          if (dtype == SRHIP_F32)
-            HIP_CHECK(launch_pack_vec<float>((const float*)rawv, rows, n_pad, (float*)dst, ctx->stream));
-          else
-            HIP_CHECK(launch_pack_vec<double>((const double*)rawv, rows, n_pad, (double*)dst, ctx->stream));
-        }
+        for (size_t k = 0; k < K; ++k)
+          upload_column(ctx, st, dtype, static_cast<const char*>(blocks[b]) + (k * (size_t)n + (size_t)row_begin) * es,
+                        rows, n_pad, static_cast<char*>(dsts[b]) + k * (size_t)n_pad * es);
       }
-      int hbad = 0;
-      HIP_CHECK(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      ds->x_finite = hbad == 0;
+      ds->x_finite = finish_upload(ctx, st);
     }
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    // Σw and Σ y·w of every target over the shard, in double (src/Dataset.jl:56-60)
+    // Σw and Σ y·w of every target over the shard
     ds->t_sum_w.assign(K, 0.0);
     ds->t_sum_yw.assign(K, 0.0);
     ds->t_h_w.assign(K, std::vector<double>());
-    auto at = [&](const void* base, size_t k, int64_t i) {
-      const size_t j = k * (size_t)n + (size_t)i;
-      return dtype == SRHIP_F32 ? (double)static_cast<const float*>(base)[j] : static_cast<const double*>(base)[j];
-    };
     for (size_t k = 0; k < K; ++k) {
-      double sw = 0.0, syw = 0.0;
       if (W) ds->t_h_w[k].reserve((size_t)rows);
-      for (int64_t i = row_begin; i < row_end; ++i) {
-        double wi = 1.0;
-        if (W) {
-          wi = at(W, k, i);
-          ds->t_h_w[k].push_back(wi);
-        }
-        sw += wi;
-        syw += at(Y, k, i) * wi;
-      }
-      ds->t_sum_w[k] = sw;
-      ds->t_sum_yw[k] = syw;
+      weight_sums(dtype, Y, W, k * (size_t)n + (size_t)row_begin, k * (size_t)n + (size_t)row_end, &ds->t_sum_w[k],
+                  &ds->t_sum_yw[k], ds->t_h_w[k]);
     }
     ds->X = m->X;
     ds->y = m->Y;
@@ -3342,10 +3301,8 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
         p->const_off.assign(1, 0);
         p->consts.resize(1);
       }
-      std::lock_guard<std::mutex> lk(ctx->mu);
-      HIP_CHECK(hipSetDevice(ctx->device));
-      if (dtype == SRHIP_F32) build_program<float>(p);
-      else build_program<double>(p);
+      CALL_SCOPE(ctx);
+      by_dtype(dtype, [&](auto t) { build_program<decltype(t)>(p); });
     } catch (...) {
       free_program_device(p);
       delete p;
@@ -3385,10 +3342,8 @@ int32_t srhip_program_set_constants(srhip_program* prog, const void* consts) {
     const size_t cb = (size_t)prog->const_off.back() * dtype_size(prog->dtype);
     if (cb && !consts) throw Error(SRHIP_ERR_INVALID, "null constants");
     if (cb) std::memcpy(prog->consts.data(), consts, cb);
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
-    if (prog->dtype == SRHIP_F32) update_constants<float>(prog);
-    else update_constants<double>(prog);
+    CALL_SCOPE(prog->ctx);
+    by_dtype(prog->dtype, [&](auto t) { update_constants<decltype(t)>(prog); });
     return SRHIP_OK;
   });
 }
@@ -3429,11 +3384,10 @@ int32_t srhip_eval_loss(srhip_dataset* ds, const srhip_program* prog, int32_t lo
     check_program_vs_dataset(ds, prog);
     check_loss(loss_kind, loss_params);
     check_expr_loss_weights(loss_kind, ds->w != nullptr);
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
-    if (ds->dtype == SRHIP_F32)
-      return eval_loss_impl<float>(ds, prog, loss_kind, loss_params, row_idx, nidx, out_loss_sum, out_weight_sum, out_ok);
-    return eval_loss_impl<double>(ds, prog, loss_kind, loss_params, row_idx, nidx, out_loss_sum, out_weight_sum, out_ok);
+    CALL_SCOPE(prog->ctx);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_impl<decltype(t)>(ds, prog, loss_kind, loss_params, row_idx, nidx, out_loss_sum, out_weight_sum, out_ok);
+    });
   });
 }
 
@@ -3450,10 +3404,10 @@ int32_t srhip_eval_loss_packed(srhip_dataset* ds, srhip_program* prog, int32_t l
     if (at.device != prog->ctx->device)
       throw Error(SRHIP_ERR_INVALID, "d_out is on device " + std::to_string(at.device) + ", the program on device " +
                                          std::to_string(prog->ctx->device));
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
-    if (ds->dtype == SRHIP_F32) return eval_loss_packed_impl<float>(ds, prog, loss_kind, loss_params, d_out);
-    return eval_loss_packed_impl<double>(ds, prog, loss_kind, loss_params, d_out);
+    CALL_SCOPE(prog->ctx);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_packed_impl<decltype(t)>(ds, prog, loss_kind, loss_params, d_out);
+    });
   });
 }
 
@@ -3470,14 +3424,9 @@ int32_t srhip_eval_loss_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip
                                   double* out_loss_sum, double* out_weight_sum, uint8_t* out_ok) {
   if (!ds) return set_error(SRHIP_ERR_INVALID, "null dataset");
   if (!ctx) return set_error(SRHIP_ERR_INVALID, "null ctx");
-  srhip_program* p = nullptr;
-  int32_t rc = srhip_program_create(ctx, ds->dtype, trees, &p);
-  if (rc != SRHIP_OK) return rc;
-  rc = srhip_eval_loss(ds, p, loss_kind, loss_params, row_idx, nidx, out_loss_sum, out_weight_sum, out_ok);
-  std::string err = g_last_error;
-  srhip_program_destroy(p);
-  g_last_error = err;
-  return rc;
+  return with_temp_program(ctx, ds, trees, 0u, [&](srhip_program* p) {
+    return srhip_eval_loss(ds, p, loss_kind, loss_params, row_idx, nidx, out_loss_sum, out_weight_sum, out_ok);
+  });
 }
 
 int32_t srhip_eval_loss_rowsets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
@@ -3487,13 +3436,11 @@ int32_t srhip_eval_loss_rowsets(srhip_dataset* ds, const srhip_program* prog, in
     check_program_vs_dataset(ds, prog);
     check_loss(loss_kind, loss_params);
     check_expr_loss_weights(loss_kind, ds->w != nullptr);
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
-    if (ds->dtype == SRHIP_F32)
-      return eval_loss_rowsets_impl<float>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
-                                           out_weight_sum, out_ok);
-    return eval_loss_rowsets_impl<double>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
-                                          out_weight_sum, out_ok);
+    CALL_SCOPE(prog->ctx);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_rowsets_impl<decltype(t)>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
+                                                 out_weight_sum, out_ok);
+    });
   });
 }
 
@@ -3502,17 +3449,11 @@ int32_t srhip_eval_loss_batch_rowsets_ctx(srhip_ctx* ctx, srhip_dataset* ds, con
                                           int64_t batch_size, double* out_loss_sum, double* out_weight_sum,
                                           uint8_t* out_ok) {
   if (!ds) return set_error(SRHIP_ERR_INVALID, "null dataset");
-  if (!ctx) ctx = ds->ctx;
-  srhip_program* p = nullptr;
   // row sets run in the interpreter: no tree code to build
-  int32_t rc = srhip_program_create_ex(ctx, ds->dtype, trees, SRHIP_PROGRAM_INTERPRETED, &p);
-  if (rc != SRHIP_OK) return rc;
-  rc = srhip_eval_loss_rowsets(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum, out_weight_sum,
-                               out_ok);
-  std::string err = g_last_error;
-  srhip_program_destroy(p);
-  g_last_error = err;
-  return rc;
+  return with_temp_program(ctx ? ctx : ds->ctx, ds, trees, SRHIP_PROGRAM_INTERPRETED, [&](srhip_program* p) {
+    return srhip_eval_loss_rowsets(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum, out_weight_sum,
+                                   out_ok);
+  });
 }
 
 // the fused calls' own checks: table losses only, every target within the dataset's columns
@@ -3533,11 +3474,11 @@ int32_t srhip_eval_loss_targets(srhip_dataset* ds, const srhip_program* prog, in
     check_program_vs_dataset(ds, prog, true);
     check_loss(loss_kind, loss_params);
     check_targets(ds, prog, loss_kind, target);
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
-    if (ds->dtype == SRHIP_F32)
-      return eval_loss_targets_impl<float>(ds, prog, loss_kind, loss_params, target, out_loss_sum, out_weight_sum, out_ok);
-    return eval_loss_targets_impl<double>(ds, prog, loss_kind, loss_params, target, out_loss_sum, out_weight_sum, out_ok);
+    CALL_SCOPE(prog->ctx);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_targets_impl<decltype(t)>(ds, prog, loss_kind, loss_params, target, out_loss_sum, out_weight_sum,
+                                                 out_ok);
+    });
   });
 }
 
@@ -3545,16 +3486,10 @@ int32_t srhip_eval_loss_batch_targets_ctx(srhip_ctx* ctx, srhip_dataset* ds, con
                                           int32_t loss_kind, const double* loss_params, const int32_t* target,
                                           double* out_loss_sum, double* out_weight_sum, uint8_t* out_ok) {
   if (!ds) return set_error(SRHIP_ERR_INVALID, "null dataset");
-  if (!ctx) ctx = ds->ctx;
-  srhip_program* p = nullptr;
   // the fused call runs in the interpreter: no tree code to build
-  int32_t rc = srhip_program_create_ex(ctx, ds->dtype, trees, SRHIP_PROGRAM_INTERPRETED, &p);
-  if (rc != SRHIP_OK) return rc;
-  rc = srhip_eval_loss_targets(ds, p, loss_kind, loss_params, target, out_loss_sum, out_weight_sum, out_ok);
-  std::string err = g_last_error;
-  srhip_program_destroy(p);
-  g_last_error = err;
-  return rc;
+  return with_temp_program(ctx ? ctx : ds->ctx, ds, trees, SRHIP_PROGRAM_INTERPRETED, [&](srhip_program* p) {
+    return srhip_eval_loss_targets(ds, p, loss_kind, loss_params, target, out_loss_sum, out_weight_sum, out_ok);
+  });
 }
 
 int32_t srhip_eval_loss_rowsets_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
@@ -3565,23 +3500,21 @@ int32_t srhip_eval_loss_rowsets_targets(srhip_dataset* ds, const srhip_program* 
     check_program_vs_dataset(ds, prog, true);
     check_loss(loss_kind, loss_params);
     check_targets(ds, prog, loss_kind, target);
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
-    if (ds->dtype == SRHIP_F32)
-      return eval_loss_rowsets_impl<float>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
-                                           out_weight_sum, out_ok, target);
-    return eval_loss_rowsets_impl<double>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
-                                          out_weight_sum, out_ok, target);
+    CALL_SCOPE(prog->ctx);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_rowsets_impl<decltype(t)>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
+                                                 out_weight_sum, out_ok, target);
+    });
   });
 }
 
 int32_t srhip_eval_tree_array(srhip_dataset* ds, const srhip_program* prog, void* out, uint8_t* out_ok) {
   return guarded([&] {
     check_program_vs_dataset(ds, prog);
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
-    if (ds->dtype == SRHIP_F32) return eval_tree_array_impl<float>(ds, prog, out, out_ok);
-    return eval_tree_array_impl<double>(ds, prog, out, out_ok);
+    CALL_SCOPE(prog->ctx);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_tree_array_impl<decltype(t)>(ds, prog, out, out_ok);
+    });
   });
 }
 
@@ -3592,12 +3525,12 @@ int32_t srhip_eval_loss_grad(srhip_dataset* ds, const srhip_program* prog, int32
     check_program_vs_dataset(ds, prog);
     check_loss(loss_kind, loss_params);
     check_expr_loss_weights(loss_kind, ds->w != nullptr);
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
+    CALL_SCOPE(prog->ctx);
     auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
-    if (ds->dtype == SRHIP_F32)
-      return eval_loss_grad_impl<float>(ds, p, loss_kind, loss_params, out_loss_sum, out_dloss, out_weight_sum, out_ok);
-    return eval_loss_grad_impl<double>(ds, p, loss_kind, loss_params, out_loss_sum, out_dloss, out_weight_sum, out_ok);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_grad_impl<decltype(t)>(ds, p, loss_kind, loss_params, out_loss_sum, out_dloss, out_weight_sum,
+                                              out_ok);
+    });
   });
 }
 
@@ -3610,14 +3543,12 @@ int32_t srhip_eval_loss_grad_rowsets(srhip_dataset* ds, const srhip_program* pro
     check_loss(loss_kind, loss_params);
     check_expr_loss_weights(loss_kind, ds->w != nullptr);
     check_row_sets(ds, prog->ntrees, row_idx, batch_size);  // before the gradient programs are built
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
+    CALL_SCOPE(prog->ctx);
     auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
-    if (ds->dtype == SRHIP_F32)
-      return eval_loss_grad_rowsets_impl<float>(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
-                                                out_dloss, out_weight_sum, out_ok);
-    return eval_loss_grad_rowsets_impl<double>(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
-                                               out_dloss, out_weight_sum, out_ok);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_grad_rowsets_impl<decltype(t)>(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
+                                                      out_dloss, out_weight_sum, out_ok);
+    });
   });
 }
 
@@ -3625,24 +3556,17 @@ int32_t srhip_eval_grad_tree_array(srhip_dataset* ds, const srhip_program* prog,
                                    void* out_grad, uint8_t* out_ok) {
   return guarded([&] {
     check_program_vs_dataset(ds, prog);
-    std::lock_guard<std::mutex> lk(prog->ctx->mu);
-    HIP_CHECK(hipSetDevice(prog->ctx->device));
-    auto* p = const_cast<srhip_program*>(prog);
-    if (ds->dtype == SRHIP_F32) return eval_grad_tree_array_impl<float>(ds, p, out_value, out_grad, out_ok);
-    return eval_grad_tree_array_impl<double>(ds, p, out_value, out_grad, out_ok);
+    CALL_SCOPE(prog->ctx);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_grad_tree_array_impl<decltype(t)>(ds, const_cast<srhip_program*>(prog), out_value, out_grad, out_ok);
+    });
   });
 }
 
 int32_t srhip_last_kernel_time(const srhip_ctx* ctx, double* out_ms, int32_t* out_launches) {
   return guarded([&] {
     if (!ctx) throw Error(SRHIP_ERR_INVALID, "null ctx");
-    auto* c = const_cast<srhip_ctx*>(ctx);
-    if (c->timing_pending || c->cnt_pending) {  // a call that returned before its results were read
-      std::lock_guard<std::mutex> lk(c->mu);
-      HIP_CHECK(hipSetDevice(c->device));
-      HIP_CHECK(hipStreamSynchronize(c->stream));
-      timing_finish(c);
-    }
+    flush_pending(const_cast<srhip_ctx*>(ctx));
     if (out_ms) *out_ms = ctx->last_ms;
     if (out_launches) *out_launches = ctx->last_launches;
     return SRHIP_OK;
@@ -3729,13 +3653,7 @@ int32_t srhip_last_tree_code(const srhip_ctx* ctx, int32_t* out_ntrees) {
 int32_t srhip_last_bailed(const srhip_ctx* ctx, int32_t* out_ntrees, int64_t* out_redone) {
   return guarded([&] {
     if (!ctx || !out_ntrees) throw Error(SRHIP_ERR_INVALID, "null argument");
-    auto* c = const_cast<srhip_ctx*>(ctx);
-    if (c->timing_pending || c->cnt_pending) {
-      std::lock_guard<std::mutex> lk(c->mu);
-      HIP_CHECK(hipSetDevice(c->device));
-      HIP_CHECK(hipStreamSynchronize(c->stream));
-      timing_finish(c);
-    }
+    flush_pending(const_cast<srhip_ctx*>(ctx));
     *out_ntrees = ctx->last_bailed;
     if (out_redone) *out_redone = ctx->last_redone;
     return SRHIP_OK;
@@ -3743,6 +3661,16 @@ int32_t srhip_last_bailed(const srhip_ctx* ctx, int32_t* out_ntrees, int64_t* ou
 }
 
 namespace {
+// the trees a tree compiler is offered: compiled, no expression-operator code, and
+// (loss and output code) within the shallow interpreter's slots
+template <typename T>
+std::vector<int32_t> candidates(const CompiledBatch<T>& cb, bool shallow) {
+  std::vector<int32_t> cand;
+  for (int t = 0; t < cb.ntrees; ++t)
+    if (cb.tree_off[t] >= 0 && (!shallow || cb.need[t] <= kShallowSlots) && !cb.expr[t]) cand.push_back(t);
+  return cand;
+}
+
 int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes, int64_t* inout_nbytes,
                          char* out_text, int64_t* inout_ntext, int32_t* out_offsets, int64_t* inout_noffsets,
                          int loss = SRHIP_LOSS_L2, double lparam = 0.0, bool out_mode = false, bool notext = false) {
@@ -3767,31 +3695,21 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
     if (mode == 6) {  // Float64 gradient tree code (jit64.cpp GradGen64)
       if (!jit::has_dloss_routine64(loss)) throw Error(SRHIP_ERR_UNSUPPORTED, "no Float64 gradient tree code for this loss");
       CompiledBatch<double> cb = compile_batch<double>(*trees, /*grad=*/true);
-      std::vector<int32_t> cand, coff(trees->const_off, trees->const_off + trees->ntrees + 1);
-      for (int t = 0; t < cb.ntrees; ++t)
-        if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
-      jit::compile_grad_only64(cb, coff, cand, &bytes, &text, &offs, loss, lbits);
+      const std::vector<int32_t> coff(trees->const_off, trees->const_off + trees->ntrees + 1);
+      jit::compile_grad_only64(cb, coff, candidates(cb, false), &bytes, &text, &offs, loss, lbits);
     } else if (mode == 5) {  // Float64 tree code (jit64.cpp): L2, another loss's tail, or per-row outputs
       CompiledBatch<double> cb = compile_batch<double>(*trees);
-      std::vector<int32_t> cand;
-      for (int t = 0; t < cb.ntrees; ++t)
-        if (cb.tree_off[t] >= 0 && cb.need[t] <= kShallowSlots && !cb.expr[t]) cand.push_back(t);
       jit::Opts64 o;
       o.out = out_mode;
       o.loss = out_mode ? SRHIP_LOSS_L2 : loss;
       o.lparam = lbits;
-      jit::compile_only64(cb, cand, &bytes, &text, &offs, o);
+      jit::compile_only64(cb, candidates(cb, true), &bytes, &text, &offs, o);
     } else if (mode == 2) {  // gradient tree code
       CompiledBatch<float> cb = compile_batch<float>(*trees, /*grad=*/true);
-      std::vector<int32_t> cand, coff(trees->const_off, trees->const_off + trees->ntrees + 1);
-      for (int t = 0; t < cb.ntrees; ++t)
-        if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
-      jit::compile_grad_only(cb, coff, cand, &bytes, &text, &offs, nullptr, loss, lbits);
+      const std::vector<int32_t> coff(trees->const_off, trees->const_off + trees->ntrees + 1);
+      jit::compile_grad_only(cb, coff, candidates(cb, false), &bytes, &text, &offs, nullptr, loss, lbits);
     } else {
       CompiledBatch<float> cb = compile_batch<float>(*trees);
-      std::vector<int32_t> cand;
-      for (int t = 0; t < cb.ntrees; ++t)
-        if (cb.tree_off[t] >= 0 && cb.need[t] <= kShallowSlots && !cb.expr[t]) cand.push_back(t);
       jit::Options jo;
       jo.fast = mode == 1 || mode == 4;
       jo.memc = mode == 3 || mode == 4;
@@ -3799,7 +3717,7 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
       jo.loss = loss;
       jo.lparam = lbits;
       jo.out = out_mode;
-      jit::compile_only(cb, cand, jo, &bytes, &text, &offs, nullptr);
+      jit::compile_only(cb, candidates(cb, true), jo, &bytes, &text, &offs, nullptr);
     }
     if ((int64_t)bytes.size() > *inout_nbytes || (int64_t)text.size() + 1 > *inout_ntext ||
         (int64_t)offs.size() > *inout_noffsets) {
@@ -4031,6 +3949,8 @@ struct EngineSet : copt::Set {
   DevBuf seg_idx, seg_rows;
   RowSegs<float> rs32;
   RowSegs<double> rs64;
+  RowSegs<float>& segs(float) { return rs32; }
+  RowSegs<double>& segs(double) { return rs64; }
   std::vector<double> wsums;  // Σ w over each member's sample
   EngineSet(srhip_ctx* c, srhip_dataset* d, const srhip_trees* trees, int dt, int ls, const double* pr,
             const std::vector<int32_t>& members, const int64_t* row_idx = nullptr, int64_t batch = 0)
@@ -4086,10 +4006,10 @@ struct EngineSet : copt::Set {
     const auto t0 = std::chrono::steady_clock::now();
     check_program_vs_dataset(ds, prog);
     {
-      std::lock_guard<std::mutex> lk(ctx->mu);
-      HIP_CHECK(hipSetDevice(ctx->device));
-      if (dtype == SRHIP_F32) rs32 = gather_row_sets<float>(ctx, ds, n, idx.data(), bs, nullptr, seg_idx, seg_rows);
-      else rs64 = gather_row_sets<double>(ctx, ds, n, idx.data(), bs, nullptr, seg_idx, seg_rows);
+      CALL_SCOPE(ctx);
+      by_dtype(dtype, [&](auto t) {
+        segs(t) = gather_row_sets<decltype(t)>(ctx, ds, n, idx.data(), bs, nullptr, seg_idx, seg_rows);
+      });
       HIP_CHECK(hipStreamSynchronize(ctx->stream));  // idx leaves scope
     }
     row_set_weight_sums(ds, n, idx.data(), bs, nullptr, wsums.data());
@@ -4098,16 +4018,14 @@ struct EngineSet : copt::Set {
   // loss (and ∂L/∂c) of every member on its gathered sample
   void eval_segments(bool grad, double* sums, double* dl, uint8_t* ok) {
     check_program_vs_dataset(ds, prog);  // as the public entry points: device, dtype, feature count, finite X
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIP_CHECK(hipSetDevice(ctx->device));
+    CALL_SCOPE(ctx);
     const double lp = params ? params[0] : 0.0;
-    if (dtype == SRHIP_F32) {
-      if (grad) run_grad<float>(ctx, prog, GRAD_LOSS, ds, loss, lp, nullptr, nullptr, 0, &rs32);
-      else run_eval<float>(ctx, prog, MODE_LOSS, rs32.X, rs32.y, rs32.w, bs, rs32.n_pad, ds->nfeat, loss, lp, nullptr, 0, rs32.seg);
-    } else {
-      if (grad) run_grad<double>(ctx, prog, GRAD_LOSS, ds, loss, lp, nullptr, nullptr, 0, &rs64);
-      else run_eval<double>(ctx, prog, MODE_LOSS, rs64.X, rs64.y, rs64.w, bs, rs64.n_pad, ds->nfeat, loss, lp, nullptr, 0, rs64.seg);
-    }
+    by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      const RowSegs<T>& rs = segs(t);
+      if (grad) run_grad<T>(ctx, prog, GRAD_LOSS, ds, loss, lp, nullptr, nullptr, 0, &rs);
+      else run_eval<T>(ctx, prog, MODE_LOSS, rs.X, rs.y, rs.w, bs, rs.n_pad, ds->nfeat, loss, lp, nullptr, 0, rs.seg);
+    });
     if (grad) collect_grad_results(ctx, prog, bs, sums, dl, ok);
     else collect_results(ctx, prog, bs, sums, ok);
   }
@@ -4206,11 +4124,10 @@ struct CallbackFactory : copt::Factory {
   }
 };
 
-}  // namespace
-
-int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
-                                       const srhip_constopt_options* opts, void* out_consts, double* out_loss,
-                                       uint8_t* out_converged, double* out_num_evals) {
+// srhip_optimize_constants_batch, and with row sets (row_idx [ntrees][batch_size]) _rowsets
+int32_t optimize_on_engine(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                           const srhip_constopt_options* opts, bool rowsets, const int64_t* row_idx, int64_t batch_size,
+                           void* out_consts, double* out_loss, uint8_t* out_converged, double* out_num_evals) {
   return guarded([&] {
     if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
     if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
@@ -4218,9 +4135,11 @@ int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const 
       throw Error(SRHIP_ERR_INVALID, "dataset has several targets: take a view of one (srhip_dataset_view)");
     check_loss(opts->loss_kind, opts->loss_params);
     check_expr_loss_weights(opts->loss_kind, ds->w != nullptr);
+    if (rowsets && batch_size < 1) throw Error(SRHIP_ERR_INVALID, "batch_size must be at least 1");
     t_copt = CoptProfile();
     const auto t0 = std::chrono::steady_clock::now();
     copt::Problem pb = make_problem(trees, ds->dtype);
+    if (rowsets) check_row_sets(ds, trees->ntrees, row_idx, batch_size);
     EngineFactory fac;
     fac.ctx = ctx ? ctx : ds->ctx;
     fac.ds = ds;
@@ -4228,6 +4147,8 @@ int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const 
     fac.dtype = ds->dtype;
     fac.loss = opts->loss_kind;
     fac.params = opts->loss_params;
+    fac.row_idx = rowsets ? row_idx : nullptr;
+    fac.batch_size = rowsets ? batch_size : 0;
     const copt::Result r = copt::optimize(pb, make_copt_options(opts), fac);
     write_result(r, ds->dtype, out_consts, out_loss, out_converged, out_num_evals, true);
     t_copt.total = secs_since(t0);
@@ -4235,36 +4156,21 @@ int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const 
   });
 }
 
+}  // namespace
+
+int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                       const srhip_constopt_options* opts, void* out_consts, double* out_loss,
+                                       uint8_t* out_converged, double* out_num_evals) {
+  return optimize_on_engine(ctx, ds, trees, opts, false, nullptr, 0, out_consts, out_loss, out_converged,
+                            out_num_evals);
+}
+
 int32_t srhip_optimize_constants_rowsets(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
                                          const srhip_constopt_options* opts, const int64_t* row_idx,
                                          int64_t batch_size, void* out_consts, double* out_loss,
                                          uint8_t* out_converged, double* out_num_evals) {
-  return guarded([&] {
-    if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
-    if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
-    if (ds->ntargets > 1)
-      throw Error(SRHIP_ERR_INVALID, "dataset has several targets: take a view of one (srhip_dataset_view)");
-    check_loss(opts->loss_kind, opts->loss_params);
-    check_expr_loss_weights(opts->loss_kind, ds->w != nullptr);
-    if (batch_size < 1) throw Error(SRHIP_ERR_INVALID, "batch_size must be at least 1");
-    t_copt = CoptProfile();
-    const auto t0 = std::chrono::steady_clock::now();
-    copt::Problem pb = make_problem(trees, ds->dtype);
-    check_row_sets(ds, trees->ntrees, row_idx, batch_size);
-    EngineFactory fac;
-    fac.ctx = ctx ? ctx : ds->ctx;
-    fac.ds = ds;
-    fac.trees = trees;
-    fac.dtype = ds->dtype;
-    fac.loss = opts->loss_kind;
-    fac.params = opts->loss_params;
-    fac.row_idx = row_idx;
-    fac.batch_size = batch_size;
-    const copt::Result r = copt::optimize(pb, make_copt_options(opts), fac);
-    write_result(r, ds->dtype, out_consts, out_loss, out_converged, out_num_evals, true);
-    t_copt.total = secs_since(t0);
-    return SRHIP_OK;
-  });
+  return optimize_on_engine(ctx, ds, trees, opts, true, row_idx, batch_size, out_consts, out_loss, out_converged,
+                            out_num_evals);
 }
 
 int32_t srhip_constopt_profile(double* out, int32_t n) {
@@ -4537,8 +4443,7 @@ void member_enqueue(srhip_group* g, int k, srhip_dataset* ds, srhip_program* p, 
                     int loss, const double* params, bool* recorded) {
   srhip_ctx* c = g->ctx[k];
   check_program_vs_dataset(ds, p);
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIP_CHECK(hipSetDevice(c->device));
+  CALL_SCOPE(c);
   const int nt = p->ntrees;
   const double wsum = ds->w ? ds->sum_w : (double)ds->rows;
   double* slot = g->slots + (size_t)k * g->slot_len;  // host address
@@ -4637,8 +4542,7 @@ void group_eval(srhip_group_dataset* gds, srhip_group_program* gp, bool grad, in
       cv.wait(lk, [&] { return left == 0; });
       if (failed) return;  // the caller drains every stream and reports the member's error
     }
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_CHECK(hipSetDevice(c->device));
+    CALL_SCOPE(c);
     for (int j = 1; j < ndev; ++j)
       if (recorded[j]) HIP_CHECK(hipStreamWaitEvent(c->stream, g->done[j], 0));
     HIP_CHECK(launch_combine_partials(g->d_slots0, g->slot_len, ndev, nt, nconst, grad ? gp->d_const_off[0] : nullptr,
@@ -4670,10 +4574,9 @@ void group_eval_checked(srhip_group_dataset* gds, srhip_group_program* gp, bool 
   if (gds->dtype != gp->dtype) throw Error(SRHIP_ERR_INVALID, "dataset and program dtypes differ");
   check_loss(loss_kind, loss_params);
   check_expr_loss_weights(loss_kind, gds->weighted);
-  if (gds->dtype == SRHIP_F32)
-    group_eval<float>(gds, gp, grad, loss_kind, loss_params, out_sum, out_dloss, out_wsum, out_ok);
-  else
-    group_eval<double>(gds, gp, grad, loss_kind, loss_params, out_sum, out_dloss, out_wsum, out_ok);
+  by_dtype(gds->dtype, [&](auto t) {
+    group_eval<decltype(t)>(gds, gp, grad, loss_kind, loss_params, out_sum, out_dloss, out_wsum, out_ok);
+  });
 }
 
 // The candidates of one evaluation set as a group program (EngineSet with the
