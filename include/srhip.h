@@ -34,7 +34,9 @@
  *    whose tile does not fit (from 79 features for the ordinary interpreter
  *    kernels, from 159 for every kernel) runs in the wide interpreter
  *    kernels, which read their feature operands from device memory, with no
- *    tree code. SRHIP_WIDE (environment, read per call; for tests and
+ *    tree code unless the program was created with
+ *    SRHIP_PROGRAM_WIDE_TREE_CODE (Float32 loss tree code that reads its
+ *    features from device memory, below). SRHIP_WIDE (environment, read per call; for tests and
  *    measurements): 1 runs every interpreter pass in the wide kernels and
  *    uses no tree code, 0 answers SRHIP_ERR_UNSUPPORTED for such a dataset
  *    ("row tile of N features does not fit in LDS") as the engine did before
@@ -335,6 +337,18 @@ int32_t srhip_program_create(srhip_ctx* ctx, int32_t dtype,
  * scored only on per-tree row sets, srhip_eval_loss_rowsets, which run in the
  * interpreter: a large batch then skips the code generation and load). */
 #define SRHIP_PROGRAM_INTERPRETED 2u
+/* SRHIP_PROGRAM_WIDE_TREE_CODE (opt-in): Float32 literal-constant loss tree
+ * code may read its features from X in device memory. When a tree-code
+ * candidate of the program reads a feature index >= 63 (past the LDS tile's
+ * reach) the program's loss code is built wide: its LDS tile holds y and w
+ * only, so it runs on a dataset of any width, and with the flag a program's
+ * tree code stays in use when an interpreter pass of the call has to run wide
+ * (without it such a call runs wholly in the wide interpreter). Per-row
+ * outputs, per-tree row sets and targets of a program with wide code run in
+ * the interpreter, and so does the program after srhip_program_set_constants.
+ * No effect on Float64 programs, with SRHIP_PROGRAM_INTERPRETED or with
+ * SRHIP_PROGRAM_VARYING_CONSTANTS (memory-constant code is never wide). */
+#define SRHIP_PROGRAM_WIDE_TREE_CODE 4u
 int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees* trees, uint32_t flags,
                                 srhip_program** out_prog);
 int32_t srhip_program_destroy(srhip_program* prog);
@@ -754,7 +768,9 @@ int32_t srhip_last_tree_code(const srhip_ctx* ctx, int32_t* out_ntrees);
  * bit 2 the per-row output code of srhip_eval_tree_array; bit 3: the trees
  * are Float64 (consts double) and go through the Float64 tree compiler; bit
  * 4: no assembly text — the multi-threaded code generation of the product
- * path, whose bytes must equal the text path's).
+ * path, whose bytes must equal the text path's; bit 5: wide loss code, whose
+ * features come from X in device memory (SRHIP_PROGRAM_WIDE_TREE_CODE;
+ * ignored with bits 1, 2 and 3)).
  * Returns the code bytes, their assembly text ('\n'-separated lines)
  * and, per compiled tree, (tree id, byte offset). Each inout_n* holds the
  * capacity on entry and the size on return; SRHIP_ERR_INVALID if too small. */
@@ -770,7 +786,8 @@ int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int
  * guarded FAST path) or the gradient tree code (grad = 1) of Float32 trees
  * for the elementwise loss `loss` (SRHIP_LOSS_*) with its parameter; fast
  * bit 3: Float64 trees through the Float64 tree compiler with that loss's
- * routine in the tile tail, or with grad = 1 their gradient tree code. SRHIP_ERR_UNSUPPORTED when Float32 tree code has no routine for that
+ * routine in the tile tail, or with grad = 1 their gradient tree code; fast
+ * bit 5 (grad = 0, Float32): wide loss code. SRHIP_ERR_UNSUPPORTED when Float32 tree code has no routine for that
  * loss (a Float64 tree without one is not compiled). The margin losses have
  * Float32 loss tree code only: grad = 1 or fast bit 3 with one of them is
  * SRHIP_ERR_UNSUPPORTED, and those calls run in the interpreter. */

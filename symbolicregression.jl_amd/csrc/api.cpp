@@ -327,6 +327,9 @@ struct srhip_program {
   // over every row of the call; jit_wanted's 256-tree bar is for the cost of loading a code object
   // per program, which this program pays once and keeps)
   bool jit_forced = false;
+  // SRHIP_PROGRAM_WIDE_TREE_CODE: literal loss tree code may be built wide (jit::Options::xg) and
+  // stays in use on a dataset whose interpreter passes run wide (run_eval)
+  bool wide_tc = false;
   // gradient tree code allowed (the rerun of Periodic's handed-back trees: none)
   bool gjit_allowed = true;
   // the gradient programs were built by a call on per-tree row sets, without tree code
@@ -1181,6 +1184,8 @@ void build_program(srhip_program* p) {
       jit::Options jo;
       jo.fast = jit_fast_enabled();
       jo.memc = p->jit_memc || env_is1("SRHIP_JIT_MEMC");  // read per build: tests
+      // wide code when a candidate reads a feature past the LDS tile's reach (features 0 .. 62)
+      jo.xg = p->wide_tc && !jo.memc && jit::max_feature_read(cb, a) >= 63;
       p->jit = jit::build(cb, a, jl, rest, jo, &p->jit_stats);
       if (p->jit) {
         p->nlist_j = (int)jl.size();
@@ -1254,7 +1259,8 @@ void build_program_f32(srhip_program* p) { build_program<float>(p); }
 // patched at the next gradient call); a changed layout rebuilds.
 template <typename T>
 void update_constants(srhip_program* p) {
-  if (p->jit64) {  // Float64 tree code holds its constants as literals: interpreted from now on
+  // (wide Float32 code likewise: memory-constant code keeps its constants where wide code's column base lives)
+  if (p->jit64 || jit::xg(p->jit)) {  // Float64 tree code holds its constants as literals: interpreted from now on
     p->jit_allowed = false;
     ++p->n_rebuild;
     const bool had_grad = p->grad_built;
@@ -1518,6 +1524,7 @@ jit::Module* loss_module(const srhip_program* p, int loss, double lparam) {
   jit::Options jo;
   jo.fast = jit_fast_enabled();
   jo.memc = jit::memc(p->jit);
+  jo.xg = jit::xg(p->jit);
   jo.loss = loss;
   jo.lparam = bits_of(lparam);
   return lazy_module<float, jit::Module>(
@@ -1563,7 +1570,7 @@ jit::Module64* module64(const srhip_program* p, int kind, double lparam) {
 jit::Module* out_module(const srhip_program* p) {
   if (!p->jit || p->nlist_j == 0) return nullptr;
   static const bool on = env_on("SRHIP_JIT_OUT");
-  if (!on) return nullptr;
+  if (!on || jit::xg(p->jit)) return nullptr;  // (no wide per-row output code)
   jit::Options jo;
   jo.fast = false;
   jo.memc = jit::memc(p->jit);
@@ -1798,6 +1805,11 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
   jit::Module* jm = (!std::is_same<T, float>::value || seg > 0 || wm == 1 || tgt) ? nullptr
                     : mode == MODE_LOSS                                     ? loss_module(p, loss, lparam)
                                                                             : out_module(p);
+  // wide code addresses a feature's column with a 32-bit stride: none for a longer column
+  if (jm && jit::xg(jm) && (uint64_t)n_pad * 4u > 0xffffffffu) jm = nullptr;
+  // SRHIP_PROGRAM_WIDE_TREE_CODE: literal loss tree code stays in use when an interpreter pass
+  // of the call runs wide (each pass follows its own plan, plan_interp)
+  const bool keep_tc = jm && p->wide_tc && mode == MODE_LOSS && !jit::memc(jm) && wm != 0;
   // Float64 programs: their tree code (this loss, or per-row outputs)
   jit::Module64* jm64 = nullptr;
   if constexpr (std::is_same<T, double>::value)
@@ -1814,7 +1826,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
       return true;
     }
     const jit::Columns& jc = jit::columns(jm);
-    if (jc.nraw > nfeat) throw Error(SRHIP_ERR_INVALID, "dataset has fewer features than the program reads");
+    if (std::max(jc.nraw, jc.xfeat) > nfeat) throw Error(SRHIP_ERR_INVALID, "dataset has fewer features than the program reads");
     const int narr = 1 + jc.nraw + jc.nder + (w ? 1 : 0);
     // partials go to global memory: LDS holds the tiles (1 byte per slot keeps the slot bound away)
     // 16384 workgroups of 4 waves, >= 64 trees per group (16 per wave): config #2 kernel
@@ -1838,10 +1850,11 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
   std::vector<EvalPlan> tc_plans;
   if ((jm || jm64) && rows > 0 && p->nlist_j > 0) {
     EvalPlan ip;
-    bool fits = (p->nlist_a == p->nlist_j ||
-                 plan_eval(p->dtype, false, p->opset, mode, w != nullptr, nfeat, rows, p->nlist_a - p->nlist_j, &ip)) &&
-                (p->nlist_b == 0 || plan_eval(p->dtype, true, p->has_expr ? (int)OPSET_EXPR : (int)OPSET_FULL, mode,
-                                              w != nullptr, nfeat, rows, p->nlist_b, &ip));
+    bool fits = keep_tc ||
+                ((p->nlist_a == p->nlist_j ||
+                  plan_eval(p->dtype, false, p->opset, mode, w != nullptr, nfeat, rows, p->nlist_a - p->nlist_j, &ip)) &&
+                 (p->nlist_b == 0 || plan_eval(p->dtype, true, p->has_expr ? (int)OPSET_EXPR : (int)OPSET_FULL, mode,
+                                               w != nullptr, nfeat, rows, p->nlist_b, &ip)));
     const int np = jm ? jit::nparts(jm) : jit::nparts64(jm64);
     for (int k = 0; k < np && fits; ++k) {
       int s0, nsl;
@@ -1978,7 +1991,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
         }
         // the shared subtrees of this call, once per row, before the first part
         // (inside the timed region: their cost is the call's)
-        const float* gcols = nullptr;
+        const float* gcols = jc.xg ? X : nullptr;  // wide code reads X itself as its columns
         if (jc.ngcol > 0) {
           if (launches[li].part == 0) derive_shared(c, p->shared, p->shared_keys, jc, X, rows, n_pad, nfeat);
           gcols = static_cast<const float*>(c->gderived.p);
@@ -3267,7 +3280,7 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
     *out_prog = nullptr;
     if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
     if (trees->ntrees < 0) throw Error(SRHIP_ERR_INVALID, "negative tree count");
-    if (flags & ~(SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED))
+    if (flags & ~(SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED | SRHIP_PROGRAM_WIDE_TREE_CODE))
       throw Error(SRHIP_ERR_INVALID, "unknown program flags");
     const int nt = trees->ntrees;
     auto* p = new srhip_program();
@@ -3276,6 +3289,7 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
     p->ntrees = nt;
     p->jit_memc = (flags & SRHIP_PROGRAM_VARYING_CONSTANTS) != 0;
     if (flags & SRHIP_PROGRAM_INTERPRETED) p->jit_allowed = false;
+    p->wide_tc = (flags & SRHIP_PROGRAM_WIDE_TREE_CODE) != 0 && dtype == SRHIP_F32;
     try {
       if (nt > 0) {
         if (!trees->node_off || !trees->const_off) throw Error(SRHIP_ERR_INVALID, "null offsets");
@@ -3673,7 +3687,8 @@ std::vector<int32_t> candidates(const CompiledBatch<T>& cb, bool shallow) {
 
 int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes, int64_t* inout_nbytes,
                          char* out_text, int64_t* inout_ntext, int32_t* out_offsets, int64_t* inout_noffsets,
-                         int loss = SRHIP_LOSS_L2, double lparam = 0.0, bool out_mode = false, bool notext = false) {
+                         int loss = SRHIP_LOSS_L2, double lparam = 0.0, bool out_mode = false, bool notext = false,
+                         bool wide = false) {
   return guarded([&] {
     if (!trees || !inout_nbytes || !inout_ntext || !inout_noffsets) throw Error(SRHIP_ERR_INVALID, "null argument");
     if (!jit::available()) throw Error(SRHIP_ERR_UNSUPPORTED, std::string("tree compiler: ") + jit::unavailable_reason());
@@ -3717,6 +3732,7 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
       jo.loss = loss;
       jo.lparam = lbits;
       jo.out = out_mode;
+      jo.xg = wide;
       jit::compile_only(cb, candidates(cb, true), jo, &bytes, &text, &offs, nullptr);
     }
     if ((int64_t)bytes.size() > *inout_nbytes || (int64_t)text.size() + 1 > *inout_ntext ||
@@ -3741,13 +3757,14 @@ int32_t srhip_jit_compile(const srhip_trees* trees, int32_t fast, uint8_t* out_b
                           char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
                           int64_t* inout_noffsets) {
   // fast: bit 0 the FAST path, bit 1 memory-constant code (mode 3 / 4 below),
-  // bit 2 per-row output code, bit 3 Float64 trees (jit64.cpp; the other bits ignored)
+  // bit 2 per-row output code, bit 3 Float64 trees (jit64.cpp; the other bits ignored),
+  // bit 4 no assembly text, bit 5 wide code (jit::Options::xg; literal loss code only)
   if (fast & 8)  // Float64 trees (bit 2: their per-row output code)
     return jit_compile_hook(trees, 5, out_bytes, inout_nbytes, out_text, inout_ntext, out_offsets, inout_noffsets,
                             SRHIP_LOSS_L2, 0.0, (fast & 4) != 0);
   return jit_compile_hook(trees, (fast & 2) ? ((fast & 1) ? 4 : 3) : ((fast & 1) ? 1 : 0), out_bytes, inout_nbytes,
                           out_text, inout_ntext, out_offsets, inout_noffsets, SRHIP_LOSS_L2, 0.0, (fast & 4) != 0,
-                          (fast & 16) != 0);
+                          (fast & 16) != 0, (fast & 32) != 0);
 }
 
 int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int64_t* inout_nbytes,
@@ -3759,9 +3776,10 @@ int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int
 int32_t srhip_jit_compile_loss(const srhip_trees* trees, int32_t grad, int32_t fast, int32_t loss, double loss_param,
                                uint8_t* out_bytes, int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext,
                                int32_t* out_offsets, int64_t* inout_noffsets) {
-  // fast bit 3: the Float64 tree compiler (jit64.cpp) with this loss's tail, or with grad its gradient code
+  // fast bit 3: the Float64 tree compiler (jit64.cpp) with this loss's tail, or with grad its gradient code;
+  // bit 5: wide loss code (Float32 loss code only)
   return jit_compile_hook(trees, (fast & 8) ? (grad ? 6 : 5) : grad ? 2 : ((fast & 1) ? 1 : 0), out_bytes, inout_nbytes, out_text,
-                          inout_ntext, out_offsets, inout_noffsets, loss, loss_param);
+                          inout_ntext, out_offsets, inout_noffsets, loss, loss_param, false, false, (fast & 32) != 0);
 }
 
 namespace {

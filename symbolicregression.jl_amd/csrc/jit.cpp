@@ -388,6 +388,72 @@ struct Gen {
   static constexpr int S_GCOL = 36, S_GSTRIDE = 38;
   bool is_g(int v) const { return v >= gbase; }
 
+  // Wide code (Options::xg): every raw feature is a column of X in device
+  // memory, s[36:37] = X at this row group's first row, s38 = n_pad·4 (the
+  // driver passes gcols = X). The tree's features are numbered locally in
+  // first-use order (xfeat[k]: the dataset feature of local number k; the
+  // per-column tables are indexed by k, gbase = 0) and loaded in that order,
+  // each into a free register block, through a window: before operation i the
+  // features it reads are issued, then up to xdepth features ahead of it while
+  // more than kXReserve blocks stay free for values. A block is released at
+  // the feature's last use (release_x). Loads return in issue order, so a
+  // feature's wait is vmcnt(issued so far − 1 − its number), gnum counting the
+  // loads issued so far in the tile. A redone tile starts at L_tile again and
+  // with it the window.
+  bool xg = false;
+  std::vector<int> xfeat;
+  int xdepth = 0;
+  static constexpr int kXReserve = 2;
+  int free_blocks() const {
+    int n = 0;
+    for (int k = 0; k < NPOOL; ++k) n += pool_owner[k] == -1 ? 1 : 0;
+    return n;
+  }
+  // local numbers are first-use numbers: the largest one operation i (or the root, i = n) reads
+  int xneed(int i) const {
+    int m = -1;
+    auto use = [&](const Opnd& q) { if (q.k == O_X) m = std::max(m, q.v); };
+    if (i < (int)ops.size()) {
+      use(ops[i].a);
+      if (!ops[i].un) use(ops[i].b);
+    } else {
+      use(root);
+    }
+    return m;
+  }
+  bool xwindow(int i) {
+    const int need = xneed(i), nf = (int)feats.size();
+    const int must = std::max(gnum, need + 1);
+    // ahead of operation i: features first read after it (gdone − 1: the last one read before it)
+    const int ahead = std::min(nf, std::max(need, gdone - 1) + 1 + xdepth);
+    int upto = must;
+    for (int room = free_blocks() - (must - gnum); upto < ahead && room > kXReserve; --room) ++upto;
+    if (upto == gnum) return true;
+    as.vop2(VOP2_LSHLREV_B32, "v_lshlrev_b32_e32", VGT, K(2), VLANE4);  // lane·16
+    as.sop2(SOP2_LSHL_B32, "s_lshl_b32", 0, S(S_TILE), K(10));         // tile·1024
+    as.sop2(SOP2_ADD_U32, "s_add_u32", 0, S(S_GCOL), S(0));
+    as.sop2(SOP2_ADDC_U32, "s_addc_u32", 1, S(S_GCOL + 1), K(0));
+    for (; gnum < upto; ++gnum) {
+      const int k = free_block();
+      if (k < 0) { why = "register pool exhausted (feature window)"; return false; }
+      const uint32_t f = (uint32_t)xfeat[gnum];
+      int sb = 0;
+      if (f > 0) {
+        as.sop2(SOP2_MUL_I32, "s_mul_i32", 2, S(S_GSTRIDE), K(f));
+        as.sop2(SOP2_MUL_HI_U32, "s_mul_hi_u32", 3, S(S_GSTRIDE), K(f));
+        as.sop2(SOP2_ADD_U32, "s_add_u32", 2, S(0), S(2));
+        as.sop2(SOP2_ADDC_U32, "s_addc_u32", 3, S(1), S(3));
+        sb = 2;
+      }
+      as.global_load_dwordx4(VPOOL0 + R * k, VGT, sb, 0);
+      pool_owner[k] = 1000 + gnum;
+      xblk[gnum] = k;
+      gidx[gnum] = gnum;
+    }
+    gwaited = false;
+    return true;
+  }
+
   // SRHIP_JIT_TRIG_FULL=1 (tests): sin / cos through the complete compiled
   // routines instead of the hand-scheduled FAST bodies
   bool trig_full = false;
@@ -639,7 +705,7 @@ struct Gen {
         if (xinl[f]) pre.push_back(f);
       feats = pre;  // the features preloaded into register blocks at the tile start
     }
-    if ((int)feats.size() > NPOOL) { why = "more features than register blocks"; return false; }
+    if (!xg && (int)feats.size() > NPOOL) { why = "more features than register blocks"; return false; }
     for (int f : feats)
       if (!is_g(f) && (1 + f) * TILE * 4 + 3 * 4 * 64 > 65535) { why = "feature offset beyond the DS immediate"; return false; }
     next_call.assign(n + 1, n);
@@ -672,6 +738,12 @@ struct Gen {
       as.waitcnt_lgkm(nloads - 1 - li);
       waited = li + 1;
     }
+  }
+  // both operands of an operation; wide code waits once, for the later feature
+  void wait_for2(const IrOp& o) {
+    if (xg && !o.un && o.a.k == O_X && o.b.k == O_X && o.b.v > o.a.v) wait_for(o.b);
+    wait_for(o.a);
+    if (!o.un) wait_for(o.b);
   }
   void wait_all() {
     if (waited < nloads) {
@@ -802,8 +874,7 @@ struct Gen {
     if (o.krid >= 0) return emit_call_k(i);
     const int va_ = o.a.k == O_VAL ? o.a.v : -1;
     const int vb_ = (!o.un && o.b.k == O_VAL) ? o.b.v : -1;
-    wait_for(o.a);
-    if (!o.un) wait_for(o.b);
+    wait_for2(o);
     // routines keep B: a unary call leaves its owner there
     if (!evict(L_A, va_, vb_) || (!o.un && !evict(L_B, va_, vb_))) return false;
     // move the operands into A (lhs) and B (rhs)
@@ -928,8 +999,7 @@ struct Gen {
 
   bool emit_inline(int i) {
     IrOp& o = ops[i];
-    wait_for(o.a);
-    if (!o.un) wait_for(o.b);
+    wait_for2(o);
     const bool gcan = fast && o.taint && o.zs && !o.un && (o.op == SRHIP_BOP_ADD || o.op == SRHIP_BOP_SUB);
     const bool gmin = fast && o.taint && o.zs &&
                       ((!o.un && o.op == SRHIP_BOP_MUL) || (o.un && (o.op == SRHIP_UOP_SQUARE || o.op == SRHIP_UOP_CUBE)));
@@ -1045,6 +1115,23 @@ struct Gen {
   bool emit_tree(const std::vector<IrOp>& ir, const Opnd& rt) {
     ops = ir;
     root = rt;
+    if (xg) {  // local feature numbers, in first-use order (the order analyze() gives feats)
+      gbase = 0;
+      gprefetch = false;
+      xfeat.clear();
+      auto local = [&](Opnd& q) {
+        if (q.k != O_X) return;
+        size_t k = std::find(xfeat.begin(), xfeat.end(), q.v) - xfeat.begin();
+        if (k == xfeat.size()) xfeat.push_back(q.v);
+        q.v = (int)k;
+      };
+      for (IrOp& o : ops) {
+        local(o.a);
+        if (!o.un) local(o.b);
+      }
+      local(root);
+      if (xfeat.size() > 256) { why = "more than 256 distinct features"; return false; }
+    }
     if (!analyze()) return false;
     for (int k = 0; k < NPOOL; ++k) pool_owner[k] = -1;
     L_tile = as.label();
@@ -1081,10 +1168,11 @@ struct Gen {
     // the columns' load order
     gany = false;
     gnum = 0;
-    for (size_t j = 0; j < feats.size(); ++j) {
+    for (size_t j = 0; j < feats.size() && !xg; ++j) {
       xblk[feats[j]] = (int)j;
       if (is_g(feats[j])) { gany = true; gidx[feats[j]] = gnum++; }
     }
+    if (xg) gany = !feats.empty();  // blocks and load numbers are given as the window issues them (xwindow)
     if (gany && gprefetch) {
       L_reload = as.label();
       as.bind(L_reload);
@@ -1092,7 +1180,7 @@ struct Gen {
     }
     // ---- tile
     as.bind(L_tile);
-    if (gany && !gprefetch) emit_gloads();  // each tile issues its own column loads
+    if (gany && !gprefetch && !xg) emit_gloads();  // each tile issues its own column loads
     if (fast || has_trig) as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHKSAVE, V(VCHK));  // for a redo / bail
     if (g_can) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGCAN, K(0xbf800000u));   // -1
     if (g_min) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGMIN, K(0x3f800000u));   // 1
@@ -1106,24 +1194,30 @@ struct Gen {
       as.ds_read_b128(VY, VLANE, 0);
       ++nloads;
     }
-    for (size_t j = 0; j < feats.size(); ++j) {
+    for (size_t j = 0; j < feats.size() && !xg; ++j) {
       const int f = feats[j];
       pool_owner[j] = 1000 + f;
       if (is_g(f)) continue;  // in flight since the tile's column loads (emit_gloads)
       load_idx[f] = nloads++;
       as.ds_read_b128(VPOOL0 + R * (int)j, VLANE, (1 + f) * TILE * 4);
     }
-    gwaited = !gany;
+    gwaited = !gany || xg;
     gdone = 0;
+    if (xg) gnum = 0;
     std::fill(loc.begin(), loc.end(), (int)L_NONE);
     for (int i = 0; i < (int)ops.size(); ++i) {
+      if (xg && !xwindow(i)) return false;
       if (ops[i].rid >= 0) { if (!emit_call(i)) return false; }
       else if (!emit_inline(i)) return false;
     }
     // root value
     int rreg;
     if (root.k == O_VAL) rreg = reg_of_loc(loc[root.v]);
-    else if (root.k == O_X) { wait_for(root); rreg = VPOOL0 + R * xblk[root.v]; }
+    else if (root.k == O_X) {
+      if (xg && !xwindow((int)ops.size())) return false;
+      wait_for(root);
+      rreg = VPOOL0 + R * xblk[root.v];
+    }
     else {
       for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGT + e, memc ? S(creg(root)) : K(root.c));
       rreg = VGT;
@@ -1392,11 +1486,18 @@ struct Gen {
 
 }  // namespace
 
+// SRHIP_JIT_XDEPTH (read per build: A/B runs): how many features ahead of the
+// running operation wide code keeps in flight (Gen::xwindow), 0 .. 7
+static int xwindow_depth() {
+  const char* e = std::getenv("SRHIP_JIT_XDEPTH");
+  return e ? std::max(0, std::min(NPOOL - 1, std::atoi(e))) : 3;
+}
+
 // One tree: returns false (nothing appended) when it cannot be compiled.
 static bool gen_tree(const Ins<float>* prog, const Tmpl& T, bool fast_opt, bool text, std::vector<uint32_t>& out,
                      std::vector<std::string>* lines, uint64_t area_va, int32_t* off, bool* is_fast,
                      std::string* why, const DerivedMap& dm, bool memc, int loss = SRHIP_LOSS_L2,
-                     uint64_t lparam = 0, bool out_mode = false) {
+                     uint64_t lparam = 0, bool out_mode = false, bool xg = false) {
   std::vector<IrOp> ir;
   Opnd root;
   if (!build_ir(prog, ir, root, &dm)) { *why = "program not translatable"; return false; }
@@ -1418,7 +1519,11 @@ static bool gen_tree(const Ins<float>* prog, const Tmpl& T, bool fast_opt, bool 
     g.loss = loss;
     g.lparam = lparam;
     if (subst && attempt == 0) g.gbase = dm.gbase;
+    // wide code: the window's depth, then (the blocks it held ahead were the values') no look-ahead
+    g.xg = xg;
+    g.xdepth = attempt == 0 ? xwindow_depth() : 0;
     if (!g.emit_tree(ir, root)) {
+      if (xg && attempt == 0 && g.xdepth > 0) continue;
       if (subst && attempt == 0) {
         ir = ir0;
         root = root0;
@@ -1526,7 +1631,7 @@ static bool codegen_par(const CompiledBatch<float>& cb, const std::vector<int32_
     R& r = res[k];
     int32_t off;
     r.ok = cb.tree_off[t] >= 0 && gen_tree(&cb.code[cb.tree_off[t]], T, opt.fast, false, r.w, nullptr, T.area_va, &off,
-                                           &r.fast, &r.why, dm, opt.memc, opt.loss, opt.lparam, opt.out);
+                                           &r.fast, &r.why, dm, opt.memc, opt.loss, opt.lparam, opt.out, opt.xg);
   });
   size_t pos = words.size(), end = n;
   for (size_t k = 0; k < n; ++k) {
@@ -1547,7 +1652,7 @@ static bool codegen_par(const CompiledBatch<float>& cb, const std::vector<int32_
     std::string why;
     const int32_t t = cand[from + k];
     if (!gen_tree(&cb.code[cb.tree_off[t]], T, opt.fast, false, r.w, nullptr, T.area_va + r.start * 4, &off, &f, &why,
-                  dm, opt.memc, opt.loss, opt.lparam, opt.out) ||
+                  dm, opt.memc, opt.loss, opt.lparam, opt.out, opt.xg) ||
         r.w.size() != sz)
       same = false;
   });
@@ -1601,7 +1706,7 @@ static size_t codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>
     const size_t lbefore = lines ? lines->size() : 0;
     const bool okc = cb.tree_off[t] >= 0 &&
                      gen_tree(&cb.code[cb.tree_off[t]], T, opt.fast, opt.text, words, lines, T.area_va, &off, &f, &why, dm, opt.memc,
-                              opt.loss, opt.lparam, opt.out);
+                              opt.loss, opt.lparam, opt.out, opt.xg);
     if (okc && words.size() * 4 > T.area_bytes) {  // area full: the next part takes it
       words.resize(before);
       if (lines) lines->resize(lbefore);
@@ -1786,6 +1891,14 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
   static const int dtiles = [] { const char* e = std::getenv("SRHIP_JIT_DERIVE_TILES"); return e ? std::max(1, std::atoi(e)) : 4; }();
   const size_t tile_bytes = (size_t)dtiles * (size_t)(64 * SR_JIT_R) * sizeof(float);
   c.waves = choose_waves(raw_max({}));  // from the raw features before any substitution
+  if (opt.xg) {  // wide code: y and w in LDS, the features from X; no derived, no shared-subtree columns
+    c.xg = true;
+    c.xfeat = raw_max({});
+    // no feature is staged, so the narrow workgroup: 4 waves 4.24 ms against 4.40 at 8 (256 features,
+    // 4096 trees x 1M rows, a process each, alternated twice; profiles/wide_tree_code_timing.json)
+    c.waves = choose_waves(0);
+    return c;
+  }
   const size_t lds_wg = lds_per_workgroup(c.waves);
   const size_t budget = lds_wg - (part_global() ? 0 : std::min<size_t>(lds_wg / 8, 4096));
   while (true) {
@@ -1803,6 +1916,27 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
   return c;
 }
 
+int max_feature_read(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand) {
+  std::vector<IrOp> ir;
+  Opnd root;
+  int m = -1;
+  for (int32_t t : cand) {
+    if (cb.tree_off[t] < 0 || !build_ir(&cb.code[cb.tree_off[t]], ir, root)) continue;
+    for (const IrOp& o : ir) {
+      if (o.a.k == O_X) m = std::max(m, o.a.v);
+      if (!o.un && o.b.k == O_X) m = std::max(m, o.b.v);
+    }
+    if (root.k == O_X) m = std::max(m, root.v);
+  }
+  return m;
+}
+
+// wide code is literal-constant loss code: the option is dropped otherwise
+static Options checked(Options opt) {
+  if (opt.memc || opt.out) opt.xg = false;
+  return opt;
+}
+
 Columns plan_grad_columns(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand) {
   Columns c;
   c.nraw = kGradGbase;  // raw features stay below (the gradient code's DS immediates end at feature 62)
@@ -1813,8 +1947,9 @@ Columns plan_grad_columns(const CompiledBatch<float>& cb, const std::vector<int3
   return c;
 }
 
-bool compile_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand, const Options& opt,
+bool compile_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand, const Options& opt_in,
                   std::vector<uint8_t>* bytes, std::string* text, std::vector<int32_t>* offsets, Stats* st) {
+  const Options opt = checked(opt_in);
   const Templates& TT = templates();
   if (!TT.ok) throw Error(SRHIP_ERR_UNSUPPORTED, std::string("jit templates unavailable: ") + TT.why);
   std::vector<uint32_t> words;
@@ -1841,7 +1976,8 @@ bool compile_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& ca
 }
 
 Module* build(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand, std::vector<int32_t>& jit_list,
-              std::vector<int32_t>& rest, const Options& opt, Stats* st) {
+              std::vector<int32_t>& rest, const Options& opt_in, Stats* st) {
+  const Options opt = checked(opt_in);
   const Templates& TT = templates();
   if (!TT.ok) { rest = cand; return nullptr; }
   auto t0 = std::chrono::steady_clock::now();
@@ -1951,6 +2087,7 @@ void destroy(Module* m) {
 uint32_t* bail_flags(Module* m) { return m->d_bail; }
 const Columns& columns(const Module* m) { return m->cols; }
 bool memc(const Module* m) { return m && m->memc; }
+bool xg(const Module* m) { return m && m->cols.xg; }
 int nslots(const Module* m) { return m->nslots; }
 int nparts(const Module* m) { return m ? (int)m->parts.size() : 0; }
 void part(const Module* m, int k, int* slot0, int* nslots) {
@@ -2047,8 +2184,8 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
   ja.dcols = dcols;
   // shared-subtree columns: tree code reads them (jit_template.hip passes
   // s[36:37] = gcols + row0, s38 = n_pad·4)
-  if (m->cols.ngcol > 0 && (!gcols || (uint64_t)a.n_pad * 4u > 0xffffffffu)) return hipErrorInvalidValue;
-  ja.gcols = m->cols.ngcol > 0 ? gcols : nullptr;
+  if ((m->cols.ngcol > 0 || m->cols.xg) && (!gcols || (uint64_t)a.n_pad * 4u > 0xffffffffu)) return hipErrorInvalidValue;
+  ja.gcols = (m->cols.ngcol > 0 || m->cols.xg) ? gcols : nullptr;  // wide code: the caller passes X
   ja.nbig = plan.nbig >= 0 ? plan.nbig : a.nrg;
   ja.ts = plan.nbig >= 0 ? plan.ts : plan.ntiles;
   // Sticky PRECISE per tree across row groups (prefetching hand-written loop):
@@ -2096,7 +2233,7 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
       ja.rot_nrg = mode == 2 ? a.nrg : resident;
     }
   }
-  if (ja.nraw > a.nfeat) return hipErrorInvalidValue;
+  if ((m->cols.xg ? m->cols.xfeat : ja.nraw) > a.nfeat) return hipErrorInvalidValue;
   if (ja.nbig > a.nrg || ja.ts < 1 || ja.ts > plan.ntiles) return hipErrorInvalidValue;
   // partials in LDS when they take little room next to the tiles (measured
   // faster on config #2: one coalesced write-out instead of a store per tree)

@@ -32,6 +32,13 @@ struct Options {
   // PRECISE routines only (the interpreter's values, bit for bit), every tile
   // evaluated whatever fails (the interpreter's MODE_OUT writes them too)
   bool out = false;
+  // wide loss tree code: the trees' raw features are read from X in device
+  // memory (one global load per feature per tile, through a bounded window of
+  // register blocks) and the LDS tile holds y and w only, so the feature
+  // index is not bound by the DS immediate (features 0 .. 65535) nor the
+  // dataset's width by LDS. Literal-constant loss code only (ignored with
+  // memc or out); no derived and no shared-subtree columns.
+  bool xg = false;
 };
 
 // Derived columns: a routine unary operator applied to a dataset feature,
@@ -60,11 +67,17 @@ struct Columns {
   std::vector<uint8_t> gkind;    // postfix node streams of the subtrees (SRHIP_NODE_*, raw features)
   std::vector<uint16_t> garg;
   std::vector<int32_t> goff;     // [ngcol + 1]
+  bool xg = false;               // wide code (Options::xg): nraw = nder = ngcol = 0, features read from X
+  int xfeat = 0;                 // wide code: the largest feature it reads + 1
   int gbase() const { return nraw + nder; }
 };
 const Columns& columns(const Module* m);
 // the module's tree code reads its constants from the device programs
 bool memc(const Module* m);
+// the module is wide loss tree code (Options::xg)
+bool xg(const Module* m);
+// the largest feature index the candidates' code reads (-1: none)
+int max_feature_read(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand);
 // waves per workgroup of the loss tree code for a batch whose code reads
 // `nraw` raw features: 8 from 10 features on (twice the LDS per workgroup, so
 // a wide row tile still fits four times; config #5's shard 20.26 -> 17.10 ms,

@@ -326,11 +326,16 @@ end
 # from the start (SRHIP_PROGRAM_VARYING_CONSTANTS: no recompile on a new set)
 const PROGRAM_VARYING_CONSTANTS = UInt32(1)
 const PROGRAM_INTERPRETED = UInt32(2)  # no loss / output tree code (per-tree row sets, per-tree targets)
+# wide_tree_code (opt-in): Float32 literal-constant loss tree code may read its
+# features from X in device memory (SRHIP_PROGRAM_WIDE_TREE_CODE), so trees that
+# read features from index 63 on and datasets too wide for LDS keep tree code
+const PROGRAM_WIDE_TREE_CODE = UInt32(4)
 function Program(trees::AbstractVector{Node{T}}, options::Options, device::Int=0;
-                 varying_constants::Bool=false) where {T}
+                 varying_constants::Bool=false, wide_tree_code::Bool=false) where {T}
     node_off, kind, arg, const_off, consts = flatten(trees, options)
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    flags = varying_constants ? PROGRAM_VARYING_CONSTANTS : UInt32(0)
+    flags = (varying_constants ? PROGRAM_VARYING_CONSTANTS : UInt32(0)) |
+            (wide_tree_code ? PROGRAM_WIDE_TREE_CODE : UInt32(0))
     GC.@preserve node_off kind arg const_off consts begin
         tr = Ref(SrhipTrees(Int32(length(trees)), pointer(node_off), pointer(kind), pointer(arg),
                             pointer(const_off), Ptr{Cvoid}(pointer(consts))))
@@ -971,10 +976,11 @@ function free!(p::GroupProgram)
 end
 destroy(p::GroupProgram) = free!(p)
 function GroupProgram(trees::AbstractVector{Node{T}}, options::Options, group::DeviceGroup;
-                      varying_constants::Bool=false) where {T}
+                      varying_constants::Bool=false, wide_tree_code::Bool=false) where {T}
     node_off, kind, arg, const_off, consts = flatten(trees, options)
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    flags = varying_constants ? PROGRAM_VARYING_CONSTANTS : UInt32(0)
+    flags = (varying_constants ? PROGRAM_VARYING_CONSTANTS : UInt32(0)) |
+            (wide_tree_code ? PROGRAM_WIDE_TREE_CODE : UInt32(0))
     GC.@preserve node_off kind arg const_off consts begin
         tr = Ref(SrhipTrees(Int32(length(trees)), pointer(node_off), pointer(kind), pointer(arg),
                             pointer(const_off), Ptr{Cvoid}(pointer(consts))))

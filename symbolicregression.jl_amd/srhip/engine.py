@@ -214,10 +214,14 @@ class MultiDeviceDataset:
 class Program:
     """srhip_program: a compiled, device-resident batch of trees.
     varying_constants (SRHIP_PROGRAM_VARYING_CONSTANTS): the caller will set
-    new constants, so Float32 tree code reads them from memory from the start."""
+    new constants, so Float32 tree code reads them from memory from the start.
+    wide_tree_code (SRHIP_PROGRAM_WIDE_TREE_CODE, opt-in): Float32 literal-constant
+    loss tree code may read its features from X in device memory, so trees that
+    read features past the LDS tile's reach (index 63 on) and datasets too wide
+    for LDS keep their tree code."""
 
     def __init__(self, ctx: Context, flat: FlatTrees, dtype, varying_constants: bool = False,
-                 interpreted: bool = False):
+                 interpreted: bool = False, wide_tree_code: bool = False):
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self.flat = flat
@@ -234,7 +238,8 @@ class Program:
         h = C.c_void_p()
         check(lib().srhip_program_create_ex(ctx.handle, dtype_code(self.dtype), C.byref(tr),
                                             (K.PROGRAM_VARYING_CONSTANTS if varying_constants else 0)
-                                            | (K.PROGRAM_INTERPRETED if interpreted else 0), C.byref(h)))
+                                            | (K.PROGRAM_INTERPRETED if interpreted else 0)
+                                            | (K.PROGRAM_WIDE_TREE_CODE if wide_tree_code else 0), C.byref(h)))
         self.handle = h
         self.ntrees = flat.ntrees
 
@@ -476,9 +481,10 @@ class DeviceGroup:
 
         return self._adopt(GroupDataset(self, X, y, weights))
 
-    def program(self, flat: FlatTrees, dtype, flags: int = 0):
-        """A GroupProgram: the trees compiled on every member (flags: PROGRAM_*)."""
-        return self._adopt(GroupProgram(self, flat, dtype, flags))
+    def program(self, flat: FlatTrees, dtype, flags: int = 0, wide_tree_code: bool = False):
+        """A GroupProgram: the trees compiled on every member (flags: PROGRAM_*;
+        wide_tree_code: PROGRAM_WIDE_TREE_CODE among them)."""
+        return self._adopt(GroupProgram(self, flat, dtype, flags, wide_tree_code=wide_tree_code))
 
     def context(self, k: int) -> Context:
         """Member k's context, for the single-device calls of an island on device k."""
@@ -520,7 +526,9 @@ class DeviceGroup:
 class GroupProgram:
     """srhip_group_program: one identical program per member of a DeviceGroup."""
 
-    def __init__(self, group: DeviceGroup, flat: FlatTrees, dtype, flags: int = 0):
+    def __init__(self, group: DeviceGroup, flat: FlatTrees, dtype, flags: int = 0, wide_tree_code: bool = False):
+        if wide_tree_code:
+            flags = int(flags) | K.PROGRAM_WIDE_TREE_CODE
         if not isinstance(group, DeviceGroup):
             raise TypeError("group must be a DeviceGroup")
         if not isinstance(flat, FlatTrees):
@@ -600,13 +608,14 @@ def _trees_struct(flat: FlatTrees, consts: np.ndarray) -> Trees:
 
 
 def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bool = False, loss=None,
-                out: bool = False, text: bool = True):
+                out: bool = False, text: bool = True, wide: bool = False):
     """Tree compiler without a device (srhip_jit_compile, or with grad=True
     srhip_jit_compile_grad: the reverse-mode gradient tree code; memc: the
     memory-constant loss tree code; loss: a Loss other than L2, through
     srhip_jit_compile_loss; out: the per-row output code of
-    srhip_eval_tree_array): (code bytes, assembly text, {tree id: byte
-    offset})."""
+    srhip_eval_tree_array; wide: Float32 literal-constant loss code that
+    reads its features from X in device memory): (code bytes, assembly text,
+    {tree id: byte offset})."""
     f64 = np.dtype(flat.consts.dtype) == np.float64
     consts = np.ascontiguousarray(flat.consts, dtype=np.float64 if f64 else np.float32)
     tr = _trees_struct(flat, consts)
@@ -624,13 +633,14 @@ def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bo
             return lib().srhip_jit_compile(C.byref(tr), 8 | (4 if out else 0), bufs[0], C.byref(nb), bufs[1],
                                            C.byref(nt), bufs[2], C.byref(no))
         if loss is not None:
-            return lib().srhip_jit_compile_loss(C.byref(tr), int(grad), int(fast), int(loss.kind), float(loss.param),
+            return lib().srhip_jit_compile_loss(C.byref(tr), int(grad), int(fast) | (32 if wide and not grad else 0),
+                                                int(loss.kind), float(loss.param),
                                                 bufs[0], C.byref(nb), bufs[1], C.byref(nt), bufs[2], C.byref(no))
         if grad:
             return lib().srhip_jit_compile_grad(C.byref(tr), bufs[0], C.byref(nb), bufs[1], C.byref(nt), bufs[2],
                                                 C.byref(no))
         return lib().srhip_jit_compile(C.byref(tr), int(fast) | (2 if memc else 0) | (4 if out else 0) |
-                                       (0 if text else 16), bufs[0],
+                                       (0 if text else 16) | (32 if wide else 0), bufs[0],
                                        C.byref(nb), bufs[1],
                                        C.byref(nt), bufs[2], C.byref(no))
 

@@ -32,10 +32,12 @@ def _as_list(trees: TreeOrTrees) -> Tuple[List[Node], bool]:
     return list(trees), False
 
 
-def compile_trees(trees: Sequence[Node], options: Options, dtype, device: Optional[int] = None) -> Program:
-    """Flatten + compile + upload a batch of trees (srhip_program_create)."""
+def compile_trees(trees: Sequence[Node], options: Options, dtype, device: Optional[int] = None,
+                  wide_tree_code: bool = False) -> Program:
+    """Flatten + compile + upload a batch of trees (srhip_program_create; wide_tree_code:
+    SRHIP_PROGRAM_WIDE_TREE_CODE, see Program)."""
     ctx = get_context(device)
-    return Program(ctx, flatten(trees, options, dtype=dtype), dtype)
+    return Program(ctx, flatten(trees, options, dtype=dtype), dtype, wide_tree_code=wide_tree_code)
 
 
 # ---- eval_tree_array ----------------------------------------------------------------
