@@ -464,10 +464,12 @@ int32_t srhip_eval_loss_batch_rowsets_ctx(srhip_ctx* ctx, srhip_dataset* ds, con
  *     own whose row tile holds every column; the wide variant when that tile does
  *     not fit in LDS): srhip_last_tree_code gives 0. Callers with large batches
  *     per target score them on views, which run tree code.
- * Not in this version: fused gradients and fused constant optimisation
- * (srhip_eval_loss_grad, srhip_optimize_constants_batch take views); expression
- * losses in the fused calls; multi-target group datasets (a device group takes
- * one srhip_group_dataset per target). */
+ * Not in this version: fused gradients and fused constant optimisation through
+ * these scoring calls or the single-target entry points (srhip_eval_loss_grad and
+ * srhip_optimize_constants_batch take views): see srhip_eval_loss_grad_targets and
+ * srhip_optimize_constants_targets below, which carry a target per tree;
+ * expression losses in the fused calls; multi-target group datasets (a device
+ * group takes one srhip_group_dataset per target). */
 #define SRHIP_MAX_TARGETS 16
 /* Y: [ntargets][n] (target-major); W: NULL or [ntargets][n]. Rows [row_begin,row_end) as srhip_dataset_create. */
 int32_t srhip_dataset_create_multi(srhip_ctx* ctx, int32_t dtype, int32_t x_layout, const void* X, const void* Y,
@@ -531,6 +533,39 @@ int32_t srhip_eval_loss_grad_rowsets(srhip_dataset* ds, const srhip_program* pro
                                      double* out_loss_sum, double* out_dloss, double* out_weight_sum,
                                      uint8_t* out_ok);
 
+/* ---- constant gradients with a target per tree --------------------------------
+ * srhip_eval_loss_grad and srhip_eval_loss_grad_rowsets on a multi-target dataset
+ * (srhip_dataset_create_multi), tree t against column target[t]:
+ *   out_loss_sum[t], out_dloss[c], out_ok[t] mean what they mean for the plain call
+ *     with (y, w) = (Y[target[t]], W[target[t]]); a failed tree has a NaN sum and
+ *     NaN gradients;
+ *   out_weight_sum is [ntargets] (Σ w of every column) for srhip_eval_loss_grad_targets
+ *     and [ntrees] (Σ w of tree t's sample in its column) with row sets.
+ * Rules, all answered before any launch and before anything is written: those of
+ * srhip_eval_loss_targets (a null target with ntrees > 0 or a target outside
+ * 0..ntargets-1 is SRHIP_ERR_INVALID; an expression-loss handle is
+ * SRHIP_ERR_UNSUPPORTED: take a view) and, with row sets, those of
+ * srhip_eval_loss_grad_rowsets. A single-target dataset is accepted; its targets
+ * are all 0.
+ * Always the forward-mode interpreter, never gradient tree code
+ * (srhip_last_tree_code gives 0; none is built for such a call). Over all rows the
+ * kernel variants are their own ("grad_kernel_targets<float>",
+ * "grad_kernel_wide_targets<float>" and the double forms): the row tile holds every
+ * column of Y (and of W), and the wide variant runs when that tile does not fit in
+ * LDS. With one column an item's arithmetic is srhip_eval_loss_grad's in the
+ * interpreter, bit for bit. With row sets the gather takes each tree's rows from
+ * its own column and the launch is srhip_eval_loss_grad_rowsets' ("grad_kernel_seg<float>"
+ * and its kin): the results equal that call's on a view of target[t], bit for bit.
+ * Not in this version: expression losses; multi-target group datasets; staging
+ * only the columns that a launch's work items use (every column is staged). */
+int32_t srhip_eval_loss_grad_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                     const double* loss_params, const int32_t* target, double* out_loss_sum,
+                                     double* out_dloss, double* out_weight_sum, uint8_t* out_ok);
+int32_t srhip_eval_loss_grad_rowsets_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                             const double* loss_params, const int32_t* target,
+                                             const int64_t* row_idx, int64_t batch_size, double* out_loss_sum,
+                                             double* out_dloss, double* out_weight_sum, uint8_t* out_ok);
+
 /* Per-row constant gradients for few trees: out_grad is
  * [total consts][rows] (∂ŷ_i/∂c), out_value [ntrees][rows]. */
 int32_t srhip_eval_grad_tree_array(srhip_dataset* ds, const srhip_program* prog,
@@ -586,13 +621,40 @@ int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const 
  * srhip_optimize_constants_batch does: a caller that follows the reference's
  * convention (src/Mutate.jl:43) scales it by batch_size / n.
  * Not in this version: group datasets (srhip_group_optimize_constants); a
- * target per tree (take a view); one gather shared among all sets through a
- * segment indirection; row sets in srhip_optimize_constants_cb, whose evaluator
- * owns the rows. */
+ * target per tree through this call (a multi-target dataset is SRHIP_ERR_INVALID
+ * here: take a view, or use srhip_optimize_constants_targets); one gather shared
+ * among all sets through a segment indirection; row sets in
+ * srhip_optimize_constants_cb, whose evaluator owns the rows. */
 int32_t srhip_optimize_constants_rowsets(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
                                          const srhip_constopt_options* opts, const int64_t* row_idx,
                                          int64_t batch_size, void* out_consts, double* out_loss,
                                          uint8_t* out_converged, double* out_num_evals);
+/* srhip_optimize_constants_batch (row_idx NULL) or srhip_optimize_constants_rowsets
+ * (row_idx [ntrees][batch_size]) on a multi-target dataset, input tree t optimised
+ * against column target[t]: the populations of all outputs in one lockstep run.
+ * Every candidate of an evaluation set — straggler sets of a line search, the
+ * Nelder-Mead simplex programs and the final evaluation included — is scored
+ * against the column of its input tree: loss-only phases as srhip_eval_loss_targets /
+ * srhip_eval_loss_rowsets_targets, gradient phases as srhip_eval_loss_grad_targets /
+ * srhip_eval_loss_grad_rowsets_targets, and a candidate's loss and gradient are
+ * divided by the Σ w of its own column (of its sample in that column with row
+ * sets). The sets' programs are interpreted (no tree code). Outputs as
+ * srhip_optimize_constants_batch; srhip_constopt_profile counts these calls as it
+ * counts the others.
+ * Rules, answered before any launch and before anything is written: a null dataset
+ * or options, a null target with ntrees > 0, a target outside 0..ntargets-1, a
+ * negative batch_size, and with row_idx a batch_size < 1 or an index outside
+ * [0, rows) are SRHIP_ERR_INVALID; an expression-loss handle is
+ * SRHIP_ERR_UNSUPPORTED (take views). A single-target dataset is accepted; its
+ * targets are all 0.
+ * Not in this version: expression losses; multi-target group datasets; targets in
+ * srhip_optimize_constants_cb, whose evaluator owns the data; staging only the
+ * columns that a launch's work items use. */
+int32_t srhip_optimize_constants_targets(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                         const srhip_constopt_options* opts, const int32_t* target,
+                                         const int64_t* row_idx /* NULL: all rows */, int64_t batch_size,
+                                         void* out_consts, double* out_loss, uint8_t* out_converged,
+                                         double* out_num_evals);
 /* Where the last srhip_optimize_constants_batch call of this thread spent
  * its time: out[0..8] = total, program builds, set_constants, loss calls,
  * gradient calls, the kernels inside those calls (HIP events) — seconds —

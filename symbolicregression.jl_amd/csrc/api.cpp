@@ -2378,10 +2378,13 @@ int eval_tree_array_impl(srhip_dataset* ds, const srhip_program* p, void* out, u
 
 template <typename T>
 void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds, int loss, double lparam,
-              T* out_value, T* out_grad, int64_t out_stride, const RowSegs<T>* rs = nullptr) {
+              T* out_value, T* out_grad, int64_t out_stride, const RowSegs<T>* rs = nullptr,
+              const int32_t* tgt = nullptr, int ntgt = 0) {
   // rs (GRAD_LOSS): tree t on its own gathered sample, segment t of rs; the
   // interpreter, one work item per workgroup of one wave, no tree code
-  build_grad_program<T>(p, rs == nullptr);
+  // tgt (GRAD_LOSS, shared rows; device memory, per tree id): a target per tree; y / w
+  // are then ntgt columns. The interpreter only (grad_targets_*.hip), no tree code
+  build_grad_program<T>(p, rs == nullptr && tgt == nullptr);
   const T* const vX = rs ? rs->X : static_cast<const T*>(ds->X);
   const T* const vy = rs ? rs->y : static_cast<const T*>(ds->y);
   const T* const vw = rs ? rs->w : static_cast<const T*>(ds->w);
@@ -2399,7 +2402,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
   // interpreter items of the other trees follow
   bool use_gjit = false;
   if constexpr (std::is_same<T, float>::value) {
-    jit::GradModule* gm = (p->gjit && !rs && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
+    jit::GradModule* gm = (p->gjit && !rs && !tgt && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
                               ? grad_module(p, loss, lparam)
                               : nullptr;
     if (gm) {
@@ -2473,7 +2476,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
                                          p->d_gjit_cidx, p->ngjit_cidx, static_cast<double*>(c->dloss.p), s));
       }
     }
-  } else if (jit::GradModule64* gm = (p->gjit64 && !rs && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
+  } else if (jit::GradModule64* gm = (p->gjit64 && !rs && !tgt && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
                                          ? grad_module64(p, loss, lparam)
                                          : nullptr) {
     // Float64 gradient tree code: 128-row tiles of y, the features it reads, w
@@ -2543,10 +2546,11 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     int G = pass == 0 ? 1 : pass == 1 ? 2 : kGradG;
     EvalPlan plan;
     const int wm = wide_mode();
-    if (wm == 1 || !plan_grad(p->dtype, deep, G, mode, vw != nullptr, ds->nfeat, vrows, nitems, &plan)) {
+    const int ncol = tgt ? ntgt : 0;  // columns of y (and of w) in the row tile
+    if (wm == 1 || !plan_grad(p->dtype, deep, G, mode, vw != nullptr, ds->nfeat, vrows, nitems, &plan, ncol)) {
       // the wide variant: one configuration, kGradG tangents (a tree's tangents past its constants stay 0)
       G = kGradG;
-      if (wm == 0 || !plan_grad_wide(p->dtype, mode, vw != nullptr, vrows, nitems, &plan)) throw_lds(ds->nfeat);
+      if (wm == 0 || !plan_grad_wide(p->dtype, mode, vw != nullptr, vrows, nitems, &plan, ncol)) throw_lds(ds->nfeat);
     }
     if (seg > 0) {
       // per-tree row sets: the tiles and row groups of a dataset of vrows rows (the
@@ -2571,6 +2575,8 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     a.n = vrows;
     a.n_pad = vpad;
     a.seg = seg;
+    a.tgt = tgt;
+    a.ntgt = ncol;
     a.nfeat = ds->nfeat;
     a.ntiles = plan.ntiles;
     a.ntg = plan.ntg;
@@ -2590,6 +2596,9 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     if (seg > 0)
       note_kernel(plan.wide ? (sizeof(T) == 4 ? "grad_kernel_wide_seg<float>" : "grad_kernel_wide_seg<double>")
                             : (sizeof(T) == 4 ? "grad_kernel_seg<float>" : "grad_kernel_seg<double>"));
+    else if (tgt)
+      note_kernel(plan.wide ? (sizeof(T) == 4 ? "grad_kernel_wide_targets<float>" : "grad_kernel_wide_targets<double>")
+                            : (sizeof(T) == 4 ? "grad_kernel_targets<float>" : "grad_kernel_targets<double>"));
     else
       note_kernel(plan.wide ? (sizeof(T) == 4 ? "grad_kernel_wide<float>" : "grad_kernel_wide<double>")
                             : (sizeof(T) == 4 ? "grad_kernel<float>" : "grad_kernel<double>"));
@@ -2722,12 +2731,35 @@ int eval_loss_grad_impl(srhip_dataset* ds, srhip_program* p, int loss, const dou
 template <typename T>
 int eval_loss_grad_rowsets_impl(srhip_dataset* ds, srhip_program* p, int loss, const double* params,
                                 const int64_t* row_idx, int64_t bs, double* out_sum, double* out_dloss,
-                                double* out_wsum, uint8_t* out_ok) {
+                                double* out_wsum, uint8_t* out_ok, const int32_t* target = nullptr) {
+  // target (srhip_eval_loss_grad_rowsets_targets, checked by the caller): the gather takes
+  // tree t's y / w rows from column target[t]; the launch is the row-set one
   srhip_ctx* c = p->ctx;
-  const RowSegs<T> rs = gather_row_sets<T>(c, ds, p->ntrees, row_idx, bs, nullptr, c->scratch_idx, c->gather);
+  const RowSegs<T> rs = gather_row_sets<T>(c, ds, p->ntrees, row_idx, bs, target, c->scratch_idx, c->gather);
   run_grad<T>(c, p, GRAD_LOSS, ds, loss, params ? params[0] : 0.0, nullptr, nullptr, 0, &rs);
   collect_grad_results(c, p, bs, out_sum, out_dloss, out_ok);
-  if (out_wsum) row_set_weight_sums(ds, p->ntrees, row_idx, bs, nullptr, out_wsum);
+  if (out_wsum) row_set_weight_sums(ds, p->ntrees, row_idx, bs, target, out_wsum);
+  return SRHIP_OK;
+}
+
+// srhip_eval_loss_grad with tree t scored against column target[t] (checked by the
+// caller) of a multi-target dataset: the forward-mode interpreter with a row tile
+// of every column (run_grad tgt). No tree code. A single-target dataset has one column.
+template <typename T>
+int eval_loss_grad_targets_impl(srhip_dataset* ds, srhip_program* p, int loss, const double* params,
+                                const int32_t* target, double* out_sum, double* out_dloss, double* out_wsum,
+                                uint8_t* out_ok) {
+  srhip_ctx* c = p->ctx;
+  const int nt = p->ntrees;
+  c->tgt.ensure((size_t)std::max(nt, 1) * sizeof(int32_t));
+  if (nt > 0)
+    HIP_CHECK(hipMemcpyAsync(c->tgt.p, target, (size_t)nt * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  run_grad<T>(c, p, GRAD_LOSS, ds, loss, params ? params[0] : 0.0, nullptr, nullptr, 0, nullptr,
+              static_cast<const int32_t*>(c->tgt.p), ds->ntargets);
+  collect_grad_results(c, p, ds->rows, out_sum, out_dloss, out_ok);  // (the copy of target is ordered before its wait)
+  if (out_wsum)
+    for (int k = 0; k < ds->ntargets; ++k)
+      out_wsum[k] = !ds->w ? (double)ds->rows : (ds->ntargets > 1 ? ds->t_sum_w[(size_t)k] : ds->sum_w);
   return SRHIP_OK;
 }
 
@@ -3471,11 +3503,11 @@ int32_t srhip_eval_loss_batch_rowsets_ctx(srhip_ctx* ctx, srhip_dataset* ds, con
 }
 
 // the fused calls' own checks: table losses only, every target within the dataset's columns
-static void check_targets(const srhip_dataset* ds, const srhip_program* p, int32_t loss_kind, const int32_t* target) {
+static void check_targets(const srhip_dataset* ds, int ntrees, int32_t loss_kind, const int32_t* target) {
   if (loss_kind >= SRHIP_EXPR_LOSS_BEGIN)
     throw Error(SRHIP_ERR_UNSUPPORTED, "expression losses are not scored per target in this version: take views");
-  if (p->ntrees > 0 && !target) throw Error(SRHIP_ERR_INVALID, "target is NULL");
-  for (int t = 0; t < p->ntrees; ++t)
+  if (ntrees > 0 && !target) throw Error(SRHIP_ERR_INVALID, "target is NULL");
+  for (int t = 0; t < ntrees; ++t)
     if (target[t] < 0 || target[t] >= ds->ntargets)
       throw Error(SRHIP_ERR_INVALID, "target " + std::to_string(target[t]) + " of tree " + std::to_string(t) +
                                          " is outside 0.." + std::to_string(ds->ntargets - 1));
@@ -3487,7 +3519,7 @@ int32_t srhip_eval_loss_targets(srhip_dataset* ds, const srhip_program* prog, in
   return guarded([&] {
     check_program_vs_dataset(ds, prog, true);
     check_loss(loss_kind, loss_params);
-    check_targets(ds, prog, loss_kind, target);
+    check_targets(ds, prog->ntrees, loss_kind, target);
     CALL_SCOPE(prog->ctx);
     return by_dtype(ds->dtype, [&](auto t) {
       return eval_loss_targets_impl<decltype(t)>(ds, prog, loss_kind, loss_params, target, out_loss_sum, out_weight_sum,
@@ -3513,7 +3545,7 @@ int32_t srhip_eval_loss_rowsets_targets(srhip_dataset* ds, const srhip_program* 
   return guarded([&] {
     check_program_vs_dataset(ds, prog, true);
     check_loss(loss_kind, loss_params);
-    check_targets(ds, prog, loss_kind, target);
+    check_targets(ds, prog->ntrees, loss_kind, target);
     CALL_SCOPE(prog->ctx);
     return by_dtype(ds->dtype, [&](auto t) {
       return eval_loss_rowsets_impl<decltype(t)>(ds, prog, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
@@ -3562,6 +3594,40 @@ int32_t srhip_eval_loss_grad_rowsets(srhip_dataset* ds, const srhip_program* pro
     return by_dtype(ds->dtype, [&](auto t) {
       return eval_loss_grad_rowsets_impl<decltype(t)>(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
                                                       out_dloss, out_weight_sum, out_ok);
+    });
+  });
+}
+
+int32_t srhip_eval_loss_grad_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                     const double* loss_params, const int32_t* target, double* out_loss_sum,
+                                     double* out_dloss, double* out_weight_sum, uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog, true);
+    check_loss(loss_kind, loss_params);
+    check_targets(ds, prog->ntrees, loss_kind, target);
+    CALL_SCOPE(prog->ctx);
+    auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_grad_targets_impl<decltype(t)>(ds, p, loss_kind, loss_params, target, out_loss_sum, out_dloss,
+                                                      out_weight_sum, out_ok);
+    });
+  });
+}
+
+int32_t srhip_eval_loss_grad_rowsets_targets(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                             const double* loss_params, const int32_t* target,
+                                             const int64_t* row_idx, int64_t batch_size, double* out_loss_sum,
+                                             double* out_dloss, double* out_weight_sum, uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog, true);
+    check_loss(loss_kind, loss_params);
+    check_targets(ds, prog->ntrees, loss_kind, target);
+    check_row_sets(ds, prog->ntrees, row_idx, batch_size);  // before the gradient programs are built
+    CALL_SCOPE(prog->ctx);
+    auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_grad_rowsets_impl<decltype(t)>(ds, p, loss_kind, loss_params, row_idx, batch_size, out_loss_sum,
+                                                      out_dloss, out_weight_sum, out_ok, target);
     });
   });
 }
@@ -3970,16 +4036,28 @@ struct EngineSet : copt::Set {
   RowSegs<float>& segs(float) { return rs32; }
   RowSegs<double>& segs(double) { return rs64; }
   std::vector<double> wsums;  // Σ w over each member's sample
+  // a target per tree (srhip_optimize_constants_targets): member m is scored against
+  // column target[members[m]] of the dataset in every evaluation, through the fused
+  // calls (interpreter only); empty with fused == false: one y, one w
+  bool fused = false;
+  std::vector<int32_t> mtgt;
+  const int32_t* member_targets() const { return fused ? mtgt.data() : nullptr; }
   EngineSet(srhip_ctx* c, srhip_dataset* d, const srhip_trees* trees, int dt, int ls, const double* pr,
-            const std::vector<int32_t>& members, const int64_t* row_idx = nullptr, int64_t batch = 0)
-      : ctx(c), ds(d), dtype(dt), loss(ls), params(pr), bs(row_idx ? batch : 0) {
-    MemberTrees mt(trees, dt, members);
+            const std::vector<int32_t>& members, const int64_t* row_idx = nullptr, int64_t batch = 0,
+            const int32_t* target = nullptr)
+      : ctx(c), ds(d), dtype(dt), loss(ls), params(pr), bs(row_idx ? batch : 0), fused(target != nullptr) {
+    MemberTrees mt(trees, dt, members);  // (checks the members' range)
+    if (fused) {
+      mtgt.resize(std::max<size_t>(members.size(), 1), 0);
+      for (size_t m = 0; m < members.size(); ++m) mtgt[m] = target[members[m]];
+    }
     coff = mt.coff;
     const srhip_trees& tr = mt.tr;
     const auto t0 = std::chrono::steady_clock::now();
     // (row sets run in the interpreter: no tree code to build)
     check_rc(srhip_program_create_ex(
-        ctx, dtype, &tr, SRHIP_PROGRAM_VARYING_CONSTANTS | (bs > 0 ? SRHIP_PROGRAM_INTERPRETED : 0u), &prog));
+        ctx, dtype, &tr, SRHIP_PROGRAM_VARYING_CONSTANTS | ((bs > 0 || fused) ? SRHIP_PROGRAM_INTERPRETED : 0u),
+        &prog));
     t_copt.create += secs_since(t0);
     t_copt.ncreate += 1;
     if (bs > 0) {
@@ -4022,20 +4100,20 @@ struct EngineSet : copt::Set {
       std::copy(row_idx + (size_t)members[m] * bs, row_idx + (size_t)(members[m] + 1) * bs, idx.begin() + (size_t)m * bs);
     wsums.assign(std::max(n, 1), 0.0);
     const auto t0 = std::chrono::steady_clock::now();
-    check_program_vs_dataset(ds, prog);
+    check_program_vs_dataset(ds, prog, fused);
     {
       CALL_SCOPE(ctx);
       by_dtype(dtype, [&](auto t) {
-        segs(t) = gather_row_sets<decltype(t)>(ctx, ds, n, idx.data(), bs, nullptr, seg_idx, seg_rows);
+        segs(t) = gather_row_sets<decltype(t)>(ctx, ds, n, idx.data(), bs, member_targets(), seg_idx, seg_rows);
       });
       HIP_CHECK(hipStreamSynchronize(ctx->stream));  // idx leaves scope
     }
-    row_set_weight_sums(ds, n, idx.data(), bs, nullptr, wsums.data());
+    row_set_weight_sums(ds, n, idx.data(), bs, member_targets(), wsums.data());
     t_copt.gather += secs_since(t0);
   }
   // loss (and ∂L/∂c) of every member on its gathered sample
   void eval_segments(bool grad, double* sums, double* dl, uint8_t* ok) {
-    check_program_vs_dataset(ds, prog);  // as the public entry points: device, dtype, feature count, finite X
+    check_program_vs_dataset(ds, prog, fused);  // as the public entry points: device, dtype, feature count, finite X
     CALL_SCOPE(ctx);
     const double lp = params ? params[0] : 0.0;
     by_dtype(dtype, [&](auto t) {
@@ -4063,10 +4141,16 @@ struct EngineSet : copt::Set {
     std::vector<double> sums(std::max(n, 1)), dl(std::max<size_t>(nc, 1));
     std::vector<uint8_t> ok(std::max(n, 1));
     double wsum = 0.0;
+    std::vector<double> twsum(fused ? std::max(ds->ntargets, 1) : 0);  // Σ w per target
     t0 = std::chrono::steady_clock::now();
     if (bs > 0) {
       eval_segments(grad, sums.data(), dl.data(), ok.data());
       t_copt.nseg += 1;
+    } else if (fused && grad) {
+      check_rc(srhip_eval_loss_grad_targets(ds, prog, loss, params, mtgt.data(), sums.data(), dl.data(), twsum.data(),
+                                            ok.data()));
+    } else if (fused) {
+      check_rc(srhip_eval_loss_targets(ds, prog, loss, params, mtgt.data(), sums.data(), twsum.data(), ok.data()));
     } else if (grad) {
       check_rc(srhip_eval_loss_grad(ds, prog, loss, params, sums.data(), dl.data(), &wsum, ok.data()));
     } else {
@@ -4080,14 +4164,15 @@ struct EngineSet : copt::Set {
     }
     f.assign(n, 0.0);
     for (int t = 0; t < n; ++t) {
-      const double ws = bs > 0 ? wsums[t] : wsum;  // (row sets: Σ w of the member's own sample)
+      // (row sets: Σ w of the member's own sample; a target per tree: of the member's target)
+      const double ws = bs > 0 ? wsums[t] : fused ? twsum[(size_t)mtgt[t]] : wsum;
       const double v = sums[t] / ws;
       f[t] = (ok[t] && std::isfinite(v)) ? v : INFINITY;
     }
     if (grad) {
       g.assign(nc, 0.0);
       for (int t = 0; t < n; ++t) {
-        const double ws = bs > 0 ? wsums[t] : wsum;
+        const double ws = bs > 0 ? wsums[t] : fused ? twsum[(size_t)mtgt[t]] : wsum;
         for (int32_t j = coff[t]; j < coff[t + 1]; ++j) g[j] = ok[t] ? dl[j] / ws : NAN;
       }
     }
@@ -4102,9 +4187,11 @@ struct EngineFactory : copt::Factory {
   // srhip_optimize_constants_rowsets: [ntrees][batch_size], input tree t's sample
   const int64_t* row_idx = nullptr;
   int64_t batch_size = 0;
+  // srhip_optimize_constants_targets: [ntrees], input tree t's target
+  const int32_t* target = nullptr;
   std::unique_ptr<copt::Set> make(const std::vector<int32_t>& members) override {
     return std::unique_ptr<copt::Set>(
-        new EngineSet(ctx, ds, trees, dtype, loss, params, members, row_idx, batch_size));
+        new EngineSet(ctx, ds, trees, dtype, loss, params, members, row_idx, batch_size, target));
   }
 };
 
@@ -4142,14 +4229,19 @@ struct CallbackFactory : copt::Factory {
   }
 };
 
-// srhip_optimize_constants_batch, and with row sets (row_idx [ntrees][batch_size]) _rowsets
+// srhip_optimize_constants_batch, and with row sets (row_idx [ntrees][batch_size]) _rowsets;
+// targets: srhip_optimize_constants_targets (target [ntrees], a multi-target dataset allowed)
 int32_t optimize_on_engine(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
                            const srhip_constopt_options* opts, bool rowsets, const int64_t* row_idx, int64_t batch_size,
-                           void* out_consts, double* out_loss, uint8_t* out_converged, double* out_num_evals) {
+                           void* out_consts, double* out_loss, uint8_t* out_converged, double* out_num_evals,
+                           bool targets = false, const int32_t* target = nullptr) {
   return guarded([&] {
     if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
     if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
-    if (ds->ntargets > 1)
+    if (targets && opts->loss_kind >= SRHIP_EXPR_LOSS_BEGIN)
+      throw Error(SRHIP_ERR_UNSUPPORTED, "expression losses are not optimised per target in this version: take views");
+    if (targets && batch_size < 0) throw Error(SRHIP_ERR_INVALID, "negative batch size");
+    if (ds->ntargets > 1 && !targets)
       throw Error(SRHIP_ERR_INVALID, "dataset has several targets: take a view of one (srhip_dataset_view)");
     check_loss(opts->loss_kind, opts->loss_params);
     check_expr_loss_weights(opts->loss_kind, ds->w != nullptr);
@@ -4157,6 +4249,11 @@ int32_t optimize_on_engine(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees*
     t_copt = CoptProfile();
     const auto t0 = std::chrono::steady_clock::now();
     copt::Problem pb = make_problem(trees, ds->dtype);
+    static const int32_t no_trees = 0;  // (an empty batch: the sets still run fused)
+    if (targets) {
+      check_targets(ds, trees->ntrees, opts->loss_kind, target);
+      if (!target) target = &no_trees;
+    }
     if (rowsets) check_row_sets(ds, trees->ntrees, row_idx, batch_size);
     EngineFactory fac;
     fac.ctx = ctx ? ctx : ds->ctx;
@@ -4167,6 +4264,7 @@ int32_t optimize_on_engine(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees*
     fac.params = opts->loss_params;
     fac.row_idx = rowsets ? row_idx : nullptr;
     fac.batch_size = rowsets ? batch_size : 0;
+    fac.target = targets ? target : nullptr;
     const copt::Result r = copt::optimize(pb, make_copt_options(opts), fac);
     write_result(r, ds->dtype, out_consts, out_loss, out_converged, out_num_evals, true);
     t_copt.total = secs_since(t0);
@@ -4189,6 +4287,14 @@ int32_t srhip_optimize_constants_rowsets(srhip_ctx* ctx, srhip_dataset* ds, cons
                                          uint8_t* out_converged, double* out_num_evals) {
   return optimize_on_engine(ctx, ds, trees, opts, true, row_idx, batch_size, out_consts, out_loss, out_converged,
                             out_num_evals);
+}
+
+int32_t srhip_optimize_constants_targets(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                         const srhip_constopt_options* opts, const int32_t* target,
+                                         const int64_t* row_idx, int64_t batch_size, void* out_consts,
+                                         double* out_loss, uint8_t* out_converged, double* out_num_evals) {
+  return optimize_on_engine(ctx, ds, trees, opts, row_idx != nullptr, row_idx, batch_size, out_consts, out_loss,
+                            out_converged, out_num_evals, true, target);
 }
 
 int32_t srhip_constopt_profile(double* out, int32_t n) {

@@ -34,8 +34,16 @@ constexpr int kGradLossExpr = 2;
 // dataset of a.n rows, so an item's tiles, lane sums, shuffle tree and row-group
 // partials are the ones it has in a launch over such a dataset. A template
 // parameter: the instantiations without it keep their code.
-template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = false, bool SEG = false>
+//
+// TG: a target per tree (srhip_eval_loss_grad_targets; GRAD_LOSS only, never with
+// SEG: a row-set launch gathers each tree's own column into its segment). a.y / a.w
+// are a.ntgt columns, n_pad rows apart; the row tile stages all of them and a work
+// item reads column a.tgt[t] of its tree. With one column an item's arithmetic is
+// the plain kernel's. A template parameter, as SEG: the others keep their code.
+template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = false, bool SEG = false,
+          bool TG = false>
 __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
+  static_assert(!TG || (MODE == GRAD_LOSS && !SEG), "per-tree targets: table losses over shared rows");
   constexpr int S = 2 + G;
   constexpr int TILE = 64 * R;
   using V = typename V16<T>::type;
@@ -43,10 +51,11 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int rows = a.ntiles * TILE;
   const int nx = XG ? 0 : a.nfeat;  // feature arrays staged in LDS
-  const int narr = nx + (MODE == GRAD_LOSS ? (W ? 2 : 1) : MODE == kGradLossExpr ? (a.w ? 2 : 1) : 0);
+  const int ncol = TG ? a.ntgt : 1;  // columns of y (and of w)
+  const int narr = nx + (MODE == GRAD_LOSS ? ncol * (W ? 2 : 1) : MODE == kGradLossExpr ? (a.w ? 2 : 1) : 0);
   T* sX = reinterpret_cast<T*>(smem);
   T* sY = sX + (size_t)nx * rows;
-  T* sW = sY + rows;
+  T* sW = sY + (size_t)ncol * rows;
   T* sPart = sX + (size_t)narr * rows;
 
   const int rg = blockIdx.x / a.ntg;
@@ -61,6 +70,9 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
       const int arr = idx / vper;
       const int v = idx - arr * vper;
       const T* src = arr < nx ? a.X + (size_t)arr * a.n_pad : (arr == nx ? a.y : a.w);
+      if constexpr (TG) {  // columns of y, then of w, n_pad rows apart
+        if (arr >= nx) src = arr < nx + ncol ? a.y + (size_t)(arr - nx) * a.n_pad : a.w + (size_t)(arr - nx - ncol) * a.n_pad;
+      }
       reinterpret_cast<V*>(sX + (size_t)arr * rows)[v] = reinterpret_cast<const V*>(src + seg0 + row0)[v];
     }
     for (int i = threadIdx.x; i < a.tpb * S; i += blockDim.x) sPart[i] = T(0);
@@ -93,6 +105,8 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
     CIns<T>* p = const_prog(a.prog + __builtin_amdgcn_readfirstlane(a.tree_off[t]));
     const int cbase = __builtin_amdgcn_readfirstlane(a.const_off[t]);
     const int nc = __builtin_amdgcn_readfirstlane(a.const_off[t + 1]) - cbase;
+    int col = 0;  // this tree's column of the staged y (and w): wave-uniform, one scalar load per item
+    if constexpr (TG) col = __builtin_amdgcn_readfirstlane(a.tgt[t]) * rows;
     T acc[S];
 #pragma unroll
     for (int k = 0; k < S; ++k) acc[k] = T(0);  // [0] Σ w·ℓ, [1] marker, [2+j] Σ w·ℓ'·∂ŷ/∂c
@@ -115,8 +129,8 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
             store_rows<T, R>(a.out_grad + (size_t)(cbase + g0 + j) * a.out_stride + off, lane, d.d[j]);
       } else {
         T yv[R], wv[R];
-        lds_rows<T, R>(sY + tl * TILE, lane, yv);
-        if constexpr (W) lds_rows<T, R>(sW + tl * TILE, lane, wv);
+        lds_rows<T, R>(sY + col + tl * TILE, lane, yv);
+        if constexpr (W) lds_rows<T, R>(sW + col + tl * TILE, lane, wv);
         const int valid = (tl < nt_valid - 1) ? TILE : last_valid;
         if constexpr (MODE == kGradLossExpr) {
           if (a.w) lds_rows<T, R>(sW + tl * TILE, lane, wv);
@@ -157,16 +171,17 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
   for (int i = threadIdx.x; i < a.tpb * S; i += blockDim.x) dst[i] = sPart[i];
 }
 
-template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = false, bool SEG = false>
+template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = false, bool SEG = false,
+          bool TG = false>
 hipError_t launch_grad_one(const EvalPlan& plan, const GradArgs<T>& a, hipStream_t stream) {
   // raise the dynamic-LDS ceiling once per kernel instantiation: a function-
   // local static is initialised exactly once even with concurrent callers
   static const hipError_t attr_err = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&grad_kernel<T, R, D, MODE, W, G, SET, XG, SEG>), hipFuncAttributeMaxDynamicSharedMemorySize,
+      reinterpret_cast<const void*>(&grad_kernel<T, R, D, MODE, W, G, SET, XG, SEG, TG>), hipFuncAttributeMaxDynamicSharedMemorySize,
       160 * 1024);
   if (attr_err != hipSuccess) return attr_err;
   const unsigned grid = (unsigned)a.nrg * (unsigned)a.ntg;
-  hipLaunchKernelGGL((grad_kernel<T, R, D, MODE, W, G, SET, XG, SEG>), dim3(grid), dim3(plan.threads), plan.lds_bytes,
+  hipLaunchKernelGGL((grad_kernel<T, R, D, MODE, W, G, SET, XG, SEG, TG>), dim3(grid), dim3(plan.threads), plan.lds_bytes,
                      stream, a);
   return hipGetLastError();
 }
@@ -217,6 +232,40 @@ hipError_t launch_grad_all(const EvalPlan& plan, const GradArgs<T>& a, int mode,
   if (a.G == 1) return launch_grad_g<T, 1, SEG>(plan, a, mode, stream);
   if (a.G == 2) return launch_grad_g<T, 2, SEG>(plan, a, mode, stream);
   return launch_grad_g<T, kGradG, SEG>(plan, a, mode, stream);
+}
+
+// ---- a target per tree (grad_targets_f32.hip / grad_targets_f64.hip) ------------
+// GRAD_LOSS with a table loss only; weighted or not.
+template <typename T, int R, int D, int G, int SET, bool XG = false>
+hipError_t launch_grad_targets_rd(const EvalPlan& plan, const GradArgs<T>& a, hipStream_t stream) {
+  if (a.w) return launch_grad_one<T, R, D, GRAD_LOSS, true, G, SET, XG, false, true>(plan, a, stream);
+  return launch_grad_one<T, R, D, GRAD_LOSS, false, G, SET, XG, false, true>(plan, a, stream);
+}
+
+template <typename T, int G>
+hipError_t launch_grad_targets_g(const EvalPlan& plan, const GradArgs<T>& a, hipStream_t stream) {
+  constexpr int RS = sizeof(T) == 4 ? (G <= 2 ? 4 : 2) : 1;  // grad_R, shallow
+  if (plan.D == 4) {
+    if (a.opset == OPSET_BASIC) return launch_grad_targets_rd<T, RS, 4, G, OPSET_BASIC>(plan, a, stream);
+    return launch_grad_targets_rd<T, RS, 4, G, OPSET_FULL>(plan, a, stream);
+  }
+  if (a.opset == OPSET_EXPR) return launch_grad_targets_rd<T, 1, kMaxSlots, G, OPSET_EXPR>(plan, a, stream);
+  return launch_grad_targets_rd<T, 1, kMaxSlots, G, OPSET_FULL>(plan, a, stream);
+}
+
+// the variants of launch_grad_all that a per-tree-targets call reaches
+template <typename T>
+hipError_t launch_grad_targets_all(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
+  if (mode != GRAD_LOSS || a.loss >= SRHIP_EXPR_LOSS_BEGIN || a.seg > 0 || !a.tgt || a.ntgt < 1)
+    return hipErrorInvalidValue;
+  if (plan.wide) {
+    if (a.opset == OPSET_EXPR) return launch_grad_targets_rd<T, 1, kMaxSlots, kGradG, OPSET_EXPR, true>(plan, a, stream);
+    return launch_grad_targets_rd<T, 1, kMaxSlots, kGradG, OPSET_FULL, true>(plan, a, stream);
+  }
+  if (plan.D != 4) return launch_grad_targets_g<T, kGradG>(plan, a, stream);  // deep programs: one variant
+  if (a.G == 1) return launch_grad_targets_g<T, 1>(plan, a, stream);
+  if (a.G == 2) return launch_grad_targets_g<T, 2>(plan, a, stream);
+  return launch_grad_targets_g<T, kGradG>(plan, a, stream);
 }
 
 }  // namespace

@@ -60,15 +60,17 @@ __global__ void __launch_bounds__(256) grad_finalize_kernel(GradArgs<T> a, doubl
 }  // namespace
 
 bool plan_grad(int dtype, bool deep, int G, int mode, bool weighted, int nfeat, int64_t n, int nitems,
-               EvalPlan* p) {
+               EvalPlan* p, int ntgt) {
   const size_t esz = dtype == SRHIP_F32 ? 4 : 8;
-  const int narr = nfeat + (mode == GRAD_LOSS ? (weighted ? 2 : 1) : 0);
+  const int ncol = ntgt > 0 ? ntgt : 1;  // columns of y (and of w) in the tile
+  const int narr = nfeat + (mode == GRAD_LOSS ? ncol * (weighted ? 2 : 1) : 0);
   return plan_geometry(esz, grad_R(dtype, deep, G), deep ? kMaxSlots : 4, narr, (2 + G) * esz, n, nitems, p);
 }
 
-bool plan_grad_wide(int dtype, int mode, bool weighted, int64_t n, int nitems, EvalPlan* p) {
+bool plan_grad_wide(int dtype, int mode, bool weighted, int64_t n, int nitems, EvalPlan* p, int ntgt) {
   const size_t esz = dtype == SRHIP_F32 ? 4 : 8;
-  const int narr = mode == GRAD_LOSS ? (weighted ? 2 : 1) : 0;  // y, w: no feature array
+  const int ncol = ntgt > 0 ? ntgt : 1;
+  const int narr = mode == GRAD_LOSS ? ncol * (weighted ? 2 : 1) : 0;  // y, w: no feature array
   const bool ok = plan_geometry(esz, grad_R(dtype, true, kGradG), kMaxSlots, narr, (2 + kGradG) * esz, n, nitems, p);
   p->wide = true;
   return ok;
@@ -77,6 +79,7 @@ bool plan_grad_wide(int dtype, int mode, bool weighted, int64_t n, int nitems, E
 template <typename T>
 hipError_t launch_grad(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream) {
   if (a.seg > 0) return launch_grad_seg<T>(plan, a, mode, stream);  // grad_seg_f32.hip / grad_seg_f64.hip
+  if (a.tgt) return launch_grad_targets<T>(plan, a, mode, stream);  // grad_targets_f32.hip / grad_targets_f64.hip
   return launch_grad_all<T, false>(plan, a, mode, stream);
 }
 

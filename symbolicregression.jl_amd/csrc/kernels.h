@@ -131,17 +131,26 @@ struct GradArgs {
   // per-tree row sets (srhip_eval_loss_grad_rowsets; GRAD_LOSS, one item per workgroup: tpb = 1,
   // ntg = nitems): tree t reads rows [t·seg, t·seg + n) of X / y / w; 0 = shared rows
   int64_t seg = 0;
+  // per-tree targets (srhip_eval_loss_grad_targets; the TG variants of
+  // grad_targets_*.hip): tree id t is scored against column tgt[t] of y / w, which
+  // are then [ntgt][n_pad] (target-major); nullptr / 0: one y, one w
+  const int32_t* tgt = nullptr;
+  int ntgt = 0;
 };
 
+// ntgt > 0 (a per-tree-targets launch): the tile holds ntgt columns of y (and of w).
 bool plan_grad(int dtype, bool deep, int G, int mode, bool weighted, int nfeat, int64_t n,
-               int nitems, EvalPlan* plan);
+               int nitems, EvalPlan* plan, int ntgt = 0);
 // The wide plan: the deep configuration, kGradG tangents, no feature array in LDS.
-bool plan_grad_wide(int dtype, int mode, bool weighted, int64_t n, int nitems, EvalPlan* plan);
+bool plan_grad_wide(int dtype, int mode, bool weighted, int64_t n, int nitems, EvalPlan* plan, int ntgt = 0);
 template <typename T>
 hipError_t launch_grad(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream);
 // the per-tree row-set variants (a.seg > 0, GRAD_LOSS; launch_grad forwards to them)
 template <typename T>
 hipError_t launch_grad_seg(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream);
+// the per-tree-targets variants (a.tgt set, GRAD_LOSS, shared rows; launch_grad forwards to them)
+template <typename T>
+hipError_t launch_grad_targets(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream);
 template <typename T>
 hipError_t launch_grad_finalize(const GradArgs<T>& a, double* out_sum, uint8_t* out_ok,
                                 double* out_dloss, hipStream_t stream);

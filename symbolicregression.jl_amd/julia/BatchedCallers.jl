@@ -227,6 +227,61 @@ function optimize_constants_batched(dataset::Dataset{T}, members::AbstractVector
     return evals
 end
 
+# Members per call up to which optimize_constants_batched_multi runs the fused optimiser
+# by default (DESIGN.md §3.17, profiles/grad_targets_timing.json): the largest measured batch
+# at which all three fused medians lie below those of one call per output (4 × 256 members on
+# 100k rows: 274 ms against 362 ms); nothing larger was measured (`fused=true` forces it).
+const FUSED_CONSTOPT_MAX_MEMBERS = 1024
+
+"""
+    optimize_constants_batched_multi(datasets, js, members, options) -> num_evals::Vector{Float64}
+
+optimize_constants_batched for the members of several outputs of a multi-output search in ONE
+lockstep run: `members[i]` belongs to output `js[i]` and is optimised against `datasets[js[i]]`,
+the Datasets EquationSearch builds over one shared `X` (src/SymbolicRegression.jl:304-315,
+:459-494), uploaded once (SRHip.MultiCopy). A converged member's score uses
+`datasets[js[i]].baseline_loss`. `minibatch` as optimize_constants_batched. `fused` (default: up
+to FUSED_CONSTOPT_MAX_MEMBERS members) forces the fused run or the per-output calls. Outside the
+engine's coverage (`Unsupported`, or datasets that do not share their X):
+optimize_constants_batched per output.
+"""
+function optimize_constants_batched_multi(datasets::AbstractVector{<:Dataset{T}}, js::AbstractVector{<:Integer},
+                                          members::AbstractVector{<:PopMember{T}}, options::Options;
+                                          device::Int=0, minibatch::Bool=false,
+                                          fused::Union{Nothing,Bool}=nothing) where {T}
+    length(js) == length(members) || throw(ArgumentError("one output index per member"))
+    isempty(members) && return Float64[]
+    shared = all(d -> d.X === datasets[1].X && d.weighted == datasets[1].weighted, datasets)
+    use_fused = fused === nothing ? length(members) <= FUSED_CONSTOPT_MAX_MEMBERS : fused
+    if use_fused && shared && SRHip.enabled(options)
+        try
+            trees = Node{T}[m.tree for m in members]
+            sampled = minibatch && options.batching
+            n = datasets[1].n
+            row_idx = sampled ? rand(1:n, options.batch_size, length(trees)) : nothing  # column t: member t's sample
+            losses, converged, num_evals = SRHip.optimize_constants_targets!(trees, js, datasets, options;
+                                                                             device=device, row_idx=row_idx)
+            sampled && (num_evals = num_evals .* (options.batch_size / n))
+            for (m, l, c, j) in zip(members, losses, converged, js)
+                c || continue
+                m.score = loss_to_score(l, datasets[j].baseline_loss, m.tree, options)
+                m.loss = l
+                m.birth = get_birth_order(; deterministic=options.deterministic)
+            end
+            return num_evals
+        catch e
+            e isa SRHip.Unsupported || rethrow()
+        end
+    end
+    evals = zeros(Float64, length(members))
+    for j in unique(js)   # regroup by output, optimise, scatter back
+        sel = findall(==(j), js)
+        evals[sel] .= optimize_constants_batched(datasets[j], members[sel], options; device=device,
+                                                 minibatch=minibatch)
+    end
+    return evals
+end
+
 """
     optimize_and_simplify_population_batched(dataset, pop, options, curmaxsize, record) -> (pop, num_evals)
 

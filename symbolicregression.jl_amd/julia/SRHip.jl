@@ -752,6 +752,120 @@ function optimize_constants_batch!(trees::AbstractVector{Node{T}}, dataset::Data
     return T.(out_l), converged, out_n
 end
 
+# ---- gradients and constant optimisation with an output per tree --------------------
+"""
+    eval_loss_grad_targets(trees, js, datasets, options; device=0, idx=nothing) -> (losses, grads, ok)
+
+Loss and ∂loss/∂c of `trees[i]` against `datasets[js[i]]` (the outputs of one MultiCopy) for the
+members of several outputs in one call (srhip_eval_loss_grad_targets), each divided by the Σw of
+its own output. `idx` (batch_size, ntrees), column t the 1-based rows of trees[t]: every tree on
+its own sample (srhip_eval_loss_grad_rowsets_targets), divided by the sample's Σw. Expression
+losses are `Unsupported` here (the callers fall back to one call per output).
+"""
+function eval_loss_grad_targets(trees::AbstractVector{Node{T}}, js::AbstractVector{<:Integer},
+                                datasets::AbstractVector{<:Dataset{T}}, options::Options;
+                                device::Int=0,
+                                idx::Union{Nothing,AbstractMatrix{<:Integer}}=nothing) where {T}
+    nt = length(trees)
+    length(js) == nt || throw(ArgumentError("one output index per tree"))
+    idx === nothing || size(idx, 2) == nt || throw(ArgumentError("one row sample (column of idx) per tree"))
+    m = MultiCopy(datasets, device)
+    node_off, kind, arg, const_off, consts = flatten(trees, options)
+    ncon = Int(const_off[end])
+    sums = Vector{Float64}(undef, nt); ok = Vector{UInt8}(undef, nt)
+    wsum = Vector{Float64}(undef, idx === nothing ? length(datasets) : nt)
+    dloss = Vector{Float64}(undef, ncon)
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    target = Int32.(js .- 1)
+    rows = idx === nothing ? Matrix{Int64}(undef, 0, 0) : Matrix{Int64}(idx .- 1)
+    prog = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve node_off kind arg const_off consts sums ok wsum dloss params target rows m datasets begin
+        tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
+                            Ptr{Cvoid}(pointer(consts))))
+        # the fused calls run in the interpreter: no tree code to build
+        check(ccall((:srhip_program_create_ex, libsrhip), Int32,
+                    (Ptr{Cvoid}, Int32, Ref{SrhipTrees}, UInt32, Ptr{Ptr{Cvoid}}),
+                    context(device), dtype_code(T), tr, PROGRAM_INTERPRETED, prog))
+        try
+            if idx === nothing
+                check(ccall((:srhip_eval_loss_grad_targets, libsrhip), Int32,
+                            (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+                             Ptr{Float64}, Ptr{UInt8}),
+                            m.h, prog[], kindcode, params, target, sums, dloss, wsum, ok))
+            else
+                check(ccall((:srhip_eval_loss_grad_rowsets_targets, libsrhip), Int32,
+                            (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Int64}, Int64,
+                             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                            m.h, prog[], kindcode, params, target, rows, size(rows, 1), sums, dloss, wsum, ok))
+            end
+        finally
+            ccall((:srhip_program_destroy, libsrhip), Int32, (Ptr{Cvoid},), prog[])
+        end
+    end
+    ws = [idx === nothing ? wsum[js[i]] : wsum[i] for i in 1:nt]
+    losses = [ok[i] == 1 ? T(sums[i] / ws[i]) : T(Inf) for i in 1:nt]
+    grads = [dloss[(const_off[i] + 1):const_off[i + 1]] ./ ws[i] for i in 1:nt]
+    return losses, grads, ok .== 1
+end
+
+"""
+    optimize_constants_targets!(trees, js, datasets, options; device=0, row_idx=nothing)
+        -> (losses, converged, num_evals)
+
+optimize_constants_batch! for the members of several outputs in ONE lockstep run
+(srhip_optimize_constants_targets): `trees[i]` is optimised against `datasets[js[i]]` (the outputs
+of one MultiCopy). The start noise is drawn tree by tree, restart by restart, as
+optimize_constants_batch! draws it. `row_idx` as there. Expression losses are `Unsupported`.
+"""
+function optimize_constants_targets!(trees::AbstractVector{Node{T}}, js::AbstractVector{<:Integer},
+                                     datasets::AbstractVector{<:Dataset{T}}, options::Options;
+                                     device::Int=0,
+                                     row_idx::Union{Nothing,AbstractMatrix{<:Integer}}=nothing) where {T}
+    algo = options.optimizer_algorithm == "BFGS" ? OPT_BFGS :
+           options.optimizer_algorithm == "NelderMead" ? OPT_NELDERMEAD :
+           error("Optimization function not implemented.")
+    nt = length(trees)
+    length(js) == nt || throw(ArgumentError("one output index per tree"))
+    m = MultiCopy(datasets, device)
+    node_off, kind, arg, const_off, consts = flatten(trees, options)
+    nr = options.optimizer_nrestarts
+    noise = Float64[]
+    for i in 1:nt
+        nc = Int(const_off[i + 1] - const_off[i])
+        nc == 0 && continue
+        for _ in 1:nr
+            append!(noise, Float64.(randn(T, nc)))
+        end
+    end
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    target = Int32.(js .- 1)
+    out_c = similar(consts); out_l = Vector{Float64}(undef, nt)
+    out_k = Vector{UInt8}(undef, nt); out_n = Vector{Float64}(undef, nt)
+    if row_idx !== nothing
+        size(row_idx, 2) == nt || throw(ArgumentError("one row sample (column of row_idx) per tree"))
+    end
+    rows = row_idx === nothing ? Matrix{Int64}(undef, 0, 0) : Matrix{Int64}(row_idx .- 1)
+    GC.@preserve node_off kind arg const_off consts noise params target out_c out_l out_k out_n rows m datasets begin
+        tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
+                            Ptr{Cvoid}(pointer(consts))))
+        opts = Ref(ConstOptOptions(algo, Int32(options.optimizer_options.iterations), Int32(nr), kindcode,
+                                   pointer(params), pointer(noise), UInt64(0)))
+        check(ccall((:srhip_optimize_constants_targets, libsrhip), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Ref{ConstOptOptions}, Ptr{Int32}, Ptr{Int64}, Int64,
+                     Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}),
+                    context(device), m.h, tr, opts, target,
+                    row_idx === nothing ? Ptr{Int64}(C_NULL) : pointer(rows), size(rows, 1), out_c, out_l,
+                    out_k, out_n))
+    end
+    converged = out_k .== 1
+    for i in 1:nt
+        converged[i] && set_constants(trees[i], out_c[(const_off[i] + 1):const_off[i + 1]])
+    end
+    return T.(out_l), converged, out_n
+end
+
 # ---- eval_tree_array (src/InterfaceDynamicExpressions.jl:50-52) -------------------
 """
     eval_tree_array(tree, X, options) -> (output, did_succeed)

@@ -34,7 +34,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from ._lib import CONSTOPT_EVAL_FN, ConstOptOptions, check, lib
-from .dataset import Dataset, GroupDataset
+from .dataset import Dataset, GroupDataset, MultiDataset
 from .engine import _trees_struct
 from .node import Node, flatten, set_constants
 from .options import Options
@@ -83,7 +83,9 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
                              rng: Optional[np.random.Generator] = None, device: Optional[int] = None,
                              evaluator_factory: Optional[Callable] = None,
                              noise: Optional[np.ndarray] = None,
-                             row_idx: Optional[np.ndarray] = None) -> ConstOptResult:
+                             row_idx: Optional[np.ndarray] = None,
+                             targets: Optional[Sequence[int]] = None,
+                             fused: Optional[bool] = None) -> ConstOptResult:
     """`optimize_constants` for many trees at once. Trees are updated in place
     (constants of the best start when it converged, else left at x0).
     `noise` (default: drawn from `rng`) is the standard normal draws of the
@@ -95,7 +97,23 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
     those on the samples, num_evals counts evaluations as without it). Not on a
     GroupDataset. With `evaluator_factory` the evaluator owns the rows: a factory
     whose signature accepts `members=` is given the input tree index of each
-    candidate and picks their samples itself."""
+    candidate and picks their samples itself.
+    A MultiDataset takes `targets` (one target index per tree): tree t is
+    optimised against target targets[t], the populations of all outputs in one
+    lockstep run (srhip_optimize_constants_targets) up to
+    interface.FUSED_GRAD_TARGETS_MAX_TREES trees. Larger batches, expression
+    losses, `loss_function` and `evaluator_factory` regroup the trees by target
+    and optimise each group on dataset.target(k) with its slice of the start
+    noise (a factory whose signature accepts `target=` is told k); `fused`
+    forces either where both apply. The noise array is the same either way:
+    start_noise's order over the trees as given."""
+    multi = isinstance(dataset, MultiDataset)
+    if multi:
+        from .interface import _check_targets
+
+        tg = _check_targets(trees, dataset, targets)
+    elif targets is not None:
+        raise ValueError("targets= needs a MultiDataset")
     if row_idx is not None:
         from .interface import _check_row_sets
 
@@ -115,6 +133,16 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
     if noise.shape != (need,):
         raise ValueError(f"start noise has {noise.size} values, the trees' restarts need {need}")
     loss = options.elementwise_loss
+    if multi:
+        from . import constants as K
+        from .interface import FUSED_GRAD_TARGETS_MAX_TREES
+
+        if fused is None:
+            fused = len(trees) <= FUSED_GRAD_TARGETS_MAX_TREES
+        if (not fused or evaluator_factory is not None or options.loss_function is not None
+                or loss.kind >= K.EXPR_LOSS_BEGIN):
+            return _optimize_by_target(dataset, trees, options, device, evaluator_factory, noise, row_idx, tg,
+                                       flat.const_off, nrestarts)
     par = None if loss.params is None else np.ascontiguousarray(loss.params, dtype=np.float64)
     opts = ConstOptOptions(ALGORITHMS[algorithm], int(getattr(options, "optimizer_iterations", 8)), nrestarts,
                            int(loss.kind), None if par is None else par.ctypes.data_as(C.POINTER(C.c_double)),
@@ -127,7 +155,14 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
     out_k = np.zeros(max(nt, 1), dtype=np.uint8)
     out_n = np.zeros(max(nt, 1))
     ptrs = [a.ctypes.data_as(C.c_void_p) for a in (out_c, out_l, out_k, out_n)]
-    if evaluator_factory is None and isinstance(dataset, GroupDataset):
+    if multi:
+        dev = dataset.device(device)
+        tgc = np.ascontiguousarray(tg, dtype=np.int32)
+        check(lib().srhip_optimize_constants_targets(
+            dev.ctx.handle, dev.handle, C.byref(tr), C.byref(opts), tgc.ctypes.data_as(C.c_void_p),
+            None if row_idx is None else row_idx.ctypes.data_as(C.c_void_p),
+            0 if row_idx is None else row_idx.shape[1], *ptrs))
+    elif evaluator_factory is None and isinstance(dataset, GroupDataset):
         # the rows sharded over a device group (srhip_group_optimize_constants)
         check(lib().srhip_group_optimize_constants(dataset.handle, C.byref(tr), C.byref(opts), *ptrs))
     elif evaluator_factory is None and row_idx is not None:
@@ -149,6 +184,40 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
     for i in np.flatnonzero(conv):
         set_constants(trees[i], [T(v) for v in out_c[co[i]:co[i + 1]]])
     return ConstOptResult(out_l[:nt].copy(), conv, out_n[:nt].copy())
+
+
+def _optimize_by_target(dataset, trees, options, device, evaluator_factory, noise, row_idx, tg, const_off,
+                        nrestarts) -> ConstOptResult:
+    """The regroup fallback of a MultiDataset: each target's trees on dataset.target(k), with the
+    group's slice of the start noise (tree t's draws are noise[nrestarts·const_off[t] :
+    nrestarts·const_off[t+1]]), results scattered back in the trees' order."""
+    nt = len(trees)
+    losses, conv, nev = np.zeros(nt), np.zeros(nt, dtype=bool), np.zeros(nt)
+    co = np.asarray(const_off, dtype=np.int64) * nrestarts
+    for k in np.unique(tg):
+        idx = np.flatnonzero(tg == k)
+        sub = np.concatenate([noise[co[t]:co[t + 1]] for t in idx]) if len(idx) else np.zeros(0)
+        fac = evaluator_factory
+        if fac is not None:
+            try:
+                takes_target = "target" in inspect.signature(fac).parameters
+            except (TypeError, ValueError):
+                takes_target = False
+            if takes_target:
+                fac = _with_target(evaluator_factory, int(k))
+        r = optimize_constants_batch(dataset.target(int(k)), [trees[t] for t in idx], options, device=device,
+                                     evaluator_factory=fac, noise=sub,
+                                     row_idx=None if row_idx is None else row_idx[idx])
+        losses[idx], conv[idx], nev[idx] = r.losses, r.converged, r.num_evals
+    return ConstOptResult(losses, conv, nev)
+
+
+def _with_target(factory, k: int):
+    """factory with target=k bound; `members=` is passed through when the factory takes it."""
+    takes_members = "members" in inspect.signature(factory).parameters
+    if takes_members:
+        return lambda cands, members=None: factory(cands, members=members, target=k)
+    return lambda cands: factory(cands, target=k)
 
 
 class _Callback:

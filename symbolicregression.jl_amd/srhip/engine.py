@@ -392,6 +392,47 @@ class Program:
                                                  _p(sums), _p(grads), _p(wsum), _p(ok)))
         return sums[:nt], grads[:nc], wsum[:nt], ok[:nt].astype(bool)
 
+    def eval_loss_grad_targets(self, ds, loss_kind: int, targets, params=None):
+        """srhip_eval_loss_grad_targets: tree t against column targets[t] of a
+        MultiDeviceDataset in one launch per pass: (Σ w·ℓ per tree, Σ w·∂ℓ/∂c per
+        constant [const_off order], Σ w per target, ok)."""
+        nt = self.ntrees
+        nc = int(self.flat.const_off[-1])
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        if tg.shape != (nt,):
+            raise ValueError("targets must have one entry per tree")
+        ntg = getattr(ds, "ntargets", 1)
+        sums = np.zeros(max(nt, 1), dtype=np.float64)
+        grads = np.zeros(max(nc, 1), dtype=np.float64)
+        wsum = np.zeros(ntg, dtype=np.float64)
+        ok = np.zeros(max(nt, 1), dtype=np.uint8)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_eval_loss_grad_targets(ds.handle, self.handle, int(loss_kind), _p(par), _p(tg), _p(sums),
+                                                 _p(grads), _p(wsum), _p(ok)))
+        return sums[:nt], grads[:nc], wsum, ok[:nt].astype(bool)
+
+    def eval_loss_grad_rowsets_targets(self, ds, loss_kind: int, targets, row_idx, params=None):
+        """srhip_eval_loss_grad_rowsets_targets: tree t on its own rows row_idx[t]
+        against column targets[t]: (Σ w·ℓ per tree, Σ w·∂ℓ/∂c per constant, Σ w per
+        tree, ok)."""
+        nt = self.ntrees
+        nc = int(self.flat.const_off[-1])
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        if tg.shape != (nt,):
+            raise ValueError("targets must have one entry per tree")
+        idx = np.ascontiguousarray(row_idx, dtype=np.int64)
+        if idx.ndim != 2 or idx.shape[0] != nt:
+            raise ValueError("row_idx must be (ntrees, batch_size)")
+        sums = np.zeros(max(nt, 1), dtype=np.float64)
+        grads = np.zeros(max(nc, 1), dtype=np.float64)
+        wsum = np.zeros(max(nt, 1), dtype=np.float64)
+        ok = np.zeros(max(nt, 1), dtype=np.uint8)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_eval_loss_grad_rowsets_targets(ds.handle, self.handle, int(loss_kind), _p(par), _p(tg),
+                                                         _p(idx), idx.shape[1], _p(sums), _p(grads), _p(wsum),
+                                                         _p(ok)))
+        return sums[:nt], grads[:nc], wsum[:nt], ok[:nt].astype(bool)
+
     def eval_grad_tree_array(self, ds: DeviceDataset):
         """(ŷ [ntrees][rows], ∂ŷ/∂c [total consts][rows], ok)."""
         nt = self.ntrees

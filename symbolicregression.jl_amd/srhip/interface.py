@@ -167,15 +167,62 @@ def eval_grad_tree_array(tree: TreeOrTrees, X: np.ndarray, options: Options, var
     return val, grads, ok
 
 
+def _eval_loss_grad_targets(trees, dataset, options: Options, device, row_idx, targets, fused):
+    """eval_loss_grad_batch on a MultiDataset: one fused call (srhip_eval_loss_grad_targets,
+    with row_idx srhip_eval_loss_grad_rowsets_targets), or the trees regrouped by target and
+    each group on its view."""
+    tg = _check_targets(trees, dataset, targets)
+    R = None if row_idx is None else _check_row_sets(row_idx, len(trees))
+    loss = options.elementwise_loss
+    T = dataset.T
+    if fused is None:
+        fused = len(trees) <= FUSED_GRAD_TARGETS_MAX_TREES
+    if not fused or loss.kind >= K.EXPR_LOSS_BEGIN:  # expression losses: views
+        losses = np.zeros(len(trees), dtype=T)
+        ok = np.zeros(len(trees), dtype=bool)
+        g = [None] * len(trees)
+        for k in np.unique(tg):
+            idx = np.flatnonzero(tg == k)
+            lv, gv, kv = eval_loss_grad_batch([trees[t] for t in idx], dataset.target(int(k)), options, device,
+                                              None if R is None else R[idx])
+            losses[idx] = lv
+            ok[idx] = kv
+            for j, t in enumerate(idx):
+                g[t] = gv[j]
+        return losses, g, ok
+    dev = dataset.device(device)
+    prog = Program(dev.ctx, flatten(trees, options, dtype=T), T, interpreted=True)
+    if R is None:
+        sums, grads, wsum, ok = prog.eval_loss_grad_targets(dev, loss.kind, tg, loss.params)
+        wsums = wsum[tg]
+    else:
+        sums, grads, wsums, ok = prog.eval_loss_grad_rowsets_targets(dev, loss.kind, tg, R, loss.params)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        losses = (sums / wsums).astype(T)
+        co = prog.flat.const_off
+        g = [grads[co[t]:co[t + 1]] / wsums[t] for t in range(len(trees))]
+    losses[~ok] = T(np.inf)
+    return losses, g, ok
+
+
 def eval_loss_grad_batch(trees: Sequence[Node], dataset: Dataset, options: Options,
-                         device: Optional[int] = None, row_idx: Optional[np.ndarray] = None):
+                         device: Optional[int] = None, row_idx: Optional[np.ndarray] = None,
+                         targets: Optional[Sequence[int]] = None, fused: Optional[bool] = None):
     """Batched loss + constant gradients for ConstantOptimization
     (src/ConstantOptimization.jl:12-65): per tree (loss in T, ∂loss/∂c as a
     float64 vector in get_constants order, did_succeed). A GroupDataset runs
     over its device group (`device` is then unused). row_idx, an
     (ntrees, batch_size) integer array: tree t on its own row sample row_idx[t]
     (srhip_eval_loss_grad_rowsets), loss and gradient divided by that sample's
-    Σw; not on a GroupDataset."""
+    Σw; not on a GroupDataset. A MultiDataset takes targets (one target index
+    per tree): tree t against target targets[t], each loss and gradient divided
+    by its own target's Σw, in one fused call up to
+    FUSED_GRAD_TARGETS_MAX_TREES trees and on per-target views beyond; `fused`
+    forces either."""
+    if isinstance(dataset, MultiDataset):
+        return _eval_loss_grad_targets(list(trees), dataset, options, device, row_idx, targets, fused)
+    if targets is not None:
+        raise ValueError("targets= needs a MultiDataset")
     loss = options.elementwise_loss
     if row_idx is not None:
         if isinstance(dataset, GroupDataset):
@@ -240,6 +287,19 @@ def eval_loss_batch(trees: Sequence[Node], dataset: Dataset, options: Options,
 # to there and the views beyond it. A caller that keeps its programs (srhip.Program on
 # mds.target(k).device()) pays for the tree code once and is not covered by this.
 FUSED_TARGETS_MAX_TREES = 4096
+
+# Trees per call up to which a MultiDataset's gradients and constant optimisation
+# run fused (srhip_eval_loss_grad_targets, srhip_optimize_constants_targets); larger
+# batches are regrouped by target and run on the views, whose gradient passes are
+# reverse-mode tree code from 256 candidates per program on. Set from the measured
+# table (tools/bench_grad_targets.py, profiles/grad_targets_timing.json, DESIGN.md
+# §3.17): the largest measured batch at which all three fused medians lie below the
+# views' three. Float32, L2, 5 features, K = 4, 8 BFGS iterations, 1 + 2 starts:
+# 4 x 33 trees on 100k rows: fused 73 ms, four view runs 145-148 ms; 4 x 256 trees:
+# fused 273-275 ms, views 362-363 ms. The ratio falls from 2.0 to 1.3 over that range;
+# nothing above 1024 trees was measured, so the views take over there (fused=True
+# forces the fused path).
+FUSED_GRAD_TARGETS_MAX_TREES = 1024
 
 
 def _check_targets(trees, dataset: MultiDataset, targets) -> np.ndarray:
