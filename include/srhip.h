@@ -825,6 +825,26 @@ int32_t srhip_last_bailed(const srhip_ctx* ctx, int32_t* out_ntrees, int64_t* ou
  * interpreted; srhip_eval_loss_grad: L2 and, compiled at their first use,
  * the other losses with a dℓ/dr routine, Float32 and Float64). */
 int32_t srhip_last_tree_code(const srhip_ctx* ctx, int32_t* out_ntrees);
+/* Shared-subtree columns. Float32 loss tree code reads the constant-free
+ * subtrees that several trees of its batch contain from columns of device
+ * memory. A context numbers them (canonical subtree text -> slot, at most
+ * SRHIP_COLUMN_SLOTS = 64 slots, least recently used replaced) and a dataset
+ * keeps the columns derived over its own rows, so a call — of the same
+ * program or of another program of the dataset's context — derives only the
+ * columns the dataset does not hold under the program's slots. Calls on
+ * gathered rows, programs of another context, a pool beyond
+ * SRHIP_COLUMN_CACHE_MB (1024) and SRHIP_COLUMN_CACHE=0 derive every column
+ * at every call. Results do not depend on any of this.
+ * Counters of a context since srhip_open (NULL outputs are skipped): columns
+ * derived, columns that calls found in a dataset's pool, derive programs
+ * built, and the registry's slot count. */
+int32_t srhip_column_cache_info(const srhip_ctx* ctx, int64_t* out_derived, int64_t* out_reused,
+                                int64_t* out_programs, int32_t* out_nslot);
+/* The shared-subtree columns of the program's L2 loss tree code, one line
+ * "<slot> <canonical text>\n" each (no device needed beyond the program's
+ * own). inout_n: capacity on entry, size (without the final NUL) on return;
+ * SRHIP_ERR_INVALID if too small. */
+int32_t srhip_program_shared_columns(const srhip_program* prog, char* out_text, int64_t* inout_n);
 /* Testing hook (no device needed): compile Float32 trees with the tree
  * compiler (fast: bit 0 the guarded FAST path, bit 1 memory-constant code,
  * bit 2 the per-row output code of srhip_eval_tree_array; bit 3: the trees

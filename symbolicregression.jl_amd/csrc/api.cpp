@@ -225,8 +225,14 @@ struct srhip_ctx {
   int last_jit_trees = 0;  // trees the last evaluation ran as tree code
   int64_t last_redone = 0;  // tiles tree code redid with the PRECISE routines
   DevBuf partial, sums, oks, dloss, scratch_idx, gather, derived;
-  DevBuf gderived;  // [ngcol][n_pad] shared-subtree columns of the tree code (jit.h Columns)
+  DevBuf gderived;  // [gspan][n_pad] shared-subtree columns of a call that cannot use a dataset's pool (jit.h Columns)
   DevBuf gpartial, gsum, gok, gti;  // their derive pass's partials, per-column results, threaded records
+  // the stable column numbers of this context's shared subtrees (slots.h; SRHIP_COLUMN_SLOTS,
+  // default 64), the datasets holding a column pool under them, and what the derive passes did:
+  // columns derived, columns a call found in a pool, derive programs built
+  SlotRegistry slots{std::max(0, env_int("SRHIP_COLUMN_SLOTS", 64))};
+  std::vector<srhip_dataset*> pooled;
+  int64_t cols_derived = 0, cols_reused = 0, derive_programs = 0;
   DevBuf tgt;  // [ntrees] the target of each tree (srhip_eval_loss_targets, _rowsets_targets)
   DevBuf fail;  // [list slots] early-exit flags of the eval kernel (MODE_LOSS)
   bool fail_clean = false;  // all of `fail` is zero: the finalize kernels clear the flags they read
@@ -277,6 +283,13 @@ struct srhip_dataset {
   std::shared_ptr<MultiMem> mem;
   std::vector<double> t_sum_w, t_sum_yw;
   std::vector<std::vector<double>> t_h_w;
+  // column pool: the shared-subtree columns of loss tree code over this dataset's own X
+  // ([pool_cols][n_pad] Float32, column = the subtree's slot in the context's registry) and the
+  // canonical text each column holds ("": none). Kept from call to call: run_eval derives only
+  // the columns whose key differs from the calling program's (shared_columns).
+  DevBuf pool;
+  int pool_cols = 0;
+  std::vector<std::string> pool_key;
 };
 
 struct srhip_program {
@@ -403,6 +416,11 @@ struct srhip_program {
   // the same for the gradient tree code's columns (jit::grad_columns)
   mutable srhip_program* gshared = nullptr;
   mutable std::vector<std::string> gshared_keys;
+  // a derive program: the column of each list slot's subtree ([nlist_a + nlist_b], device; in place
+  // of d_list, so per-row outputs and per-column results land in the subtree's column) and the
+  // column of each subtree (host)
+  int32_t* d_col_list = nullptr;
+  std::vector<int32_t> h_cols;
 };
 
 namespace {
@@ -756,6 +774,8 @@ void free_program_device(srhip_program* p) {
   p->verdict_stale = true;
   if (p->d_tree_off) (void)hipFree(p->d_tree_off);
   if (p->d_list) (void)hipFree(p->d_list);
+  if (p->d_col_list) (void)hipFree(p->d_col_list);
+  p->d_col_list = nullptr;
   p->d_code = nullptr;
   p->d_tree_off = nullptr;
   p->d_list = nullptr;
@@ -1136,6 +1156,14 @@ size_t jit_tile_budget() {
   return b;
 }
 bool jit_fast_enabled() { return env_on("SRHIP_JIT_FAST"); }
+// SRHIP_COLUMN_CACHE=0 (read per build and per call: tests): shared-subtree columns numbered per
+// program and derived at every call, as before the datasets' column pools
+bool column_cache_enabled() { return env_on("SRHIP_COLUMN_CACHE"); }
+// the registry that numbers a program's shared-subtree columns, or null: the program's own numbering
+// (a derive program's subtrees are not shared further)
+SlotRegistry* column_slots(const srhip_program* p) {
+  return column_cache_enabled() && !p->jit_forced ? &p->ctx->slots : nullptr;
+}
 
 template <typename T>
 void build_program(srhip_program* p) {
@@ -1186,6 +1214,7 @@ void build_program(srhip_program* p) {
       jo.memc = p->jit_memc || env_is1("SRHIP_JIT_MEMC");  // read per build: tests
       // wide code when a candidate reads a feature past the LDS tile's reach (features 0 .. 62)
       jo.xg = p->wide_tc && !jo.memc && jit::max_feature_read(cb, a) >= 63;
+      jo.slots = column_slots(p);
       p->jit = jit::build(cb, a, jl, rest, jo, &p->jit_stats);
       if (p->jit) {
         p->nlist_j = (int)jl.size();
@@ -1527,6 +1556,7 @@ jit::Module* loss_module(const srhip_program* p, int loss, double lparam) {
   jo.xg = jit::xg(p->jit);
   jo.loss = loss;
   jo.lparam = bits_of(lparam);
+  jo.slots = column_slots(p);
   return lazy_module<float, jit::Module>(
       p, p->jit_loss, loss, jo.lparam, p->jit_consts, false,
       [&](const CompiledBatch<float>& cb, std::vector<int32_t>& jl, std::vector<int32_t>& rest) {
@@ -1634,14 +1664,27 @@ jit::GradModule64* grad_module64(srhip_program* p, int loss, double lparam) {
 // node on any row (src/InterfaceDynamicExpressions.jl:17-48).
 // slot / keys: the program's cache of the subtree program (p->shared for the
 // loss tree code, p->gshared for the gradient tree code).
+// which: the subtrees to derive (indices into jc.gkey, ascending), a program
+// of just those; out: the column buffer ([jc.gspan()][n_pad]: c->gderived or
+// a dataset's pool), subtree g into column jc.slot(g). The other columns of
+// `out` are neither written nor poisoned.
 bool derive_jit_enabled() {
   static const bool on = env_on("SRHIP_DERIVE_JIT");
   return on;
 }
 void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>& keys, const jit::Columns& jc,
-                   const float* X, int64_t rows, int64_t n_pad, int nfeat) {
+                   const std::vector<int>& which, float* out, const float* X, int64_t rows, int64_t n_pad,
+                   int nfeat) {
   hipStream_t s = c->stream;
-  if (!slot || keys != jc.gkey) {
+  const int ng = (int)which.size();
+  if (ng == 0) return;
+  std::vector<std::string> wkeys;
+  std::vector<int32_t> wcols;
+  for (int g : which) {
+    wkeys.push_back(jc.gkey[(size_t)g]);
+    wcols.push_back(jc.slot(g));
+  }
+  if (!slot || keys != wkeys || slot->h_cols != wcols) {
     if (slot) {
       free_program_device(slot);
       delete slot;
@@ -1650,31 +1693,41 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
     auto* q = new srhip_program();
     q->ctx = c;
     q->dtype = SRHIP_F32;
-    q->ntrees = jc.ngcol;
+    q->ntrees = ng;
     // per-row output tree code for the subtrees (SRHIP_DERIVE_JIT=0: the interpreter's MODE_OUT)
     q->jit_allowed = derive_jit_enabled();
     q->jit_forced = true;
-    q->node_off.assign(jc.goff.begin(), jc.goff.end());
-    q->const_off.assign((size_t)jc.ngcol + 1, 0);
-    q->kind = jc.gkind;
-    q->arg = jc.garg;
+    q->node_off.assign(1, 0);
+    for (int g : which) {
+      q->kind.insert(q->kind.end(), jc.gkind.begin() + jc.goff[(size_t)g], jc.gkind.begin() + jc.goff[(size_t)g + 1]);
+      q->arg.insert(q->arg.end(), jc.garg.begin() + jc.goff[(size_t)g], jc.garg.begin() + jc.goff[(size_t)g + 1]);
+      q->node_off.push_back((int32_t)q->kind.size());
+    }
+    q->const_off.assign((size_t)ng + 1, 0);
     q->consts.resize(1);
     try {
       build_program_f32(q);
+      // the column of every list slot's subtree, in list order
+      const size_t nl = (size_t)q->nlist_a + q->nlist_b;
+      std::vector<int32_t> list(std::max<size_t>(nl, 1));
+      if (nl > 0) HIP_CHECK(hipMemcpy(list.data(), q->d_list, nl * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < nl; ++k) list[k] = wcols[(size_t)list[k]];
+      HIP_CHECK(hipMalloc((void**)&q->d_col_list, list.size() * sizeof(int32_t)));
+      HIP_CHECK(hipMemcpy(q->d_col_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      q->h_cols = wcols;
+      ++c->derive_programs;
     } catch (...) {
       free_program_device(q);
       delete q;
       throw;
     }
     slot = q;
-    keys = jc.gkey;
+    keys = wkeys;
   }
   const srhip_program* q = slot;
-  const int ng = jc.ngcol;
-  c->gderived.ensure((size_t)ng * (size_t)n_pad * sizeof(float));
-  c->gsum.ensure((size_t)ng * sizeof(double));
-  c->gok.ensure((size_t)ng);
-  float* out = static_cast<float*>(c->gderived.p);
+  c->cols_derived += ng;
+  c->gsum.ensure((size_t)jc.gspan() * sizeof(double));
+  c->gok.ensure((size_t)jc.gspan());
   if (q->nlist_a + q->nlist_b != ng) throw Error(SRHIP_ERR_INVALID, "shared subtree failed statically");
   // every subtree as per-row output tree code (jit_template.hip sr_jit_out_d, PRECISE routines:
   // the interpreter's values bit for bit, test_jit_out_gpu.py): one launch per code object part
@@ -1700,7 +1753,7 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
       EvalArgs<float> a;
       a.prog = static_cast<const Ins<float>*>(q->d_code);
       a.tree_off = q->d_tree_off;
-      a.list = q->d_list + s0;
+      a.list = q->d_col_list + s0;
       a.list_off = q->d_list + (q->nlist_a + q->nlist_b) + s0;
       a.fail = nullptr;
       a.ti_rec = nullptr;
@@ -1726,7 +1779,7 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
       HIP_CHECK(jit::launch(om, k, plan, a, false, nullptr, s, nullptr));
       HIP_CHECK(launch_finalize<float>(a, static_cast<double*>(c->gsum.p), static_cast<uint8_t*>(c->gok.p), s));
     }
-    HIP_CHECK(launch_poison_columns(static_cast<const uint8_t*>(c->gok.p), ng, out, n_pad, s));
+    HIP_CHECK(launch_poison_columns(static_cast<const uint8_t*>(c->gok.p), q->d_col_list, ng, out, n_pad, s));
     return;
   }
   const int lists[2][2] = {{0, q->nlist_a}, {q->nlist_a, q->nlist_b}};
@@ -1740,7 +1793,7 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
     EvalArgs<float> a;
     a.prog = static_cast<const Ins<float>*>(q->d_code);
     a.tree_off = q->d_tree_off;
-    a.list = q->d_list + s0;
+    a.list = q->d_col_list + s0;
     a.list_off = q->d_list + (q->nlist_a + q->nlist_b) + s0;
     a.fail = nullptr;
     a.ti_rec = nullptr;
@@ -1772,15 +1825,91 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
     HIP_CHECK(launch_eval<float>(plan, a, MODE_OUT, s));
     HIP_CHECK(launch_finalize<float>(a, static_cast<double*>(c->gsum.p), static_cast<uint8_t*>(c->gok.p), s));
   }
-  HIP_CHECK(launch_poison_columns(static_cast<const uint8_t*>(c->gok.p), ng, out, n_pad, s));
+  HIP_CHECK(launch_poison_columns(static_cast<const uint8_t*>(c->gok.p), q->d_col_list, ng, out, n_pad, s));
+}
+
+// every shared subtree of jc into the context's per-call buffer
+const float* percall_columns(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>& keys,
+                             const jit::Columns& jc, const float* X, int64_t rows, int64_t n_pad, int nfeat) {
+  std::vector<int> all((size_t)jc.ngcol);
+  for (int g = 0; g < jc.ngcol; ++g) all[(size_t)g] = g;
+  c->gderived.ensure((size_t)jc.gspan() * (size_t)n_pad * sizeof(float));
+  derive_shared(c, slot, keys, jc, all, static_cast<float*>(c->gderived.p), X, rows, n_pad, nfeat);
+  return static_cast<const float*>(c->gderived.p);
+}
+
+// Room for `span` columns in the dataset's pool, within SRHIP_COLUMN_CACHE_MB (default 1024):
+// allocated at the first call that needs it and grown, its columns kept, to the highest slot
+// used, rounded up to 8 columns. False: over budget or out of memory (the per-call path).
+bool pool_reserve(srhip_ctx* c, srhip_dataset* ds, int span) {
+  if (span <= ds->pool_cols) return true;
+  const size_t col = (size_t)ds->n_pad * sizeof(float);
+  const size_t budget = (size_t)std::max(0, env_int("SRHIP_COLUMN_CACHE_MB", 1024)) << 20;
+  if ((size_t)span * col > budget) return false;
+  const int want = (int)std::min<size_t>(((size_t)span + 7) / 8 * 8, budget / col);
+  DevBuf nb;
+  try {
+    nb.ensure((size_t)want * col);
+  } catch (const Error&) {
+    return false;
+  }
+  if (ds->pool_cols > 0) {
+    const hipError_t e =
+        hipMemcpyAsync(nb.p, ds->pool.p, (size_t)ds->pool_cols * col, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) {
+      nb.release();
+      HIP_CHECK(e);
+    }
+  } else {
+    c->pooled.push_back(ds);
+  }
+  ds->pool.release();  // (hipFree waits for the device: the copy and every earlier reader are done)
+  ds->pool = nb;
+  ds->pool_cols = want;
+  ds->pool_key.resize((size_t)want);
+  return true;
+}
+void pool_release(srhip_dataset* ds) {
+  ds->pool.release();
+  ds->pool_cols = 0;
+  ds->pool_key.clear();
+  auto& v = ds->ctx->pooled;
+  v.erase(std::remove(v.begin(), v.end(), ds), v.end());
+}
+
+// The shared-subtree columns of a loss tree-code launch. On the dataset's own rows, by the
+// dataset's own context and with registry-numbered columns (pool != null, jc.pooled): the
+// dataset's pool, after deriving the columns whose key the pool does not hold under the
+// program's slot — none when an earlier call, of this program or another, left them all.
+// Otherwise (a gathered row subset, a program of another context and so another stream, a pool
+// over budget, SRHIP_COLUMN_CACHE=0): every column into c->gderived for this call.
+const float* shared_columns(srhip_ctx* c, const srhip_program* p, const jit::Columns& jc, srhip_dataset* pool,
+                            const float* X, int64_t rows, int64_t n_pad, int nfeat) {
+  if (pool && jc.pooled && pool->ctx == c && X == pool->X && rows == pool->rows && n_pad == pool->n_pad &&
+      column_cache_enabled() && pool_reserve(c, pool, jc.gspan())) {
+    std::vector<int> miss;
+    for (int g = 0; g < jc.ngcol; ++g)
+      if (pool->pool_key[(size_t)jc.slot(g)] != jc.gkey[(size_t)g]) miss.push_back(g);
+    c->cols_reused += jc.ngcol - (int64_t)miss.size();
+    float* base = static_cast<float*>(pool->pool.p);
+    if (!miss.empty()) {
+      for (int g : miss) pool->pool_key[(size_t)jc.slot(g)].clear();  // not valid until the launches are enqueued
+      derive_shared(c, p->shared, p->shared_keys, jc, miss, base, X, rows, n_pad, nfeat);
+      for (int g : miss) pool->pool_key[(size_t)jc.slot(g)] = jc.gkey[(size_t)g];
+    }
+    return base;
+  }
+  return percall_columns(c, p->shared, p->shared_keys, jc, X, rows, n_pad, nfeat);
 }
 
 // Run the evaluation kernels for both tree lists. The view (X, y, w, rows,
 // n_pad) may be the dataset itself or a gathered row subset.
+// pool: the dataset, when the view is the dataset itself (its column pool, shared_columns).
 template <typename T>
 void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const T* y,
               const T* w, int64_t rows, int64_t n_pad, int nfeat, int loss, double lparam,
-              T* out, int64_t out_stride, int64_t seg = 0, const int32_t* tgt = nullptr, int ntgt = 0) {
+              T* out, int64_t out_stride, int64_t seg = 0, const int32_t* tgt = nullptr, int ntgt = 0,
+              srhip_dataset* pool = nullptr) {
   // tgt (device memory, per tree id): a target per tree; y / w are then ntgt columns
   // n_pad rows apart and every pass runs the interpreter's per-tree-targets variants
   hipStream_t s = c->stream;
@@ -1911,6 +2040,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
   }
   launches.push_back({0, nj, p->nlist_a - nj, -1});
   launches.push_back({1, p->nlist_a, p->nlist_b, -1});
+  const float* shared_cols = nullptr;  // the shared-subtree columns of the tree-code parts
   for (size_t li = 0; li < launches.size(); ++li) {
     const int pass = launches[li].pass;
     const int s0 = launches[li].s0;
@@ -1993,8 +2123,8 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
         // (inside the timed region: their cost is the call's)
         const float* gcols = jc.xg ? X : nullptr;  // wide code reads X itself as its columns
         if (jc.ngcol > 0) {
-          if (launches[li].part == 0) derive_shared(c, p->shared, p->shared_keys, jc, X, rows, n_pad, nfeat);
-          gcols = static_cast<const float*>(c->gderived.p);
+          if (launches[li].part == 0) shared_cols = shared_columns(c, p, jc, pool, X, rows, n_pad, nfeat);
+          gcols = shared_cols;
         }
         HIP_CHECK(jit::launch(jm, launches[li].part, plan, a, jit_fast_enabled(), dcols, s, gcols));
       } else {
@@ -2118,7 +2248,8 @@ int eval_loss_impl(srhip_dataset* ds, const srhip_program* p, int loss, const do
     rows = nidx;
     n_pad = gp;
   }
-  run_eval<T>(c, p, MODE_LOSS, X, y, w, rows, n_pad, ds->nfeat, loss, params ? params[0] : 0.0, nullptr, 0);
+  run_eval<T>(c, p, MODE_LOSS, X, y, w, rows, n_pad, ds->nfeat, loss, params ? params[0] : 0.0, nullptr, 0, 0,
+              nullptr, 0, row_idx ? nullptr : ds);
   collect_results(c, p, rows, out_sum, out_ok);
   if (out_wsum) *out_wsum = wsum;
   return SRHIP_OK;
@@ -2251,7 +2382,8 @@ int eval_loss_packed_impl(srhip_dataset* ds, srhip_program* p, int loss, const d
   c->want_device_results = true;
   try {
     run_eval<T>(c, p, MODE_LOSS, static_cast<const T*>(ds->X), static_cast<const T*>(ds->y),
-                static_cast<const T*>(ds->w), ds->rows, ds->n_pad, ds->nfeat, loss, params ? params[0] : 0.0, nullptr, 0);
+                static_cast<const T*>(ds->w), ds->rows, ds->n_pad, ds->nfeat, loss, params ? params[0] : 0.0, nullptr, 0,
+                0, nullptr, 0, ds);
   } catch (...) {
     c->want_device_results = false;
     throw;
@@ -2429,10 +2561,9 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
         const float* gcols = nullptr;
         if (gcj.ngcol > 0) {
           const int tk = timed_begin(c, s);
-          derive_shared(c, p->gshared, p->gshared_keys, gcj, static_cast<const float*>(ds->X), ds->rows, ds->n_pad,
-                        ds->nfeat);
+          gcols = percall_columns(c, p->gshared, p->gshared_keys, gcj, static_cast<const float*>(ds->X), ds->rows,
+                                  ds->n_pad, ds->nfeat);
           timed_end(c, s, tk);
-          gcols = static_cast<const float*>(c->gderived.p);
         }
         for (int k = 0; k < nparts; ++k) {
           int s0, nsl;
@@ -2993,6 +3124,7 @@ int32_t srhip_close(srhip_ctx* ctx) {
     ctx->gpart.release();
     ctx->derived.release();
     ctx->gderived.release();
+    while (!ctx->pooled.empty()) pool_release(ctx->pooled.back());
     ctx->gpartial.release();
     ctx->gsum.release();
     ctx->gok.release();
@@ -3161,6 +3293,7 @@ int32_t srhip_dataset_destroy(srhip_dataset* ds) {
     std::lock_guard<std::mutex> lk(ds->ctx->mu);
     (void)hipSetDevice(ds->ctx->device);
     (void)hipStreamSynchronize(ds->ctx->stream);
+    pool_release(ds);
     if (ds->mem) {
       ds->mem.reset();  // the last of a multi-target dataset and its views frees the memory
     } else {
@@ -3726,6 +3859,35 @@ int32_t srhip_last_tree_code(const srhip_ctx* ctx, int32_t* out_ntrees) {
   return guarded([&] {
     if (!ctx || !out_ntrees) throw Error(SRHIP_ERR_INVALID, "null argument");
     *out_ntrees = ctx->last_jit_trees;
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_column_cache_info(const srhip_ctx* ctx, int64_t* out_derived, int64_t* out_reused,
+                                int64_t* out_programs, int32_t* out_nslot) {
+  return guarded([&] {
+    if (!ctx) throw Error(SRHIP_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(const_cast<srhip_ctx*>(ctx)->mu);
+    if (out_derived) *out_derived = ctx->cols_derived;
+    if (out_reused) *out_reused = ctx->cols_reused;
+    if (out_programs) *out_programs = ctx->derive_programs;
+    if (out_nslot) *out_nslot = ctx->slots.nslot();
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_program_shared_columns(const srhip_program* prog, char* out_text, int64_t* inout_n) {
+  return guarded([&] {
+    if (!prog || !inout_n) throw Error(SRHIP_ERR_INVALID, "null argument");
+    std::string text;
+    if (prog->jit) {
+      const jit::Columns& jc = jit::columns(prog->jit);
+      for (int g = 0; g < jc.ngcol; ++g) text += std::to_string(jc.slot(g)) + " " + jc.gkey[(size_t)g] + "\n";
+    }
+    const int64_t cap = *inout_n;
+    *inout_n = (int64_t)text.size();
+    if (!out_text || cap < (int64_t)text.size() + 1) throw Error(SRHIP_ERR_INVALID, "output buffer too small");
+    std::memcpy(out_text, text.c_str(), text.size() + 1);
     return SRHIP_OK;
   });
 }

@@ -104,13 +104,13 @@ bool loss_bails(int loss) {
 
 struct DerivedMap {
   const Columns* cols = nullptr;
-  // shared-subtree columns (Columns::gkey): key -> g, column gbase + g of the
-  // tree code; empty: none (memory-constant or per-row output code)
+  // shared-subtree columns (Columns::gkey): key -> its column number
+  // (Columns::slot), column gbase + number of the tree code; empty: none (memory-constant or per-row output code)
   std::unordered_map<std::string, int> gidx;
   int gbase = 1 << 30;
   void set_shared(const Columns& c) {
     gidx.clear();
-    for (int g = 0; g < c.ngcol; ++g) gidx.emplace(c.gkey[g], g);
+    for (int g = 0; g < c.ngcol; ++g) gidx.emplace(c.gkey[g], c.slot(g));
     gbase = c.gbase();
   }
   int col(int op, int f) const {
@@ -1913,6 +1913,12 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
   c.nder = (int)chosen.size();
   for (int k = 0; k < c.nder; ++k) c.der[k] = chosen[k];
   plan_shared(cb, cand, on && !opt.out && !opt.memc, c);
+  // the columns' numbers from the context's registry (the bound plan_shared observes); a batch with
+  // more columns than the registry has slots keeps its own numbering and the per-call derive pass
+  if (opt.slots && c.ngcol > 0) {
+    c.pooled = opt.slots->assign(c.gkey, 255 - c.gbase(), &c.gslot);
+    if (!c.pooled) c.gslot.clear();
+  }
   return c;
 }
 

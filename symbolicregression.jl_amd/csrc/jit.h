@@ -9,6 +9,7 @@
 
 #include "compile.h"
 #include "kernels.h"
+#include "slots.h"
 
 namespace srhip {
 namespace jit {
@@ -39,6 +40,11 @@ struct Options {
   // dataset's width by LDS. Literal-constant loss code only (ignored with
   // memc or out); no derived and no shared-subtree columns.
   bool xg = false;
+  // the context's slot registry (slots.h): the shared-subtree columns of loss
+  // tree code are numbered by it, so that a dataset can keep them from call to
+  // call and from program to program (api.cpp column pool); null: column g of
+  // the build is number g
+  SlotRegistry* slots = nullptr;
 };
 
 // Derived columns: a routine unary operator applied to a dataset feature,
@@ -53,9 +59,11 @@ constexpr int kMaxDerived = 48;
 // once per row per call by the derive pass (api.cpp derive_shared: the
 // interpreter's per-row outputs of the subtrees as a program of their own; a
 // subtree non-finite at some node on some row has its whole column set to
-// NaN) into a column of device memory, [ngcol][n_pad], and the tree code reads
+// NaN) into a column of device memory, [gspan()][n_pad], and the tree code reads
 // it with a global load at the tile start instead of computing it (tree code
-// column gbase() + g).
+// column gbase() + slot(g)). With a slot registry (Options::slots) a subtree has
+// the same column number in every program of a context, and a dataset keeps the
+// derived columns from call to call (api.cpp shared_columns).
 constexpr int kMaxGlobalCols = 128;
 struct Columns {
   int nraw = 0;                  // raw feature columns staged (max feature used + 1)
@@ -67,6 +75,18 @@ struct Columns {
   std::vector<uint8_t> gkind;    // postfix node streams of the subtrees (SRHIP_NODE_*, raw features)
   std::vector<uint16_t> garg;
   std::vector<int32_t> goff;     // [ngcol + 1]
+  // the column number of each subtree in the tree code's address arithmetic
+  // (tree code column gbase() + slot(g)): its slot in the context's registry
+  // (Options::slots; pooled), or empty: g itself
+  std::vector<int> gslot;
+  bool pooled = false;
+  int slot(int g) const { return gslot.empty() ? g : gslot[(size_t)g]; }
+  // columns of the buffer the tree code addresses: the largest slot + 1
+  int gspan() const {
+    int m = 0;
+    for (int g = 0; g < ngcol; ++g) m = std::max(m, slot(g) + 1);
+    return m;
+  }
   bool xg = false;               // wide code (Options::xg): nraw = nder = ngcol = 0, features read from X
   int xfeat = 0;                 // wide code: the largest feature it reads + 1
   int gbase() const { return nraw + nder; }
@@ -139,8 +159,8 @@ int64_t flag_words(Module* m);
 // list_off / fail / partial of the part's slots).
 // dcols: the derived columns of this call ([nder][n_pad], launch_derive), or
 // null: the driver computes the staged ones itself
-// gcols: the shared-subtree columns of this call ([ngcol][n_pad], api.cpp derive_shared), or
-// null when the module has none
+// gcols: the shared-subtree columns of this call ([Columns::gspan()][n_pad], column slot(g) the
+// subtree g: api.cpp derive_shared or the dataset's column pool), or null when the module has none
 // whether launch() of part k runs a hand-written loop, which writes 4-byte
 // partials (EvalArgs::part4 for the finalize)
 bool partials4(Module* m, int k);

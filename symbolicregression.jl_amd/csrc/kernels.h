@@ -208,9 +208,10 @@ hipError_t launch_pack_x(const T* src, int layout, int64_t src_stride,
 template <typename T>
 hipError_t launch_pack_vec(const T* src, int64_t rows, int64_t n_pad, T* dst,
                            hipStream_t stream);
-// Shared-subtree columns (jit.h Columns): every row of column g of cols
-// ([ncol][n_pad]) set to NaN when ok[g] == 0 (device memory).
-hipError_t launch_poison_columns(const uint8_t* ok, int ncol, float* cols, int64_t n_pad, hipStream_t stream);
+// Shared-subtree columns (jit.h Columns): every row of column g = list[k],
+// k < ncol, of cols ([.][n_pad]) set to NaN when ok[g] == 0 (device memory).
+hipError_t launch_poison_columns(const uint8_t* ok, const int32_t* list, int ncol, float* cols, int64_t n_pad,
+                                 hipStream_t stream);
 // Row gather for score_func_batch: dst[f][k] = src[f][idx[k]] (+ y, w);
 // seg > 0: one sample of nidx rows per segment of seg rows (per-tree samples,
 // srhip_eval_loss_rowsets), idx = [dst_pad / seg][nidx].

@@ -170,10 +170,12 @@ __global__ void gather_rows_targets_kernel(const T* __restrict__ X, const T* __r
 // Columns of shared subtrees (jit.h Columns) whose subtree failed somewhere
 // (ok[g] == 0: a node non-finite on some row) become NaN on every row, so
 // every tree reading the column fails, as DynamicExpressions fails a tree
-// whose node is non-finite on any row.
-__global__ void __launch_bounds__(256) poison_columns_kernel(const uint8_t* __restrict__ ok, float* __restrict__ cols,
+// whose node is non-finite on any row. list: the columns just derived (the
+// other columns of the buffer, a dataset's pool, are not looked at).
+__global__ void __launch_bounds__(256) poison_columns_kernel(const uint8_t* __restrict__ ok,
+                                                            const int32_t* __restrict__ list, float* __restrict__ cols,
                                                             int64_t n_pad) {
-  const int g = blockIdx.y;
+  const int g = list[blockIdx.y];
   if (ok[g]) return;
   float* o = cols + (size_t)g * n_pad;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pad; i += (int64_t)gridDim.x * blockDim.x)
@@ -182,10 +184,11 @@ __global__ void __launch_bounds__(256) poison_columns_kernel(const uint8_t* __re
 
 }  // namespace
 
-hipError_t launch_poison_columns(const uint8_t* ok, int ncol, float* cols, int64_t n_pad, hipStream_t stream) {
+hipError_t launch_poison_columns(const uint8_t* ok, const int32_t* list, int ncol, float* cols, int64_t n_pad,
+                                 hipStream_t stream) {
   if (ncol <= 0 || n_pad <= 0) return hipSuccess;
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_pad + 255) / 256, 512));
-  hipLaunchKernelGGL(poison_columns_kernel, dim3(gx, (unsigned)ncol), dim3(256), 0, stream, ok, cols, n_pad);
+  hipLaunchKernelGGL(poison_columns_kernel, dim3(gx, (unsigned)ncol), dim3(256), 0, stream, ok, list, cols, n_pad);
   return hipGetLastError();
 }
 

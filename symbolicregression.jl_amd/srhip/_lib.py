@@ -139,6 +139,9 @@ SIGNATURES = {
                                 C.POINTER(C.c_int32)],
     "srhip_last_bailed": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
     "srhip_last_tree_code": [C.c_void_p, C.POINTER(C.c_int32)],
+    "srhip_column_cache_info": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int32)],
+    "srhip_program_shared_columns": [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)],
     "srhip_jit_compile": [C.POINTER(Trees), C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_char_p,
                           C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)],
     "srhip_jit_compile_grad": [C.POINTER(Trees), C.c_void_p, C.POINTER(C.c_int64), C.c_char_p,

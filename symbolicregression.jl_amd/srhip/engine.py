@@ -79,6 +79,15 @@ class Context:
         check(lib().srhip_last_tree_code(self.handle, C.byref(n)))
         return n.value
 
+    def column_cache_info(self):
+        """Shared-subtree columns of this context (srhip_column_cache_info):
+        columns derived, columns found in a dataset's pool, derive programs
+        built, slots of the registry."""
+        d, r, b = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        n = C.c_int32(0)
+        check(lib().srhip_column_cache_info(self.handle, C.byref(d), C.byref(r), C.byref(b), C.byref(n)))
+        return dict(derived=d.value, reused=r.value, programs=b.value, nslot=n.value)
+
     def last_jit_events(self):
         """(trees handed back to the interpreter, tiles redone with the
         PRECISE routines) of the last eval."""
@@ -258,6 +267,18 @@ class Program:
         check(lib().srhip_program_jit_info(self.handle, C.byref(nt), C.byref(nf), C.byref(nb), C.byref(mc),
                                            C.byref(ml)))
         return dict(ntrees=nt.value, nfast=nf.value, code_bytes=nb.value, ms_codegen=mc.value, ms_load=ml.value)
+
+    def shared_columns(self):
+        """{canonical subtree text: slot} of the L2 loss tree code's
+        shared-subtree columns (srhip_program_shared_columns)."""
+        n = C.c_int64(1 << 16)
+        buf = C.create_string_buffer(n.value)
+        check(lib().srhip_program_shared_columns(self.handle, buf, C.byref(n)))
+        out = {}
+        for line in buf.value.decode().splitlines():
+            slot, key = line.split(" ", 1)
+            out[key] = int(slot)
+        return out
 
     def grad_jit_info(self):
         """Gradient tree code of this program (srhip_program_grad_jit_info)."""
