@@ -505,7 +505,18 @@ int32_t srhip_eval_tree_array(srhip_dataset* ds, const srhip_program* prog,
  * variable=false) src/InterfaceDynamicExpressions.jl:105-107, fused with the
  * loss: out_dloss[c] = Σ_i w_i ∂ℓ(ŷ_i, y_i)/∂c for every constant c of every
  * tree (laid out like consts, const_off order). Also returns the loss sums
- * and did_succeed like srhip_eval_loss. */
+ * and did_succeed like srhip_eval_loss.
+ *
+ * Derivative rules: the textbook ones for every operator (DESIGN.md §3.4 lists
+ * them with the conventions at kinks, ties and poles), each pinned to an
+ * independent high-precision reference (tests/golden/derivatives.npz). The
+ * piecewise-constant operators (greater, logical_or, logical_and, round, floor,
+ * ceil, sign) have derivative 0 everywhere.
+ * DEVIATION from the reference: SRHIP_UOP_GAMMA's rule, Γ(x)·ψ(x), is not
+ * provided (no device digamma): its derivative is taken as 0, so every
+ * constant below a gamma node gets gradient 0 through it and a gradient-based
+ * optimiser will not move it. Optimise such trees with Nelder-Mead
+ * (srhip_constopt_options) or on the CPU. */
 int32_t srhip_eval_loss_grad(srhip_dataset* ds, const srhip_program* prog,
                              int32_t loss_kind, const double* loss_params,
                              double* out_loss_sum, double* out_dloss,

@@ -141,6 +141,10 @@ static inline T CAT(du, SFX)(int op, T x) {
     case SRHIP_UOP_ATAN: return (T)1 / ((T)1 + x * x);
     case SRHIP_UOP_ASINH: return (T)(1.0 / sqrt((double)x * x + 1.0));
     case SRHIP_UOP_ACOSH: return (T)(1.0 / sqrt((double)x * x - 1.0));
+    case SRHIP_UOP_ATANH_CLIP: { /* atanh'(u) with u as u_atanh_clip computes it; the wrap has slope 1 */
+      T u = CAT(b_mod, SFX)(x + (T)1, (T)2) - (T)1;
+      return (T)1 / ((T)1 - u * u);
+    }
     case SRHIP_UOP_ERF: return (T)(1.1283791670955126 * exp(-(double)x * x));
     case SRHIP_UOP_ERFC: return (T)(-1.1283791670955126 * exp(-(double)x * x));
     case SRHIP_UOP_RELU: return x > (T)0 ? (T)1 : (T)0;

@@ -841,6 +841,10 @@ __device__ __forceinline__ void uop_d(T x, T& f, T& fx) {
   else if constexpr (OP == SRHIP_UOP_ATAN) fx = T(1) / (T(1) + x * x);
   else if constexpr (OP == SRHIP_UOP_ASINH) fx = T(1) / m_sqrt(x * x + T(1));
   else if constexpr (OP == SRHIP_UOP_ACOSH) fx = T(1) / m_sqrt(x * x - T(1));
+  else if constexpr (OP == SRHIP_UOP_ATANH_CLIP) {  // u as uop computes it: atanh'(u)·1, the wrap has slope 1
+    const T u = jl_mod(x + T(1), T(2)) - T(1);
+    fx = T(1) / (T(1) - u * u);
+  }
   else if constexpr (OP == SRHIP_UOP_ERF) fx = T(1.1283791670955126) * m_exp(-x * x);
   else if constexpr (OP == SRHIP_UOP_ERFC) fx = T(-1.1283791670955126) * m_exp(-x * x);
   else if constexpr (OP == SRHIP_UOP_RELU) fx = x > T(0) ? T(1) : T(0);

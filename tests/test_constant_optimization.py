@@ -73,6 +73,40 @@ def test_recovers_constants_on_oracle():
     assert res.num_evals[0] > 3 and res.num_evals[1] > 3
 
 
+def test_atanh_clip_constant_moves_and_is_recovered():
+    """y = atanh_clip(0.3 x1) fitted by atanh_clip(c x1) from c = 0.5, on the oracle. With the derivative
+    rule of atanh_clip missing (0), every gradient under the operator was 0 and the optimiser declared
+    convergence at x0. The C++ driver and tests/constopt_reference.py agree bit for bit, as everywhere in
+    test_constopt_abi.py."""
+    import constopt_reference as ref
+    from srhip.constant_optimization import start_noise
+
+    o = srhip.Options(binary_operators=["+", "-", "*", "/"], unary_operators=["atanh_clip"])
+    X = np.random.default_rng(4).uniform(-1.5, 1.5, (2, 200))
+    tree = lambda c: o.make_unary("atanh_clip", o.make_binary("*", Node(val=c), Node("x1")))  # noqa: E731
+    flat = srhip.flatten([tree(0.3)], o, dtype=np.float64)
+    y, ok = oracle.eval_trees(flat, X, dtype=np.float64)
+    assert ok[0]
+    y = y[0]
+    ds = srhip.Dataset(X, y)
+    fac = oracle_factory(o, X, y)
+    f0, g0 = fac([tree(0.5)]).loss_grad(np.array([0.5]))
+    assert f0[0] > 1e-3 and g0[0] > 1e-2  # the loss is not flat at x0 (central differences: the same slope)
+    h = 1e-6
+    fd = (fac([tree(0.5)]).loss_only(np.array([0.5 + h]))[0] - fac([tree(0.5)]).loss_only(np.array([0.5 - h]))[0]) / (2 * h)
+    assert abs(g0[0] - fd) <= 1e-6 * abs(fd)
+    t_cpp, t_ref = [tree(0.5)], [tree(0.5)]
+    res = srhip.optimize_constants_batch(ds, t_cpp, o, rng=np.random.default_rng(0), evaluator_factory=fac)
+    noise = start_noise(srhip.flatten(t_ref, o, dtype=np.float64), int(o.optimizer_nrestarts), np.random.default_rng(0))
+    rref = ref.optimize_constants_batch(ds, t_ref, o, noise, fac)
+    assert res.converged[0] and res.num_evals[0] > 3
+    assert np.allclose(srhip.get_constants(t_cpp[0]), [0.3], atol=1e-6) and res.losses[0] < 1e-10
+    np.testing.assert_array_equal(res.converged, rref.converged)
+    np.testing.assert_array_equal(res.num_evals, rref.num_evals)
+    np.testing.assert_array_equal(res.losses, rref.losses)
+    assert [float(v) for v in srhip.get_constants(t_cpp[0])] == [float(v) for v in srhip.get_constants(t_ref[0])]
+
+
 def test_not_converged_keeps_x0():
     """With one iteration nothing converges: constants go back to x0 (:61-63)."""
     o, X, y, trees = problem()
