@@ -136,6 +136,17 @@ SR_M1(m_trunc, truncf, trunc)
 SR_M1(m_fabs, fabsf, fabs)
 #undef SR_M1
 #undef SR_M1_OOL
+// OCML's double tgamma returns Inf from a little below Γ's true overflow threshold (171.62437695630272) on,
+// where Γ(x) is still finite (the reference's gamma and the oracle's succeed there). From 171 on the value is
+// taken as (x - 1)·Γ(x - 1): x - 1 is exact in that binade, one more rounding, and the product overflows where
+// Γ itself does.
+__device__ __forceinline__ float m_gamma(float x) { return m_tgamma(x); }
+__device__ __forceinline__ double m_gamma(double x) {
+  const bool top = x > 171.0;
+  const double a = top ? x - 1.0 : x;
+  const double g = m_tgamma(a);
+  return top ? g * a : g;
+}
 #if SR_PRECISE_TRANSC
 __device__ SR_NOINLINE float m_pow(float x, float y) { return (float)pow((double)x, (double)y); }
 #else
@@ -466,7 +477,7 @@ __device__ __forceinline__ T uop(T x) {
   else if constexpr (OP == SRHIP_UOP_ATANH_CLIP) return m_atanh(jl_mod(x + T(1), T(2)) - T(1));
   else if constexpr (OP == SRHIP_UOP_ERF) return m_erf(x);
   else if constexpr (OP == SRHIP_UOP_ERFC) return m_erfc(x);
-  else if constexpr (OP == SRHIP_UOP_GAMMA) { T g = m_tgamma(x); return m_isinf(g) ? qnan<T>() : g; }
+  else if constexpr (OP == SRHIP_UOP_GAMMA) { T g = m_gamma(x); return m_isinf(g) ? qnan<T>() : g; }
   else if constexpr (OP == SRHIP_UOP_RELU) return (x + m_fabs(x)) * T(0.5);  // == /2 exactly
   else if constexpr (OP == SRHIP_UOP_ROUND) return m_rint(x);
   else if constexpr (OP == SRHIP_UOP_FLOOR) return m_floor(x);

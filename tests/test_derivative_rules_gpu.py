@@ -3,7 +3,8 @@ grad_interp.h un_grad / bin_grad / loss_bin_dual) against the independent fixtur
 tests/golden/derivatives.npz, and against the oracle in T.
 
 These rules run in the interpreter only: the gradient tree code compiles `+ - * /` and neg abs square cube
-exp sin cos log sqrt (jit_grad.cpp kGradUops) with rules of its own, and every batch here is far below its
+exp sin cos log sqrt (jit_grad.cpp kGradUops) with rules of its own (pinned to the same fixture by
+test_operator_values_gpu.test_gradient_tree_code_rules), and every batch here is far below its
 bar, which pass_info (grad_rest) and last_tree_code assert.
 
 All cases use 293 rows (derivative_cases.NROWS). Constants that only carry a tangent are -0.0 or 1.0, so
