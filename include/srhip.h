@@ -306,6 +306,12 @@ int32_t srhip_op_eval(int32_t dtype, int32_t arity, int32_t id, double a, double
  * rocprofv3 reports it: ties a profile to the kernel that ran (bench.py). */
 int32_t srhip_last_kernel_name(char* buf, int32_t len);
 
+/* The geometry of the loss tree-code launch the calling thread made last:
+ * out6 = {row groups, tree groups, trees per group, workgroups launched, first
+ * row group whose tree groups are split over several workgroups (= row groups:
+ * none), workgroups per tree group there (1: none)}; zeros before any. */
+int32_t srhip_last_loss_launch(int32_t* out6);
+
 /* ---- dataset: Dataset(X, y; weights) src/Dataset.jl:43-64 ----------------
  * Uploads rows [row_begin, row_end) of X / y / w once (the row shard of this
  * device); X is transposed to feature-major on the device. w may be NULL

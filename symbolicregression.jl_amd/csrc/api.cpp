@@ -37,6 +37,12 @@ thread_local const char* t_last_kernel = "";
 }
 void note_kernel(const char* name) { t_last_kernel = name ? name : ""; }
 const char* last_kernel() { return t_last_kernel; }
+static thread_local int t_loss_launch[6] = {0, 0, 0, 0, 0, 0};
+void note_loss_launch(int nrg, int ntg, int tpb, unsigned grid, int tbig, int tsub) {
+  const int v[6] = {nrg, ntg, tpb, (int)grid, tbig, tsub};
+  std::copy(v, v + 6, t_loss_launch);
+}
+const int* last_loss_launch() { return t_loss_launch; }
 int& host_thread_cap() {
   thread_local int cap = 0;
   return cap;
@@ -1514,6 +1520,70 @@ void tail_split(const srhip_ctx* c, EvalPlan* plan, int64_t rows, int jw) {
   plan->nrg = (int)(nbig + nsmall);
 }
 
+// The tail split along trees (tail_map.h; loss tree code under its
+// hand-written loops). A launch of many rounds ends on whole workgroups: with
+// config #2's 241 trees per group one lasts ≈ 0.18 ms, and every compute unit
+// waits on units of that size while the launch drains. The row-wise split
+// above does not apply there (the last round is nearly full) and cuts the
+// wrong way for this kernel: a quarter of the rows per call multiplies the
+// per-call costs by 4. Here the last row groups keep their tiles per call and
+// each of their tree groups is run by S workgroups, launched last: the same
+// calls, in units a S-th the size.
+//   SRHIP_JIT_TAIL_TREES   S: 2, 4 or 8; 1 none; 0 the largest of them that
+//                          leaves every wave at least 4 trees; unset: 4, or
+//                          fewer by that rule
+//   SRHIP_JIT_TAIL_ROUNDS  the split workgroups come to this many rounds of
+//                          the resident workgroups (rounds as tail_split
+//                          counts them; a fraction is fine)
+//   SRHIP_JIT_TAIL_RG      n >= 0: the last n row groups are split whatever
+//                          the rounds (tests: a small grid never fills one)
+// All read per launch. SRHIP_JIT_TAIL=0 turns this split off as well. The
+// split workgroups are launched last and walk unrotated (jit_template.hip);
+// by rounds they never reach into the first round, whose simultaneous start
+// the rotation is there for (forced by SRHIP_JIT_TAIL_RG they may: that costs
+// speed, never a result). Defaults from the sweep S ∈ {2, 4, 8} × rounds ∈ {1, 1.5, 2}
+// (profiles/tail_trees_sweep.json, one process, settings alternating): config
+// #2 at 1M rows 2.299 ms unsplit, 2.281 / 2.280 / 2.281 (S = 2), 2.264 / 2.265
+// / 2.268 (S = 4), 2.284 / 2.270 / 2.265 (S = 8); its 125k-row shard and the
+// 512-tree shard unchanged within their spread. DESIGN.md §3.1.
+constexpr int kTailTreesDefault = 4;
+constexpr double kTailRoundsDefault = 1.5;
+void tail_trees(const srhip_ctx* c, EvalPlan* plan, int jw) {
+  plan->tbig = -1;
+  plan->tsub = 1;
+  if (!env_on("SRHIP_JIT_TAIL") || plan->nbig >= 0 || plan->nrg < 1) return;
+  // unset: the default, or fewer where it would leave a wave under 4 trees; 0: the same rule from 8
+  const char* es = std::getenv("SRHIP_JIT_TAIL_TREES");
+  int S = es ? std::atoi(es) : kTailTreesDefault;
+  if (!es || S == 0)
+    for (S = S == 0 ? 8 : S; S > 1 && plan->tpb / (S * std::max(1, jw)) < 4;) S >>= 1;
+  if (S != 2 && S != 4 && S != 8) return;
+  const int forced = env_int("SRHIP_JIT_TAIL_RG", -1);
+  int64_t ntail;
+  if (forced >= 0) {
+    ntail = std::min<int64_t>(forced, plan->nrg);
+  } else {
+    const char* e = std::getenv("SRHIP_JIT_TAIL_ROUNDS");
+    const double rounds = e ? std::atof(e) : kTailRoundsDefault;
+    const int64_t conc = (int64_t)device_cus(c) * std::max(1, 20 / jw);
+    const int64_t first = (conc + plan->ntg - 1) / plan->ntg;  // row groups of the first round
+    if (!(rounds > 0.0)) return;
+    ntail = std::min<int64_t>((int64_t)(rounds * (double)conc / ((double)plan->ntg * S) + 0.5), plan->nrg - first);
+  }
+  if (ntail < 1) return;
+  int64_t tbig = plan->nrg - ntail;
+  if (forced < 0 && rg_xcd()) {
+    // the XCD-dealt block order runs the head in whole octets of row groups (no padding blocks
+    // there): tbig down to a multiple of 8, but not into the first round
+    const int64_t first = ((int64_t)device_cus(c) * std::max(1, 20 / jw) + plan->ntg - 1) / plan->ntg;
+    tbig &= ~(int64_t)7;
+    if (tbig < first) tbig = (first + 7) & ~(int64_t)7;
+    if (tbig >= plan->nrg) return;
+  }
+  plan->tbig = (int)tbig;
+  plan->tsub = S;
+}
+
 // The skeleton of the tree-code modules built at first use: the module cached
 // under (kind, bits), else the program's trees compiled again with the
 // constants of the first build (`consts`), `build` run on them, a module whose
@@ -1970,6 +2040,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
       return false;
     plan->threads = 64 * jw;
     tail_split(c, plan, rows, jw);
+    if (mode == MODE_LOSS) tail_trees(c, plan, jw);
     return true;
   };
   // A call with a pass whose row tile does not fit in LDS (the tree code's, or an interpreter
@@ -3155,6 +3226,14 @@ int32_t srhip_last_kernel_name(char* buf, int32_t len) {
   return guarded([&] {
     if (!buf || len <= 0) throw Error(SRHIP_ERR_INVALID, "null or empty buffer");
     std::snprintf(buf, (size_t)len, "%s", srhip::last_kernel());
+    return SRHIP_OK;
+  });
+}
+
+int32_t srhip_last_loss_launch(int32_t* out6) {
+  return guarded([&] {
+    if (!out6) throw Error(SRHIP_ERR_INVALID, "null buffer");
+    std::copy(srhip::last_loss_launch(), srhip::last_loss_launch() + 6, out6);
     return SRHIP_OK;
   });
 }

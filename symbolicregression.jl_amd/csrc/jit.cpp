@@ -43,6 +43,7 @@
 #include <unordered_map>
 
 #include "jit_asm.h"
+#include "tail_map.h"
 
 #define HIP_CHECK(expr)                                                                  \
   do {                                                                                   \
@@ -2115,6 +2116,7 @@ struct JitArgs {
   int dyn;
   const float* gcols;  // [ngcol][n_pad] shared-subtree columns of this call, or null
   int rot_step, rot_nrg;  // the row groups' starting offsets into their tree walk (launch)
+  int tbig, tsub;         // tree groups of the row groups [tbig, nrg) run by tsub workgroups each (tail_map.h)
 };
 struct DeriveArgs {
   const float* X;
@@ -2247,8 +2249,8 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
   ja.part_lds = part_bytes <= 8192 && !part_global() ? 1 : 0;
   size_t sz = sizeof(ja);
   void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ja, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  const unsigned grid = a.rotate >= 2 ? (unsigned)((a.nrg + 7) / 8 * 8) * (unsigned)a.ntg
-                                      : (unsigned)a.nrg * (unsigned)a.ntg;
+  unsigned grid = a.rotate >= 2 ? (unsigned)((a.nrg + 7) / 8 * 8) * (unsigned)a.ntg
+                                : (unsigned)a.nrg * (unsigned)a.ntg;
   // SRHIP_JIT_LDS_PAD (experiments): extra LDS per workgroup, i.e. fewer resident waves
   static const unsigned pad = [] { const char* e = std::getenv("SRHIP_JIT_LDS_PAD"); return e ? (unsigned)std::atoi(e) : 0u; }();
   // LDS: the row tiles (+ the partials when part_lds)
@@ -2273,6 +2275,19 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
     fn = a.w ? q.fn_dlpw : q.fn_dlp;
     name = a.w ? "sr_jit_eval_dlpw" : "sr_jit_eval_dlp";
   }
+  // The tail split along trees (api.cpp tail_trees, tail_map.h): the
+  // hand-written loss loops only, in the plain or the XCD-dealt block order
+  // (not SRHIP_TG_MAJOR's), snake-dealt slots. Every other driver runs one
+  // workgroup per tree group.
+  ja.tbig = a.nrg;
+  ja.tsub = 1;
+  if (q.fn_dl && !m->out && dynloop() && a.rotate <= 2 && !a.contig && plan.tsub > 1 && plan.tbig >= 0 &&
+      plan.tbig < a.nrg) {
+    ja.tbig = plan.tbig;
+    ja.tsub = plan.tsub;
+    grid = tail_grid(tail_map(a.nrg, a.ntg, ja.tbig, ja.tsub, a.rotate == 2));
+  }
+  if (!m->out) note_loss_launch(a.nrg, a.ntg, a.tpb, grid, ja.tbig, ja.tsub);
   note_kernel(name);
   return hipModuleLaunchKernel(fn, grid, 1, 1, (unsigned)plan.threads, 1, 1, (unsigned)lds + pad, stream, nullptr, cfg);
 }

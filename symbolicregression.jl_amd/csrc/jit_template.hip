@@ -20,6 +20,7 @@
 
 #include "interp.h"
 #include "kernels.h"
+#include "tail_map.h"
 #include "gen/jit_layout_r4.h"
 #include "gen/jit_routines_r4.inc"
 
@@ -89,6 +90,8 @@ struct JitArgs {
                             // reads column g of this row group at s[36:37] + g·s38 (literal code only)
   int rot_step, rot_nrg;    // loss loops: row group rg < rot_nrg starts its tree walk at (rg·rot_step) mod tpb
                             // (jit.cpp launch, SRHIP_JIT_ROTATE); 0, 0: every row group at tree 0
+  int tbig, tsub;           // hand-written loss loops: each tree group of the row groups [tbig, nrg) is run by
+                            // tsub workgroups (tail_map.h); tsub = 1: none is
 };
 
 // Where row group rg starts its walk over the tree group's list positions:
@@ -396,18 +399,69 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
 //   memory-constant code (sr_jit_loop_m): s[98:99] the programs, s[100:101]
 //   list_off, each tree's program address into s[56:57] (SR_JIT_LOOP_PROG),
 //   s65-s68 / s79 / s84 as for the compiled loop; return address s[94:95];
-//   temps s58-s63, s96-s97, v0-v2, v89-v91.
-// The loop ends on a claim k >= tpb; a position whose slot is past nlist (the
+//   v89 the counter's step S (lane 0; no tree code or routine writes v89, so
+//   it is set once by the driver); temps s58-s63, s96-s97, v0-v2, v90-v91.
+// A tree group split over S workgroups (tail_map.h): the driver starts the
+// counter at `sub` and every claim adds S, so a claim is the list position
+// i = k·S + sub itself and costs what it costs unsplit (S = 1, sub = 0: the
+// counter counts the claims, as it always did; no branch on the mode).
+// The loop ends on a claim i >= tpb; a position whose slot is past nlist (the
 // ragged last positions, which a rotated walk meets before its end) is passed
 // over and the next one claimed.
 // Per tree i (slot s = i*ntg + (i odd ? ntg-1-g : g)): a set failure flag
-// skips it (partial {0, NaN}); else its code runs; a bail (s69 != 0) sets the
+// skips it (partial 0); else its code runs; a bail (s69 != 0) sets the
 // slot's bail flag and counts it; the loss is summed over the wave in the
-// order of interp.h wave_sum; lane 0 stores the partial {Σ, NaN or 0} and, if
-// some row failed, the slot's failure flag (vector stores only).
+// order of interp.h wave_sum; the partial Σ is stored and, if some row
+// failed, the slot's failure flag (vector stores only).
+//
+// The sum and the stores, shared by the three loops (XS: where exec is kept).
+// The last two steps of wave_sum add lane 15 of the row below into rows 1 and
+// 3, then lane 31 into rows 2 and 3: written as v_add_f32_dpp under a row
+// mask they are the same two additions on every lane that reaches lane 63
+// (rows 0 and 2 added a zero there before; they are never read again). Lane
+// 63 then stores its own v1 (exec = lane 63): no v_readlane, no copy. The
+// partial's LDS address is formed on the scalar side.
+#define SR_JIT_LOOP_SUM_TEXT(NAME, XS)                                                    \
+  ".L" #NAME "_sum:\n"                                                                      \
+  "v_cmp_u_f32_e32 vcc, v40, v40\n"                                                   \
+  "s_nop 1\n"                                                                         \
+  "v_add_f32_dpp v1, v42, v42 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
+  "s_nop 1\n"                                                                         \
+  "v_add_f32_dpp v1, v1, v1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
+  "s_nop 1\n"                                                                         \
+  "v_add_f32_dpp v1, v1, v1 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
+  "s_nop 1\n"                                                                         \
+  "v_add_f32_dpp v1, v1, v1 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n"     \
+  "s_nop 1\n"                                                                         \
+  "v_add_f32_dpp v1, v1, v1 row_bcast:15 row_mask:0xa bank_mask:0xf\n"                \
+  "s_nop 1\n"                                                                         \
+  "v_add_f32_dpp v1, v1, v1 row_bcast:31 row_mask:0xc bank_mask:0xf\n"                \
+  "s_cmp_lg_u64 vcc, 0\n"                                                             \
+  "s_cselect_b32 s63, 0x7fc00000, 0\n"                                                \
+  "s_mov_b64 " XS ", exec\n"                                                          \
+  "s_lshl_b64 exec, 1, 63\n"                                                          \
+  "s_lshl_b32 s62, s60, 2\n"                                                          \
+  "s_cmp_eq_u32 s52, 0\n"                                                             \
+  "s_cbranch_scc1 .L" #NAME "_g1\n"                                                         \
+  "s_add_u32 s62, s62, s53\n"                                                         \
+  "v_mov_b32_e32 v2, s62\n"                                                           \
+  "ds_write_b32 v2, v1\n"                                                         \
+  "s_branch .L" #NAME "_st1\n"                                                              \
+  ".L" #NAME "_g1:\n"                                                                       \
+  "v_mov_b32_e32 v2, s62\n"                                                           \
+  "global_store_dword v2, v1, s[50:51]\n"                                       \
+  ".L" #NAME "_st1:\n"                                                                      \
+  "s_cmp_eq_u32 s63, 0\n"                                                             \
+  "s_cbranch_scc1 .L" #NAME "_nf\n"                                                         \
+  "s_lshl_b32 s62, s61, 2\n"                                                          \
+  "v_mov_b32_e32 v2, s62\n"                                                           \
+  "v_mov_b32_e32 v0, 1\n"                                                             \
+  "global_store_dword v2, v0, s[46:47] sc1\n"                                         \
+  ".L" #NAME "_nf:\n"                                                                       \
+  "s_mov_b64 exec, " XS "\n"                                                          \
+  "s_branch .L" #NAME "_next\n"
 #define SR_JIT_LOOP_TEXT(NAME, PROG, ROT)                                                         \
   ".globl " #NAME "\n.hidden " #NAME "\n.p2align 6\n" #NAME ":\n"               \
-  "v_mov_b32_e32 v89, 1\n"                                                            \
   ".L" #NAME "_next:\n"                                                                     \
   "s_mov_b64 s[58:59], exec\n"                                                        \
   "s_mov_b64 exec, 1\n"                                                               \
@@ -443,7 +497,6 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "v_mov_b32_e32 v40, 0\n"                                                            \
   "s_mov_b32 s64, 0\n"                                                                \
   "s_swappc_b64 s[76:77], s[96:97]\n"                                                 \
-  "v_mov_b32_e32 v89, 1\n"                                                            \
   "s_cmp_eq_u32 s69, 0\n"                                                             \
   "s_cbranch_scc1 .L" #NAME "_sum\n"                                                        \
   "v_mov_b32_e32 v40, 0x7fc00000\n"                                                   \
@@ -451,54 +504,12 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "s_mov_b64 exec, 1\n"                                                               \
   "s_lshl_b32 s62, s61, 2\n"                                                          \
   "v_mov_b32_e32 v90, s62\n"                                                          \
-  "global_store_dword v90, v89, s[54:55] sc1\n"                                       \
+  "v_mov_b32_e32 v91, 1\n"                                                            \
+  "global_store_dword v90, v91, s[54:55] sc1\n"                                       \
   "v_mov_b32_e32 v90, 0\n"                                                            \
-  "global_atomic_add v90, v89, s[92:93]\n"                                            \
+  "global_atomic_add v90, v91, s[92:93]\n"                                            \
   "s_mov_b64 exec, s[58:59]\n"                                                        \
-  ".L" #NAME "_sum:\n"                                                                      \
-  "v_cmp_u_f32_e32 vcc, v40, v40\n"                                                   \
-  "s_nop 1\n"                                                                         \
-  "v_add_f32_dpp v1, v42, v42 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
-  "s_nop 1\n"                                                                         \
-  "v_add_f32_dpp v1, v1, v1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
-  "s_nop 1\n"                                                                         \
-  "v_add_f32_dpp v1, v1, v1 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
-  "s_nop 1\n"                                                                         \
-  "v_add_f32_dpp v1, v1, v1 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n"     \
-  "v_mov_b32_e32 v2, 0\n"                                                             \
-  "s_nop 1\n"                                                                         \
-  "v_mov_b32_dpp v2, v1 row_bcast:15 row_mask:0xa bank_mask:0xf\n"                    \
-  "v_add_f32_e32 v1, v1, v2\n"                                                        \
-  "v_mov_b32_e32 v2, 0\n"                                                             \
-  "s_nop 1\n"                                                                         \
-  "v_mov_b32_dpp v2, v1 row_bcast:31 row_mask:0xc bank_mask:0xf\n"                    \
-  "v_add_f32_e32 v1, v1, v2\n"                                                        \
-  "s_nop 1\n"                                                                         \
-  "v_readlane_b32 s62, v1, 63\n"                                                      \
-  "s_cmp_lg_u64 vcc, 0\n"                                                             \
-  "s_cselect_b32 s63, 0x7fc00000, 0\n"                                                \
-  "s_mov_b64 s[58:59], exec\n"                                                        \
-  "s_mov_b64 exec, 1\n"                                                               \
-  "v_mov_b32_e32 v0, s62\n"                                                           \
-  "s_lshl_b32 s62, s60, 2\n"                                                          \
-  "s_cmp_eq_u32 s52, 0\n"                                                             \
-  "s_cbranch_scc1 .L" #NAME "_g1\n"                                                         \
-  "v_mov_b32_e32 v2, s53\n"                                                           \
-  "v_add_u32_e32 v2, s62, v2\n"                                                       \
-  "ds_write_b32 v2, v0\n"                                                         \
-  "s_branch .L" #NAME "_st1\n"                                                              \
-  ".L" #NAME "_g1:\n"                                                                       \
-  "v_mov_b32_e32 v2, s62\n"                                                           \
-  "global_store_dword v2, v0, s[50:51]\n"                                       \
-  ".L" #NAME "_st1:\n"                                                                      \
-  "s_cmp_eq_u32 s63, 0\n"                                                             \
-  "s_cbranch_scc1 .L" #NAME "_nf\n"                                                         \
-  "s_lshl_b32 s62, s61, 2\n"                                                          \
-  "v_mov_b32_e32 v2, s62\n"                                                           \
-  "global_store_dword v2, v89, s[46:47] sc1\n"                                        \
-  ".L" #NAME "_nf:\n"                                                                       \
-  "s_mov_b64 exec, s[58:59]\n"                                                        \
-  "s_branch .L" #NAME "_next\n"                                                             \
+  SR_JIT_LOOP_SUM_TEXT(NAME, "s[58:59]")                                              \
   ".L" #NAME "_skip:\n"                                                                     \
   "s_mov_b64 s[58:59], exec\n"                                                        \
   "s_mov_b64 exec, 1\n"                                                               \
@@ -506,8 +517,8 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "s_lshl_b32 s62, s60, 2\n"                                                          \
   "s_cmp_eq_u32 s52, 0\n"                                                             \
   "s_cbranch_scc1 .L" #NAME "_g2\n"                                                         \
-  "v_mov_b32_e32 v2, s53\n"                                                           \
-  "v_add_u32_e32 v2, s62, v2\n"                                                       \
+  "s_add_u32 s62, s62, s53\n"                                                         \
+  "v_mov_b32_e32 v2, s62\n"                                                           \
   "ds_write_b32 v2, v0\n"                                                         \
   "s_branch .L" #NAME "_st2\n"                                                              \
   ".L" #NAME "_g2:\n"                                                                       \
@@ -525,7 +536,6 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
 // rot in s98 (s45 holds the FAST / sticky flags here).
 #define SR_JIT_LOOP_PF_TEXT(NAME)                                                      \
   ".globl " #NAME "\n.hidden " #NAME "\n.p2align 6\n" #NAME ":\n"               \
-  "v_mov_b32_e32 v89, 1\n"                                                       \
   ".L" #NAME "_claim0:\n"                                                   \
   "s_mov_b64 s[96:97], exec\n"                                                   \
   "s_mov_b64 exec, 1\n"                                                          \
@@ -602,7 +612,6 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "v_mov_b32_e32 v40, 0\n"                                                            \
   "s_mov_b32 s64, 0\n"                                                                \
   "s_swappc_b64 s[76:77], s[96:97]\n"                                                 \
-  "v_mov_b32_e32 v89, 1\n"                                                            \
   "s_cmp_eq_u32 s84, s91\n"                                                          \
   "s_cbranch_scc1 .L" #NAME "_nore\n"                                       \
   "s_bitcmp1_b32 s45, 1\n"                                                           \
@@ -622,54 +631,12 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "s_mov_b64 exec, 1\n"                                                               \
   "s_lshl_b32 s62, s61, 2\n"                                                          \
   "v_mov_b32_e32 v90, s62\n"                                                          \
-  "global_store_dword v90, v89, s[54:55] sc1\n"                                       \
+  "v_mov_b32_e32 v91, 1\n"                                                            \
+  "global_store_dword v90, v91, s[54:55] sc1\n"                                       \
   "v_mov_b32_e32 v90, 0\n"                                                            \
-  "global_atomic_add v90, v89, s[92:93]\n"                                            \
+  "global_atomic_add v90, v91, s[92:93]\n"                                            \
   "s_mov_b64 exec, s[96:97]\n"                                                        \
-  ".L" #NAME "_sum:\n"                                                                      \
-  "v_cmp_u_f32_e32 vcc, v40, v40\n"                                                   \
-  "s_nop 1\n"                                                                         \
-  "v_add_f32_dpp v1, v42, v42 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
-  "s_nop 1\n"                                                                         \
-  "v_add_f32_dpp v1, v1, v1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
-  "s_nop 1\n"                                                                         \
-  "v_add_f32_dpp v1, v1, v1 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n" \
-  "s_nop 1\n"                                                                         \
-  "v_add_f32_dpp v1, v1, v1 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n"     \
-  "v_mov_b32_e32 v2, 0\n"                                                             \
-  "s_nop 1\n"                                                                         \
-  "v_mov_b32_dpp v2, v1 row_bcast:15 row_mask:0xa bank_mask:0xf\n"                    \
-  "v_add_f32_e32 v1, v1, v2\n"                                                        \
-  "v_mov_b32_e32 v2, 0\n"                                                             \
-  "s_nop 1\n"                                                                         \
-  "v_mov_b32_dpp v2, v1 row_bcast:31 row_mask:0xc bank_mask:0xf\n"                    \
-  "v_add_f32_e32 v1, v1, v2\n"                                                        \
-  "s_nop 1\n"                                                                         \
-  "v_readlane_b32 s62, v1, 63\n"                                                      \
-  "s_cmp_lg_u64 vcc, 0\n"                                                             \
-  "s_cselect_b32 s63, 0x7fc00000, 0\n"                                                \
-  "s_mov_b64 s[96:97], exec\n"                                                        \
-  "s_mov_b64 exec, 1\n"                                                               \
-  "v_mov_b32_e32 v0, s62\n"                                                           \
-  "s_lshl_b32 s62, s60, 2\n"                                                          \
-  "s_cmp_eq_u32 s52, 0\n"                                                             \
-  "s_cbranch_scc1 .L" #NAME "_g1\n"                                                         \
-  "v_mov_b32_e32 v2, s53\n"                                                           \
-  "v_add_u32_e32 v2, s62, v2\n"                                                       \
-  "ds_write_b32 v2, v0\n"                                                         \
-  "s_branch .L" #NAME "_st1\n"                                                              \
-  ".L" #NAME "_g1:\n"                                                                       \
-  "v_mov_b32_e32 v2, s62\n"                                                           \
-  "global_store_dword v2, v0, s[50:51]\n"                                       \
-  ".L" #NAME "_st1:\n"                                                                      \
-  "s_cmp_eq_u32 s63, 0\n"                                                             \
-  "s_cbranch_scc1 .L" #NAME "_nf\n"                                                         \
-  "s_lshl_b32 s62, s61, 2\n"                                                          \
-  "v_mov_b32_e32 v2, s62\n"                                                           \
-  "global_store_dword v2, v89, s[46:47] sc1\n"                                        \
-  ".L" #NAME "_nf:\n"                                                                       \
-  "s_mov_b64 exec, s[96:97]\n"                                                        \
-  "s_branch .L" #NAME "_next\n"                                                             \
+  SR_JIT_LOOP_SUM_TEXT(NAME, "s[96:97]")                                              \
   ".L" #NAME "_skip:\n"                                                                     \
   "s_mov_b64 s[96:97], exec\n"                                                        \
   "s_mov_b64 exec, 1\n"                                                               \
@@ -677,8 +644,8 @@ extern "C" __global__ void __launch_bounds__(1024) sr_jit_out_md(JitArgs ja) { j
   "s_lshl_b32 s62, s60, 2\n"                                                          \
   "s_cmp_eq_u32 s52, 0\n"                                                             \
   "s_cbranch_scc1 .L" #NAME "_g2\n"                                                         \
-  "v_mov_b32_e32 v2, s53\n"                                                           \
-  "v_add_u32_e32 v2, s62, v2\n"                                                       \
+  "s_add_u32 s62, s62, s53\n"                                                         \
+  "v_mov_b32_e32 v2, s62\n"                                                           \
   "ds_write_b32 v2, v0\n"                                                         \
   "s_branch .L" #NAME "_st2\n"                                                              \
   ".L" #NAME "_g2:\n"                                                                       \
@@ -714,12 +681,19 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
   const int ncol = ja.nraw + ja.nder;
   const int narr = 1 + ncol + (W ? 1 : 0);
   const int rows = a.ntiles * TILE;
-  int rg, g;
-  if (!block_of(a, rg, g)) return;
+  int rg, g, sub = 0, S = 1;
+  // a tree group of a tail row group is run by S workgroups, this one walking
+  // the list positions sub, sub + S, ... (tail_map.h; launch() asks for it
+  // in the plain and the XCD-dealt block orders, a.rotate 0 / 1 / 2)
+  const TailMap tm = tail_map(a.nrg, a.ntg, ja.tbig, ja.tsub, a.rotate == 2);
+  if (tm.S > 1 ? !tail_block(tm, blockIdx.x, rg, g, sub, S) : !block_of(a, rg, g)) return;
   const bool tail = rg >= ja.nbig;
   const int ntl = tail ? ja.ts : a.ntiles;
   const int64_t row0 = tail ? (int64_t)ja.nbig * rows + (int64_t)(rg - ja.nbig) * ja.ts * TILE : (int64_t)rg * rows;
   const int nthreads = __builtin_amdgcn_readfirstlane((int)blockDim.x);
+  // a sub-workgroup stores its partials straight to global memory: it never
+  // flushes positions it does not own
+  const int part_lds = S > 1 ? 0 : ja.part_lds;
   // 4-byte partials (Σ only): a failed tree is known from its slot's failure
   // flag, which every loop sets when a row fails (finalize_kernel part4)
   float* gdst = reinterpret_cast<float*>(a.partial) + (size_t)rg * ((size_t)a.ntg * a.tpb) + (size_t)g * a.tpb;
@@ -754,7 +728,7 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
       reinterpret_cast<float4*>(sX + (size_t)tk * TILE)[v] =
           reinterpret_cast<const float4*>(src + row0 + (int64_t)t * TILE)[v];
     }
-    if (threadIdx.x == 0) *cnt = 0u;
+    if (threadIdx.x == 0) *cnt = (uint32_t)sub;  // a claim is a list position: sub, sub + S, ...
   }
   __syncthreads();
 
@@ -781,14 +755,19 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
   const uint32_t nt_u = (uint32_t)nt_valid;
   const uint32_t fastok = (uint32_t)ja.fast;
   const uint32_t tpb = (uint32_t)a.tpb, ntg = (uint32_t)a.ntg, gg = (uint32_t)g, g1 = (uint32_t)(a.ntg - 1 - g);
-  const uint32_t nlist = (uint32_t)a.nlist, plds = (uint32_t)ja.part_lds;
+  const uint32_t nlist = (uint32_t)a.nlist, plds = (uint32_t)part_lds;
+  const uint32_t step = (uint32_t)S;  // v89: what a claim adds to the counter
   const uint64_t failp = reinterpret_cast<uint64_t>(a.fail), codep = reinterpret_cast<uint64_t>(ja.code_off);
   const uint64_t dstp = reinterpret_cast<uint64_t>(gdst), bailp = reinterpret_cast<uint64_t>(ja.bail);
   const uint64_t cntp = reinterpret_cast<uint64_t>(ja.counters);
   const uint64_t gcb = sgpr64(ja.gcols ? reinterpret_cast<uint64_t>(ja.gcols + row0) : 0ull);
   const uint32_t gstride = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a.n_pad * 4));
   uint32_t redos = 0;
-  const uint32_t rot = rot_of(ja, rg);  // s45 (sr_jit_loop, sr_jit_loop_m) / s98 (sr_jit_loop_p)
+  // s45 (sr_jit_loop, sr_jit_loop_m) / s98 (sr_jit_loop_p). Tail workgroups are
+  // launched last (api.cpp tail_trees keeps them out of the first round, whose
+  // simultaneous start the rotation spreads): they walk from position 0 (sub)
+  // in every rotate mode.
+  const uint32_t rot = S > 1 ? 0u : rot_of(ja, rg);
   if constexpr (MEMC) {
     const uint64_t progp = reinterpret_cast<uint64_t>(a.prog), lop = reinterpret_cast<uint64_t>(a.list_off);
     asm volatile(
@@ -797,13 +776,13 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
         "s_addc_u32 s97, s97, sr_jit_loop_m@rel32@hi+12\n"
         "s_swappc_b64 s[94:95], s[96:97]"
         : "+{s84}"(redos)
-        : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
+        : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{v89}"(step), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
           "{s68}"(woff), "{s79}"(fastok), "{s40}"(tpb), "{s41}"(ntg), "{s42}"(gg), "{s43}"(g1), "{s44}"(nlist),
           "{s[46:47]}"(failp), "{s[48:49]}"(codep), "{s[50:51]}"(dstp), "{s52}"(plds), "{s53}"(spart),
           "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[98:99]}"(progp), "{s[100:101]}"(lop),
           "{s45}"(rot)
         : SR_JIT_CLOBBERS_MEMC, "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s69", "s91", "s94",
-          "s95", "s96", "s97", "v40", "v41", "v42", "v89", "v90", "v91", "memory");
+          "s95", "s96", "s97", "v40", "v41", "v42", "v90", "v91", "memory");
   } else if constexpr (PF) {
     const uint32_t fastflags = fastok | (ja.dyn ? 2u : 0u);  // JitArgs::dyn: sticky PRECISE per tree
     asm volatile(
@@ -812,13 +791,13 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
         "s_addc_u32 s97, s97, sr_jit_loop_p@rel32@hi+12\n"
         "s_swappc_b64 s[94:95], s[96:97]"
         : "+{s84}"(redos)
-        : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
+        : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{v89}"(step), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
           "{s68}"(woff), "{s45}"(fastflags), "{s40}"(tpb), "{s41}"(ntg), "{s42}"(gg), "{s43}"(g1), "{s44}"(nlist),
           "{s[46:47]}"(failp), "{s[48:49]}"(codep), "{s[50:51]}"(dstp), "{s52}"(plds), "{s53}"(spart),
           "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[36:37]}"(gcb), "{s38}"(gstride),
           "{s98}"(rot)
         : SR_JIT_CLOBBERS, "s23", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s69", "s79", "s91", "s94", "s95",
-          "s96", "s97", "v40", "v41", "v42", "v89", "v90", "v91", "v92", "memory");
+          "s96", "s97", "v40", "v41", "v42", "v90", "v91", "v92", "memory");
   } else {
     asm volatile(
         "s_getpc_b64 s[96:97]\n"
@@ -826,18 +805,18 @@ __device__ __forceinline__ void jit_eval_dl_body(const JitArgs& ja) {
         "s_addc_u32 s97, s97, sr_jit_loop@rel32@hi+12\n"
         "s_swappc_b64 s[94:95], s[96:97]"
         : "+{s84}"(redos)
-        : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
+        : "{v30}"(lds_lane), "{v31}"(cnt_addr), "{v43}"(lane4), "{v89}"(step), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
           "{s68}"(woff), "{s79}"(fastok), "{s40}"(tpb), "{s41}"(ntg), "{s42}"(gg), "{s43}"(g1), "{s44}"(nlist),
           "{s[46:47]}"(failp), "{s[48:49]}"(codep), "{s[50:51]}"(dstp), "{s52}"(plds), "{s53}"(spart),
           "{s[54:55]}"(bailp), "{s[92:93]}"(cntp), "{s[88:89]}"(area), "{s[36:37]}"(gcb), "{s38}"(gstride),
           "{s45}"(rot)
         : SR_JIT_CLOBBERS, "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s69", "s91", "s94", "s95", "s96", "s97",
-          "v40", "v41", "v42", "v89", "v90", "v91", "memory");
+          "v40", "v41", "v42", "v90", "v91", "memory");
   }
   if (lane == 0 && __builtin_amdgcn_readfirstlane((int)redos) != 0)
     __hip_atomic_fetch_add(ja.counters + 1, (uint32_t)__builtin_amdgcn_readfirstlane((int)redos),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (ja.part_lds) {  // slots no wave ran keep whatever: finalize ignores them
+  if (part_lds) {  // slots no wave ran keep whatever: finalize ignores them
     __syncthreads();
     const float* sPart4 = reinterpret_cast<const float*>(sPart);
     for (int i = threadIdx.x; i < a.tpb; i += nthreads) gdst[i] = sPart4[i];

@@ -74,6 +74,10 @@ struct EvalPlan {
   // tree code only: row groups [0, nbig) of ntiles tiles, then row groups of
   // ts tiles (the last round of workgroups in smaller pieces); nbig < 0: all full
   int nbig = -1, ts = 0;
+  // loss tree code only (tail_map.h): each tree group of the row groups
+  // [tbig, nrg) is run by tsub workgroups, launched after all the others;
+  // tsub = 1: every tree group is one workgroup
+  int tbig = -1, tsub = 1;
   // the wide kernel variant (eval_kernel.h / grad_kernels.hip XG): X is read from
   // global memory, LDS holds y, w and the partial slots only
   bool wide = false;

@@ -192,6 +192,10 @@ constexpr int kExprOpMaxDepth = 4;
 // rocprofv3 PMC summary to the kernel that ran).
 void note_kernel(const char* name);
 const char* last_kernel();
+// The geometry of the loss tree-code launch the calling thread made last
+// (jit.cpp launch; srhip_last_loss_launch): nrg, ntg, tpb, grid, tbig, tsub.
+void note_loss_launch(int nrg, int ntg, int tpb, unsigned grid, int tbig, int tsub);
+const int* last_loss_launch();
 
 // The most host threads a program build on the calling thread may start
 // (0: no cap beyond each builder's own). The members of a device group build

@@ -72,6 +72,7 @@ SIGNATURES = {
     "srhip_op_lookup": [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "srhip_op_eval": [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double)],
     "srhip_last_kernel_name": [C.c_char_p, C.c_int32],
+    "srhip_last_loss_launch": [C.POINTER(C.c_int32)],
     "srhip_loss_expr_create": [C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_double),
                                C.c_int32, C.POINTER(C.c_int32)],
     "srhip_loss_expr_destroy": [C.c_int32],

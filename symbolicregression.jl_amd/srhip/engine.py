@@ -73,6 +73,12 @@ class Context:
         check(lib().srhip_last_kernel_name(buf, 128))
         return buf.value.decode()
 
+    def last_loss_launch(self):
+        """Geometry of the loss tree-code launch this thread made last (srhip_last_loss_launch)."""
+        v = (C.c_int32 * 6)()
+        check(lib().srhip_last_loss_launch(v))
+        return dict(zip(("nrg", "ntg", "tpb", "grid", "tbig", "tsub"), (int(x) for x in v)))
+
     def last_tree_code(self) -> int:
         """Trees the last eval ran as tree code (srhip_last_tree_code)."""
         n = C.c_int32(0)

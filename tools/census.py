@@ -19,7 +19,14 @@ walked instead (forward, loss, reverse pass of one interior tile; defaults
 16384 trees x 20 features x 1.25M rows), routines by name, the tree's own
 code split into forward ("tree") and everything after the loss ("reverse").
 
-Usage: python tools/census.py [--ntrees 4096] [--grad] [--json out.json]
+The hand-written tree loop around the calls (csrc/jit_template.hip
+SR_JIT_LOOP_PF_TEXT) is priced too, "per call": its text is parsed from the
+source, its main path walked (a tree that runs, no redo mark, no bail, the
+partial to LDS, no failure flag to set), its VALU priced with the same class
+prices and counted once per tree per row group. --loop-source FILE prices the
+loop text of another jit_template.hip (an earlier revision's).
+
+Usage: python tools/census.py [--ntrees 4096] [--grad] [--json out.json] [--loop-source FILE]
 """
 import argparse
 import collections
@@ -61,6 +68,60 @@ def vclass(m):
     if m.endswith("_f64") and re.match(r"^v_(fma|mul|add)_f64", m):
         return "f64"
     return "other"
+
+
+def loop_text(source, macro):
+    """The instructions of a loop-text macro of jit_template.hip, the macros it
+    uses expanded: [(label or None, instruction or None)]."""
+    src = Path(source).read_text()
+
+    def body(name):
+        m = re.search(r"^#define " + name + r"\b[^\n]*\\\n((?:.*\\\n)*.*\n)", src, re.M)
+        if not m:
+            raise SystemExit(f"census: no macro {name} in {source}")
+        out = []
+        for line in m.group(1).splitlines():
+            line = line.rstrip("\\").strip()
+            call = re.match(r"(SR_JIT_LOOP_\w+_TEXT)\(", line)
+            if call:
+                out += body(call.group(1))
+                continue
+            # the line's string pieces joined, the #NAME pieces between them as NAME
+            text = "".join(re.findall(r'"((?:[^"\\]|\\.)*)"', re.sub(r'"\s*#NAME\s*"', "NAME", line)))
+            for piece in text.split("\\n"):
+                piece = piece.strip()
+                if not piece or piece.startswith((".globl", ".hidden", ".p2align")):
+                    continue
+                out.append((piece[:-1], None) if piece.endswith(":") else (None, piece))
+        return out
+
+    return body(macro)
+
+
+def walk_loop(items):
+    """VALU / SALU / s_nop counts of one tree call on the loop's main path: from
+    .L*_next to the branch back to it."""
+    taken = ("_nore", "_sum", "_nf")  # no redo mark to set, no bail, no failure flag to store
+    labels = {lab: k for k, (lab, _) in enumerate(items) if lab}
+    start = next(k for lab, k in labels.items() if lab.endswith("_next"))
+    cnt = collections.Counter()
+    k, steps = start, 0
+    while steps < 10000:
+        steps += 1
+        lab, ins = items[k]
+        k += 1
+        if ins is None:
+            continue
+        m = ins.split()[0]
+        cnt[m if m.startswith(("v_", "ds_", "global_")) else "S:" + m] += 1
+        if m in ("s_branch", "s_cbranch_scc1", "s_cbranch_scc0"):
+            tgt = ins.split()[1].replace('"', "").replace(" ", "")
+            tgt = next(lb for lb in labels if tgt.endswith(lb[2:]) or lb == tgt)
+            if m == "s_branch" and tgt.endswith("_next"):
+                return cnt
+            if m == "s_branch" or (m == "s_cbranch_scc1" and tgt.endswith(taken)):
+                k = labels[tgt]
+    raise SystemExit("census: the loop's main path does not return to its start")
 
 
 def readelf_syms(path):
@@ -215,6 +276,9 @@ def main():
     ap.add_argument("--fclk", type=float, default=2.4e9)
     ap.add_argument("--json", default="")
     ap.add_argument("--by-place", action="store_true", help="per routine / tree-code opcode counts")
+    ap.add_argument("--loop-source", default=str(ROOT / "symbolicregression.jl_amd" / "csrc" / "jit_template.hip"))
+    ap.add_argument("--loop", default="SR_JIT_LOOP_PF_TEXT", help="the loop-text macro to price")
+    ap.add_argument("--tiles-per-call", type=int, default=4, help="tiles of a row group (one call runs them all)")
     args = ap.parse_args()
     dflt = dict(ntrees=16384, seed=5, rows=1_250_000, nfeat=20) if args.grad else \
         dict(ntrees=4096, seed=1000, rows=1_000_000, nfeat=5)
@@ -303,8 +367,22 @@ def main():
           f"{tot_epi.get('S:s_nop', 0)} s_nop); per tile {tot_cyc:.0f}")
     print(f"predicted VALU-issue time for {args.rows} rows: {pred_ms:.3f} ms at f_clk {args.fclk / 1e9:.2f} GHz; "
           f"{pred_valu / 1e9:.3f}e9 VALU wave-instructions per launch (tile bodies only)")
+    loop_ms = 0.0
+    if not args.grad:
+        lc = walk_loop(loop_text(args.loop_source, args.loop))
+        lcyc = cyc(lc)
+        nrg = (tiles + args.tiles_per_call - 1) // args.tiles_per_call
+        loop_ms = lcyc * len(offs) * nrg / (1024 * args.fclk) * 1e3
+        lval = sum(v for k, v in lc.items() if k.startswith("v_"))
+        print(f"per call, the driver loop ({args.loop}, main path): {lcyc:.1f} SIMD-cycles "
+              f"({lval} VALU: " + ", ".join(f"{v} {k}" for k, v in sorted(lc.items()) if k.startswith("v_")) +
+              f"; {sum(v for k, v in lc.items() if k.startswith('S:'))} SALU/branch of which {lc.get('S:s_nop', 0)} s_nop, "
+              f"{sum(v for k, v in lc.items() if k.startswith(('ds_', 'global_')))} LDS / memory), "
+              f"{100 * lcyc / (tot_cyc / max(len(offs), 1) * args.tiles_per_call):.1f} % of a call's "
+              f"{args.tiles_per_call} tile bodies; once per tree per row group ({len(offs)} x {nrg}): {loop_ms:.3f} ms")
+        print(f"predicted VALU-issue time, tile bodies and driver loop: {pred_ms + loop_ms:.3f} ms")
     if args.json:
-        Path(args.json).write_text(json.dumps(dict(
+        Path(args.json).write_text(json.dumps(dict(loop_ms=loop_ms,
             ntrees=len(offs), nodes=nodes, cost_model=COST, budget=[dict(ins=k, cls=cl, count=v, cycles=c)
                                                                     for k, cl, v, c in rows_budget],
             by_class=dict(by_class), by_place=dict(attrib), predicted_ms=pred_ms, valu_per_launch=pred_valu,
