@@ -131,11 +131,11 @@ extern "C" {
 #define SRHIP_LOSS_L1 1        /* |r|                                       */
 #define SRHIP_LOSS_LP 2        /* |r|^p,        params[0] = p               */
 #define SRHIP_LOSS_HUBER 3     /* |r|<=d ? r^2/2 : d(|r|-d/2), params[0]=d  */
-#define SRHIP_LOSS_LOGCOSH 4   /* log(cosh(r))                              */
+#define SRHIP_LOSS_LOGCOSH 4   /* log(cosh(r)), as log1p(cosh(r) - 1): no cancellation near r = 0 */
 #define SRHIP_LOSS_L1EPSINS 5  /* max(0, |r|-eps),  params[0] = eps         */
 #define SRHIP_LOSS_L2EPSINS 6  /* max(0, |r|-eps)^2, params[0] = eps        */
 #define SRHIP_LOSS_QUANTILE 7  /* r>=0 ? tau*r : (tau-1)*r,  params[0] = tau */
-#define SRHIP_LOSS_PERIODIC 8  /* 1 - cos(2πr/c), params[0] = c             */
+#define SRHIP_LOSS_PERIODIC 8  /* 1 - cos(2πr/c) = 2 sin²(πr/c), params[0] = c */
 #define SRHIP_LOSS_LOGITDIST 9 /* -log(4 e^r / (1+e^r)^2)                   */
 /* LPDistLoss{n} with an INTEGER n (LPDistLoss(3), not LPDistLoss(3.0)):
  * |r|^n by Julia's T^Integer — Float32 stays Float32 (|r|*|r|*|r| for n = 3,

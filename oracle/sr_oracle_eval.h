@@ -341,6 +341,15 @@ int CAT(oracle_eval_tree, SFX)(const uint8_t* kind, const uint16_t* arg,
   return ok;
 }
 
+/* ln cosh h, h >= 0, as log1p(2 sinh²(h/2)): the textbook |r| + log1p(exp(-2|r|)) - ln 2 cancels to the
+ * rounding grain of ln 2 near 0 (worse than 1e-9 of the value below |r| = 5e-4 in double). Clamped where
+ * sinh² would overflow; beyond it the slope is 1 to the last bit. */
+static inline double CAT(lncosh_d, SFX)(double h, double hmax) {
+  double hm = h < hmax ? h : hmax; /* a NaN h: hm = hmax, and h - hm is NaN */
+  double s = sinh(0.5 * hm);
+  return log1p(2.0 * s * s) + (h - hm);
+}
+
 /* elementwise distance losses, r = ŷ - y (docs/src/losses.md) */
 static inline double CAT(elem_loss_d, SFX)(int loss, const double* p, double r) {
   double ar = fabs(r);
@@ -349,12 +358,15 @@ static inline double CAT(elem_loss_d, SFX)(int loss, const double* p, double r) 
     case SRHIP_LOSS_L1: return ar;
     case SRHIP_LOSS_LP: return pow(ar, p[0]);
     case SRHIP_LOSS_HUBER: return ar <= p[0] ? 0.5 * r * r : p[0] * (ar - 0.5 * p[0]);
-    case SRHIP_LOSS_LOGCOSH: return ar + log1p(exp(-2.0 * ar)) - 0.69314718055994530942;
+    case SRHIP_LOSS_LOGCOSH: return CAT(lncosh_d, SFX)(ar, 700.0);
     case SRHIP_LOSS_L1EPSINS: return ar > p[0] ? ar - p[0] : 0.0;
     case SRHIP_LOSS_L2EPSINS: { double e = ar > p[0] ? ar - p[0] : 0.0; return e * e; }
     case SRHIP_LOSS_QUANTILE: return r >= 0 ? p[0] * r : (p[0] - 1.0) * r;
-    case SRHIP_LOSS_PERIODIC: return 1.0 - cos(r * (2.0 * 3.14159265358979323846 / p[0])); /* k = 2π/c stored, 1 - cos(r·k) */
-    case SRHIP_LOSS_LOGITDIST: return ar + 2.0 * log1p(exp(-ar)) - 1.38629436111989061883;
+    case SRHIP_LOSS_PERIODIC: { /* k = 2π/c stored; 1 - cos(r·k) = 2 sin²(r·k/2), which does not cancel near r = 0 */
+      double s = sin(0.5 * (r * (2.0 * 3.14159265358979323846 / p[0])));
+      return 2.0 * s * s;
+    }
+    case SRHIP_LOSS_LOGITDIST: return 2.0 * CAT(lncosh_d, SFX)(0.5 * ar, 700.0); /* 2 ln cosh(r/2) */
   }
   return NAN;
 }

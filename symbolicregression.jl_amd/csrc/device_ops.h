@@ -557,14 +557,30 @@ __device__ __forceinline__ double cw_trig(double x, bool& big, int qshift) {
   return (q == 1 || q == 2) ? -v : v;
 }
 __device__ __forceinline__ double cw_cos(double x, bool& big) { return cw_trig(x, big, 0); }
-// Float32 data's PeriodicLoss value, 1 - cos(r·k), k = 2π/c (LossFunctions'
-// PeriodicLoss stores k); the interpreter's and, but for a tile with some
+// 1 - cos x as 2·sin²(x/2) by the same routine: 1 - cos x cancels to the rounding grain of 1
+// (1e-16 absolute, all of the value below |x| = 1e-8 and 1e-2 of it at 1e-7: a converged fit);
+// the square of a relatively accurate sine does not. `big` is still |x| > kCwCosMax.
+__device__ __forceinline__ double cw_versin(double x, bool& big) {
+  bool half_big;
+  const double s = cw_trig(0.5 * x, half_big, 3);
+  big = !(__builtin_fabs(x) <= kCwCosMax);
+  return 2.0 * s * s;
+}
+// PeriodicLoss's value 1 - cos(r·k) = 2·sin²(r·k/2), k = 2π/c (LossFunctions' PeriodicLoss stores k),
+// for Float64 data
+__device__ __forceinline__ double periodic_f64(double r, double p) {
+  const double s = m_sin(0.5 * (r * (6.28318530717958647692 / p)));
+  return 2.0 * s * s;
+}
+// and for Float32 data: the interpreter's and, but for a tile with some
 // |r·k| > kCwCosMax (handed back), the tree code's
 __device__ __forceinline__ double periodic_f32(double r, double p) {
   const double x = r * (6.28318530717958647692 / p);
   bool big;
-  const double c = cw_cos(x, big);
-  return 1.0 - (big ? m_cos(x) : c);
+  const double v = cw_versin(x, big);
+  if (!big) return v;
+  const double s = m_sin(0.5 * x);
+  return 2.0 * s * s;
 }
 
 // LPDistLoss's dℓ/dr of Float64 data for the Float64 gradient tree code
@@ -593,9 +609,9 @@ __device__ __forceinline__ double lp_dloss_f64(double a, double p) {
 __device__ __forceinline__ double periodic_g_f32(double r, double p, bool deriv) {
   const double k = 6.28318530717958647692 / p;
   bool big;
-  const double v = cw_trig(r * k, big, deriv ? 3 : 0);
+  const double v = deriv ? cw_trig(r * k, big, 3) : cw_versin(r * k, big);
   if (big) return __builtin_nan("");
-  return deriv ? k * v : 1.0 - v;
+  return deriv ? k * v : v;
 }
 
 // |r|^n of LPDistLoss{n} for an INTEGER n (SRHIP_LOSS_LPINT). Julia's
@@ -671,9 +687,14 @@ __device__ __forceinline__ double mg_cosh(double x) { return cosh(x); }
 // a^n of DWDMargin for its integral q (check_loss) by squaring: a loop over the
 // wave-uniform n that fits the tree code's loss routine, as LPINT's, and keeps
 // margin_loss_ool free of pow's registers.
+// Float32 data round the Float64 power once; Float64 data have no wider type to round from, and plain squaring
+// leaves DWDMargin(3)'s L'(a) = -s^4 / a^4 2.7 ulp off (two roundings per power and the division): they take
+// ipow's products with their errors carried (within an ulp); a zero keeps the plain product, whose sign is
+// (-0)^q's (ipow's last fused multiply-add turns -0 into +0, and DWDMargin's c / a^q is ±Inf by that sign).
 template <typename T>
 __device__ __forceinline__ double margin_pow(double a, double q) {
-  return pow_by_squaring(a, (long long)q);
+  if constexpr (std::is_same<T, double>::value) return a == 0.0 ? pow_by_squaring(a, (long long)q) : ipow(a, (long long)q);
+  else return pow_by_squaring(a, (long long)q);
 }
 template <typename T>
 __device__ __forceinline__ double margin_loss_param(int kind, double p, double a) {
@@ -747,23 +768,19 @@ __device__ __forceinline__ double elem_loss_param(int kind, double p, double r) 
     // LossFunctions' PeriodicLoss stores k = 2π/c and evaluates 1 - cos(r·k)
     case SRHIP_LOSS_PERIODIC:
       if constexpr (std::is_same<T, float>::value) return periodic_f32(r, p);
-      else return 1.0 - m_cos(r * (6.28318530717958647692 / p));
+      else return periodic_f64(r, p);
   }
   return qnan<double>();
 }
-// LogitDist of a Float32 residual, |r| + 2·log1p(exp(-|r|)) - ln 4 = 2·ln cosh(r/2): the three
-// Float32 terms are about 1.39 near r = 0 and cancel to r²/4, which left the value with the
-// rounding grain of 1.39 (1e-7 absolute, 3e-4 of the loss at |r| = 0.03). With h = |r|/2 and
-// q = exp(-h), cosh(h) - 1 = (1 - q)² / 2q, and 1 - q is taken from its series to h^7 below
-// h = 0.5 (the h^8 term is 2e-7 of it there) and by subtraction above (q <= 0.61), so every
-// factor is relatively accurate (v_rcp_f32 is within 1 ulp, q a normal number) and so is the
-// loss: within 6e-7 of it at every |r|. Beyond |r| = 160, where q would underflow, the loss has
-// slope 1 to the last bit: the excess is added (0 below 160; an Inf or NaN residual stays one).
-// All Float32 and no IEEE division. The interpreters use it; the Float32 tree code's loss routine
-// does not (SR_LOSS_ROUTINE below): sums of 256 trees' batches over whole datasets.
-__device__ __forceinline__ float logitdist_f32(float ar) {
-  const float am = __builtin_fminf(ar, 160.0f);
-  const float h = 0.5f * am, qf = m_exp(-h);
+// ln cosh h of a Float32 h in [0, 80]. The textbook forms |r| + log1p(exp(-2|r|)) - ln 2 (LogCosh) and
+// |r| + 2·log1p(exp(-|r|)) - ln 4 (LogitDist = 2·ln cosh(r/2)) cancel near r = 0 to the rounding grain of
+// ln 2 (1e-7 absolute in Float32: 3e-4 of LogitDist at |r| = 0.03, all of LogCosh below |r| = 3e-4, where a
+// converged population then scores exactly 0). With q = exp(-h), cosh(h) - 1 = (1 - q)² / 2q, and 1 - q is
+// taken from its series to h^7 below h = 0.5 (the h^8 term is 2e-7 of it there) and by subtraction above
+// (q <= 0.61), so every factor is relatively accurate (v_rcp_f32 is within 1 ulp, q a normal number down to
+// exp(-80)) and so is the value: within 6e-7 of it at every h. All Float32 and no IEEE division.
+__device__ __forceinline__ float lncosh_f32(float h) {
+  const float qf = m_exp(-h);
   float s = 1.0f / 5040.0f;
   s = s * h - 1.0f / 720.0f;
   s = s * h + 1.0f / 120.0f;
@@ -774,7 +791,35 @@ __device__ __forceinline__ float logitdist_f32(float ar) {
   const float d = h < 0.5f ? s * h : 1.0f - qf;
   float x = d * d * (0.5f * __builtin_amdgcn_rcpf(qf));
   asm volatile("" : "+v"(x));  // the series' registers are free before log1p's are taken
-  return 2.0f * m_log1p(x) + (ar - am);
+  return m_log1p(x);
+}
+// LogitDist and LogCosh of a Float32 residual. Beyond |r| = 160 (80), where q would underflow, the loss has
+// slope 1 to the last bit: the excess is added (0 below; an Inf or NaN residual stays one). Every Float32
+// family uses them, the tree code's loss routines included.
+__device__ __forceinline__ float logitdist_f32(float ar) {
+  const float am = __builtin_fminf(ar, 160.0f);
+  return 2.0f * lncosh_f32(0.5f * am) + (ar - am);
+}
+__device__ __forceinline__ float logcosh_f32(float ar) {
+  const float am = __builtin_fminf(ar, 80.0f);
+  return lncosh_f32(am) + (ar - am);
+}
+// The same for Float64 data: cosh(h) - 1 = 2·sinh²(h/2), so ln cosh h = log1p(2·sinh²(h/2)) with no
+// cancellation (the three-term forms are worse than 1e-9 of the value below |r| = 5e-4). h is clamped at
+// 700 (sinh(350)² is finite), beyond which the slope is 1 to the last bit.
+__device__ __forceinline__ double lncosh_f64(double h) {
+  const double s = m_sinh(0.5 * h);
+  double x = 2.0 * s * s;
+  asm volatile("" : "+v"(x));  // sinh's registers are free before log1p's are taken
+  return m_log1p(x);
+}
+__device__ __forceinline__ double logitdist_f64(double ar) {
+  const double am = __builtin_fmin(ar, 1400.0);
+  return 2.0 * lncosh_f64(0.5 * am) + (ar - am);
+}
+__device__ __forceinline__ double logcosh_f64(double ar) {
+  const double am = __builtin_fmin(ar, 700.0);
+  return lncosh_f64(am) + (ar - am);
 }
 template <typename T>
 __device__ __forceinline__ T elem_loss(int kind, double p, T yhat, T y) {
@@ -784,12 +829,12 @@ __device__ __forceinline__ T elem_loss(int kind, double p, T yhat, T y) {
   switch (kind) {
     case SRHIP_LOSS_L2: return r * r;
     case SRHIP_LOSS_L1: return ar;
-    case SRHIP_LOSS_LOGCOSH: return ar + m_log1p(m_exp(T(-2) * ar)) - T(0.69314718055994530942);
+    case SRHIP_LOSS_LOGCOSH:
+      if constexpr (std::is_same<T, float>::value) return logcosh_f32(ar);
+      else return logcosh_f64(ar);
     case SRHIP_LOSS_LOGITDIST:
-#ifndef SR_LOSS_ROUTINE  // gen_jit.py: the Float32 tree code's loss routine keeps the three-term form
       if constexpr (std::is_same<T, float>::value) return logitdist_f32(ar);
-#endif
-      return ar + T(2) * m_log1p(m_exp(-ar)) - T(1.38629436111989061883);
+      else return logitdist_f64(ar);
     case SRHIP_LOSS_LPINT: return ipow(ar, (long long)p);  // T^Integer stays in T
   }
   return (T)elem_loss_param<T>(kind, p, (double)r);

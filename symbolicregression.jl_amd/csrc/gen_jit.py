@@ -95,9 +95,7 @@ def sgpr_pinned(name):
 def snippet_source(rg, routines):
     R = rg.R
     _, rest = rg.vstate()
-    # SR_LOSS_ROUTINE: device_ops.h keeps LogitDist's three-term Float32 form in the loss routine (the
-    # longer routine moved every routine after it and cost the L2 tree code 1.5 %)
-    out = ["#define SRHIP_INLINE_ALL 1", "#define SR_LOSS_ROUTINE 1", '#include "interp.h"',
+    out = ["#define SRHIP_INLINE_ALL 1", '#include "interp.h"',
            "using namespace srhip; using namespace srhip::interp;",
            "namespace {", "struct St {", f"  float a[{R}]; float b[{R}]; float chk;", f"  unsigned v[{len(rest)}];"]
     for n, _ in rg.sregs():
@@ -274,10 +272,10 @@ def routine_list():
             continue
         imm = ("const double imm = __builtin_bit_cast(double, ((unsigned long long)s.s_kh << 32) | "
                "(unsigned long long)s.s_k); ")
-        if name == "PERIODIC":  # Cody-Waite cos; a row beyond it hands the tile back (the bail flag)
+        if name == "PERIODIC":  # Cody-Waite 2·sin²(x/2); a row beyond it hands the tile back (the bail flag)
             body = (imm + "bool big = false; " +
                     rows_serial("bool b; const double x = (double)s.a[r] * (6.28318530717958647692 / imm); "
-                                "const double c = dev::cw_cos(x, b); big = big || b; s.a[r] = (float)(1.0 - c);") +
+                                "const double v = dev::cw_versin(x, b); big = big || b; s.a[r] = (float)v;") +
                     " const unsigned long long fl = __builtin_amdgcn_ballot_w64(big);"
                     " s.s_flag = (unsigned)fl; s.s_flag_hi = (unsigned)(fl >> 32);")
             rs.append((f"l_{name.lower()}", body, True))
@@ -315,6 +313,9 @@ def routine_list():
         rs.append((f"d_{name.lower()}",
                    imm + rows_serial(f"s.a[r] = dev::elem_dloss<float>(SRHIP_LOSS_{name}, imm, s.a[r], 0.0f);"),
                    False))
+    # l_logcosh and l_logitdist (device_ops.h lncosh_f32: longer than the three-term forms they replaced) go
+    # last: no other routine's offset inside its region moves with their length
+    rs.sort(key=lambda r: r[0] in ("l_logcosh", "l_logitdist"))
     return rs
 
 

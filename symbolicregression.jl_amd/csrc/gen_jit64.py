@@ -141,6 +141,10 @@ def rows(expr):
     return f"_Pragma(\"unroll\") for (int r = 0; r < R; ++r) {{ {expr} }}"
 
 
+def rows_serial(expr):
+    return " ".join("{ constexpr int r = %d; %s } __builtin_amdgcn_sched_barrier(0);" % (r, expr) for r in range(2))  # R = 2 (JitRegs64)
+
+
 def routine_list():
     """(name, body): one per operator not emitted inline; constant-operand
     variants with the Float64 constant in s_k (low word) : s_kh (high word)."""
@@ -168,8 +172,11 @@ def routine_list():
     for name in sorted(LOSSES, key=lambda k: LOSSES[k]):
         if name in NO_LOSS_ROUTINE or name in MARGIN_LOSSES:
             continue
+        # LogCosh / LogitDist (device_ops.h lncosh_f64: sinh, then log1p): one row after the other, the
+        # scheduler fenced between them (both rows at once exceed the routine registers)
+        rw = rows_serial if name in ("LOGCOSH", "LOGITDIST") else rows
         rs.append((f"l_{name.lower()}",
-                   imm + rows(f"s.a[r] = dev::elem_loss<double>(SRHIP_LOSS_{name}, imm, s.a[r], 0.0);")))
+                   imm + rw(f"s.a[r] = dev::elem_loss<double>(SRHIP_LOSS_{name}, imm, s.a[r], 0.0);")))
     # dℓ/dr of the same losses (the Float64 gradient tree code's seed, jit64.cpp GradGen64);
     # LP's Float64 pow runs its two rows one after the other (scheduler fenced between them:
     # both at once exceed the routine registers)

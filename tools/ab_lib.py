@@ -18,6 +18,10 @@ events) of each of --rounds rounds of --steps calls, their median and spread
 (max − min), and whether loss sums and did_succeed equal the first variant's
 bit for bit.
 
+--loss NAME[:PARAM] (a comma list; default L2) times eval_loss with that elementwise loss, and --problem
+jit_losses takes the batch of tests/test_jit_losses_gpu.py (1024 trees x 40 001 rows, --rows / --ntrees unused)
+instead of config #2's: what a change to a loss routine is timed on.
+
 Usage: python tools/ab_lib.py --root parent=/path/to/parent/checkout --root new=. [--rows 1000000,125000]
            [--ntrees 4096,512] [--rounds 5] [--steps 20] [--out FILE.json] parent new:SRHIP_JIT_TAIL_TREES=1 new
        python tools/ab_lib.py SRHIP_JIT_TAIL_TREES=1 SRHIP_JIT_TAIL_TREES=4,SRHIP_JIT_TAIL_ROUNDS=1.5
@@ -63,6 +67,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--loss", default="L2", help="NAME[:PARAM] of srhip.constants.LOSS, comma list")
+    ap.add_argument("--problem", default="config2", choices=["config2", "jit_losses"])
     ap.add_argument("variants", nargs="+")
     args = ap.parse_args()
     import numpy as np
@@ -76,26 +82,31 @@ def main():
         if name not in mods:  # knobs only: the (first) root
             name, kv = roots[0][0], v
         vs.append((v or "default", name, dict(x.split("=", 1) for x in kv.split(",") if x)))
-    rng = np.random.default_rng(1)
-    X = rng.standard_normal((5, 1_000_000)).astype(np.float32)
+    jl = args.problem == "jit_losses"
+    rng = np.random.default_rng(71 if jl else 1)
+    X = rng.standard_normal((5, 40_001 if jl else 1_000_000)).astype(np.float32)
     y = (np.float32(2) * np.cos(X[3]) + X[0] * X[0] - np.float32(2)).astype(np.float32)
     results = []
-    for ntrees in (int(n) for n in args.ntrees.split(",")):
-        for rows in (int(r) for r in args.rows.split(",")):
+    shapes = [(1024, 40_001)] if jl else [(int(n), int(r)) for n in args.ntrees.split(",") for r in args.rows.split(",")]
+    for lname, _, lpar in (l.partition(":") for l in args.loss.split(",")):
+        for ntrees, rows in shapes:
             builds = {}
             for name, m in mods.items():
                 o = m.Options(binary_operators=["+", "-", "*", "/"], unary_operators=["cos", "exp"])
-                trees = m.random_population(4096, o, 5, np.float32, seed=1000, maxsize=30)[:: 4096 // ntrees]
+                if jl:
+                    trees = m.random_population(1024, o, 5, np.float32, seed=72)
+                else:
+                    trees = m.random_population(4096, o, 5, np.float32, seed=1000, maxsize=30)[:: 4096 // ntrees]
                 ctx = m.get_context(0)
                 ds = m.DeviceDataset(ctx, np.ascontiguousarray(X[:, :rows]), np.ascontiguousarray(y[:rows]))
                 builds[name] = (ctx, ds, m.Program(ctx, m.flatten(trees, o, dtype=np.float32), np.float32),
-                                m.constants.LOSS["L2"])
+                                (m.constants.LOSS[lname], [float(lpar)] if lpar else None))
             first, same = None, []
             for v, name, kv in vs:  # warm-up and the results
                 ctx, ds, prog, L2 = builds[name]
                 with env(kv):
                     for _ in range(5):
-                        s, _, ok = prog.eval_loss(ds, L2)
+                        s, _, ok = prog.eval_loss(ds, *L2)
                 got = (np.array(s, copy=True), np.array(ok, copy=True))
                 first = first or got
                 same.append(bool(np.array_equal(got[0], first[0], equal_nan=True) and np.array_equal(got[1], first[1])))
@@ -106,12 +117,12 @@ def main():
                     for k, (v, name, kv) in enumerate(vs):
                         ctx, ds, prog, L2 = builds[name]
                         with env(kv):
-                            prog.eval_loss(ds, L2)
+                            prog.eval_loss(ds, *L2)
                         ts[k].append(ctx.last_kernel_time()[0])
                 for k in range(len(vs)):
                     med[k].append(float(np.median(ts[k])))
             for k, (v, name, kv) in enumerate(vs):
-                r = dict(variant=v, trees=ntrees, rows=rows, round_ms=[round(x, 5) for x in med[k]],
+                r = dict(variant=v, loss=lname + (":" + lpar if lpar else ""), trees=ntrees, rows=rows, round_ms=[round(x, 5) for x in med[k]],
                          median_ms=round(float(np.median(med[k])), 5), spread_ms=round(max(med[k]) - min(med[k]), 5),
                          bit_identical_to_first=same[k], kernel=builds[name][0].last_kernel_name())
                 results.append(r)
