@@ -28,6 +28,7 @@
 #include "compile.h"
 #include "host_ops.h"
 #include "constopt.h"
+#include "env.h"
 #include "jit.h"
 #include "kernels.h"
 
@@ -116,20 +117,6 @@ constexpr int64_t kRowPad = 8192;  // dataset rows are padded to a multiple of t
 int64_t pad_rows(int64_t rows) { return ((std::max<int64_t>(rows, 1) + kRowPad - 1) / kRowPad) * kRowPad; }
 
 size_t dtype_size(int dtype) { return dtype == SRHIP_F32 ? 4 : 8; }
-
-// Environment knobs: 0 or 1 as the value starts, else -1 (unset, anything else);
-// on unless 0; on only if 1; an integer with a default. When a knob is read
-// (once, per build, per call or launch) is decided where it is used.
-int env_01(const char* name) {
-  const char* e = std::getenv(name);
-  return (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : -1;
-}
-bool env_on(const char* name) { return env_01(name) != 0; }
-bool env_is1(const char* name) { return env_01(name) == 1; }
-int env_int(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
 
 // f(T()) with T the element type of dtype (checked by the caller): float or double
 template <typename F>
@@ -727,12 +714,9 @@ bool gjit_wanted(int ntrees) {
   return k >= 0 ? k == 1 : ntrees >= 256;
 }
 
-// LDS for the row tiles of a gradient tree-code workgroup (SRHIP_GJIT_LDS, KiB:
-// experiments); more tiles per workgroup amortise each tree's call over more rows
-size_t gjit_tile_budget() {
-  static const size_t b = (size_t)env_int("SRHIP_GJIT_LDS", 52) * 1024;
-  return b;
-}
+// LDS for the row tiles of a gradient tree-code workgroup; more tiles per
+// workgroup amortise each tree's call over more rows
+size_t gjit_tile_budget() { return (size_t)52 * 1024; }
 
 // the constants the gradient tree code reads (s_load), 16 of padding: Float32
 // (jit_grad.cpp) or Float64 (jit64.cpp) as the program's
@@ -862,7 +846,7 @@ bool patch_image(srhip_program* p, std::vector<unsigned char>& code, const std::
     redo.push_back(t);
   }
   if (n_recompiled) *n_recompiled = (int64_t)redo.size();
-  if (std::getenv("SRHIP_DEBUG_SETC")) std::fprintf(stderr, "srhip set_constants: %d of %d trees recompiled\n", (int)redo.size(), nt);
+  if (env_set("SRHIP_DEBUG_SETC")) std::fprintf(stderr, "srhip set_constants: %d of %d trees recompiled\n", (int)redo.size(), nt);
   if (redo.empty()) {
     cprev = p->consts;
     return true;
@@ -1139,8 +1123,7 @@ void wait_stream(hipStream_t s) {
     return;
   }
   static const double budget_us = [] {
-    const char* b = std::getenv("SRHIP_SPIN_US");
-    return b ? std::max(0.0, std::atof(b)) : 200.0;
+    return std::max(0.0, env_double("SRHIP_SPIN_US", 200.0));
   }();
   const auto t0 = std::chrono::steady_clock::now();
   hipError_t r;
@@ -1330,7 +1313,7 @@ void update_constants(srhip_program* p) {
                       &p->fail_if_rows, /*grad=*/false, &vchg, p->h_cprev)) {
     ++p->n_rebuild;
     build_program<T>(p);
-    if (std::getenv("SRHIP_DEBUG_SETC"))
+    if (env_set("SRHIP_DEBUG_SETC"))
       std::fprintf(stderr, "srhip set_constants: full rebuild of %d trees %.1f us\n", p->ntrees,
                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
     return;
@@ -1341,7 +1324,7 @@ void update_constants(srhip_program* p) {
   HIP_CHECK(hipMemcpyAsync(p->d_code, p->h_code.data(), p->h_code.size(), hipMemcpyHostToDevice, s));
   if (p->grad_built) p->grad_stale = true;  // patched by the next gradient call (patch_grad_constants)
   HIP_CHECK(hipStreamSynchronize(s));
-  if (std::getenv("SRHIP_DEBUG_SETC"))
+  if (env_set("SRHIP_DEBUG_SETC"))
     std::fprintf(stderr, "srhip set_constants: patch %.1f us, upload of %zu bytes %.1f us\n",
                  std::chrono::duration<double, std::micro>(t1 - t0).count(), p->h_code.size(),
                  std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count());
@@ -1378,7 +1361,7 @@ static bool ti_enabled() { return ti_compiled() && env_on("SRHIP_TI"); }  // rea
 // wide only where the LDS plan fails; 1: every interpreter pass wide and no
 // tree code (tests, A/B runs); 0: no wide kernels, UNSUPPORTED as before them.
 static int wide_mode() {
-  const char* e = std::getenv("SRHIP_WIDE");
+  const char* e = env_str("SRHIP_WIDE");
   return (!e || !e[0]) ? -1 : (e[0] == '0' ? 0 : 1);
 }
 [[noreturn]] static void throw_lds(int nfeat) {
@@ -1473,7 +1456,7 @@ void rerun_bailed(srhip_ctx* c, const srhip_program* p, jit::Module* jm, const E
     timed_end(c, s, tk);
     HIP_CHECK(launch_finalize<T>(a, c->res_sum, c->res_ok, s));
     c->last_bailed = nb;
-    if (std::getenv("SRHIP_DEBUG_PASSES")) std::fprintf(stderr, "srhip pass bail-rerun: %d trees\n", nb);
+    if (env_set("SRHIP_DEBUG_PASSES")) std::fprintf(stderr, "srhip pass bail-rerun: %d trees\n", nb);
   }
 }
 
@@ -1553,7 +1536,7 @@ void tail_trees(const srhip_ctx* c, EvalPlan* plan, int jw) {
   plan->tsub = 1;
   if (!env_on("SRHIP_JIT_TAIL") || plan->nbig >= 0 || plan->nrg < 1) return;
   // unset: the default, or fewer where it would leave a wave under 4 trees; 0: the same rule from 8
-  const char* es = std::getenv("SRHIP_JIT_TAIL_TREES");
+  const char* es = env_str("SRHIP_JIT_TAIL_TREES");
   int S = es ? std::atoi(es) : kTailTreesDefault;
   if (!es || S == 0)
     for (S = S == 0 ? 8 : S; S > 1 && plan->tpb / (S * std::max(1, jw)) < 4;) S >>= 1;
@@ -1563,8 +1546,7 @@ void tail_trees(const srhip_ctx* c, EvalPlan* plan, int jw) {
   if (forced >= 0) {
     ntail = std::min<int64_t>(forced, plan->nrg);
   } else {
-    const char* e = std::getenv("SRHIP_JIT_TAIL_ROUNDS");
-    const double rounds = e ? std::atof(e) : kTailRoundsDefault;
+    const double rounds = env_double("SRHIP_JIT_TAIL_ROUNDS", kTailRoundsDefault);
     const int64_t conc = (int64_t)device_cus(c) * std::max(1, 20 / jw);
     const int64_t first = (conc + plan->ntg - 1) / plan->ntg;  // row groups of the first round
     if (!(rounds > 0.0)) return;
@@ -1809,7 +1791,7 @@ void derive_shared(srhip_ctx* c, srhip_program*& slot, std::vector<std::string>&
     const int jw = jc2.waves;
     const size_t lds_wg = jit::lds_per_workgroup(jw);
     const size_t budget = std::max(jit_tile_budget() * jw / 4,
-                                   lds_wg - (jit::part_global() ? 0 : std::min<size_t>(lds_wg / 4, 8192)));
+                                   lds_wg - std::min<size_t>(lds_wg / 4, 8192));
     for (int k = 0; k < jit::nparts(om); ++k) {
       int s0, nsl;
       jit::part(om, k, &s0, &nsl);
@@ -2034,7 +2016,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
     const int jw = jc.waves;
     const size_t lds_wg = jit::lds_per_workgroup(jw);
     const size_t budget = std::max(jit_tile_budget() * jw / 4,
-                                   lds_wg - (jit::part_global() ? 0 : std::min<size_t>(lds_wg / 4, 8192)));
+                                   lds_wg - std::min<size_t>(lds_wg / 4, 8192));
     if (!plan_geometry(4, 4, kShallowSlots, narr, 1, rows, nlist, plan, budget, 52 * 1024 * jw / 4,
                        16384 * 4 / jw, 64 * jw / 4))
       return false;
@@ -2183,9 +2165,8 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
       if constexpr (std::is_same<T, float>::value) {
         // the derived columns of this call, once per row, before the first part
         const jit::Columns& jc = jit::columns(jm);
-        static const bool precompute = env_on("SRHIP_JIT_DERIVE_PRE");
         const float* dcols = nullptr;
-        if (jc.nder > 0 && precompute) {
+        if (jc.nder > 0) {
           c->derived.ensure((size_t)jc.nder * (size_t)n_pad * sizeof(float));
           if (launches[li].part == 0) HIP_CHECK(jit::launch_derive(jm, X, n_pad, static_cast<float*>(c->derived.p), s));
           dcols = static_cast<const float*>(c->derived.p);
@@ -2215,7 +2196,7 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
     if constexpr (std::is_same<T, float>::value) af.part4 = (pass == -1 && jit::partials4(jm, launches[li].part)) ? 1 : 0;
     HIP_CHECK(launch_finalize<T>(af, c->res_sum, c->res_ok, s, cnt, cnt ? c->pin_cnt : nullptr));
     if (cnt) c->cnt_pending = true;
-    static const bool dbg = std::getenv("SRHIP_DEBUG_PASSES") != nullptr;
+    static const bool dbg = env_set("SRHIP_DEBUG_PASSES");
     if (dbg) {  // debugging only: wait for the launch to report its time
       HIP_CHECK(hipStreamSynchronize(s));
       float ms = 0.f;
@@ -2665,7 +2646,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
                                           s, gcols));
           timed_end(c, s, tk);
           HIP_CHECK(launch_finalize<float>(a, static_cast<double*>(c->sums.p), static_cast<uint8_t*>(c->oks.p), s));
-          static const bool dbg = std::getenv("SRHIP_DEBUG_PASSES") != nullptr;
+          static const bool dbg = env_set("SRHIP_DEBUG_PASSES");
           if (dbg) {
             HIP_CHECK(hipStreamSynchronize(s));
             float ms = 0.f;
@@ -2808,7 +2789,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
     timed_end(c, s, tk);
     HIP_CHECK(launch_grad_finalize<T>(a, static_cast<double*>(c->sums.p), static_cast<uint8_t*>(c->oks.p),
                                       static_cast<double*>(c->dloss.p), s));
-    static const bool dbg = std::getenv("SRHIP_DEBUG_PASSES") != nullptr;
+    static const bool dbg = env_set("SRHIP_DEBUG_PASSES");
     if (dbg) {
       HIP_CHECK(hipStreamSynchronize(s));
       float ms = 0.f;
@@ -4126,7 +4107,7 @@ void constant_map_check(const srhip_trees* trees, bool grad, bool keep, const vo
       bad = cb.tree_off[t] < 0 || cb.len[t] != fresh.len[t] ||
             std::memcmp(ins + cb.tree_off[t], &fresh.code[fresh.tree_off[t]], sizeof(Ins<T>) * fresh.len[t]) != 0;
     }
-    if (bad && std::getenv("SRHIP_DEBUG_CMAP"))
+    if (bad && env_set("SRHIP_DEBUG_CMAP"))
       std::fprintf(stderr, "cmap mismatch tree %d: sfail %d/%d fir %d/%d toff %d/%d len %d/%d\n", t, sfail[t],
                    fresh.static_fail[t], fir[t], fresh.fail_if_rows[t], cb.tree_off[t], fresh.tree_off[t], cb.len[t],
                    fresh.len[t]);

@@ -42,6 +42,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "env.h"
 #include "jit_asm.h"
 #include "tail_map.h"
 
@@ -336,7 +337,6 @@ struct Gen {
   int xblk[256];
   int xlast[256];
   bool xinl[256];                // feature read by an inline operator or as the root
-  bool xdirect = false;          // call operands that are features: ds_read straight into A / B
   std::vector<int> feats;        // features in first-use order
   int load_idx[256];             // load number (0 = y)
   int nloads = 0, waited = 0;
@@ -357,15 +357,8 @@ struct Gen {
   int gidx[256];
   int gnum = 0, gdone = 0;
   bool gany = false;   // the tree reads shared-subtree columns
-  // SRHIP_JIT_GPREFETCH=1 (read per build): the next tile's column loads
-  // issued at the end of the current one instead of at its start; measured
-  // no faster (config #2 2.589 vs 2.563 ms, interleaved, profiles/r06_ab_build1.jsonl)
-  bool gprefetch = [] { const char* e = std::getenv("SRHIP_JIT_GPREFETCH"); return e && e[0] == '1'; }();
-  int L_reload = -1;   // issue this tile's column loads, then the tile (a FAST redo)
-  // The column loads of tile S_TILE into their pool blocks (xblk): issued
-  // before the tile runs — for the first tile in the prologue, for the next
-  // one at the end of the current tile (their latency under its tail and the
-  // next tile's LDS reads) — and again before a redone tile.
+  // The column loads of tile S_TILE into their pool blocks (xblk): each tile
+  // issues its own at its start, a redone tile again.
   void emit_gloads() {
     as.vop2(VOP2_LSHLREV_B32, "v_lshlrev_b32_e32", VGT, K(2), VLANE4);  // lane·16
     as.sop2(SOP2_LSHL_B32, "s_lshl_b32", 0, S(S_TILE), K(10));         // tile·1024
@@ -461,7 +454,6 @@ struct Gen {
   // SRHIP_JIT_MANUAL=0 (tests): sin, cos, exp and / through the compiled
   // routines instead of the hand-scheduled packed bodies (gen_jit.py manual_*)
   bool manual_off = false;
-  bool off_exp = false, off_trig = false, off_div = false;
   static int div_rk() {
     static const int r = [] {
       for (int k = 0; k < kNumRoutines; ++k)
@@ -476,7 +468,6 @@ struct Gen {
       if (want == kRoutineName[k]) return k;
     return rid;
   }
-  bool inline_ok = false;  // copy mode-independent small routines into the tree code
   // + - * (and square / cube, residuals, the root check) two rows per
   // instruction on v_pk_*_f32; block moves on v_pk_mov_b32
   bool packed = true, pkmov = true;
@@ -515,41 +506,20 @@ struct Gen {
     throw Error(SRHIP_ERR_INVALID, "jit: constant without a slot");
   }
   Gen(Asm& a, const Tmpl& t, uint64_t va, bool f) : as(a), T(t), base_va(va), fast_opt(f) {
-    const char* e = std::getenv("SRHIP_JIT_INLINE");  // measured no faster: off by default
-    inline_ok = e && e[0] == '1';
-    const char* xd = std::getenv("SRHIP_JIT_XDIRECT");
-    xdirect = !(xd && xd[0] == '0');  // measured 1 % faster on config #2
-    const char* pk = std::getenv("SRHIP_JIT_PACKED");
-    packed = !(pk && pk[0] == '0');
-    const char* pm = std::getenv("SRHIP_JIT_PKMOV");
-    pkmov = !(pm && pm[0] == '0');
-    const char* tf = std::getenv("SRHIP_JIT_TRIG_FULL");
-    trig_full = tf && tf[0] == '1';
-    const char* mo = std::getenv("SRHIP_JIT_MANUAL");
-    manual_off = mo && mo[0] == '0';
-    const char* tr = std::getenv("SRHIP_JIT_TRIM_ROOT");
-    trim_root = !(tr && tr[0] == '0');
-    // SRHIP_JIT_MANUAL_OFF=exp,trig,div (debugging): only these through the compiled routines
-    if (const char* mf = std::getenv("SRHIP_JIT_MANUAL_OFF")) {
-      const std::string l(mf);
-      off_exp = l.find("exp") != std::string::npos;
-      off_trig = l.find("trig") != std::string::npos;
-      off_div = l.find("div") != std::string::npos;
-    }
+    // read per generator, so per tree of every program build: the tests set them between builds
+    packed = env_on("SRHIP_JIT_PACKED");
+    pkmov = env_on("SRHIP_JIT_PKMOV");
+    trig_full = env_is1("SRHIP_JIT_TRIG_FULL");
+    manual_off = env_01("SRHIP_JIT_MANUAL") == 0;
+    trim_root = env_on("SRHIP_JIT_TRIM_ROOT");
   }
 
   uint64_t cur_va() const { return base_va + as.bytes(); }
   // sin / cos of a value that carries FAST rounding: the result's phase error
   // grows with |x| (a 1-ulp change of x = 2^14 moves it by 2^-9), so such
   // arguments are guarded like a cancellation
-  static bool trig_guard_on() {  // SRHIP_JIT_TRIG_GUARD=0 (experiments): no such guard
-    static const bool on = [] { const char* e = std::getenv("SRHIP_JIT_TRIG_GUARD"); return !(e && e[0] == '0'); }();
-    return on;
-  }
   bool trig_of_tainted(const IrOp& o) const {
-    static const bool zs_only = [] { const char* e = std::getenv("SRHIP_JIT_TRIG_GUARD_ZS"); return e && e[0] == '1'; }();
-    return o.un && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS) && o.a.k == O_VAL && ops[o.a.v].taint &&
-           (o.zs || !zs_only);
+    return o.un && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS) && o.a.k == O_VAL && ops[o.a.v].taint;
   }
   // Loss-parity guards (round 4; thresholds from
   // tools/fast_guard_sim.py): FAST rounding in a value that reaches a divisor
@@ -561,29 +531,19 @@ struct Gen {
   // (default 7); an exp of a FAST-derived u when |u| > 16 (relative error
   // amplified |u|-fold); a sin / cos of a FAST-derived u when |u| > 2^10
   // (absolute error |u|·ε).
-  static bool loss_guards_on() {  // SRHIP_JIT_LOSS_GUARDS=0 (experiments): the round-3 guards only
-    static const bool on = [] { const char* e = std::getenv("SRHIP_JIT_LOSS_GUARDS"); return !(e && e[0] == '0'); }();
-    return on;
-  }
+  // The three thresholds are read once per process (tools/guard_sweep.py and
+  // tools/guard_seeds.py start one process per setting); defaults in jit.h.
   static uint32_t can_eps_bits() {  // 2^-k
-    static const uint32_t b = [] {
-      const char* e = std::getenv("SRHIP_JIT_CAN_LOG2");
-      const int k = e ? std::max(1, std::min(100, std::atoi(e))) : (loss_guards_on() ? 7 : 14);
-      return (uint32_t)(127 - k) << 23;
-    }();
+    static const uint32_t b = (uint32_t)(127 - env_int("SRHIP_JIT_CAN_LOG2", kCanLog2, 1, 100)) << 23;
     return b;
   }
   static uint32_t exp_scale_bits() {  // 87 / 2^k, k = SRHIP_JIT_EXP_GUARD_LOG2 (default 4: |x| > 16)
-    static const uint32_t b = [] {
-      const char* e = std::getenv("SRHIP_JIT_EXP_GUARD_LOG2");
-      const int k = e ? std::max(0, std::min(6, std::atoi(e))) : 4;
-      return fbits(87.0f / (float)(1 << k));
-    }();
+    static const uint32_t b = fbits(87.0f / (float)(1 << env_int("SRHIP_JIT_EXP_GUARD_LOG2", kExpGuardLog2, 0, 6)));
     return b;
   }
-  bool trig_small(const IrOp& o) const { return loss_guards_on() && trig_of_tainted(o) && o.zs; }
+  bool trig_small(const IrOp& o) const { return trig_of_tainted(o) && o.zs; }
   bool exp_tainted(const IrOp& o) const {
-    return loss_guards_on() && o.un && o.op == SRHIP_UOP_EXP && o.a.k == O_VAL && ops[o.a.v].taint;
+    return o.un && o.op == SRHIP_UOP_EXP && o.a.k == O_VAL && ops[o.a.v].taint;
   }
   int reg_of_loc(int l) const { return l == L_A ? VA : l == L_B ? VB : VPOOL0 + R * l; }
 
@@ -599,14 +559,11 @@ struct Gen {
         if (manual_off && ((o.un && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS || o.op == SRHIP_UOP_EXP)) ||
                            (!o.un && o.op == SRHIP_BOP_DIV)))
           o.rid = full_routine(o.rid);
-        if ((off_exp && o.un && o.op == SRHIP_UOP_EXP) || (off_trig && o.un && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS)) ||
-            (off_div && !o.un && o.op == SRHIP_BOP_DIV))
-          o.rid = full_routine(o.rid);
         has_call = true;
         // a constant operand rides in s_k: the routine variant takes the other one in A
         if (!o.un && o.b.k == O_C && o.a.k != O_C && kBopRoutineRC[o.op] >= 0) o.krid = kBopRoutineRC[o.op];
         if (!o.un && o.a.k == O_C && o.b.k != O_C && kBopRoutineLC[o.op] >= 0) o.krid = kBopRoutineLC[o.op];
-        if ((manual_off || off_div) && o.krid >= 0 && !o.un && o.op == SRHIP_BOP_DIV) o.krid = full_routine(o.krid);
+        if (manual_off && o.krid >= 0 && !o.un && o.op == SRHIP_BOP_DIV) o.krid = full_routine(o.krid);
         if (kRoutineTrig[o.rid]) has_trig = true;
       }
       for (int s = 0; s < 2; ++s) {
@@ -635,7 +592,7 @@ struct Gen {
       if (o.un && (o.op == SRHIP_UOP_EXP || o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS)) trans = true;
       // a hand-scheduled division: its FAST-region body checks a lower bound
       // only (gen_jit.py manual_div_fast) and leaves an overflow to the verdict
-      if (!o.un && o.op == SRHIP_BOP_DIV && !manual_off && !off_div) pdiv = true;
+      if (!o.un && o.op == SRHIP_BOP_DIV && !manual_off) pdiv = true;
     }
     // A tree without a transcendental has no FAST rounding, so no taint and no
     // guard; with a packed division it still starts in the FAST region, for
@@ -669,7 +626,7 @@ struct Gen {
     if (fast) {
       for (auto& o : ops) {
         if (o.un && o.op == SRHIP_UOP_EXP) g_exp = true;
-        if (trig_of_tainted(o) && trig_guard_on()) g_trig = true;
+        if (trig_of_tainted(o)) g_trig = true;
         if (trig_small(o)) g_can = true;  // its guard shares the cancellation accumulator
         if (o.taint && o.zs) {
           if (!o.un && (o.op == SRHIP_BOP_ADD || o.op == SRHIP_BOP_SUB)) g_can = true;
@@ -691,7 +648,7 @@ struct Gen {
     for (int i = 0; i < n; ++i) {
       if (!usef(ops[i].a, i)) return false;
       if (!ops[i].un && !usef(ops[i].b, i)) return false;
-      if (ops[i].rid < 0 || !xdirect) {
+      if (ops[i].rid < 0) {  // a call's feature operands are read from the LDS tile straight into A / B
         if (ops[i].a.k == O_X) xinl[ops[i].a.v] = true;
         if (!ops[i].un && ops[i].b.k == O_X) xinl[ops[i].b.v] = true;
       }
@@ -793,9 +750,9 @@ struct Gen {
       as.vop3p(opc, nm, d + e, pa, pb, nullptr, lo, hi, negb ? 2 : 0, negb ? 2 : 0);
     }
   }
-  // a call operand into block `dst` (A or B): features not preloaded (or all
-  // of them with xdirect) are read from the LDS tile, other operands moved
-  bool load_x_direct(const Opnd& q) const { return q.k == O_X && !is_g(q.v) && (xdirect || xblk[q.v] < 0); }
+  // a call operand into block `dst` (A or B): features are read from the LDS
+  // tile, other operands (and shared-subtree columns) moved
+  bool load_x_direct(const Opnd& q) const { return q.k == O_X && !is_g(q.v); }
   void operand_to(int dst, const Opnd& q, bool* issued) {
     if (load_x_direct(q)) {
       as.ds_read_b128(dst, VLANE, (1 + q.v) * TILE * 4);
@@ -848,15 +805,6 @@ struct Gen {
     as.sop2(up ? SOP2_ADDC_U32 : SOP2_SUBB_U32, up ? "s_addc_u32" : "s_subb_u32", S_BASE + 1, S(S_BASE + 1), K(0));
   }
   void call_routine(int rid) {
-    static const size_t inline_max = [] {  // SRHIP_JIT_INLINE_MAX: only bodies up to this many bytes
-      const char* e = std::getenv("SRHIP_JIT_INLINE_MAX");
-      return e ? (size_t)std::atoi(e) : (size_t)1 << 30;
-    }();
-    if (inline_ok && !T.body[rid].empty() && T.body[rid].size() * 4 <= inline_max) {  // a copy of the body
-      for (uint32_t w : T.body[rid]) as.raw(w);
-      as.sopp(0x00, "s_nop", 0);  // a trans result read right after the body
-      return;
-    }
     as.sop2(SOP2_ADD_U32, "s_add_u32", S_TGT, S(S_BASE), K((uint32_t)(T.rt_va[rid] - T.fast0)));
     as.sop2(SOP2_ADDC_U32, "s_addc_u32", S_TGT + 1, S(S_BASE + 1), K(0));
     as.sop1(SOP1_SWAPPC, "s_swappc_b64", S_RR, S(S_TGT), "s[" + std::to_string(S_RR) + ":" + std::to_string(S_RR + 1) + "]");
@@ -1118,7 +1066,6 @@ struct Gen {
     root = rt;
     if (xg) {  // local feature numbers, in first-use order (the order analyze() gives feats)
       gbase = 0;
-      gprefetch = false;
       xfeat.clear();
       auto local = [&](Opnd& q) {
         if (q.k != O_X) return;
@@ -1174,14 +1121,9 @@ struct Gen {
       if (is_g(feats[j])) { gany = true; gidx[feats[j]] = gnum++; }
     }
     if (xg) gany = !feats.empty();  // blocks and load numbers are given as the window issues them (xwindow)
-    if (gany && gprefetch) {
-      L_reload = as.label();
-      as.bind(L_reload);
-      emit_gloads();
-    }
     // ---- tile
     as.bind(L_tile);
-    if (gany && !gprefetch && !xg) emit_gloads();  // each tile issues its own column loads
+    if (gany && !xg) emit_gloads();  // each tile issues its own column loads
     if (fast || has_trig) as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHKSAVE, V(VCHK));  // for a redo / bail
     if (g_can) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGCAN, K(0xbf800000u));   // -1
     if (g_min) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGMIN, K(0x3f800000u));   // 1
@@ -1273,11 +1215,8 @@ struct Gen {
         as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
       }
       if (g_trig) {
-        static const uint32_t lim = [] {  // 2^k, k = SRHIP_JIT_TRIG_GUARD_LOG2 (default 14)
-          const char* e = std::getenv("SRHIP_JIT_TRIG_GUARD_LOG2");
-          const int k = e ? std::max(1, std::min(100, std::atoi(e))) : (loss_guards_on() ? 10 : 14);
-          return (uint32_t)(127 + k) << 23;
-        }();
+        // 2^k, k = SRHIP_JIT_TRIG_GUARD_LOG2 (default 10), read once per process
+        static const uint32_t lim = (uint32_t)(127 + env_int("SRHIP_JIT_TRIG_GUARD_LOG2", kTrigGuardLog2, 1, 100)) << 23;
         as.vopc(VOPC_NGE_F32, "v_cmp_nge_f32_e32", K(lim), VGTRIG);  // !(2^k >= max|x|)
         as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
       }
@@ -1435,7 +1374,7 @@ struct Gen {
     // after a redone tile the call's remaining tiles run PRECISE directly
     // (a tree whose guards fire on one tile mostly fires on the next: poles,
     // large arguments); SRHIP_JIT_STICKY=0: the next tile starts FAST again
-    static const bool sticky = [] { const char* e = std::getenv("SRHIP_JIT_STICKY"); return !(e && e[0] == '0'); }();
+    static const bool sticky = env_on("SRHIP_JIT_STICKY");  // read once per process
     if (fast && !sticky) {
       const int L_keep = as.label();
       as.sopc(SOPC_EQ_U32, "s_cmp_eq_u32", S(S_FASTOK), K(0));
@@ -1449,13 +1388,7 @@ struct Gen {
     as.vop2(VOP2_ADD_U32, "v_add_u32_e32", VLANE, S(S_TILEBYTES), VLANE);
     as.sop2(SOP2_ADD_U32, "s_add_u32", S_TILE, S(S_TILE), K(1));
     as.sopc(SOPC_LT_U32, "s_cmp_lt_u32", S(S_TILE), S(S_NT));
-    if (gany && gprefetch) {  // the next tile's column loads before it starts
-      as.branch(SOPP_SCC0, "s_cbranch_scc0", L_done);
-      emit_gloads();
-      as.branch(SOPP_BRANCH, "s_branch", L_tile);
-    } else {
-      as.branch(SOPP_SCC1, "s_cbranch_scc1", L_tile);
-    }
+    as.branch(SOPP_SCC1, "s_cbranch_scc1", L_tile);
     as.bind(L_done);
     as.sop1(SOP1_SETPC, "s_setpc_b64", 0, S(S_RT), "");
     if (as.want_text) as.lines.back() = "s_setpc_b64 s[" + std::to_string(S_RT) + ":" + std::to_string(S_RT + 1) + "]";
@@ -1465,7 +1398,7 @@ struct Gen {
       as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHK, V(VCHKSAVE));
       as.sop1(SOP1_MOV, "s_mov_b32", S_MODE, K(1), "s" + std::to_string(S_MODE));
       shift_base(true);
-      as.branch(SOPP_BRANCH, "s_branch", (gany && gprefetch) ? L_reload : L_tile);  // the columns' blocks were reused
+      as.branch(SOPP_BRANCH, "s_branch", L_tile);
     }
     if (root2) {  // the failing path: the driver reads chk
       as.bind(L_fail);
@@ -1490,8 +1423,7 @@ struct Gen {
 // SRHIP_JIT_XDEPTH (read per build: A/B runs): how many features ahead of the
 // running operation wide code keeps in flight (Gen::xwindow), 0 .. 7
 static int xwindow_depth() {
-  const char* e = std::getenv("SRHIP_JIT_XDEPTH");
-  return e ? std::max(0, std::min(NPOOL - 1, std::atoi(e))) : 3;
+  return env_int("SRHIP_JIT_XDEPTH", 3, 0, NPOOL - 1);
 }
 
 // One tree: returns false (nothing appended) when it cannot be compiled.
@@ -1584,13 +1516,12 @@ bool can_bail() {
 bool module_bails(const Module* m) { return m && m->bails; }
 const char* unavailable_reason() { return templates().why.c_str(); }
 
-// Host threads for code generation (SRHIP_JIT_THREADS, default min(16,
-// hardware threads); 1: serial).
+// Host threads for code generation (SRHIP_JIT_THREADS, read once per process;
+// default min(16, hardware threads); 1: serial).
 static int codegen_threads() {
   static const int n = [] {
-    const char* e = std::getenv("SRHIP_JIT_THREADS");
     const int hw = (int)std::max(1u, std::thread::hardware_concurrency());
-    return e ? std::max(1, std::atoi(e)) : std::min(16, hw);
+    return std::max(1, env_int("SRHIP_JIT_THREADS", std::min(16, hw)));
   }();
   const int cap = host_thread_cap();  // a device group's members build concurrently
   return cap > 0 ? std::min(n, cap) : n;
@@ -1658,7 +1589,7 @@ static bool codegen_par(const CompiledBatch<float>& cb, const std::vector<int32_
       same = false;
   });
   if (!same) return false;
-  static const bool dbg = std::getenv("SRHIP_JIT_DEBUG") != nullptr;
+  static const bool dbg = env_set("SRHIP_JIT_DEBUG");
   for (size_t k = 0; k < end; ++k) {
     const R& r = res[k];
     if (!r.ok) {
@@ -1722,33 +1653,23 @@ static size_t codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>
       if (lines) lines->resize(lbefore);
       rest.push_back(t);
       if (st) st->nrejected++;
-      static const bool dbg = std::getenv("SRHIP_JIT_DEBUG") != nullptr;
+      static const bool dbg = env_set("SRHIP_JIT_DEBUG");
       if (dbg) std::fprintf(stderr, "jit: tree %d not compiled: %s\n", t, why.c_str());
     }
   }
   return cand.size();
 }
 
-// SRHIP_JIT_PART_GLOBAL=1 (experiments): per-tree partials always straight to global memory
-bool part_global() {
-  static const bool g = [] { const char* e = std::getenv("SRHIP_JIT_PART_GLOBAL"); return e && e[0] == '1'; }();
-  return g;
-}
 bool has_loss_routine(int loss) {
   return loss == SRHIP_LOSS_L2 || (loss >= 0 && loss < SRHIP_NUM_LOSSES && kLossRoutine[loss] >= 0);
 }
 int choose_waves(int nraw) {
-  static const int forced = [] {
-    const char* e = std::getenv("SRHIP_JIT_WAVES");
-    const int v = e ? std::atoi(e) : 0;
+  static const int forced = [] {  // SRHIP_JIT_WAVES = 1 .. 16, read once per process
+    const int v = env_int("SRHIP_JIT_WAVES", 0);
     return v >= 1 && v <= 16 ? v : 0;
   }();
   if (forced) return forced;
-  static const int wide = [] {  // SRHIP_JIT_WIDE_FEATURES: the feature count from which 8 waves
-    const char* e = std::getenv("SRHIP_JIT_WIDE_FEATURES");
-    return e ? std::max(1, std::atoi(e)) : 10;
-  }();
-  return nraw >= wide ? 8 : 4;
+  return nraw >= 10 ? 8 : 4;
 }
 // 94 VGPRs: 5 waves per SIMD, 20 per CU; the CU's 160 KiB shared by its workgroups
 size_t lds_per_workgroup(int waves) {
@@ -1769,8 +1690,7 @@ size_t lds_per_workgroup(int waves) {
 // forward), so an occurrence saves the PRECISE price; env: the cap's variable.
 static void plan_shared(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand, bool on, Columns& c,
                         bool precise = false, const char* env = "SRHIP_JIT_GCOLS", int dflt = 32) {
-  const char* ge = std::getenv(env);  // read per build: A/B tests
-  const int gmax = ge ? std::max(0, std::min(kMaxGlobalCols, std::atoi(ge))) : dflt;
+  const int gmax = env_int(env, dflt, 0, kMaxGlobalCols);  // read per build: A/B tests
   const int room = std::min(gmax, 255 - c.gbase());
   if (!on || room <= 0) return;
   struct Info {
@@ -1836,13 +1756,13 @@ static void plan_shared(const CompiledBatch<float>& cb, const std::vector<int32_
     c.goff.push_back((int32_t)c.gkind.size());
   }
   c.ngcol = (int)kept.size();
-  if (std::getenv("SRHIP_JIT_DEBUG"))
+  if (env_set("SRHIP_JIT_DEBUG"))
     for (size_t g = 0; g < kept.size(); ++g)
       std::fprintf(stderr, "jit: shared column %zu: %s gain %lld\n", g, kept[g].second->c_str(), (long long)kept[g].first);
 }
 
 // The derived columns of a batch: every u(x_f) (u a routine operator) used by
-// at least SRHIP_JIT_DERIVE_MIN (default 4) trees' code, most used first, as
+// at least four trees' code, most used first, as
 // many as leave room for four row tiles in the workgroup's LDS; nraw = the
 // raw features still read after the substitution.
 static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand, const Options& opt) {
@@ -1851,13 +1771,11 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
   Opnd root;
   struct Cnt { uint32_t key; int n; };
   std::vector<Cnt> cnt;
-  static const int min_uses = [] { const char* e = std::getenv("SRHIP_JIT_DERIVE_MIN"); return e ? std::max(1, std::atoi(e)) : 4; }();
-  static const bool env_on = [] { const char* e = std::getenv("SRHIP_JIT_DERIVE"); return !(e && e[0] == '0'); }();
-  const bool on = opt.derive && env_on;
+  constexpr int min_uses = 4;
   for (int32_t t : cand) {
     if (cb.tree_off[t] < 0 || !build_ir(&cb.code[cb.tree_off[t]], ir, root)) continue;
     for (const IrOp& o : ir) {
-      if (o.un && o.a.k == O_X && !o.a.der && is_routine_uop(o.op) && on) {
+      if (o.un && o.a.k == O_X && !o.a.der && is_routine_uop(o.op)) {
         const uint32_t key = ((uint32_t)o.op << 16) | (uint32_t)o.a.v;
         auto it = std::find_if(cnt.begin(), cnt.end(), [&](const Cnt& q) { return q.key == key; });
         if (it == cnt.end()) cnt.push_back({key, 1}); else ++it->n;
@@ -1887,10 +1805,9 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
     }
     return m + 1;
   };
-  // room: four tiles (SRHIP_JIT_DERIVE_TILES) of (y, raw, derived) in the
-  // workgroup's LDS, less the partials' share
-  static const int dtiles = [] { const char* e = std::getenv("SRHIP_JIT_DERIVE_TILES"); return e ? std::max(1, std::atoi(e)) : 4; }();
-  const size_t tile_bytes = (size_t)dtiles * (size_t)(64 * SR_JIT_R) * sizeof(float);
+  // room: four tiles of (y, raw, derived) in the workgroup's LDS, less the
+  // partials' share
+  const size_t tile_bytes = (size_t)4 * (size_t)(64 * SR_JIT_R) * sizeof(float);
   c.waves = choose_waves(raw_max({}));  // from the raw features before any substitution
   if (opt.xg) {  // wide code: y and w in LDS, the features from X; no derived, no shared-subtree columns
     c.xg = true;
@@ -1901,7 +1818,7 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
     return c;
   }
   const size_t lds_wg = lds_per_workgroup(c.waves);
-  const size_t budget = lds_wg - (part_global() ? 0 : std::min<size_t>(lds_wg / 8, 4096));
+  const size_t budget = lds_wg - std::min<size_t>(lds_wg / 8, 4096);
   while (true) {
     const int nraw = raw_max(chosen);
     const size_t cols = 1 + (size_t)nraw + chosen.size();  // y, raw, derived (w, when weighted, may cost a tile)
@@ -1913,7 +1830,7 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
   }
   c.nder = (int)chosen.size();
   for (int k = 0; k < c.nder; ++k) c.der[k] = chosen[k];
-  plan_shared(cb, cand, on && !opt.out && !opt.memc, c);
+  plan_shared(cb, cand, !opt.out && !opt.memc, c);
   // the columns' numbers from the context's registry (the bound plan_shared observes); a batch with
   // more columns than the registry has slots keeps its own numbering and the per-call derive pass
   if (opt.slots && c.ngcol > 0) {
@@ -1947,10 +1864,9 @@ static Options checked(Options opt) {
 Columns plan_grad_columns(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand) {
   Columns c;
   c.nraw = kGradGbase;  // raw features stay below (the gradient code's DS immediates end at feature 62)
-  static const bool env_on = [] { const char* e = std::getenv("SRHIP_JIT_DERIVE"); return !(e && e[0] == '0'); }();
   // 64: config #5's shard gradient 42.2 ms against 42.8 at 32 and 45.9 without (interleaved,
   // tools/ab_build.py --grad, profiles/r06_grad_gcols_ab.txt)
-  plan_shared(cb, cand, env_on, c, /*precise=*/true, "SRHIP_GJIT_GCOLS", 64);
+  plan_shared(cb, cand, true, c, /*precise=*/true, "SRHIP_GJIT_GCOLS", 64);
   return c;
 }
 
@@ -2158,10 +2074,7 @@ bool dynamic_trees() { return false; }
 // A/B (tools/loop_ab.py, profiles/r04_loop_ab.jsonl): config #2 3.380 →
 // 3.247 ms, its 125k-row shard 0.546 → 0.506, a 512-tree shard 0.515 → 0.503.
 // SRHIP_JIT_DYNLOOP=0 (read per launch): the compiled static loop.
-static bool dynloop() {
-  const char* e = std::getenv("SRHIP_JIT_DYNLOOP");
-  return !(e && e[0] == '0');
-}
+static bool dynloop() { return env_on("SRHIP_JIT_DYNLOOP"); }
 
 // SRHIP_JIT_ROTATE's default (launch). One process, the mode alternating call
 // by call (profiles/rotate_trim_ab.json): config #2 at 1M rows 2.480 / 2.400 /
@@ -2209,8 +2122,8 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
   // per launch) forces it on / off. The mark is bit 1 of the tree's flag word
   // (bit 0: failed), which the finalize ignores.
   {
-    const char* e = std::getenv("SRHIP_JIT_STICKY_TREE");
-    ja.dyn = (e && e[0] == '1') ? 1 : (e && e[0] == '0') ? 0 : (a.nrg <= 48 ? 1 : 0);
+    const int forced = env_01("SRHIP_JIT_STICKY_TREE");
+    ja.dyn = forced >= 0 ? forced : (a.nrg <= 48 ? 1 : 0);
   }
   // Each row group starts its walk over the tree group's list at an offset of
   // its own (jit_template.hip rot_of). Every workgroup used to walk from
@@ -2225,8 +2138,7 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
   ja.rot_step = 0;
   ja.rot_nrg = 0;
   if (!m->out && a.tpb > 1 && a.ntg > 0) {
-    const char* e = std::getenv("SRHIP_JIT_ROTATE");
-    const int mode = e ? std::atoi(e) : kRotateDefault;
+    const int mode = env_int("SRHIP_JIT_ROTATE", kRotateDefault);
     if (mode == 1 || mode == 2) {
       static const int ncu = [] {
         int dev = 0, n = 0;
@@ -2246,13 +2158,11 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
   // partials in LDS when they take little room next to the tiles (measured
   // faster on config #2: one coalesced write-out instead of a store per tree)
   const size_t part_bytes = (size_t)a.tpb * sizeof(Part<float>);
-  ja.part_lds = part_bytes <= 8192 && !part_global() ? 1 : 0;
+  ja.part_lds = part_bytes <= 8192 ? 1 : 0;
   size_t sz = sizeof(ja);
   void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ja, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   unsigned grid = a.rotate >= 2 ? (unsigned)((a.nrg + 7) / 8 * 8) * (unsigned)a.ntg
                                 : (unsigned)a.nrg * (unsigned)a.ntg;
-  // SRHIP_JIT_LDS_PAD (experiments): extra LDS per workgroup, i.e. fewer resident waves
-  static const unsigned pad = [] { const char* e = std::getenv("SRHIP_JIT_LDS_PAD"); return e ? (unsigned)std::atoi(e) : 0u; }();
   // LDS: the row tiles (+ the partials when part_lds)
   const size_t narr = 1 + (size_t)(ja.nraw + ja.nder) + (a.w ? 1 : 0);
   const size_t lds = narr * (size_t)plan.ntiles * (size_t)plan.tile * sizeof(float) + (ja.part_lds ? part_bytes : 0) + 16;
@@ -2270,8 +2180,7 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
   // code offset before running this one (interleaved A/B, profiles/
   // r04_loop_ab.jsonl: config #2 3.247 → 3.231 ms, a 512-tree shard 0.503 →
   // 0.483); SRHIP_JIT_PREFETCH=0 (read per launch): without
-  static const auto prefetch = [] { const char* e = std::getenv("SRHIP_JIT_PREFETCH"); return !(e && e[0] == '0'); };
-  if (q.fn_dlp && !m->out && dynloop() && prefetch()) {
+  if (q.fn_dlp && !m->out && dynloop() && env_on("SRHIP_JIT_PREFETCH")) {
     fn = a.w ? q.fn_dlpw : q.fn_dlp;
     name = a.w ? "sr_jit_eval_dlpw" : "sr_jit_eval_dlp";
   }
@@ -2289,7 +2198,7 @@ hipError_t launch(Module* m, int k, const EvalPlan& plan, const EvalArgs<float>&
   }
   if (!m->out) note_loss_launch(a.nrg, a.ntg, a.tpb, grid, ja.tbig, ja.tsub);
   note_kernel(name);
-  return hipModuleLaunchKernel(fn, grid, 1, 1, (unsigned)plan.threads, 1, 1, (unsigned)lds + pad, stream, nullptr, cfg);
+  return hipModuleLaunchKernel(fn, grid, 1, 1, (unsigned)plan.threads, 1, 1, (unsigned)lds, stream, nullptr, cfg);
 }
 
 }  // namespace jit

@@ -20,7 +20,6 @@ struct Module;
 struct Options {
   bool fast = true;       // emit the FAST-routine path + guards in eligible trees
   bool text = false;      // also produce the assembly text (tests: checked against llvm-mc)
-  bool derive = true;     // derived columns (below); SRHIP_JIT_DERIVE=0 turns them off
   bool memc = false;      // constants read from the program's immediates (set_constants needs no new code)
   // the elementwise loss of the tile tail (SRHIP_LOSS_*) and its parameter
   // (Float64 bits, literals of the code): L2 inline, the others through the
@@ -112,8 +111,16 @@ bool has_loss_routine(int loss);
 // the others through their loss and dℓ/dr routines)
 bool has_dloss_routine(int loss);
 size_t lds_per_workgroup(int waves);
-bool part_global();
 bool dynamic_trees();
+
+// The loss-parity guards of the FAST loss tree code (jit.cpp Gen, DESIGN.md
+// §3.1): a cancellation or a small sin / cos of a FAST-derived value redoes
+// the tile below 2^-kCanLog2 of its operands, an exp of a FAST-derived u
+// beyond |u| = 2^kExpGuardLog2, a sin / cos of one beyond 2^kTrigGuardLog2.
+// SRHIP_JIT_CAN_LOG2, SRHIP_JIT_EXP_GUARD_LOG2 and SRHIP_JIT_TRIG_GUARD_LOG2
+// move them (tools/guard_sweep.py). The gradient tree code (jit_grad.cpp
+// GradGen) runs its forward PRECISE and has no guards.
+constexpr int kCanLog2 = 7, kExpGuardLog2 = 4, kTrigGuardLog2 = 10;
 
 // Statistics of one build.
 struct Stats {

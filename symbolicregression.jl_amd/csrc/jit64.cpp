@@ -29,6 +29,7 @@
 #include <cstring>
 
 #include "jit.h"
+#include "env.h"
 #include "jit_asm.h"
 #include "gen/jit64_layout.h"
 
@@ -629,7 +630,7 @@ size_t codegen64(const CompiledBatch<double>& cb, const std::vector<int32_t>& ca
       if (lines) lines->resize(lbefore);
       rest.push_back(t);
       if (st) st->nrejected++;
-      static const bool dbg = std::getenv("SRHIP_JIT_DEBUG") != nullptr;
+      static const bool dbg = env_set("SRHIP_JIT_DEBUG");
       if (dbg) std::fprintf(stderr, "jit64: tree %d not compiled: %s\n", t, why.c_str());
     }
   }
@@ -1551,7 +1552,7 @@ size_t grad_codegen64(const CompiledBatch<double>& cb, const std::vector<int32_t
       if (lines) lines->resize(lbefore);
       rest.push_back(t);
       if (st) st->nrejected++;
-      static const bool dbg = std::getenv("SRHIP_JIT_DEBUG") != nullptr;
+      static const bool dbg = env_set("SRHIP_JIT_DEBUG");
       if (dbg) std::fprintf(stderr, "jit64-grad: tree %d not compiled: %s\n", t, why.c_str());
     }
   }
@@ -1698,8 +1699,7 @@ hipError_t launch_grad_code64(GradModule64* m, int part, const EvalPlan& plan, c
   const size_t narr = 1 + (size_t)m->nraw + (a.w ? 1 : 0);
   const size_t lds = narr * (size_t)plan.ntiles * (size_t)TILE2 * sizeof(double) + 16;
   // the hand-written tree loop (its counter in the last 16 bytes); SRHIP_JIT_DYNLOOP=0: the compiled one
-  const char* dl = std::getenv("SRHIP_JIT_DYNLOOP");
-  const bool stl = dl && dl[0] == '0';
+  const bool stl = !env_on("SRHIP_JIT_DYNLOOP");  // read per launch
   hipFunction_t fn = stl ? (a.w ? q.fn_w : q.fn) : (a.w ? q.fn_dlw : q.fn_dl);
   note_kernel(stl ? (a.w ? "sr_jit64_grad_w" : "sr_jit64_grad") : (a.w ? "sr_jit64_grad_dlw" : "sr_jit64_grad_dl"));
   return hipModuleLaunchKernel(fn, (unsigned)a.nrg * (unsigned)a.ntg, 1, 1, 256, 1, 1, (unsigned)lds, stream, nullptr,
@@ -1848,8 +1848,7 @@ hipError_t launch64(Module64* m, int k, const EvalPlan& plan, const EvalArgs<dou
   const size_t narr = 1 + (size_t)m->nraw + (a.w ? 1 : 0);
   const size_t lds = narr * (size_t)plan.ntiles * (size_t)TILE2 * sizeof(double) + 16;
   // the hand-written tree loop (its counter in the last 16 bytes); SRHIP_JIT_DYNLOOP=0: the compiled one
-  const char* dl = std::getenv("SRHIP_JIT_DYNLOOP");
-  const bool st = dl && dl[0] == '0';
+  const bool st = !env_on("SRHIP_JIT_DYNLOOP");  // read per launch
   hipFunction_t fn = st ? (a.w ? q.fn_w : q.fn) : (a.w ? q.fn_dlw : q.fn_dl);
   note_kernel(st ? (a.w ? "sr_jit64_eval_w" : "sr_jit64_eval") : (a.w ? "sr_jit64_eval_dlw" : "sr_jit64_eval_dl"));
   if (m->out) {  // per-row outputs: the compiled loop, every tree on every tile

@@ -57,8 +57,6 @@ const int kDLossRoutine[SRHIP_NUM_LOSSES] = SR_JIT_DLOSS_ROUTINE;   // dℓ/dr; 
 const int kGradLossRoutine[SRHIP_NUM_LOSSES] = SR_JIT_GRAD_LOSS_ROUTINE;  // ℓ in the gradient code
 const char* const kRoutineName[kNumRoutines] = SR_JIT_ROUTINE_NAMES;
 const int kRoutineTrig[kNumRoutines] = SR_JIT_ROUTINE_TRIG;
-const int kRoutineInline[kNumRoutines] = SR_JIT_ROUTINE_INLINE;        // same FAST / PRECISE code, small
-const int kRoutineBodyBytes[kNumRoutines] = SR_JIT_ROUTINE_BODY_BYTES;  // up to the return
 
 // ---- the code-object template ---------------------------------------------------
 struct Tmpl {
@@ -70,7 +68,6 @@ struct Tmpl {
   uint64_t rt_va[kNumRoutines] = {};  // FAST routine addresses
   uint64_t delta = 0;      // PRECISE - FAST region offset
   uint64_t fast0 = 0;      // FAST region start (sr_rt_fast)
-  std::vector<uint32_t> body[kNumRoutines];  // inlinable routine bodies (without the return)
   bool ok = false;
   std::string why;
 };
@@ -127,18 +124,6 @@ inline bool parse_tmpl(const uint8_t* img, size_t size, Tmpl* t) {
       text = &s;
   if (!text) { t->why = "code area outside .text"; return false; }
   t->area_va = code_va;
-  for (int k = 0; k < kNumRoutines; ++k) {
-    if (!kRoutineInline[k]) continue;
-    const uint64_t va = t->rt_va[k];
-    const size_t nb = (size_t)kRoutineBodyBytes[k];
-    if (va < text->sh_addr || va + nb + 4 > text->sh_addr + text->sh_size || nb % 4) continue;
-    const size_t off = (size_t)(va - text->sh_addr + text->sh_offset);
-    uint32_t ret;
-    std::memcpy(&ret, img + off + nb, 4);
-    if (ret != (0xbe801d00u | (uint32_t)S_RR)) { t->why = "routine body does not end in its return"; return false; }
-    t->body[k].resize(nb / 4);
-    std::memcpy(t->body[k].data(), img + off, nb);
-  }
   t->area_off = (size_t)(code_va - text->sh_addr + text->sh_offset);
   // the area function: s_endpgm, the area, the compiler's closing s_endpgm
   const uint64_t end = area_fn_va + area_fn_size;
@@ -259,10 +244,6 @@ struct Asm {
   void sopp(int op, const char* nm, int imm, bool show = true) {
     put(0xbf800000u | ((uint32_t)op << 16) | ((uint32_t)imm & 0xffffu));
     if (want_text) t(show ? std::string(nm) + " " + std::to_string(imm) : std::string(nm));
-  }
-  void raw(uint32_t x) {
-    put(x);
-    if (want_text) t(".long " + hex32(x));
   }
   void branch(int op, const char* nm, int l) {
     fix.push_back({w.size(), l, want_text ? lines.size() : 0});

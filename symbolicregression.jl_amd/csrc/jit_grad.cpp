@@ -39,6 +39,7 @@
 #include <unordered_map>
 
 #include "jit.h"
+#include "env.h"
 #include "jit_asm.h"
 
 #define HIP_CHECK(expr)                                                                  \
@@ -61,8 +62,6 @@ constexpr int SGPTR = SR_JIT_G_SGPTR;  // s[84:85]: this row group's ∂L/∂c p
 constexpr int XS0 = 0, XS1 = 4;   // feature values read in the reverse pass
 constexpr int TS = 8;             // 2 registers: row sums
 constexpr int TP = 12, TR = 16, TQ = 20;  // product / reciprocal / quotient-adjoint blocks
-// guard of sin / cos arguments (FAST forward), above the accumulators
-constexpr int VGTRIG_G = GACC + NGACC;
 enum : int { VOP1_RCP_F32 = 0x22, VOPC_NEQ_F32 = 0x4d, VOP3_MUL_F32 = 0x105 };
 // forward sin / cos with the reverse factor in VB (gen_jit.py u_sin_pd / u_cos_pd)
 const int kSinCosPd[2] = SR_JIT_SINCOS_PD_ROUTINE;
@@ -263,7 +262,7 @@ struct GradGen {
   std::vector<int> feats;
   int nloads = 0, waited = 0;
   bool has_call = false;
-  int L_tile = -1, L_done = -1, L_redo = -1;
+  int L_tile = -1, L_done = -1;
   // shared-subtree columns: G_X features from gbase on are read from device
   // memory — s[98:99] = column 0 at this row group's first row, s100 = the
   // column stride in bytes (jit_template.hip's gradient drivers) — one global
@@ -275,54 +274,8 @@ struct GradGen {
   int gidx[256];
   int gnum = 0, gdone = 0;
   bool is_g(int f) const { return f >= gbase; }
-  // guarded FAST forward (as the loss tree code, jit.cpp): exp / sin / cos by
-  // their FAST routines; a tile whose guards fire (or that fails) runs its
-  // forward again with the PRECISE routines before the loss and the reverse
-  // pass, so did_succeed and the values the gradients see stay those of the
-  // Float64-evaluated routines wherever the FAST ones could change them
-  bool fast = false;
-  bool g_can = false, g_min = false, g_exp = false, g_trig = false;
-  std::vector<uint8_t> taint, zs;
 
   GradGen(Asm& a, const Tmpl& t, uint64_t va) : as(a), T(t), base_va(va) {}
-  // sin / cos of a FAST-derived value: its argument guard (|u| > 2^10, or
-  // 2^14 on a divisor path only with SRHIP_JIT_LOSS_GUARDS=0); on a divisor
-  // path also the condition guard |result| < 2^-7·|u| (jit.cpp Gen: the
-  // round-4 loss-parity guards, same thresholds)
-  static bool loss_guards_on() {
-    static const bool on = [] { const char* e = std::getenv("SRHIP_JIT_LOSS_GUARDS"); return !(e && e[0] == '0'); }();
-    return on;
-  }
-  // The gradient's thresholds (SRHIP_GJIT_*_LOG2, own defaults): a term
-  // w·2r·∂ŷ/∂c near a pole weighs the row's FAST rounding more than the loss
-  // does (the derivative factor 1/b, or the reverse pass's sin / cos at the
-  // forward argument), so the gradient code guards tighter than the loss code
-  static int env_log2(const char* name, int dflt, int lo, int hi) {
-    const char* e = std::getenv(name);
-    return e ? std::max(lo, std::min(hi, std::atoi(e))) : dflt;
-  }
-  static uint32_t can_eps_bits() {  // 2^-k
-    static const uint32_t b = [] {
-      const int k = env_log2("SRHIP_GJIT_CAN_LOG2", loss_guards_on() ? 7 : 14, 1, 100);
-      return (uint32_t)(127 - k) << 23;
-    }();
-    return b;
-  }
-  static uint32_t trig_lim_bits() {  // 2^k
-    static const uint32_t b = [] {
-      const int k = env_log2("SRHIP_GJIT_TRIG_GUARD_LOG2", loss_guards_on() ? 10 : 14, 1, 100);
-      return (uint32_t)(127 + k) << 23;
-    }();
-    return b;
-  }
-  bool trig_tainted(const GOp& o) const {
-    return o.kind == K_UN && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS) && o.a.k == G_VAL && taint[o.a.v] &&
-           (loss_guards_on() || zs[&o - ops.data()]);
-  }
-  bool trig_small(const GOp& o) const { return loss_guards_on() && trig_tainted(o) && zs[&o - ops.data()]; }
-  bool exp_tainted(const GOp& o) const {
-    return loss_guards_on() && o.kind == K_UN && o.op == SRHIP_UOP_EXP && o.a.k == G_VAL && taint[o.a.v];
-  }
   uint64_t cur_va() const { return base_va + as.bytes(); }
   static int blk_reg(int k) { return GPOOL0 + R * k; }
   int bstep(int i) const { return 2 * n - i; }  // reverse steps n+1 .. 2n (n: the loss)
@@ -355,68 +308,6 @@ struct GradGen {
       }
     }
     if (root.k == G_C && root.ci >= nc) { why = "constant index out of range"; return false; }
-    // FAST forward: taint (a FAST-routine value flows in), zero sensitivity
-    // (a divisor depends on it), the guards they need (jit.cpp Gen::analyze)
-    taint.assign(n, 0);
-    zs.assign(n, 0);
-    bool trans = false;
-    for (int i = 0; i < n; ++i) {
-      const GOp& o = ops[i];
-      const bool t = o.kind == K_UN && (o.op == SRHIP_UOP_EXP || o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS);
-      trans = trans || t;
-      taint[i] = t || (o.a.k == G_VAL && taint[o.a.v]) || (o.kind == K_BIN && o.b.k == G_VAL && taint[o.b.v]);
-    }
-    for (int i = n - 1; i >= 0; --i) {
-      const GOp& o = ops[i];
-      auto mark = [&](const GOpnd& q) { if (q.k == G_VAL) zs[q.v] = 1; };
-      if (o.kind == K_BIN) {
-        if (o.op == SRHIP_BOP_DIV) { mark(o.b); if (zs[i]) mark(o.a); }
-        else if (zs[i]) { mark(o.a); mark(o.b); }
-      } else if (o.kind == K_UN && zs[i] && (o.op == SRHIP_UOP_NEG || o.op == SRHIP_UOP_ABS || o.op == SRHIP_UOP_SQUARE ||
-                                               o.op == SRHIP_UOP_CUBE || o.op == SRHIP_UOP_SIN)) {
-        mark(o.a);
-      }
-    }
-    // The forward pass runs the PRECISE routines by default (round 4): with
-    // guards tight enough that every constant's ∂L/∂c stays within 1e-5 of
-    // Σ|terms| of the oracle's Float32 gradient (SRHIP_GJIT_TRIG_GUARD_LOG2=6),
-    // the guarded FAST forward redoes so many tiles that it costs what the
-    // PRECISE forward does (config #5 shard 48.5 vs 48.5 ms), and with the
-    // loss code's thresholds it leaves constants up to 1.8 % of Σ|terms| off
-    // (round 3's guards: 112 %; profiles/r04_grad_guards.txt).
-    // SRHIP_GJIT_FAST=1: the guarded FAST forward.
-    static const bool fast_env = [] { const char* e = std::getenv("SRHIP_GJIT_FAST"); return e && e[0] == '1'; }();
-    fast = fast_env && trans;
-    if (fast) {
-      // The FAST region's packed division bodies leave an overflow to the loss
-      // code's tile verdict (gen_jit.py manual_div_fast); this code keeps its
-      // forward values for the reverse pass, so its divisions take the compiled
-      // IEEE routines (b_div_full, b_div_lc_full: the same in both regions).
-      auto full = [](int rid) {
-        if (rid < 0) return rid;
-        const std::string want = std::string(kRoutineName[rid]) + "_full";
-        for (int k = 0; k < kNumRoutines; ++k)
-          if (want == kRoutineName[k]) return k;
-        return rid;
-      };
-      for (GOp& o : ops)
-        if (o.kind == K_BIN && o.op == SRHIP_BOP_DIV && !g_inline(o)) {
-          o.rid = full(o.rid);
-          if (o.a.k == G_C) o.krid = full(o.krid);  // c / a (a / c: b_div_rc, compiled)
-        }
-      for (int i = 0; i < n; ++i) {
-        const GOp& o = ops[i];
-        if (o.kind == K_UN && o.op == SRHIP_UOP_EXP) g_exp = true;
-        if (trig_tainted(o)) g_trig = true;
-        if (trig_small(o)) g_can = true;
-        if (taint[i] && zs[i]) {
-          if (o.kind == K_BIN && (o.op == SRHIP_BOP_ADD || o.op == SRHIP_BOP_SUB)) g_can = true;
-          if ((o.kind == K_BIN && (o.op == SRHIP_BOP_MUL || o.op == SRHIP_BOP_DIV)) ||
-              (o.kind == K_UN && (o.op == SRHIP_UOP_SQUARE || o.op == SRHIP_UOP_CUBE)))
-            g_min = true;
-        }
-      }
-    }
     // reverse-pass reads of saved values (operands and own results)
     int xg_rev[256];
     for (int f = 0; f < 256; ++f) xg_rev[f] = -1;
@@ -562,12 +453,11 @@ struct GradGen {
   bool in_va(const GOpnd& q) const { return q.k == G_VAL && loc[q.v] == LOC_VA; }
   // a routine's result may stay in VA when its one use is the next forward
   // operation (no reverse use, not the root): that operation reads VA before
-  // anything writes it (SRHIP_GJIT_KEEP_VA=0: always moved to a pool block)
+  // anything writes it;
   // an inline result whose one use is the next operation, a routine call,
   // is written straight into the call's argument registers: VA or VB (0: no)
   int arg_reg_for(int i) const {
-    static const bool on = [] { const char* e = std::getenv("SRHIP_GJIT_KEEP_VA"); return !(e && e[0] == '0'); }();
-    if (!on || i + 1 >= n || last[i] != i + 1 || (root.k == G_VAL && root.v == i)) return 0;
+    if (i + 1 >= n || last[i] != i + 1 || (root.k == G_VAL && root.v == i)) return 0;
     const GOp& c = ops[i + 1];
     if (c.kind == K_MAT || g_inline(c)) return 0;
     const bool a = c.a.k == G_VAL && c.a.v == i, b = c.kind == K_BIN && c.b.k == G_VAL && c.b.v == i;
@@ -575,8 +465,7 @@ struct GradGen {
     return a ? VA : b ? VB : 0;
   }
   bool keep_in_va(int i) const {
-    static const bool on = [] { const char* e = std::getenv("SRHIP_GJIT_KEEP_VA"); return !(e && e[0] == '0'); }();
-    if (!on || i + 1 >= n || last[i] != i + 1 || (root.k == G_VAL && root.v == i)) return false;
+    if (i + 1 >= n || last[i] != i + 1 || (root.k == G_VAL && root.v == i)) return false;
     const GOp& c = ops[i + 1];
     if (c.kind == K_MAT) return false;
     return (c.a.k == G_VAL && c.a.v == i) || (c.kind == K_BIN && c.b.k == G_VAL && c.b.v == i);
@@ -611,12 +500,7 @@ struct GradGen {
     if (y.enc >= 256) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", d, x, y.enc - 256);
     else as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", d, y, x.enc - 256);
   }
-  // acc_ci ±= x·y for one row (the product and the sum in one rounding);
-  // SRHIP_GJIT_ACC_FMA=0: products to a block, then acc_add
-  static bool acc_fma_on() {
-    static const bool on = [] { const char* e = std::getenv("SRHIP_GJIT_ACC_FMA"); return !(e && e[0] == '0'); }();
-    return on;
-  }
+  // acc_ci ±= x·y for one row (the product and the sum in one rounding)
   void acc_fma(int ci, const Src& x, const Src& y, bool neg) {
     const Src a = V(GACC + ci);
     as.vop3(VOP3_FMA_F32, "v_fma_f32", GACC + ci, x, y, &a, 0, neg ? 1 : 0);
@@ -628,20 +512,6 @@ struct GradGen {
     as.vop2(VOP2_ADD_F32, "v_add_f32_e32", TS, V(TS), TS + 1);
     if (neg) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", GACC + ci, V(GACC + ci), TS);
     else as.vop2(VOP2_ADD_F32, "v_add_f32_e32", GACC + ci, V(GACC + ci), TS);
-  }
-
-  // ---- FAST-forward guards
-  void guard_max(int g, int reg) {  // g = max(g, |reg_e|) over the block, two rows per instruction
-    for (int e = 0; e < R; e += 2) {
-      const Src gg = V(g), x0 = V(reg + e), x1 = V(reg + e + 1);
-      as.vop3(VOP3_MAX3_F32, "v_max3_f32", g, gg, x0, &x1, 6, 0);
-    }
-  }
-  void guard_min(int reg) {
-    for (int e = 0; e < R; e += 2) {
-      const Src gg = V(VGMIN), x0 = V(reg + e), x1 = V(reg + e + 1);
-      as.vop3(VOP3_MIN3_F32, "v_min3_f32", VGMIN, gg, x0, &x1, 6, 0);
-    }
   }
 
   // ---- forward
@@ -663,12 +533,6 @@ struct GradGen {
       a[e] = fsrc(o.a, e);
       if (o.kind == K_BIN) b[e] = fsrc(o.b, e);
     }
-    const bool gcan = fast && taint[i] && zs[i] && o.kind == K_BIN && (o.op == SRHIP_BOP_ADD || o.op == SRHIP_BOP_SUB);
-    const bool gmin = fast && taint[i] && zs[i] &&
-                      ((o.kind == K_BIN && o.op == SRHIP_BOP_MUL) ||
-                       (o.kind == K_UN && (o.op == SRHIP_UOP_SQUARE || o.op == SRHIP_UOP_CUBE)));
-    if (gcan)  // t = |a| + |b| before the operands' blocks may be reused
-      for (int e = 0; e < R; ++e) as.vop3(VOP3_ADD_F32, "v_add_f32_e64", VGT + e, a[e], b[e], nullptr, 3, 0);
     // blocks dying here may hold the result (rows are independent)
     free_values_at(i);
     free_feats_at(i);
@@ -706,17 +570,6 @@ struct GradGen {
         }
       }
     }
-    if (gcan) {  // t·2^-14 - |r| <= 0 unless a cancellation: max into GCAN
-      for (int e = 0; e < R; ++e) {
-        const Src t_ = V(VGT + e), eps = S(S_EPS), r = V(d + e);
-        as.vop3(VOP3_FMA_F32, "v_fma_f32", VGT + e, t_, eps, &r, 4, 4);
-      }
-      for (int e = 0; e < R; e += 2) {
-        const Src g = V(VGCAN), t0 = V(VGT + e), t1 = V(VGT + e + 1);
-        as.vop3(VOP3_MAX3_F32, "v_max3_f32", VGCAN, g, t0, &t1, 0, 0);
-      }
-    }
-    if (gmin) guard_min(d);
     if (areg) {
       loc[i] = areg == VA ? LOC_VA : LOC_VB;
       return true;
@@ -737,15 +590,12 @@ struct GradGen {
   }
   bool emit_call(int i) {
     const GOp& o = ops[i];
-    // FAST forward: routines relative to the region base in s[S_BASE] (FAST,
-    // or PRECISE while a tile is redone); else always the PRECISE region
-    const bool prec = !fast;
     if (o.krid >= 0) {
       const bool kr = o.b.k == G_C;
       operand_to(VA, kr ? o.a : o.b);
       as.sop1(SOP1_MOV, "s_mov_b32", S_K, S(SC0 + (kr ? o.b.ci : o.a.ci)), "s" + std::to_string(S_K));
       free_values_at(i);
-      routine(o.krid, prec);
+      routine(o.krid, true);  // the forward runs the PRECISE region's routines
     } else {
       if (o.kind == K_BIN && in_va(o.b)) {  // VB first: VA still holds it
         operand_to(VB, o.b);
@@ -755,25 +605,7 @@ struct GradGen {
         if (o.kind == K_BIN) operand_to(VB, o.b);
       }
       free_values_at(i);
-      if (fast && o.kind == K_UN && o.op == SRHIP_UOP_EXP) {
-        if (exp_tainted(o)) {  // |u| > 16 fires the 87 check: u counts 87/16 = 5.4375 times
-          static const uint32_t scale = [] {  // 87 / 2^k (jit.cpp Gen::exp_scale_bits)
-            const int k = env_log2("SRHIP_GJIT_EXP_GUARD_LOG2", 4, 0, 6);
-            const float v = 87.0f / (float)(1 << k);
-            uint32_t u;
-            std::memcpy(&u, &v, 4);
-            return u;
-          }();
-          for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", VGT + e, K(scale), VA + e);
-          guard_max(VGEXP, VGT);
-        } else {
-          guard_max(VGEXP, VA);
-        }
-      }
-      if (fast && g_trig && trig_tainted(o)) guard_max(VGTRIG_G, VA);
-      const bool tsmall = fast && trig_small(o);
-      if (tsmall) mov4(VGT, VA);
-      routine(fused(i) ? kSinCosPd[o.op == SRHIP_UOP_COS ? 1 : 0] : o.rid, prec);
+      routine(fused(i) ? kSinCosPd[o.op == SRHIP_UOP_COS ? 1 : 0] : o.rid, true);
       if (fused(i)) {  // the reverse factor out of VB before anything reuses it
         const int kd = free_block();
         if (kd < 0) { why = "register pool exhausted (sin / cos factor)"; return false; }
@@ -781,27 +613,15 @@ struct GradGen {
         owner[kd] = 3000 + i;
         dloc[i] = kd;
       }
-      if (tsmall) {  // fires when 2^-k·|u| - |sin/cos u| >= 0 (or NaN): max into GCAN
-        for (int e = 0; e < R; ++e) {
-          const Src u = V(VGT + e), eps = S(S_EPS), r = V(VA + e);
-          as.vop3(VOP3_FMA_F32, "v_fma_f32", VGT + e, u, eps, &r, 5, 4);
-        }
-        for (int e = 0; e < R; e += 2) {
-          const Src g = V(VGCAN), t0 = V(VGT + e), t1 = V(VGT + e + 1);
-          as.vop3(VOP3_MAX3_F32, "v_max3_f32", VGCAN, g, t0, &t1, 0, 0);
-        }
-      }
     }
     free_feats_at(i);
     if (keep_in_va(i)) {
-      if (fast && taint[i] && zs[i] && o.kind == K_BIN && o.op == SRHIP_BOP_DIV) guard_min(VA);
       loc[i] = LOC_VA;
       return true;
     }
     const int k = free_block();
     if (k < 0) { why = "register pool exhausted"; return false; }
     mov4(blk_reg(k), VA);
-    if (fast && taint[i] && zs[i] && o.kind == K_BIN && o.op == SRHIP_BOP_DIV) guard_min(blk_reg(k));
     owner[k] = i;
     loc[i] = k;
     return true;
@@ -861,7 +681,7 @@ struct GradGen {
         case SRHIP_BOP_MUL: {
           fetch(o.a, XS0);
           fetch(o.b, XS1);
-          if (aa && o.a.k == G_C && acc_fma_on()) {  // ∂c = g·b, summed straight into c's accumulator
+          if (aa && o.a.k == G_C) {  // ∂c = g·b, summed straight into c's accumulator
             for (int e = 0; e < R; ++e) acc_fma(o.a.ci, gv(e), rsrc(o.b, XS1, e), g.neg);
           } else if (aa) {
             int blk;
@@ -870,7 +690,7 @@ struct GradGen {
             for (int e = 0; e < R; ++e) vmul(d + e, rsrc(o.b, XS1, e), gv(e));
             give(o.a, d, g.neg, blk);
           }
-          if (ab && o.b.k == G_C && acc_fma_on()) {
+          if (ab && o.b.k == G_C) {
             for (int e = 0; e < R; ++e) acc_fma(o.b.ci, gv(e), rsrc(o.a, XS0, e), g.neg);
           } else if (ab) {
             int blk;
@@ -934,7 +754,7 @@ struct GradGen {
           if (ra < 0) return false;
           for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", ra + e, gv(e), TR + e);
           if (aa) give(o.a, ra, g.neg, blk_a);
-          if (ab && o.b.k == G_C && acc_fma_on()) {  // ∂c = -(g/c)·q into c's accumulator
+          if (ab && o.b.k == G_C) {  // ∂c = -(g/c)·q into c's accumulator
             const int qreg = blk_reg(loc[i]);
             for (int e = 0; e < R; ++e) acc_fma(o.b.ci, V(ra + e), V(qreg + e), !g.neg);
           } else if (ab) {
@@ -1082,24 +902,12 @@ struct GradGen {
     for (const GOp& o : ops)
       if (o.kind == K_UN && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS)) trig = true;
     if (has_call || trig || loss != SRHIP_LOSS_L2) set_base();
-    L_redo = as.label();
-    if (fast) {
-      as.sop1(SOP1_MOV, "s_mov_b32", S_MODE, K(0), "s" + std::to_string(S_MODE));  // FAST
-      if (g_can) as.sop1(SOP1_MOV, "s_mov_b32", S_EPS, K(can_eps_bits()), "s" + std::to_string(S_EPS));  // 2^-k
-    }
     for (int j = 0; j < nc; ++j) as.vop1(VOP1_MOV, "v_mov_b32_e32", GACC + j, K(0));
     if (nc > 0) as.waitcnt_lgkm(0);
     as.sopc(SOPC_GE_U32, "s_cmp_ge_u32", S(S_TILE), S(S_NT));
     as.branch(SOPP_SCC1, "s_cbranch_scc1", L_done);
     // ---- tile: forward
     as.bind(L_tile);
-    if (fast) {
-      as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHKSAVE, V(VCHK));  // for a redo
-      if (g_can) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGCAN, K(0xbf800000u));   // -1
-      if (g_min) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGMIN, K(0x3f800000u));   // 1
-      if (g_exp) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGEXP, K(0));
-      if (g_trig) as.vop1(VOP1_MOV, "v_mov_b32_e32", VGTRIG_G, K(0));
-    }
     nloads = 0;
     waited = 0;
     for (size_t j = 0; j < feats.size(); ++j) {
@@ -1136,41 +944,9 @@ struct GradGen {
       as.vop3(VOP3_FMA_F32, "v_fma_f32", VCHK, r, z, &c, 0, 0);
     }
     wait_all();
-    if (fast) {  // FAST verdict (NaN-true checks, as jit.cpp): a failure or a guard redoes the forward
-      const int L_skip = as.label();
-      as.sopc(SOPC_LG_U32, "s_cmp_lg_u32", S(S_MODE), K(0));
-      as.branch(SOPP_SCC1, "s_cbranch_scc1", L_skip);
-      as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(VCHK), VCHK);
-      as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
-      if (g_can) {
-        as.vopc(VOPC_NGT_F32, "v_cmp_ngt_f32_e32", K(0), VGCAN);
-        as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
-      }
-      if (g_min) {
-        as.vopc(VOPC_NLE_F32, "v_cmp_nle_f32_e32", K(0x03800000u), VGMIN);
-        as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
-      }
-      if (g_exp) {
-        as.vopc(VOPC_NGE_F32, "v_cmp_nge_f32_e32", K(0x42ae0000u), VGEXP);
-        as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
-      }
-      if (g_trig) {
-        as.vopc(VOPC_NGE_F32, "v_cmp_nge_f32_e32", K(trig_lim_bits()), VGTRIG_G);  // !(2^k >= max|x|)
-        as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_redo);
-      }
-      as.bind(L_skip);
-    }
     // a failed tile ends the tree (no reverse pass)
     as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(VCHK), VCHK);
     as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_done);
-    if (fast) {  // after a redone forward: the FAST base again (the reverse pass's sin / cos), next tile FAST
-      const int L_keep = as.label();
-      as.sopc(SOPC_EQ_U32, "s_cmp_eq_u32", S(S_MODE), K(0));
-      as.branch(SOPP_SCC1, "s_cbranch_scc1", L_keep);
-      shift_base(false);
-      as.sop1(SOP1_MOV, "s_mov_b32", S_MODE, K(0), "s" + std::to_string(S_MODE));
-      as.bind(L_keep);
-    }
     // ---- loss of the tile and the seed 2·w·r (masked rows: r = 0)
     for (int e = 0; e < R; ++e) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", VY + e, V(rreg + e), VY + e);
     free_values_at(n);
@@ -1247,24 +1023,7 @@ struct GradGen {
       }
       as.sopp(0x00, "s_nop", 1);
     }
-    const char* st1e = std::getenv("SRHIP_GJIT_STORE1");  // read per build (tools/ab_build.py)
-    const bool store1 = !(st1e && st1e[0] == '0');
-    for (int j = 0; j < nc && !store1; ++j) {  // SRHIP_GJIT_STORE1=0: one store per constant (round 5)
-      const int a = GACC + j;
-      as.put(0xd2890000u | 20u);  // v_readlane_b32 s20, v_a, 63
-      as.put((uint32_t)(256 + a) | (191u << 9));
-      if (as.want_text) as.lines.push_back("v_readlane_b32 s20, v" + std::to_string(a) + ", 63");
-      as.sopp(0x00, "s_nop", 4);
-      as.vop1(VOP1_MOV, "v_mov_b32_e32", TS, S(20));
-      // global_store_dword v[TS+1] (= 0), v[TS], s[SGPTR:SGPTR+1] offset:4j
-      as.put(0xdc708000u | (uint32_t)((4 * j) & 0x1fff));
-      as.put((uint32_t)(TS + 1) | ((uint32_t)TS << 8) | ((uint32_t)SGPTR << 16));
-      if (as.want_text)
-        as.lines.push_back("global_store_dword v" + std::to_string(TS + 1) + ", v" + std::to_string(TS) + ", s[" +
-                           std::to_string(SGPTR) + ":" + std::to_string(SGPTR + 1) + "]" +
-                           (j ? " offset:" + std::to_string(4 * j) : ""));
-    }
-    if (nc > 0 && store1) {
+    if (nc > 0) {
       // lane 63 of each accumulator holds its sum: v_readlane_b32 s_j, v_acc_j, 63 (s0..s15: routine
       // temporaries, free here), then lane j of TS takes constant j's sum and ONE store of lanes
       // 0..nc-1 writes the tree's nc contiguous partials (one write request per tree and row group,
@@ -1302,13 +1061,6 @@ struct GradGen {
     }
     as.sop1(SOP1_SETPC, "s_setpc_b64", 0, S(S_RT), "");
     if (as.want_text) as.lines.back() = "s_setpc_b64 s[" + std::to_string(S_RT) + ":" + std::to_string(S_RT + 1) + "]";
-    as.bind(L_redo);
-    if (fast) {  // the forward again with the PRECISE routines
-      as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHK, V(VCHKSAVE));
-      as.sop1(SOP1_MOV, "s_mov_b32", S_MODE, K(1), "s" + std::to_string(S_MODE));
-      shift_base(true);
-      as.branch(SOPP_BRANCH, "s_branch", L_tile);
-    }
     return true;
   }
   // Σ w·ℓ(r) into the lane's loss sum and the seed w·ℓ'(r) into VY (r in VY,
@@ -1354,10 +1106,6 @@ struct GradGen {
     mov4(VY, VA);
     return true;
   }
-  void shift_base(bool up) {
-    as.sop2(up ? SOP2_ADD_U32 : SOP2_SUB_U32, up ? "s_add_u32" : "s_sub_u32", S_BASE, S(S_BASE), K((uint32_t)T.delta));
-    as.sop2(up ? SOP2_ADDC_U32 : SOP2_SUBB_U32, up ? "s_addc_u32" : "s_subb_u32", S_BASE + 1, S(S_BASE + 1), K(0));
-  }
 };
 
 using ColIndex = std::unordered_map<std::string, int>;
@@ -1378,12 +1126,8 @@ bool gen_grad_tree(const Ins<float>* prog, int nc, const Tmpl& T, bool text, std
   const size_t start = (out.size() + 15) / 16 * 16;
   Asm as;
   bool ok = false;
-  // SRHIP_GJIT_SINCOS=0: sin / cos derivatives by the FAST routines in the reverse pass (round 5);
-  // a tree whose fused factors exhaust the register pool is compiled without them
-  const char* sce = std::getenv("SRHIP_GJIT_SINCOS");
-  const bool fuse = !(sce && sce[0] == '0');
+  // a tree whose fused sin / cos factors exhaust the register pool is compiled without them
   for (int attempt = subst ? 0 : 2; attempt < 4 && !ok; ++attempt) {
-    if ((attempt & 1) == 0 && !fuse) continue;
     as = Asm();
     as.want_text = text;
     GradGen g(as, T, T.area_va + start * 4);
@@ -1444,7 +1188,7 @@ size_t grad_codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>& 
       if (lines) lines->resize(lbefore);
       rest.push_back(t);
       if (st) st->nrejected++;
-      static const bool dbg = std::getenv("SRHIP_JIT_DEBUG") != nullptr;
+      static const bool dbg = env_set("SRHIP_JIT_DEBUG");
       if (dbg) std::fprintf(stderr, "jit-grad: tree %d not compiled: %s\n", t, why.c_str());
     }
   }
@@ -1633,8 +1377,7 @@ hipError_t launch_grad_code(GradModule* m, int part, const EvalPlan& plan, const
   const size_t narr = 1 + (size_t)a.nfeat + (a.w ? 1 : 0);
   const size_t lds = narr * (size_t)plan.ntiles * (size_t)plan.tile * sizeof(float) + 16;
   // the hand-written tree loop (its counter in the last 16 bytes); SRHIP_JIT_DYNLOOP=0: the compiled one
-  const char* dl = std::getenv("SRHIP_JIT_DYNLOOP");
-  const bool st = dl && dl[0] == '0';
+  const bool st = !env_on("SRHIP_JIT_DYNLOOP");  // read per launch
   hipFunction_t fn = st ? (a.w ? pt.fn_w : pt.fn) : (a.w ? pt.fn_dlw : pt.fn_dl);
   note_kernel(st ? (a.w ? "sr_jit_grad_w" : "sr_jit_grad") : (a.w ? "sr_jit_grad_dlw" : "sr_jit_grad_dl"));
   return hipModuleLaunchKernel(fn, grid, 1, 1, (unsigned)plan.threads, 1, 1, (unsigned)lds,

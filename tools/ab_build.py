@@ -3,7 +3,8 @@
 
 Every variant's program is built in this one process with its environment
 set (knobs the tree compiler reads per build: SRHIP_JIT_GCOLS,
-SRHIP_JIT_GPREFETCH, ...), then the variants' eval_loss calls alternate
+SRHIP_GJIT_GCOLS, SRHIP_JIT_PACKED, ...; DESIGN.md "Environment switches"
+says which are), then the variants' eval_loss calls alternate
 A B C A B C ... so that clock drift hits all of them alike. Prints, per
 variant, the median kernel time of the call (HIP events of the context:
 every launch of the call, the derive passes included) and checks that every
@@ -86,7 +87,7 @@ def main():
                               "did_succeed_equal": bool(np.array_equal(k, k0)),
                               "loss_equal": bool(np.array_equal(s[k & k0], s0[k & k0])),
                               "grad_equal": bool(np.array_equal(g[okc], g0[okc], equal_nan=True)),
-                              # a variant that evaluates a derivative differently (SRHIP_GJIT_SINCOS):
+                              # a variant that evaluates a derivative differently:
                               # constants off the first variant's by > 1e-4 relative, and the largest
                               "grad_rel_gt_1e-4": int(np.sum(~(np.abs(g[okc] - g0[okc]) <= 1e-4 * np.abs(g0[okc])))),
                               "grad_max_rel": float(np.nanmax(np.abs(g[okc] - g0[okc]) / np.maximum(np.abs(g0[okc]), 1e-30))),
