@@ -583,6 +583,50 @@ int32_t srhip_eval_loss_grad_rowsets_targets(srhip_dataset* ds, const srhip_prog
                                              const int64_t* row_idx, int64_t batch_size, double* out_loss_sum,
                                              double* out_dloss, double* out_weight_sum, uint8_t* out_ok);
 
+/* ---- derivative objectives: fused losses on ŷ and ∂ŷ/∂x --------------------------
+ * One table loss reduced on the prediction and on its derivatives with respect to
+ * ndir features, for every tree of a program in one pass ("a loss that takes into
+ * account derivatives", src/Options.jl:203-210; eval_diff_tree_array /
+ * eval_grad_tree_array(...; variable=true) on the host).
+ * ds is a dataset of srhip_dataset_create_multi with ntargets = 1 + ndir columns:
+ * column 0 is y, column 1 + k the target of ∂ŷ/∂x_dir[k] (each with its own weight
+ * column when the dataset is weighted). dir holds 0-based feature indices.
+ *   out_loss_sum[t][0]     = Σ_i W[0][i] · ℓ(ŷ_t(x_i), Y[0][i])
+ *   out_loss_sum[t][1 + k] = Σ_i W[1+k][i] · ℓ(∂ŷ_t/∂x_dir[k](x_i), Y[1+k][i])
+ *   out_weight_sum[c]      = Σ_i W[c][i] (rows when unweighted), c < 1 + ndir
+ *   out_ok[t]              = did_succeed of the tree's value evaluation
+ * ℓ takes the derivative in the prediction's place. The engine's rule for the
+ * flag is the one its eval_diff_tree_array follows: only the value evaluation is
+ * checked, so a non-finite derivative gives a non-finite channel sum with ok = 1
+ * (the expression losses' rule), and a failed tree's whole row is NaN. Parity with
+ * DynamicExpressions' own completion flag for derivatives is unpinned.
+ * Answered before any launch and before anything is written: a null dir with
+ * ndir > 0, an ndir outside 1..15, ds->ntargets != 1 + ndir, a direction outside
+ * 0..nfeat-1, a repeated direction and a margin loss (loss_kind >=
+ * SRHIP_MARGIN_LOSS_BEGIN) are SRHIP_ERR_INVALID; an expression-loss handle and a
+ * program that holds expression operators are SRHIP_ERR_UNSUPPORTED. The loss
+ * kind and its parameter are checked as everywhere.
+ * Always the forward-mode interpreter with tangents seeded at feature leaves, in
+ * kernel variants of its own ("grad_kernel_deriv<float>",
+ * "grad_kernel_wide_deriv<float>" and the double forms; the wide one when the row
+ * tile of every feature and column does not fit in LDS). One work item per tree
+ * when ndir <= 2, one per group of 4 directions otherwise. srhip_last_tree_code
+ * gives 0 and no tree code is built for such a call (the one-shot form makes its
+ * program with SRHIP_PROGRAM_INTERPRETED). srhip_last_loss_launch gives the row
+ * groups, tree groups and items per group of the call's last launch.
+ * Not in this version: row sets; group datasets; constant optimisation under the
+ * objective (it needs ∂²ŷ/∂c∂x or finite differences); expression losses and
+ * expression operators; tree code. */
+int32_t srhip_eval_loss_deriv(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                              const double* loss_params, const int32_t* dir, int32_t ndir,
+                              double* out_loss_sum,   /* [ntrees][1 + ndir] */
+                              double* out_weight_sum, /* [1 + ndir]: Σw of each column, or rows */
+                              uint8_t* out_ok);
+int32_t srhip_eval_loss_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                        int32_t loss_kind, const double* loss_params, const int32_t* dir,
+                                        int32_t ndir, double* out_loss_sum, double* out_weight_sum,
+                                        uint8_t* out_ok);
+
 /* Per-row constant gradients for few trees: out_grad is
  * [total consts][rows] (∂ŷ_i/∂c), out_value [ntrees][rows]. */
 int32_t srhip_eval_grad_tree_array(srhip_dataset* ds, const srhip_program* prog,

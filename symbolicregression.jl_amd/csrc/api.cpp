@@ -367,6 +367,10 @@ struct srhip_program {
   bool grad_built = false;
   bool grad_stale = false;  // constants changed since the gradient programs were patched
   std::vector<uint8_t> g_static_fail;
+  // per tree, for the calls that deal their own work items (srhip_eval_loss_deriv): the
+  // cost of its gradient program, and 0 shallow / 1 deep / 2 never run (a static verdict)
+  std::vector<int32_t> g_cost;
+  std::vector<uint8_t> g_class;
   void* d_gcode = nullptr;
   int32_t* d_gtree_off = nullptr;
   int32_t* d_gitems = nullptr;  // work items (tree | group << 24): shallow then deep
@@ -1018,6 +1022,13 @@ void build_grad_program(srhip_program* p, bool tree_code = true) {
   auto by_cost = [](const std::pair<int, int32_t>& x, const std::pair<int, int32_t>& y) {
     return x.first != y.first ? x.first > y.first : x.second < y.second;
   };
+  p->g_cost.assign(p->ntrees, 0);
+  p->g_class.assign(p->ntrees, 2);
+  for (int t = 0; t < p->ntrees; ++t) {
+    if (cb.tree_off[t] < 0) continue;
+    p->g_cost[t] = cb.cost[t];
+    p->g_class[t] = (cb.need[t] > 4 || cb.expr[t]) ? 1 : 0;
+  }
   std::vector<int32_t> items;
   for (int rest_only = 0; rest_only < 2; ++rest_only) {
     std::vector<std::pair<int, int32_t>> cls[4];  // (cost, item)
@@ -2946,6 +2957,113 @@ int eval_loss_grad_targets_impl(srhip_dataset* ds, srhip_program* p, int loss, c
   return SRHIP_OK;
 }
 
+// srhip_eval_loss_deriv (checked by the caller): the forward-mode interpreter with its
+// tangents seeded at feature leaves (grad_kernel.h kGradLossDeriv), one work item per
+// (tree, group of kGradG directions) — one per tree, carrying ndir tangents, when
+// ndir <= 2 and the tree is shallow. Shallow trees, then deep ones; the wide variant
+// where the row tile of every feature and column does not fit in LDS. No tree code.
+template <typename T>
+int eval_loss_deriv_impl(srhip_dataset* ds, srhip_program* p, int loss, const double* params, const int32_t* dir,
+                         int ndir, double* out_sum, double* out_wsum, uint8_t* out_ok) {
+  srhip_ctx* c = p->ctx;
+  build_grad_program<T>(p, false);
+  hipStream_t s = c->stream;
+  timing_reset(c);
+  c->last_jit_trees = 0;
+  const int nt = p->ntrees, ncol = 1 + ndir;
+  const int ngroups = (ndir + kGradG - 1) / kGradG;
+  const int64_t rows = ds->rows;
+  std::vector<int32_t> hdir((size_t)ngroups * kGradG, -1);  // (no feature index is negative)
+  std::copy(dir, dir + ndir, hdir.begin());
+  std::vector<int32_t> items;
+  int nitems_of[2] = {0, 0};
+  for (int cl = 0; cl < 2; ++cl) {
+    std::vector<int32_t> ts;
+    for (int t = 0; t < nt; ++t)
+      if (p->g_class[t] == cl) ts.push_back(t);
+    std::stable_sort(ts.begin(), ts.end(), [&](int32_t x, int32_t y) { return p->g_cost[x] > p->g_cost[y]; });
+    for (int32_t t : ts)
+      for (int gi = 0; gi < ngroups; ++gi) items.push_back((int32_t)(t | (gi << 24)));
+    nitems_of[cl] = (int)ts.size() * ngroups;
+  }
+  c->tgt.ensure(hdir.size() * sizeof(int32_t));
+  c->scratch_idx.ensure(std::max<size_t>(items.size(), 1) * sizeof(int32_t));
+  c->dloss.ensure(std::max<size_t>((size_t)nt * ncol, 1) * sizeof(double));
+  c->oks.ensure(std::max<size_t>(nt, 1));
+  double* d_sum = static_cast<double*>(c->dloss.p);
+  HIP_CHECK(hipMemcpyAsync(c->tgt.p, hdir.data(), hdir.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (!items.empty())
+    HIP_CHECK(hipMemcpyAsync(c->scratch_idx.p, items.data(), items.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  int first = 0;
+  bool ran = false;
+  for (int cl = 0; cl < 2; ++cl) {
+    const int nitems = nitems_of[cl], item0 = first;
+    first += nitems;
+    if (nitems == 0 || rows == 0) continue;
+    const bool deep = cl == 1;
+    int G = (deep || ndir > 2) ? kGradG : ndir;
+    EvalPlan plan;
+    const int wm = wide_mode();
+    if (wm == 1 || !plan_grad(p->dtype, deep, G, GRAD_LOSS, ds->w != nullptr, ds->nfeat, rows, nitems, &plan, ncol)) {
+      G = kGradG;
+      if (wm == 0 || !plan_grad_wide(p->dtype, GRAD_LOSS, ds->w != nullptr, rows, nitems, &plan, ncol)) throw_lds(ds->nfeat);
+    }
+    GradArgs<T> a;
+    a.prog = static_cast<const Ins<T>*>(p->d_gcode);
+    a.tree_off = p->d_gtree_off;
+    a.items = static_cast<const int32_t*>(c->scratch_idx.p) + item0;
+    a.nitems = nitems;
+    a.dyn = interp_dyn() ? 1 : 0;
+    a.const_off = p->d_const_off;
+    a.X = static_cast<const T*>(ds->X);
+    a.y = static_cast<const T*>(ds->y);
+    a.w = static_cast<const T*>(ds->w);
+    a.n = rows;
+    a.n_pad = ds->n_pad;
+    a.ntgt = ncol;
+    a.dir = static_cast<const int32_t*>(c->tgt.p);
+    a.nfeat = ds->nfeat;
+    a.ntiles = plan.ntiles;
+    a.ntg = plan.ntg;
+    a.tpb = plan.tpb;
+    a.nrg = plan.nrg;
+    a.loss = loss;
+    a.lparam = params ? params[0] : 0.0;
+    a.G = G;
+    a.opset = OPSET_FULL;
+    c->partial.ensure((size_t)plan.nrg * plan.ntg * plan.tpb * (2 + G) * sizeof(T));
+    a.partial = static_cast<T*>(c->partial.p);
+    a.out_value = nullptr;
+    a.out_grad = nullptr;
+    a.out_stride = 0;
+    const int tk = timed_begin(c, s);
+    note_kernel(plan.wide ? (sizeof(T) == 4 ? "grad_kernel_wide_deriv<float>" : "grad_kernel_wide_deriv<double>")
+                          : (sizeof(T) == 4 ? "grad_kernel_deriv<float>" : "grad_kernel_deriv<double>"));
+    HIP_CHECK(launch_grad_deriv<T>(plan, a, s));
+    timed_end(c, s, tk);
+    HIP_CHECK(launch_grad_deriv_finalize<T>(a, d_sum, static_cast<uint8_t*>(c->oks.p), s));
+    note_loss_launch(plan.nrg, plan.ntg, plan.tpb, (unsigned)plan.nrg * (unsigned)plan.ntg, plan.nrg, 1);
+    ran = true;
+  }
+  std::vector<double> hs((size_t)nt * ncol, 0.0);
+  c->h_ok.assign(nt, 1);
+  if (ran) {
+    HIP_CHECK(hipMemcpyAsync(hs.data(), d_sum, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(c->h_ok.data(), c->oks.p, nt, hipMemcpyDeviceToHost, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  timing_finish(c);
+  for (int t = 0; t < nt; ++t) {
+    const bool fail = p->g_static_fail[t] || (rows > 0 && !c->h_ok[t]);
+    if (out_ok) out_ok[t] = fail ? 0 : 1;
+    if (out_sum)
+      for (int k = 0; k < ncol; ++k) out_sum[(size_t)t * ncol + k] = fail ? NAN : (rows > 0 ? hs[(size_t)t * ncol + k] : 0.0);
+  }
+  if (out_wsum)
+    for (int k = 0; k < ncol; ++k) out_wsum[k] = !ds->w ? (double)rows : ds->t_sum_w[(size_t)k];
+  return SRHIP_OK;
+}
+
 template <typename T>
 int eval_grad_tree_array_impl(srhip_dataset* ds, srhip_program* p, void* out_value, void* out_grad,
                               uint8_t* out_ok) {
@@ -3804,6 +3922,55 @@ int32_t srhip_eval_loss_grad_targets(srhip_dataset* ds, const srhip_program* pro
       return eval_loss_grad_targets_impl<decltype(t)>(ds, p, loss_kind, loss_params, target, out_loss_sum, out_dloss,
                                                       out_weight_sum, out_ok);
     });
+  });
+}
+
+// srhip_eval_loss_deriv's own checks, made before anything is built, launched or written
+static void check_deriv(const srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind, const double* loss_params,
+                        const int32_t* dir, int32_t ndir) {
+  if (ndir > 0 && !dir) throw Error(SRHIP_ERR_INVALID, "dir is NULL");
+  if (ndir < 1 || ndir > 15) throw Error(SRHIP_ERR_INVALID, "ndir must be within 1..15");
+  if (ds->ntargets != 1 + ndir)
+    throw Error(SRHIP_ERR_INVALID, "a derivative objective over " + std::to_string(ndir) + " directions needs a dataset of " +
+                                       std::to_string(1 + ndir) + " columns (y, then one per direction); this one has " +
+                                       std::to_string(ds->ntargets));
+  for (int k = 0; k < ndir; ++k) {
+    if (dir[k] < 0 || dir[k] >= ds->nfeat)
+      throw Error(SRHIP_ERR_INVALID, "direction " + std::to_string(dir[k]) + " is outside 0.." + std::to_string(ds->nfeat - 1));
+    for (int j = 0; j < k; ++j)
+      if (dir[j] == dir[k]) throw Error(SRHIP_ERR_INVALID, "direction " + std::to_string(dir[k]) + " is repeated");
+  }
+  if (loss_kind >= SRHIP_MARGIN_LOSS_BEGIN && loss_kind < SRHIP_EXPR_LOSS_BEGIN)
+    throw Error(SRHIP_ERR_INVALID, "a margin loss scores a class label, not a derivative");
+  check_loss(loss_kind, loss_params);
+  if (loss_kind >= SRHIP_EXPR_LOSS_BEGIN)
+    throw Error(SRHIP_ERR_UNSUPPORTED, "expression losses are not part of derivative objectives in this version");
+  if (prog->has_expr || !prog->xops.empty())
+    throw Error(SRHIP_ERR_UNSUPPORTED, "expression operators are not part of derivative objectives in this version");
+}
+
+int32_t srhip_eval_loss_deriv(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                              const double* loss_params, const int32_t* dir, int32_t ndir, double* out_loss_sum,
+                              double* out_weight_sum, uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog, true);
+    check_deriv(ds, prog, loss_kind, loss_params, dir, ndir);
+    CALL_SCOPE(prog->ctx);
+    auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_loss_deriv_impl<decltype(t)>(ds, p, loss_kind, loss_params, dir, ndir, out_loss_sum, out_weight_sum,
+                                               out_ok);
+    });
+  });
+}
+
+int32_t srhip_eval_loss_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees, int32_t loss_kind,
+                                        const double* loss_params, const int32_t* dir, int32_t ndir,
+                                        double* out_loss_sum, double* out_weight_sum, uint8_t* out_ok) {
+  if (!ds) return set_error(SRHIP_ERR_INVALID, "null dataset");
+  // the fused call runs in the interpreter: no tree code to build
+  return with_temp_program(ctx ? ctx : ds->ctx, ds, trees, SRHIP_PROGRAM_INTERPRETED, [&](srhip_program* p) {
+    return srhip_eval_loss_deriv(ds, p, loss_kind, loss_params, dir, ndir, out_loss_sum, out_weight_sum, out_ok);
   });
 }
 

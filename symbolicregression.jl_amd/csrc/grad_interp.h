@@ -45,10 +45,11 @@ __device__ __forceinline__ void un_grad(Dual<T, R, G>& a, T& chk) {
 }
 
 // RS: int for the LDS row tile, int64_t for the wide kernels' global array (interp.h)
-template <int V, int B, typename T, int R, int G, typename RS = int>
+// FEAT (run_program_grad): a feature operand seeds the slots whose direction dir[j] it is
+template <int V, int B, typename T, int R, int G, typename RS = int, bool FEAT = false>
 __device__ __forceinline__ void bin_grad(Dual<T, R, G>& a, const Dual<T, R, G>& t,
                                          const T* __restrict__ sXt, RS rs, int lane, int f,
-                                         T imm, int jc, T& chk) {
+                                         T imm, int jc, T& chk, const int* dir = nullptr) {
   constexpr int SL = src_l(V), SR = src_r(V);
   constexpr bool LL = bop_lossy_lhs(B), LR = bop_lossy_rhs(B);
   T xa[R], xb[R];
@@ -76,9 +77,12 @@ __device__ __forceinline__ void bin_grad(Dual<T, R, G>& a, const Dual<T, R, G>& 
       if constexpr (SL == S_ACC) nd = fx * a.d[j][r];
       else if constexpr (SL == S_TMP) nd = fx * t.d[j][r];
       else if constexpr (SL == S_C) nd = (j == jc) ? fx : T(0);
+      else if constexpr (FEAT && SL == S_X) nd = (f == dir[j]) ? fx : T(0);
       if constexpr (SR == S_ACC) nd = nd + fy * a.d[j][r];
       else if constexpr (SR == S_TMP) nd = nd + fy * t.d[j][r];
       else if constexpr (SR == S_C) nd = (j == jc) ? nd + fy : nd;
+      else if constexpr (FEAT && SR == S_X) nd = (f == dir[j]) ? nd + fy : nd;
+      else if constexpr (FEAT && SR == S_X2) nd = (imm_int(imm) == dir[j]) ? nd + fy : nd;
       a.d[j][r] = nd;
     }
     a.v[r] = fv;
@@ -100,16 +104,23 @@ __device__ __forceinline__ void bin_grad(Dual<T, R, G>& a, const Dual<T, R, G>& 
 #define SRG_UN(U) \
   case OP_UN0 + U: if constexpr (opset_has_uop(SET, U)) un_grad<U, T, R, G>(a, chk); break;
 #define SRG_BV(V, B) \
-  case bin_opcode(V, B): if constexpr (opset_has_bop(SET, B)) bin_grad<V, B, T, R, G>(a, t, sXt, rs, lane, f, imm, jc, chk); break;
+  case bin_opcode(V, B): if constexpr (opset_has_bop(SET, B)) bin_grad<V, B, T, R, G, RS, FEAT>(a, t, sXt, rs, lane, f, imm, jc, chk, dir); break;
 #define SRG_BIN(B) SRG_BV(V_AX, B) SRG_BV(V_XA, B) SRG_BV(V_AC, B) SRG_BV(V_CA, B) \
   SRG_BV(V_AT, B) SRG_BV(V_TA, B) SRG_BV(V_XX, B) SRG_BV(V_XC, B) SRG_BV(V_CX, B)
 
 // Run one tree's program over one row tile with tangents for constants
 // g0 .. g0+G-1; the result is left in a.
-template <typename T, int R, int D, int G, int SET, typename RS = int>
+//
+// FEAT (feature tangents, grad_kernel.h kGradLossDeriv): tangent slot j belongs to
+// the feature dir[j] instead (wave-uniform; an unused slot holds a negative
+// sentinel, which no feature index equals, and stays 0), so that a.d[j] = ∂ŷ/∂x_dir[j].
+// A feature leaf seeds 1 on the slots of its own feature, a feature operand adds
+// its partial derivative to them (both operands of V_XX, each by its own index),
+// and no constant seeds anything. The programs are the same gradient programs.
+template <typename T, int R, int D, int G, int SET, typename RS = int, bool FEAT = false>
 __device__ __forceinline__ void run_program_grad(CIns<T>* __restrict__ p,
                                                  const T* __restrict__ sXt, RS rs, int lane,
-                                                 int g0, Dual<T, R, G>& a, T& chk) {
+                                                 int g0, Dual<T, R, G>& a, T& chk, const int* dir = nullptr) {
   Dual<T, R, G> t;
   Dual<T, R, G> slot[D];
 #pragma unroll
@@ -126,6 +137,7 @@ __device__ __forceinline__ void run_program_grad(CIns<T>* __restrict__ p,
     const T imm = uni(cur.imm);
     int f = (int)(code >> 16);
     int jc = (int)((code >> 8) & 0xffu) - g0;  // tangent seeded by a constant operand
+    if constexpr (FEAT) jc = -1;
     T held = T(0);
     if constexpr (SET == OPSET_EXPR) {
       // expression operators: the no-mark flag shares the feature field, a body
@@ -156,7 +168,7 @@ __device__ __forceinline__ void run_program_grad(CIns<T>* __restrict__ p,
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
-          for (int j = 0; j < G; ++j) a.d[j][r] = T(0);
+          for (int j = 0; j < G; ++j) a.d[j][r] = (FEAT && f == dir[j]) ? T(1) : T(0);
         break;
       case OP_LDC:
 #pragma unroll

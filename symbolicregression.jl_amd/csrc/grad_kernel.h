@@ -24,6 +24,23 @@ using namespace interp;
 // column is the run-time a.w): the others keep their code.
 constexpr int kGradLossExpr = 2;
 
+// Kernel mode of a derivative objective (srhip_eval_loss_deriv): the tangents are
+// those of G features, the directions a.dir[g0 .. g0+G-1] (grad_interp.h FEAT), and
+// a table loss is reduced per channel in the same pass. The row tile stages the
+// a.ntgt = 1 + ndir columns of y (and of w) as TG does: column 0 is y, column 1 + k
+// the target of ∂ŷ/∂x_dir[k]. Per row, acc[0] += w₀·ℓ(ŷ, y) and acc[2 + j] +=
+// w_c·ℓ(∂ŷ/∂x_dir[g0+j], Y[c]) with c = 1 + g0 + j: the derivative stands in the
+// prediction's place. A slot past the last direction reads no column and stays 0.
+//
+// The engine's rule for the flag: acc[1] is the marker of the value evaluation
+// only, as in GRAD_LOSS, so a tree's ok is its did_succeed (the rule
+// eval_diff_tree_array follows here); a non-finite derivative gives a non-finite
+// channel sum with ok = 1 (the expression losses' rule). Parity
+// with DynamicExpressions' own completion flag for derivatives is unpinned.
+// Instantiations of their own (grad_deriv_f32.hip / grad_deriv_f64.hip; the full
+// operator set): the others keep their code.
+constexpr int kGradLossDeriv = 3;
+
 // XG: the wide variant (eval_kernel.h): y and w staged in LDS only, the programs'
 // feature operands read from a.X in global memory.
 //
@@ -44,6 +61,8 @@ template <typename T, int R, int D, int MODE, bool W, int G, int SET, bool XG = 
           bool TG = false>
 __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
   static_assert(!TG || (MODE == GRAD_LOSS && !SEG), "per-tree targets: table losses over shared rows");
+  constexpr bool DV = MODE == kGradLossDeriv;
+  static_assert(!DV || (!SEG && !TG), "derivative objectives: shared rows, their own columns");
   constexpr int S = 2 + G;
   constexpr int TILE = 64 * R;
   using V = typename V16<T>::type;
@@ -51,8 +70,8 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int rows = a.ntiles * TILE;
   const int nx = XG ? 0 : a.nfeat;  // feature arrays staged in LDS
-  const int ncol = TG ? a.ntgt : 1;  // columns of y (and of w)
-  const int narr = nx + (MODE == GRAD_LOSS ? ncol * (W ? 2 : 1) : MODE == kGradLossExpr ? (a.w ? 2 : 1) : 0);
+  const int ncol = (TG || DV) ? a.ntgt : 1;  // columns of y (and of w)
+  const int narr = nx + ((MODE == GRAD_LOSS || DV) ? ncol * (W ? 2 : 1) : MODE == kGradLossExpr ? (a.w ? 2 : 1) : 0);
   T* sX = reinterpret_cast<T*>(smem);
   T* sY = sX + (size_t)nx * rows;
   T* sW = sY + (size_t)ncol * rows;
@@ -70,7 +89,7 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
       const int arr = idx / vper;
       const int v = idx - arr * vper;
       const T* src = arr < nx ? a.X + (size_t)arr * a.n_pad : (arr == nx ? a.y : a.w);
-      if constexpr (TG) {  // columns of y, then of w, n_pad rows apart
+      if constexpr (TG || DV) {  // columns of y, then of w, n_pad rows apart
         if (arr >= nx) src = arr < nx + ncol ? a.y + (size_t)(arr - nx) * a.n_pad : a.w + (size_t)(arr - nx - ncol) * a.n_pad;
       }
       reinterpret_cast<V*>(sX + (size_t)arr * rows)[v] = reinterpret_cast<const V*>(src + seg0 + row0)[v];
@@ -107,16 +126,23 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
     const int nc = __builtin_amdgcn_readfirstlane(a.const_off[t + 1]) - cbase;
     int col = 0;  // this tree's column of the staged y (and w): wave-uniform, one scalar load per item
     if constexpr (TG) col = __builtin_amdgcn_readfirstlane(a.tgt[t]) * rows;
+    int dir[G];  // DV: the feature of each tangent slot, wave-uniform, one scalar load each per item
+    if constexpr (DV) {
+#pragma unroll
+      for (int j = 0; j < G; ++j) dir[j] = __builtin_amdgcn_readfirstlane(a.dir[g0 + j]);
+    }
     T acc[S];
 #pragma unroll
-    for (int k = 0; k < S; ++k) acc[k] = T(0);  // [0] Σ w·ℓ, [1] marker, [2+j] Σ w·ℓ'·∂ŷ/∂c
+    for (int k = 0; k < S; ++k) acc[k] = T(0);  // [0] Σ w·ℓ, [1] marker, [2+j] Σ w·ℓ'·∂ŷ/∂c (DV: Σ w·ℓ(∂ŷ/∂x))
     for (int tl = 0; tl < nt_valid; ++tl) {
       Dual<T, R, G> d;
       if constexpr (XG) {
-        run_program_grad<T, R, D, G, SET>(p, a.X + seg0 + row0 + tl * TILE, a.n_pad, lane, g0, d, acc[1]);
+        if constexpr (DV) run_program_grad<T, R, D, G, SET, int64_t, true>(p, a.X + row0 + tl * TILE, a.n_pad, lane, g0, d, acc[1], dir);
+        else run_program_grad<T, R, D, G, SET>(p, a.X + seg0 + row0 + tl * TILE, a.n_pad, lane, g0, d, acc[1]);
       } else {
         const T* sXt = sX + tl * TILE;
-        run_program_grad<T, R, D, G, SET>(p, sXt, rows, lane, g0, d, acc[1]);
+        if constexpr (DV) run_program_grad<T, R, D, G, SET, int, true>(p, sXt, rows, lane, g0, d, acc[1], dir);
+        else run_program_grad<T, R, D, G, SET>(p, sXt, rows, lane, g0, d, acc[1]);
       }
 #pragma unroll
       for (int r = 0; r < R; ++r) acc[1] = mark(d.v[r], acc[1]);
@@ -143,6 +169,27 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs<T> a) {
             acc[0] += in ? ld.v[e] : T(0);
 #pragma unroll
             for (int j = 0; j < G; ++j) acc[2 + j] += in ? ld.d[0][e] * d.d[j][e] : T(0);
+          }
+        } else if constexpr (DV) {
+#pragma unroll
+          for (int e = 0; e < R; ++e) {
+            T l = dev::elem_loss<T>(a.loss, lp, d.v[e], yv[e]);
+            if constexpr (W) l = wv[e] * l;
+            acc[0] += row_of<T, R>(e, lane) < valid ? l : T(0);
+          }
+#pragma unroll
+          for (int j = 0; j < G; ++j) {
+            const int c = 1 + g0 + j;  // the channel's column: wave-uniform
+            if (c < ncol) {
+              lds_rows<T, R>(sY + c * rows + tl * TILE, lane, yv);
+              if constexpr (W) lds_rows<T, R>(sW + c * rows + tl * TILE, lane, wv);
+#pragma unroll
+              for (int e = 0; e < R; ++e) {
+                T l = dev::elem_loss<T>(a.loss, lp, d.d[j][e], yv[e]);
+                if constexpr (W) l = wv[e] * l;
+                acc[2 + j] += row_of<T, R>(e, lane) < valid ? l : T(0);
+              }
+            }
           }
         } else {
 #pragma unroll
@@ -266,6 +313,84 @@ hipError_t launch_grad_targets_all(const EvalPlan& plan, const GradArgs<T>& a, i
   if (a.G == 1) return launch_grad_targets_g<T, 1>(plan, a, stream);
   if (a.G == 2) return launch_grad_targets_g<T, 2>(plan, a, stream);
   return launch_grad_targets_g<T, kGradG>(plan, a, stream);
+}
+
+// ---- derivative objectives (grad_deriv_f32.hip / grad_deriv_f64.hip) ---------------
+// kGradLossDeriv with a table loss, weighted or not, the full operator set: the shallow
+// variants at 1, 2 and kGradG tangents, the deep one, the wide one.
+template <typename T, int R, int D, int G, bool XG = false>
+hipError_t launch_grad_deriv_rd(const EvalPlan& plan, const GradArgs<T>& a, hipStream_t stream) {
+  if (a.w) return launch_grad_one<T, R, D, kGradLossDeriv, true, G, OPSET_FULL, XG>(plan, a, stream);
+  return launch_grad_one<T, R, D, kGradLossDeriv, false, G, OPSET_FULL, XG>(plan, a, stream);
+}
+
+template <typename T>
+hipError_t launch_grad_deriv_all(const EvalPlan& plan, const GradArgs<T>& a, hipStream_t stream) {
+  if (a.loss >= SRHIP_MARGIN_LOSS_BEGIN || a.opset == OPSET_EXPR || a.seg > 0 || a.tgt || !a.dir || a.ntgt < 2)
+    return hipErrorInvalidValue;
+  if (plan.wide) return launch_grad_deriv_rd<T, 1, kMaxSlots, kGradG, true>(plan, a, stream);
+  if (plan.D != 4) return launch_grad_deriv_rd<T, 1, kMaxSlots, kGradG>(plan, a, stream);  // deep programs: one variant
+  constexpr int R12 = sizeof(T) == 4 ? 4 : 1, R4 = sizeof(T) == 4 ? 2 : 1;  // grad_R, shallow
+  if (a.G == 1) return launch_grad_deriv_rd<T, R12, 4, 1>(plan, a, stream);
+  if (a.G == 2) return launch_grad_deriv_rd<T, R12, 4, 2>(plan, a, stream);
+  return launch_grad_deriv_rd<T, R4, 4, kGradG>(plan, a, stream);
+}
+
+// Σ over row groups of a derivative launch's partials in fp64, in grad_finalize_kernel's
+// fixed order, into out_sum [ntrees][1 + ndir]: group 0 writes channel 0 and the flag,
+// every group the channels of its own directions. Each group evaluated the value, so
+// each holds the tree's marker: a failed tree's whole row is NaN.
+template <typename T, int G>
+__global__ void __launch_bounds__(256) deriv_finalize_kernel(GradArgs<T> a, double* __restrict__ out_sum,
+                                                             uint8_t* __restrict__ out_ok) {
+  constexpr int S = 2 + G;
+  __shared__ double sh[4][S][64];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int npos = a.ntg * a.tpb;
+  const int pos = blockIdx.x * 64 + lane;
+  double acc[S];
+  for (int k = 0; k < S; ++k) acc[k] = 0.0;
+  if (pos < npos) {
+    for (int rg = w; rg < a.nrg; rg += 4) {
+      const T* q = a.partial + ((size_t)rg * npos + pos) * S;
+      for (int k = 0; k < S; ++k) acc[k] += (double)q[k];
+    }
+  }
+  for (int k = 0; k < S; ++k) sh[w][k][lane] = acc[k];
+  __syncthreads();
+  if (w == 0 && pos < npos) {
+    for (int k = 0; k < S; ++k) acc[k] = (sh[0][k][lane] + sh[1][k][lane]) + (sh[2][k][lane] + sh[3][k][lane]);
+    const int g = pos / a.tpb;
+    const int i = pos - g * a.tpb;
+    const int sidx = i * a.ntg + ((i & 1) ? (a.ntg - 1 - g) : g);
+    if (sidx < a.nitems) {
+      const int item = a.items[sidx];
+      const int t = item & 0xffffff;
+      const int g0 = (item >> 24) * kGradG;
+      const bool ok = !__builtin_isnan(acc[1]);
+      double* row = out_sum + (size_t)t * a.ntgt;
+      if (g0 == 0) {
+        row[0] = ok ? acc[0] : __builtin_nan("");
+        out_ok[t] = ok ? 1 : 0;
+      }
+      for (int j = 0; j < G; ++j)
+        if (1 + g0 + j < a.ntgt) row[1 + g0 + j] = ok ? acc[2 + j] : __builtin_nan("");
+    }
+  }
+}
+
+template <typename T>
+hipError_t launch_grad_deriv_finalize_all(const GradArgs<T>& a, double* out_sum, uint8_t* out_ok, hipStream_t stream) {
+  const int npos = a.ntg * a.tpb;
+  const unsigned grid = (unsigned)((npos + 63) / 64);
+  if (a.G == 1)
+    hipLaunchKernelGGL((deriv_finalize_kernel<T, 1>), dim3(grid), dim3(256), 0, stream, a, out_sum, out_ok);
+  else if (a.G == 2)
+    hipLaunchKernelGGL((deriv_finalize_kernel<T, 2>), dim3(grid), dim3(256), 0, stream, a, out_sum, out_ok);
+  else
+    hipLaunchKernelGGL((deriv_finalize_kernel<T, kGradG>), dim3(grid), dim3(256), 0, stream, a, out_sum, out_ok);
+  return hipGetLastError();
 }
 
 }  // namespace

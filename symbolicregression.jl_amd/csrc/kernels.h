@@ -140,6 +140,11 @@ struct GradArgs {
   // are then [ntgt][n_pad] (target-major); nullptr / 0: one y, one w
   const int32_t* tgt = nullptr;
   int ntgt = 0;
+  // derivative objectives (srhip_eval_loss_deriv; the kGradLossDeriv variants of
+  // grad_deriv_*.hip): the feature of each tangent, [groups · kGradG] with a negative
+  // sentinel past the last direction; y / w are then ntgt = 1 + ndir columns
+  // (y, then one per direction) and tgt is null
+  const int32_t* dir = nullptr;
 };
 
 // ntgt > 0 (a per-tree-targets launch): the tile holds ntgt columns of y (and of w).
@@ -155,6 +160,12 @@ hipError_t launch_grad_seg(const EvalPlan& plan, const GradArgs<T>& a, int mode,
 // the per-tree-targets variants (a.tgt set, GRAD_LOSS, shared rows; launch_grad forwards to them)
 template <typename T>
 hipError_t launch_grad_targets(const EvalPlan& plan, const GradArgs<T>& a, int mode, hipStream_t stream);
+// the derivative-objective variants (a.dir set; grad_deriv_f32.hip / grad_deriv_f64.hip) and
+// their finalisation into out_sum [ntrees][a.ntgt], out_ok [ntrees]
+template <typename T>
+hipError_t launch_grad_deriv(const EvalPlan& plan, const GradArgs<T>& a, hipStream_t stream);
+template <typename T>
+hipError_t launch_grad_deriv_finalize(const GradArgs<T>& a, double* out_sum, uint8_t* out_ok, hipStream_t stream);
 template <typename T>
 hipError_t launch_grad_finalize(const GradArgs<T>& a, double* out_sum, uint8_t* out_ok,
                                 double* out_dloss, hipStream_t stream);

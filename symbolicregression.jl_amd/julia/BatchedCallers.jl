@@ -66,13 +66,20 @@ import ..SRHip
     score_batch(dataset, trees, options) -> (scores, losses)
 
 score_func (src/LossFunctions.jl:86-92) for every tree: one SRHip launch when
-the engine covers the options, else the reference, tree by tree.
+the engine covers the options (a `loss_function` that is a
+SRHip.DerivativeObjective included: SRHip.eval_loss_deriv), else the reference,
+tree by tree.
 """
 function score_batch(dataset::Dataset{T}, trees::AbstractVector{Node{T}}, options::Options;
                      device::Int=0) where {T}
     if !isempty(trees) && SRHip.enabled(options)
         try
-            losses = SRHip.eval_loss_batch(trees, dataset, options; device=device)
+            # a derivative objective: every channel of every tree in one fused call
+            if options.loss_function isa SRHip.DerivativeObjective
+                losses = SRHip.eval_loss_deriv(trees, dataset, options; device=device)[1]
+            else
+                losses = SRHip.eval_loss_batch(trees, dataset, options; device=device)
+            end
             scores = [loss_to_score(l, dataset.baseline_loss, t, options) for (l, t) in zip(losses, trees)]
             return scores, losses
         catch e
@@ -94,7 +101,8 @@ the reference.
 """
 function score_batch_minibatch(dataset::Dataset{T}, trees::AbstractVector{Node{T}}, options::Options;
                                device::Int=0) where {T}
-    if !isempty(trees) && SRHip.enabled(options)
+    # (a loss_function, a DerivativeObjective included, is scored on all rows only)
+    if !isempty(trees) && SRHip.enabled(options) && options.loss_function === nothing
         try
             idx = rand(1:(dataset.n), options.batch_size, length(trees))  # column t: tree t's sample
             losses = SRHip.eval_loss_batch_rowsets(trees, dataset, options, idx; device=device)
@@ -123,7 +131,7 @@ function score_batch_multi(datasets::AbstractVector{<:Dataset{T}}, js::AbstractV
                            trees::AbstractVector{Node{T}}, options::Options; device::Int=0) where {T}
     length(js) == length(trees) || throw(ArgumentError("one output index per tree"))
     shared = all(d -> d.X === datasets[1].X && d.weighted == datasets[1].weighted, datasets)
-    if !isempty(trees) && shared && SRHip.enabled(options)
+    if !isempty(trees) && shared && SRHip.enabled(options) && options.loss_function === nothing
         try
             if options.batching
                 idx = rand(1:(datasets[1].n), options.batch_size, length(trees))  # column t: tree t's sample
@@ -200,7 +208,8 @@ reference's full-data optimiser either way.
 function optimize_constants_batched(dataset::Dataset{T}, members::AbstractVector{<:PopMember{T}},
                                     options::Options; device::Int=0, minibatch::Bool=false) where {T}
     isempty(members) && return Float64[]
-    if SRHip.enabled(options)
+    # (no constant optimisation under a derivative objective on the engine: the reference's optimiser)
+    if SRHip.enabled(options) && options.loss_function === nothing
         try
             trees = Node{T}[m.tree for m in members]
             sampled = minibatch && options.batching
@@ -253,7 +262,7 @@ function optimize_constants_batched_multi(datasets::AbstractVector{<:Dataset{T}}
     isempty(members) && return Float64[]
     shared = all(d -> d.X === datasets[1].X && d.weighted == datasets[1].weighted, datasets)
     use_fused = fused === nothing ? length(members) <= FUSED_CONSTOPT_MAX_MEMBERS : fused
-    if use_fused && shared && SRHip.enabled(options)
+    if use_fused && shared && SRHip.enabled(options) && options.loss_function === nothing
         try
             trees = Node{T}[m.tree for m in members]
             sampled = minibatch && options.batching

@@ -12,6 +12,7 @@ module SRHip
 
 using DynamicExpressions: Node, count_nodes, set_constants
 import DynamicExpressions  # DynamicExpressions.eval_tree_array: the CPU path of ExprLoss
+import LossFunctions  # LossFunctions.value: the CPU definition of DerivativeObjective
 using LossFunctions: L2DistLoss, L1DistLoss, LPDistLoss, HuberLoss, LogCoshLoss, L1EpsilonInsLoss,
     L2EpsilonInsLoss, QuantileLoss, PeriodicLoss, LogitDistLoss,
     ZeroOneLoss, PerceptronLoss, LogitMarginLoss, L1HingeLoss, L2HingeLoss, SmoothedL1HingeLoss,
@@ -202,7 +203,8 @@ end
     enabled(options) -> Bool
 
 Whether `options` can run on the engine: a device is visible, `loss_function`
-is not set (arbitrary Julia stays on the CPU, src/LossFunctions.jl:60-67), the
+is not set (arbitrary Julia stays on the CPU, src/LossFunctions.jl:60-67) or is
+a `DerivativeObjective` (scored by the fused call `eval_loss_deriv`), the
 elementwise loss and every operator are in the engine's table. Set
 ENV["SRHIP_DISABLE"] = "1" to force the reference path.
 """
@@ -211,7 +213,7 @@ function enabled(options::Options)
     # the recorder's genealogy (src/Recorder.jl, Options.jl:597-599) is written by
     # the reference's per-candidate loops: with it on, the search stays there
     options.recorder && return false
-    options.loss_function === nothing || return false
+    (options.loss_function === nothing || options.loss_function isa DerivativeObjective) || return false
     device_available() || return false
     try
         loss_code(options.elementwise_loss)
@@ -1201,6 +1203,137 @@ function optimize_constants_batch!(trees::AbstractVector{Node{T}}, dataset::Data
         converged[i] && set_constants(trees[i], out_c[(const_off[i] + 1):const_off[i + 1]])
     end
     return T.(out_l), converged, out_n
+end
+
+# ---- derivative objectives (srhip.h "derivative objectives") -------------------------
+"""
+    DerivativeObjective(coefficients, directions, dydx; weights=nothing)
+
+A `loss_function` that scores the prediction and its derivatives with respect to features
+("a loss that takes into account derivatives", src/Options.jl:203-210):
+`Σ_k coefficients[k] · mean_k`, where `mean_1` is the (weighted) mean of
+`options.elementwise_loss` on `(ŷ, dataset.y)` and `mean_{1+j}` that of the same loss on
+`(∂ŷ/∂x_d, dydx[j, :])` along `d = directions[j]` (1-based features, as
+`eval_diff_tree_array`'s `direction`). `weights` is `nothing` (the dataset's own weights, if
+any, on every channel) or `(1 + ndir, n)`, one row per channel. `T(Inf)` when an evaluation
+does not complete or the result is not finite.
+
+The method `(f)(tree, dataset, options)` is the CPU definition, built from
+DynamicExpressions' `eval_tree_array` / `eval_diff_tree_array`, so the struct is a legal
+`loss_function` on its own; `enabled(options)` accepts it and `eval_loss_deriv` /
+`BatchedCallers.score_batch` score whole batches with one engine call
+(srhip_eval_loss_deriv). Not covered there (the CPU definition runs): row samples
+(`options.batching`), constant optimisation, expression losses and operators.
+"""
+struct DerivativeObjective{T} <: Function
+    coefficients::Vector{Float64}
+    directions::Vector{Int}
+    dydx::Matrix{T}                      # (ndir, n)
+    weights::Union{Nothing,Matrix{T}}    # (1 + ndir, n) or nothing
+    function DerivativeObjective(coefficients::AbstractVector{<:Real}, directions::AbstractVector{<:Integer},
+                                 dydx::AbstractMatrix{T};
+                                 weights::Union{Nothing,AbstractMatrix{T}}=nothing) where {T}
+        nd = length(directions)
+        1 <= nd <= 15 || throw(ArgumentError("1 to 15 directions"))
+        allunique(directions) || throw(ArgumentError("directions must not repeat"))
+        all(>=(1), directions) || throw(ArgumentError("directions are 1-based feature indices"))
+        length(coefficients) == 1 + nd || throw(ArgumentError("one coefficient per channel: y, then one per direction"))
+        size(dydx, 1) == nd || throw(ArgumentError("dydx must be (ndir, n)"))
+        weights === nothing || size(weights) == (1 + nd, size(dydx, 2)) ||
+            throw(ArgumentError("weights must be (1 + ndir, n)"))
+        return new{T}(Float64.(coefficients), Int.(directions), Matrix{T}(dydx),
+                      weights === nothing ? nothing : Matrix{T}(weights))
+    end
+end
+
+# the weights of channel k (1 = y), or nothing
+function channel_weights(f::DerivativeObjective{T}, dataset::Dataset{T}, k::Int) where {T}
+    f.weights !== nothing && return f.weights[k, :]
+    return dataset.weighted ? dataset.weights : nothing
+end
+
+function channel_mean(loss, pred::AbstractVector{T}, target::AbstractVector{T}, w) where {T}
+    w === nothing && return Float64(LossFunctions.value(loss, target, pred, LossFunctions.AggMode.Mean()))
+    return Float64(LossFunctions.value(loss, target, pred, LossFunctions.AggMode.WeightedMean(w)))
+end
+
+function (f::DerivativeObjective{T})(tree::Node{T}, dataset::Dataset{T}, options::Options)::T where {T}
+    size(f.dydx, 2) == dataset.n || throw(ArgumentError("dydx has $(size(f.dydx, 2)) rows, the dataset $(dataset.n)"))
+    all(<=(size(dataset.X, 1)), f.directions) || throw(ArgumentError("direction outside the dataset's features"))
+    loss = options.elementwise_loss
+    pred, complete = DynamicExpressions.eval_tree_array(tree, dataset.X, options.operators)
+    complete || return T(Inf)
+    total = f.coefficients[1] * channel_mean(loss, pred, dataset.y, channel_weights(f, dataset, 1))
+    for (j, d) in enumerate(f.directions)
+        _, g, complete = DynamicExpressions.eval_diff_tree_array(tree, dataset.X, options.operators, d)
+        complete || return T(Inf)
+        total += f.coefficients[1 + j] * channel_mean(loss, g, f.dydx[j, :], channel_weights(f, dataset, 1 + j))
+    end
+    return isfinite(total) ? T(total) : T(Inf)
+end
+
+"""
+    eval_loss_deriv(trees, dataset, options; device=0) -> (losses, means, ok)
+
+The derivative objective `options.loss_function::DerivativeObjective` for every tree in one
+engine call (srhip_eval_loss_deriv): `losses[i] = T(Σ_k coefficients[k] · means[i, k])`,
+`T(Inf)` where the tree fails or the result is not finite; `means` is (ntrees, 1 + ndir) in
+Float64. The columns `[y; dydx]` go up once per call next to `dataset.X`
+(srhip_dataset_create_multi). `Unsupported` for expression losses and expression operators
+(the callers fall back to the CPU definition).
+"""
+function eval_loss_deriv(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, options::Options;
+                         device::Int=0) where {T}
+    f = options.loss_function::DerivativeObjective{T}
+    nt = length(trees)
+    nd = length(f.directions)
+    nfeat, n = size(dataset.X)
+    size(f.dydx, 2) == n || throw(ArgumentError("dydx has $(size(f.dydx, 2)) rows, the dataset $(n)"))
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    node_off, kind, arg, const_off, consts = flatten(trees, options)
+    Xc = Matrix{T}(dataset.X)
+    Yc = Matrix{T}(undef, n, 1 + nd)     # column k = channel k: [1 + ndir][n] in C
+    Yc[:, 1] .= dataset.y
+    for j in 1:nd
+        Yc[:, 1 + j] .= f.dydx[j, :]
+    end
+    weighted = f.weights !== nothing || dataset.weighted
+    Wc = weighted ? Matrix{T}(undef, n, 1 + nd) : nothing
+    if weighted
+        for k in 1:(1 + nd)
+            Wc[:, k] .= channel_weights(f, dataset, k)
+        end
+    end
+    dir = Int32.(f.directions .- 1)
+    sums = Matrix{Float64}(undef, 1 + nd, nt)   # [ntrees][1 + ndir] in C
+    wsum = Vector{Float64}(undef, 1 + nd)
+    ok = Vector{UInt8}(undef, nt)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve node_off kind arg const_off consts Xc Yc Wc dir sums wsum ok params begin
+        check(ccall((:srhip_dataset_create_multi, libsrhip), Int32,
+                    (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Int64, Int32, Int32, Int64, Int64,
+                     Ptr{Ptr{Cvoid}}),
+                    context(device), dtype_code(T), X_JULIA, Xc, Yc,
+                    Wc === nothing ? Ptr{T}(C_NULL) : Wc, n, nfeat, 1 + nd, 0, n, h))
+        try
+            tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
+                                Ptr{Cvoid}(pointer(consts))))
+            check(ccall((:srhip_eval_loss_deriv_batch_ctx, libsrhip), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Int32, Ptr{Float64}, Ptr{Int32}, Int32,
+                         Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                        context(device), h[], tr, kindcode, params, dir, Int32(nd), sums, wsum, ok))
+        finally
+            destroy_dataset(h[])
+        end
+    end
+    means = permutedims(sums ./ wsum)
+    losses = Vector{T}(undef, nt)
+    for i in 1:nt
+        v = sum(f.coefficients[k] * means[i, k] for k in 1:(1 + nd))
+        losses[i] = (ok[i] == 1 && isfinite(v)) ? T(v) : T(Inf)
+    end
+    return losses, means, ok .== 1
 end
 
 end # module

@@ -34,7 +34,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from ._lib import CONSTOPT_EVAL_FN, ConstOptOptions, check, lib
-from .dataset import Dataset, GroupDataset, MultiDataset
+from .dataset import Dataset, DerivativeDataset, GroupDataset, MultiDataset
 from .engine import _trees_struct
 from .node import Node, flatten, set_constants
 from .options import Options
@@ -107,6 +107,9 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
     noise (a factory whose signature accepts `target=` is told k); `fused`
     forces either where both apply. The noise array is the same either way:
     start_noise's order over the trees as given."""
+    if isinstance(dataset, DerivativeDataset):
+        raise ValueError("constant optimisation under a derivative objective is not supported in this version (it needs "
+                         "∂²ŷ/∂c∂x or finite differences): optimise on dataset.target(0) to fit the value alone")
     multi = isinstance(dataset, MultiDataset)
     if multi:
         from .interface import _check_targets

@@ -119,6 +119,71 @@ class MultiDataset:
         return d
 
 
+class DerivativeDataset(Dataset):
+    """A Dataset with targets for the derivatives of the prediction as well: dydx
+    (ndir, n) holds, per row, the target of ∂ŷ/∂x_d for each d of `directions`
+    (1-based feature indices, as the reference's `direction::Int` of
+    eval_diff_tree_array). weights is None, (n,) — shared by all channels — or
+    (1 + ndir, n), channel 0 being y's. It wraps a MultiDataset with
+    Y = [y; dydx], so X is stored and uploaded once: `multi` is that dataset,
+    target(k) channel k as an ordinary Dataset, and the object itself is the
+    Dataset over (X, y, weights of channel 0) wherever only the value is scored.
+    A DerivativeObjective (options.loss_function) scores all channels."""
+
+    def __init__(self, X: np.ndarray, y: np.ndarray, dydx: np.ndarray, directions: Sequence[int],
+                 weights: Optional[np.ndarray] = None, varMap: Optional[Sequence[str]] = None):
+        X = np.asarray(X)
+        y = np.asarray(y)
+        dydx = np.asarray(dydx)
+        if X.ndim != 2:
+            raise ValueError("X must be (nfeatures, n)")
+        nfeat, n = X.shape
+        try:
+            dirs = [int(d) for d in directions]
+        except TypeError:
+            raise ValueError("directions must be a sequence of 1-based feature indices") from None
+        if any(d != dd for d, dd in zip(dirs, directions)):
+            raise ValueError("directions must be integers")
+        if not 1 <= len(dirs) <= 15:
+            raise ValueError("a DerivativeDataset takes 1 to 15 directions")
+        if any(not 1 <= d <= nfeat for d in dirs):
+            raise ValueError(f"directions must be 1-based feature indices within 1..{nfeat}")
+        if len(set(dirs)) != len(dirs):
+            raise ValueError("directions must not repeat")
+        if y.shape != (n,):
+            raise ValueError(f"y must be (n,) = ({n},), not {y.shape}")
+        if dydx.shape != (len(dirs), n):
+            raise ValueError(f"dydx must be (ndir, n) = ({len(dirs)}, {n}), not {dydx.shape}")
+        for name, a in (("X", X), ("y", y), ("dydx", dydx)):
+            if a.dtype not in (np.float32, np.float64):
+                raise ValueError(f"{name} must be float32 or float64")
+        if not (X.dtype == y.dtype == dydx.dtype):
+            raise ValueError("X, y and dydx must have one dtype")
+        W = None
+        if weights is not None:
+            w = np.asarray(weights)
+            if w.dtype != X.dtype:
+                raise ValueError("weights must have the dtype of X")
+            if w.shape == (n,):
+                W = np.broadcast_to(w, (1 + len(dirs), n))
+            elif w.shape == (1 + len(dirs), n):
+                W = w
+            else:
+                raise ValueError(f"weights must be (n,) or (1 + ndir, n) = ({1 + len(dirs)}, {n}), not {w.shape}")
+        super().__init__(X, y, None if W is None else W[0], varMap)
+        self.dydx = dydx
+        self.directions = tuple(dirs)
+        self.ndir = len(dirs)
+        self.multi = MultiDataset(X, np.concatenate([y[None, :], dydx]), W, varMap)
+
+    def target(self, k: int) -> Dataset:
+        """Channel k (0: y; 1 + j: the derivative along directions[j]) as a Dataset."""
+        return self.multi.target(k)
+
+    def device(self, device: Optional[int] = None) -> DeviceDataset:
+        return self.multi.target(0).device(device)
+
+
 class GroupDataset(Dataset):
     """A Dataset whose rows are sharded over the members of a DeviceGroup
     (srhip_group_dataset), uploaded when it is made. eval_loss_batch_ok,

@@ -438,6 +438,25 @@ class Program:
                                                  _p(grads), _p(wsum), _p(ok)))
         return sums[:nt], grads[:nc], wsum, ok[:nt].astype(bool)
 
+    def eval_loss_deriv(self, ds, loss_kind: int, directions, params=None):
+        """srhip_eval_loss_deriv: one table loss on ŷ and on ∂ŷ/∂x_d for every d of
+        directions (0-based feature indices), over a MultiDeviceDataset whose columns
+        are y and one target per direction: (Σ w·ℓ [ntrees, 1 + ndir], Σ w per column
+        [1 + ndir], ok). A failed tree's row is NaN; a non-finite derivative leaves
+        ok set and its channel non-finite."""
+        nt = self.ntrees
+        d = np.ascontiguousarray(directions, dtype=np.int32)
+        if d.ndim != 1:
+            raise ValueError("directions must be a list of feature indices")
+        nd = len(d)
+        sums = np.zeros((max(nt, 1), 1 + nd), dtype=np.float64)
+        wsum = np.zeros(1 + nd, dtype=np.float64)
+        ok = np.zeros(max(nt, 1), dtype=np.uint8)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_eval_loss_deriv(ds.handle, self.handle, int(loss_kind), _p(par), _p(d) if nd else None, nd,
+                                          _p(sums), _p(wsum), _p(ok)))
+        return sums[:nt], wsum, ok[:nt].astype(bool)
+
     def eval_loss_grad_rowsets_targets(self, ds, loss_kind: int, targets, row_idx, params=None):
         """srhip_eval_loss_grad_rowsets_targets: tree t on its own rows row_idx[t]
         against column targets[t]: (Σ w·ℓ per tree, Σ w·∂ℓ/∂c per constant, Σ w per

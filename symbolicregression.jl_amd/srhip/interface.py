@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import constants as K
-from .dataset import Dataset, GroupDataset, MultiDataset
+from .dataset import Dataset, DerivativeDataset, GroupDataset, MultiDataset
 from .engine import DeviceDataset, Program, get_context
 from .node import Node, count_nodes, flatten
 from .options import Options
@@ -165,6 +165,142 @@ def eval_grad_tree_array(tree: TreeOrTrees, X: np.ndarray, options: Options, var
     if single:
         return val[0], grads[0], bool(ok[0])
     return val, grads, ok
+
+
+# ---- derivative objectives: losses on ŷ and on ∂ŷ/∂x ----------------------------------
+def _host_loss(loss, pred: np.ndarray, target: np.ndarray) -> np.ndarray:
+    """The distance losses of srhip.h per row on the host, in float64
+    (LossFunctions.jl's definitions on the residual r = prediction - target)."""
+    name = K.LOSSES[loss.kind] if 0 <= loss.kind < len(K.LOSSES) else None
+    if name is None or loss.kind >= K.MARGIN_LOSS_BEGIN:
+        raise ValueError("a derivative objective takes a distance loss (L2DistLoss, L1DistLoss, HuberLoss, ...)")
+    r = np.asarray(pred, dtype=np.float64) - np.asarray(target, dtype=np.float64)
+    ar = np.abs(r)
+    p = float(loss.param)
+    with np.errstate(all="ignore"):
+        if name == "L2":
+            return r * r
+        if name == "L1":
+            return ar
+        if name in ("LP", "LPINT"):
+            return ar ** p
+        if name == "HUBER":
+            return np.where(ar <= p, 0.5 * r * r, p * (ar - 0.5 * p))
+        if name == "LOGCOSH":
+            return ar + np.log1p(np.exp(-2.0 * ar)) - np.log(2.0)
+        if name == "L1EPSINS":
+            return np.maximum(ar - p, 0.0)
+        if name == "L2EPSINS":
+            return np.maximum(ar - p, 0.0) ** 2
+        if name == "QUANTILE":
+            return np.where(r >= 0.0, p * r, (p - 1.0) * r)
+        if name == "PERIODIC":
+            return 1.0 - np.cos(r * (2.0 * np.pi / p))
+        return ar + 2.0 * np.log1p(np.exp(-ar)) - np.log(4.0)  # LOGITDIST
+
+
+class DerivativeObjective:
+    """A `loss_function` that scores the prediction and its derivatives with
+    respect to features ("a loss that takes into account derivatives",
+    src/Options.jl:203-210): Σ_k coefficients[k] · mean_k, where mean_0 is the
+    weighted mean of ℓ(ŷ, y) and mean_{1+j} that of ℓ(∂ŷ/∂x_d, dydx[j]) along
+    d = dataset.directions[j], over a DerivativeDataset. ℓ is `elementwise_loss`
+    (a distance loss; default: options.elementwise_loss). +Inf when the tree
+    fails or the result is not finite.
+
+    Called as f(tree, dataset, options) it evaluates one tree through
+    eval_tree_array and eval_diff_tree_array, so it is a valid
+    options.loss_function anywhere; eval_loss_batch_ok recognises it on a
+    DerivativeDataset and scores the whole batch in one fused engine call
+    (eval_deriv_loss_batch). `eval_tree_array` / `eval_diff_tree_array` replace the
+    two evaluators of the per-tree call (tests run it on a CPU evaluator)."""
+
+    def __init__(self, coefficients: Sequence[float], elementwise_loss=None, eval_tree_array=None,
+                 eval_diff_tree_array=None):
+        c = np.asarray(coefficients, dtype=np.float64)
+        if c.ndim != 1 or len(c) < 2:
+            raise ValueError("coefficients must hold one value per channel: y, then one per direction")
+        if not np.isfinite(c).all():
+            raise ValueError("coefficients must be finite")
+        if elementwise_loss is not None and (not hasattr(elementwise_loss, "kind")
+                                             or not 0 <= elementwise_loss.kind < K.MARGIN_LOSS_BEGIN):
+            raise ValueError("a derivative objective takes a distance loss (L2DistLoss, L1DistLoss, HuberLoss, ...)")
+        self.coefficients = c
+        self.elementwise_loss = elementwise_loss
+        self._eval = eval_tree_array
+        self._diff = eval_diff_tree_array
+
+    def loss(self, options: Options):
+        loss = self.elementwise_loss if self.elementwise_loss is not None else options.elementwise_loss
+        if not hasattr(loss, "kind") or not 0 <= loss.kind < K.MARGIN_LOSS_BEGIN:
+            raise ValueError("a derivative objective takes a distance loss (L2DistLoss, L1DistLoss, HuberLoss, ...)")
+        return loss
+
+    def check(self, dataset) -> "DerivativeDataset":
+        if not isinstance(dataset, DerivativeDataset):
+            raise ValueError("a DerivativeObjective scores a DerivativeDataset")
+        if len(self.coefficients) != 1 + dataset.ndir:
+            raise ValueError(f"{len(self.coefficients)} coefficients for {1 + dataset.ndir} channels "
+                             "(y, then one per direction)")
+        return dataset
+
+    def combine(self, means: np.ndarray, ok: np.ndarray, T) -> np.ndarray:
+        """Σ_k coefficients[k] · means[:, k] in float64, cast to T; +Inf where !ok or not finite."""
+        with np.errstate(all="ignore"):
+            v = np.asarray(means, dtype=np.float64) @ self.coefficients
+            out = v.astype(T)
+        out[~(np.asarray(ok, dtype=bool) & np.isfinite(v))] = T(np.inf)
+        return out
+
+    def __call__(self, tree: Node, dataset, options: Options):
+        ds = self.check(dataset)
+        loss = self.loss(options)
+        ev = self._eval if self._eval is not None else eval_tree_array
+        df = self._diff if self._diff is not None else eval_diff_tree_array
+        T = ds.T
+        W = ds.multi.weights
+        val, ok = ev(tree, ds.X, options)
+        if not ok:
+            return T(np.inf)
+        chans = [(val, ds.y)]
+        for j, d in enumerate(ds.directions):
+            _, g, okd = df(tree, ds.X, options, d)
+            if not okd:
+                return T(np.inf)
+            chans.append((g, ds.dydx[j]))
+        means = np.empty(len(chans), dtype=np.float64)
+        for k, (pred, tgt) in enumerate(chans):
+            l = _host_loss(loss, pred, tgt)
+            with np.errstate(all="ignore"):
+                if W is None:
+                    means[k] = l.sum() / ds.n
+                else:
+                    w = np.asarray(W[k], dtype=np.float64)
+                    means[k] = (w * l).sum() / w.sum()
+        return self.combine(means[None, :], np.ones(1, dtype=bool), T)[0]
+
+
+def eval_deriv_loss_batch(trees: Sequence[Node], dataset: DerivativeDataset, options: Options,
+                          device: Optional[int] = None, elementwise_loss=None):
+    """The channel means of a derivative objective for many trees in one fused
+    engine call (srhip_eval_loss_deriv): (means [ntrees, 1 + ndir] in float64 —
+    column 0 the weighted mean of ℓ(ŷ, y), column 1 + j that of
+    ℓ(∂ŷ/∂x_d, dydx[j]) along d = dataset.directions[j] — and did_succeed per
+    tree). A failed tree's row is NaN. ℓ is elementwise_loss (default:
+    options.elementwise_loss), a distance loss."""
+    if not isinstance(dataset, DerivativeDataset):
+        raise ValueError("eval_deriv_loss_batch scores a DerivativeDataset")
+    loss = elementwise_loss if elementwise_loss is not None else options.elementwise_loss
+    if not hasattr(loss, "kind") or not 0 <= loss.kind < K.MARGIN_LOSS_BEGIN:
+        raise ValueError("a derivative objective takes a distance loss (L2DistLoss, L1DistLoss, HuberLoss, ...)")
+    trees = list(trees)
+    T = dataset.T
+    dev = dataset.multi.device(device)
+    prog = Program(dev.ctx, flatten(trees, options, dtype=T), T, interpreted=True)
+    sums, wsum, ok = prog.eval_loss_deriv(dev, loss.kind, [d - 1 for d in dataset.directions], loss.params)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        means = sums / wsum[None, :]
+    return means, ok
 
 
 def _eval_loss_grad_targets(trees, dataset, options: Options, device, row_idx, targets, fused):
@@ -368,6 +504,16 @@ def eval_loss_batch_ok(trees: Sequence[Node], dataset: Dataset, options: Options
         return _eval_loss_targets(list(trees), dataset, options, row_idx, device, targets, fused)
     if targets is not None:
         raise ValueError("targets= needs a MultiDataset")
+    if isinstance(options.loss_function, DerivativeObjective) and isinstance(dataset, DerivativeDataset):
+        # the fused call: every channel of every tree in one pass (all rows, the program built here)
+        if row_idx is not None or program is not None:
+            raise ValueError("a DerivativeObjective scores all rows of its DerivativeDataset; row_idx= and program= "
+                             "are not supported with it")
+        f = options.loss_function
+        f.check(dataset)
+        means, ok = eval_deriv_loss_batch(trees, dataset, options, device, f.loss(options))
+        out = f.combine(means, ok, dataset.T)
+        return out, ok & np.isfinite(out)
     if options.loss_function is not None:
         f = options.loss_function
         vals = np.asarray([f(t, dataset, options) for t in trees], dtype=dataset.T)
