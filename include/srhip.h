@@ -614,9 +614,10 @@ int32_t srhip_eval_loss_grad_rowsets_targets(srhip_dataset* ds, const srhip_prog
  * gives 0 and no tree code is built for such a call (the one-shot form makes its
  * program with SRHIP_PROGRAM_INTERPRETED). srhip_last_loss_launch gives the row
  * groups, tree groups and items per group of the call's last launch.
- * Not in this version: row sets; group datasets; constant optimisation under the
- * objective (it needs ∂²ŷ/∂c∂x or finite differences); expression losses and
- * expression operators; tree code. */
+ * The sums' gradients with respect to the constants and constant optimisation under
+ * the objective are srhip_eval_loss_grad_deriv and srhip_optimize_constants_deriv below.
+ * Not in this version: row sets; group datasets; expression losses and expression
+ * operators; tree code. */
 int32_t srhip_eval_loss_deriv(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
                               const double* loss_params, const int32_t* dir, int32_t ndir,
                               double* out_loss_sum,   /* [ntrees][1 + ndir] */
@@ -626,6 +627,50 @@ int32_t srhip_eval_loss_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const
                                         int32_t loss_kind, const double* loss_params, const int32_t* dir,
                                         int32_t ndir, double* out_loss_sum, double* out_weight_sum,
                                         uint8_t* out_ok);
+
+/* ---- derivative objectives: constant gradients (∂²ŷ/∂c∂x) ------------------------
+ * srhip_eval_loss_deriv's sums and their derivatives with respect to every constant,
+ * one launch for every channel (ds, dir, ndir, loss as there):
+ *   out_loss_sum[t][c]     as srhip_eval_loss_deriv gives it, bit for bit
+ *   out_grad_sum[j][0]     = Σ_i W[0][i] · ℓ'(ŷ_t(x_i), Y[0][i]) · ∂ŷ_t/∂c_j(x_i)
+ *   out_grad_sum[j][1 + k] = Σ_i W[1+k][i] · ℓ'(d_k(x_i), Y[1+k][i]) · ∂d_k/∂c_j(x_i)
+ * with d_k = ∂ŷ_t/∂x_dir[k], j over the constants of all trees in order (tree t's are
+ * const_off[t] .. const_off[t+1]-1) and ℓ' the loss's derivative in its first
+ * argument. ∂d_k/∂c_j comes from second-order forward mode over the gradient
+ * programs: every operator's second partials are the derivatives of its first-order
+ * rules as written (so a piecewise-constant rule, and gamma's missing one, give 0;
+ * safe_pow's ∂/∂y branch for x <= 0 gives fxy = fyy = 0).
+ * The flag is srhip_eval_loss_deriv's: ok is did_succeed of the value evaluation; a
+ * non-finite derivative or mixed partial gives non-finite sums with ok = 1; a failed
+ * tree's rows of both outputs are NaN.
+ * A work item is (tree, direction, group of constants) in two words: up to 2^24
+ * trees, 256 constant groups of 1 or 2 constants per tree (more than a gradient
+ * program's 254 constants), any ndir within srhip_eval_loss_deriv's 1..15.
+ * Refusals are srhip_eval_loss_deriv's, before any launch with the outputs untouched,
+ * and one more: there is no wide variant, so a dataset whose row tile of every
+ * feature and column does not fit in LDS (or SRHIP_WIDE=1) is SRHIP_ERR_UNSUPPORTED.
+ * Kernel variants of their own ("grad_kernel_deriv2<float>" / "<double>");
+ * srhip_last_tree_code gives 0.
+ * Not in this version: the wide variant; margin and expression losses; expression
+ * operators; row sets; group datasets; tree code. */
+int32_t srhip_eval_loss_grad_deriv(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                   const double* loss_params, const int32_t* dir, int32_t ndir,
+                                   double* out_loss_sum,   /* [ntrees][1 + ndir] */
+                                   double* out_grad_sum,   /* [const_off[ntrees]][1 + ndir] */
+                                   double* out_weight_sum, /* [1 + ndir] */
+                                   uint8_t* out_ok);
+int32_t srhip_eval_loss_grad_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                             int32_t loss_kind, const double* loss_params, const int32_t* dir,
+                                             int32_t ndir, double* out_loss_sum, double* out_grad_sum,
+                                             double* out_weight_sum, uint8_t* out_ok);
+/* Per row, for few trees: out_deriv [ntrees][ndir][rows] = ∂ŷ/∂x_dir[k] and out_mixed
+ * [const_off[ntrees]][ndir][rows] = ∂²ŷ/∂x_dir[k]∂c_j, of the dataset's dtype (the
+ * companion of srhip_eval_grad_tree_array; "grad_kernel_deriv2_out<float>"). Any
+ * dataset (no column is read); dir / ndir, expression operators and the missing wide
+ * variant are answered as above. out_ok is 0 only for a tree the compiler refuses
+ * (its rows are NaN): a tree that fails on some row shows it in that row. */
+int32_t srhip_eval_mixed_tree_array(srhip_dataset* ds, const srhip_program* prog, const int32_t* dir, int32_t ndir,
+                                    void* out_deriv, void* out_mixed, uint8_t* out_ok);
 
 /* Per-row constant gradients for few trees: out_grad is
  * [total consts][rows] (∂ŷ_i/∂c), out_value [ntrees][rows]. */
@@ -716,6 +761,24 @@ int32_t srhip_optimize_constants_targets(srhip_ctx* ctx, srhip_dataset* ds, cons
                                          const int64_t* row_idx /* NULL: all rows */, int64_t batch_size,
                                          void* out_consts, double* out_loss, uint8_t* out_converged,
                                          double* out_num_evals);
+/* srhip_optimize_constants_batch under a derivative objective: a candidate's loss is
+ *   f = Σ_c coef[c] · out_loss_sum[t][c] / out_weight_sum[c],  c = 0 .. ndir
+ * added in channel order in float64 (+Inf when the tree failed or f is not finite),
+ * and its gradient the same combination of out_grad_sum (NaN for a failed candidate).
+ * ds, dir, ndir as srhip_eval_loss_deriv; the loss is opts->loss_kind / loss_params.
+ * Loss-only phases run srhip_eval_loss_deriv, gradient phases
+ * srhip_eval_loss_grad_deriv; BFGS, Newton for one constant and Nelder-Mead as in
+ * srhip_optimize_constants_batch. The sets' programs are interpreted. Outputs as
+ * srhip_optimize_constants_batch, except that out_loss is the float64 objective, not
+ * rounded to the dtype. srhip_constopt_profile counts these calls as the others.
+ * Refused before any launch with the outputs untouched: what srhip_eval_loss_grad_deriv
+ * refuses, a null coef and a coefficient that is not finite (SRHIP_ERR_INVALID).
+ * Not in this version: the wide variant; row sets; group datasets; margin and
+ * expression losses; expression operators; tree code. */
+int32_t srhip_optimize_constants_deriv(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                       const srhip_constopt_options* opts, const int32_t* dir, int32_t ndir,
+                                       const double* coef /* [1 + ndir] */, void* out_consts, double* out_loss,
+                                       uint8_t* out_converged, double* out_num_evals);
 /* Where the last srhip_optimize_constants_batch call of this thread spent
  * its time: out[0..8] = total, program builds, set_constants, loss calls,
  * gradient calls, the kernels inside those calls (HIP events) — seconds —

@@ -3064,6 +3064,185 @@ int eval_loss_deriv_impl(srhip_dataset* ds, srhip_program* p, int loss, const do
   return SRHIP_OK;
 }
 
+// The refusal of run_deriv2's planning, made before an optimisation starts: both classes at
+// one work item each (the row tile does not depend on the item count).
+void check_deriv2_fits(const srhip_dataset* ds, int ndir) {
+  if (ds->rows == 0) return;
+  for (int cl = 0; cl < 2; ++cl) {
+    EvalPlan plan;
+    if (wide_mode() == 1 || !plan_grad_deriv2(ds->dtype, cl == 1, ndir, DERIV2_LOSS, ds->w != nullptr, ds->nfeat,
+                                              ds->rows, 1, &plan))
+      throw Error(SRHIP_ERR_UNSUPPORTED,
+                  "constant gradients of a derivative objective have no wide variant in this version: the row tile of " +
+                      std::to_string(ds->nfeat) + " features and " + std::to_string(1 + ndir) +
+                      " columns does not fit in LDS");
+  }
+}
+
+// srhip_eval_loss_grad_deriv / srhip_eval_mixed_tree_array (checked by the caller):
+// second-order forward mode (grad_deriv2.h), one work item per (tree, direction,
+// group of GC constants) — one per direction for a tree without constants, so its loss
+// sums are still reported. Shallow trees, then deep ones. Both launches are planned
+// before anything is enqueued: a dataset whose row tile does not fit in LDS (the wide
+// plan of srhip_eval_loss_deriv) is refused with the outputs untouched. No tree code.
+// mode DERIV2_LOSS: out_loss [nt][1 + ndir], out_grad [nconst][1 + ndir] (host);
+// DERIV2_OUT: out_deriv [nt][ndir][rows], out_mixed [nconst][ndir][rows] (host, T).
+template <typename T>
+int run_deriv2(srhip_dataset* ds, srhip_program* p, int mode, int loss, const double* params, const int32_t* dir,
+               int ndir, double* out_loss, double* out_grad, double* out_wsum, void* out_deriv, void* out_mixed,
+               uint8_t* out_ok) {
+  srhip_ctx* c = p->ctx;
+  build_grad_program<T>(p, false);
+  hipStream_t s = c->stream;
+  const int nt = p->ntrees, ncol = 1 + ndir, nconst = p->const_off.back();
+  const int64_t rows = ds->rows, n_pad = ds->n_pad;
+  const bool weighted = mode == DERIV2_LOSS && ds->w != nullptr;
+  // items and plans of the two classes
+  std::vector<int32_t> items;
+  int nitems_of[2] = {0, 0}, gc_of[2] = {0, 0};
+  EvalPlan plans[2];
+  for (int cl = 0; cl < 2; ++cl) {
+    int R = 0, GC = 0;
+    deriv2_variant(p->dtype, cl == 1, ndir, &R, &GC);
+    gc_of[cl] = GC;
+    std::vector<int32_t> ts;
+    for (int t = 0; t < nt; ++t)
+      if (p->g_class[t] == cl) ts.push_back(t);
+    std::stable_sort(ts.begin(), ts.end(), [&](int32_t x, int32_t y) { return p->g_cost[x] > p->g_cost[y]; });
+    int n = 0;
+    for (int32_t t : ts) {
+      const int nc = p->const_off[t + 1] - p->const_off[t];
+      const int ngroups = std::max(1, (nc + GC - 1) / GC);
+      if (ngroups > 256)
+        throw Error(SRHIP_ERR_UNSUPPORTED, "a tree of " + std::to_string(nc) + " constants has more than 256 constant groups");
+      for (int gi = 0; gi < ngroups; ++gi)
+        for (int k = 0; k < ndir; ++k) {
+          items.push_back((int32_t)((uint32_t)t | ((uint32_t)gi << 24)));
+          items.push_back(k);
+          ++n;
+        }
+    }
+    nitems_of[cl] = n;
+    if (n == 0 || rows == 0) continue;
+    if (wide_mode() == 1 ||
+        !plan_grad_deriv2(p->dtype, cl == 1, ndir, mode, weighted, ds->nfeat, rows, n, &plans[cl]))
+      throw Error(SRHIP_ERR_UNSUPPORTED,
+                  "constant gradients of a derivative objective have no wide variant in this version: the row tile of " +
+                      std::to_string(ds->nfeat) + " features and " + std::to_string(ncol) + " columns does not fit in LDS");
+  }
+  timing_reset(c);
+  c->last_jit_trees = 0;
+  c->tgt.ensure((size_t)ndir * sizeof(int32_t));
+  c->scratch_idx.ensure(std::max<size_t>(items.size(), 1) * sizeof(int32_t));
+  c->sums.ensure(std::max<size_t>((size_t)nt * ncol, 1) * sizeof(double));
+  c->dloss.ensure(std::max<size_t>((size_t)nconst * ncol, 1) * sizeof(double));
+  c->oks.ensure(std::max<size_t>(nt, 1));
+  const size_t es = sizeof(T);
+  T* d_deriv = nullptr;
+  T* d_mixed = nullptr;
+  if (mode == DERIV2_OUT) {
+    c->gather.ensure(std::max<size_t>((size_t)(nt + nconst) * ndir * n_pad * es, es));
+    d_deriv = static_cast<T*>(c->gather.p);
+    d_mixed = d_deriv + (size_t)nt * ndir * n_pad;
+  }
+  HIP_CHECK(hipMemcpyAsync(c->tgt.p, dir, (size_t)ndir * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (!items.empty())
+    HIP_CHECK(hipMemcpyAsync(c->scratch_idx.p, items.data(), items.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  int first = 0;
+  bool ran = false;
+  for (int cl = 0; cl < 2; ++cl) {
+    const int nitems = nitems_of[cl], item0 = first;
+    first += nitems;
+    if (nitems == 0 || rows == 0) continue;
+    const EvalPlan& plan = plans[cl];
+    Deriv2Args<T> a;
+    a.prog = static_cast<const Ins<T>*>(p->d_gcode);
+    a.tree_off = p->d_gtree_off;
+    a.items = static_cast<const int32_t*>(c->scratch_idx.p) + 2 * (size_t)item0;
+    a.nitems = nitems;
+    a.dyn = interp_dyn() ? 1 : 0;
+    a.const_off = p->d_const_off;
+    a.dir = static_cast<const int32_t*>(c->tgt.p);
+    a.ndir = ndir;
+    a.X = static_cast<const T*>(ds->X);
+    a.y = static_cast<const T*>(ds->y);
+    a.w = weighted ? static_cast<const T*>(ds->w) : nullptr;
+    a.n = rows;
+    a.n_pad = n_pad;
+    a.nfeat = ds->nfeat;
+    a.ntiles = plan.ntiles;
+    a.ntg = plan.ntg;
+    a.tpb = plan.tpb;
+    a.nrg = plan.nrg;
+    a.loss = loss;
+    a.lparam = params ? params[0] : 0.0;
+    a.GC = gc_of[cl];
+    c->partial.ensure((size_t)plan.nrg * plan.ntg * plan.tpb * (3 + 2 * a.GC) * sizeof(T));
+    a.partial = static_cast<T*>(c->partial.p);
+    a.out_deriv = d_deriv;
+    a.out_mixed = d_mixed;
+    a.out_stride = n_pad;
+    const int tk = timed_begin(c, s);
+    note_kernel(mode == DERIV2_OUT ? (sizeof(T) == 4 ? "grad_kernel_deriv2_out<float>" : "grad_kernel_deriv2_out<double>")
+                                   : (sizeof(T) == 4 ? "grad_kernel_deriv2<float>" : "grad_kernel_deriv2<double>"));
+    HIP_CHECK(launch_grad_deriv2<T>(plan, a, mode, s));
+    timed_end(c, s, tk);
+    if (mode == DERIV2_LOSS)
+      HIP_CHECK(launch_grad_deriv2_finalize<T>(a, static_cast<double*>(c->sums.p), static_cast<double*>(c->dloss.p),
+                                               static_cast<uint8_t*>(c->oks.p), s));
+    note_loss_launch(plan.nrg, plan.ntg, plan.tpb, (unsigned)plan.nrg * (unsigned)plan.ntg, plan.nrg, 1);
+    ran = true;
+  }
+  c->h_ok.assign(nt, 1);
+  if (mode == DERIV2_OUT) {
+    // the per-row mode reports the static verdict only (a tree that fails on some row
+    // has NaN or Inf in its rows)
+    if (ran) {
+      if (out_deriv && nt > 0)
+        HIP_CHECK(hipMemcpy2DAsync(out_deriv, rows * es, d_deriv, n_pad * es, rows * es, (size_t)nt * ndir,
+                                   hipMemcpyDeviceToHost, s));
+      if (out_mixed && nconst > 0)
+        HIP_CHECK(hipMemcpy2DAsync(out_mixed, rows * es, d_mixed, n_pad * es, rows * es, (size_t)nconst * ndir,
+                                   hipMemcpyDeviceToHost, s));
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    timing_finish(c);
+    for (int t = 0; t < nt; ++t) {
+      if (out_ok) out_ok[t] = p->g_static_fail[t] ? 0 : 1;
+      if (!p->g_static_fail[t] || rows == 0) continue;
+      // a tree that is never run: its rows are NaN
+      const T nan = std::numeric_limits<T>::quiet_NaN();
+      if (out_deriv) std::fill_n(static_cast<T*>(out_deriv) + (size_t)t * ndir * rows, (size_t)ndir * rows, nan);
+      if (out_mixed)
+        std::fill_n(static_cast<T*>(out_mixed) + (size_t)p->const_off[t] * ndir * rows,
+                    (size_t)(p->const_off[t + 1] - p->const_off[t]) * ndir * rows, nan);
+    }
+    return SRHIP_OK;
+  }
+  std::vector<double> hs((size_t)nt * ncol, 0.0), hg((size_t)nconst * ncol, 0.0);
+  if (ran) {
+    HIP_CHECK(hipMemcpyAsync(hs.data(), c->sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (nconst > 0)
+      HIP_CHECK(hipMemcpyAsync(hg.data(), c->dloss.p, hg.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(c->h_ok.data(), c->oks.p, nt, hipMemcpyDeviceToHost, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  timing_finish(c);
+  for (int t = 0; t < nt; ++t) {
+    const bool fail = p->g_static_fail[t] || (rows > 0 && !c->h_ok[t]);
+    if (out_ok) out_ok[t] = fail ? 0 : 1;
+    for (int k = 0; k < ncol; ++k) {
+      if (out_loss) out_loss[(size_t)t * ncol + k] = fail ? NAN : (rows > 0 ? hs[(size_t)t * ncol + k] : 0.0);
+      if (out_grad)
+        for (int j = p->const_off[t]; j < p->const_off[t + 1]; ++j)
+          out_grad[(size_t)j * ncol + k] = fail ? NAN : (rows > 0 ? hg[(size_t)j * ncol + k] : 0.0);
+    }
+  }
+  if (out_wsum)
+    for (int k = 0; k < ncol; ++k) out_wsum[k] = !ds->w ? (double)rows : ds->t_sum_w[(size_t)k];
+  return SRHIP_OK;
+}
+
 template <typename T>
 int eval_grad_tree_array_impl(srhip_dataset* ds, srhip_program* p, void* out_value, void* out_grad,
                               uint8_t* out_ok) {
@@ -3926,6 +4105,24 @@ int32_t srhip_eval_loss_grad_targets(srhip_dataset* ds, const srhip_program* pro
 }
 
 // srhip_eval_loss_deriv's own checks, made before anything is built, launched or written
+static void check_direction_list(const srhip_dataset* ds, const int32_t* dir, int32_t ndir) {
+  for (int k = 0; k < ndir; ++k) {
+    if (dir[k] < 0 || dir[k] >= ds->nfeat)
+      throw Error(SRHIP_ERR_INVALID, "direction " + std::to_string(dir[k]) + " is outside 0.." + std::to_string(ds->nfeat - 1));
+    for (int j = 0; j < k; ++j)
+      if (dir[j] == dir[k]) throw Error(SRHIP_ERR_INVALID, "direction " + std::to_string(dir[k]) + " is repeated");
+  }
+}
+
+// srhip_eval_mixed_tree_array's: the directions alone (no column is read)
+static void check_directions(const srhip_dataset* ds, const srhip_program* prog, const int32_t* dir, int32_t ndir) {
+  if (ndir > 0 && !dir) throw Error(SRHIP_ERR_INVALID, "dir is NULL");
+  if (ndir < 1 || ndir > 15) throw Error(SRHIP_ERR_INVALID, "ndir must be within 1..15");
+  check_direction_list(ds, dir, ndir);
+  if (prog->has_expr || !prog->xops.empty())
+    throw Error(SRHIP_ERR_UNSUPPORTED, "expression operators are not part of derivative objectives in this version");
+}
+
 static void check_deriv(const srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind, const double* loss_params,
                         const int32_t* dir, int32_t ndir) {
   if (ndir > 0 && !dir) throw Error(SRHIP_ERR_INVALID, "dir is NULL");
@@ -3934,12 +4131,7 @@ static void check_deriv(const srhip_dataset* ds, const srhip_program* prog, int3
     throw Error(SRHIP_ERR_INVALID, "a derivative objective over " + std::to_string(ndir) + " directions needs a dataset of " +
                                        std::to_string(1 + ndir) + " columns (y, then one per direction); this one has " +
                                        std::to_string(ds->ntargets));
-  for (int k = 0; k < ndir; ++k) {
-    if (dir[k] < 0 || dir[k] >= ds->nfeat)
-      throw Error(SRHIP_ERR_INVALID, "direction " + std::to_string(dir[k]) + " is outside 0.." + std::to_string(ds->nfeat - 1));
-    for (int j = 0; j < k; ++j)
-      if (dir[j] == dir[k]) throw Error(SRHIP_ERR_INVALID, "direction " + std::to_string(dir[k]) + " is repeated");
-  }
+  check_direction_list(ds, dir, ndir);
   if (loss_kind >= SRHIP_MARGIN_LOSS_BEGIN && loss_kind < SRHIP_EXPR_LOSS_BEGIN)
     throw Error(SRHIP_ERR_INVALID, "a margin loss scores a class label, not a derivative");
   check_loss(loss_kind, loss_params);
@@ -3971,6 +4163,46 @@ int32_t srhip_eval_loss_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const
   // the fused call runs in the interpreter: no tree code to build
   return with_temp_program(ctx ? ctx : ds->ctx, ds, trees, SRHIP_PROGRAM_INTERPRETED, [&](srhip_program* p) {
     return srhip_eval_loss_deriv(ds, p, loss_kind, loss_params, dir, ndir, out_loss_sum, out_weight_sum, out_ok);
+  });
+}
+
+int32_t srhip_eval_loss_grad_deriv(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                   const double* loss_params, const int32_t* dir, int32_t ndir, double* out_loss_sum,
+                                   double* out_grad_sum, double* out_weight_sum, uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog, true);
+    check_deriv(ds, prog, loss_kind, loss_params, dir, ndir);
+    CALL_SCOPE(prog->ctx);
+    auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
+    return by_dtype(ds->dtype, [&](auto t) {
+      return run_deriv2<decltype(t)>(ds, p, DERIV2_LOSS, loss_kind, loss_params, dir, ndir, out_loss_sum, out_grad_sum,
+                                     out_weight_sum, nullptr, nullptr, out_ok);
+    });
+  });
+}
+
+int32_t srhip_eval_loss_grad_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                             int32_t loss_kind, const double* loss_params, const int32_t* dir,
+                                             int32_t ndir, double* out_loss_sum, double* out_grad_sum,
+                                             double* out_weight_sum, uint8_t* out_ok) {
+  if (!ds) return set_error(SRHIP_ERR_INVALID, "null dataset");
+  return with_temp_program(ctx ? ctx : ds->ctx, ds, trees, SRHIP_PROGRAM_INTERPRETED, [&](srhip_program* p) {
+    return srhip_eval_loss_grad_deriv(ds, p, loss_kind, loss_params, dir, ndir, out_loss_sum, out_grad_sum,
+                                      out_weight_sum, out_ok);
+  });
+}
+
+int32_t srhip_eval_mixed_tree_array(srhip_dataset* ds, const srhip_program* prog, const int32_t* dir, int32_t ndir,
+                                    void* out_deriv, void* out_mixed, uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog, true);
+    check_directions(ds, prog, dir, ndir);
+    CALL_SCOPE(prog->ctx);
+    auto* p = const_cast<srhip_program*>(prog);
+    return by_dtype(ds->dtype, [&](auto t) {
+      return run_deriv2<decltype(t)>(ds, p, DERIV2_OUT, SRHIP_LOSS_L2, nullptr, dir, ndir, nullptr, nullptr, nullptr,
+                                     out_deriv, out_mixed, out_ok);
+    });
   });
 }
 
@@ -4661,7 +4893,139 @@ int32_t optimize_on_engine(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees*
   });
 }
 
+// srhip_optimize_constants_deriv: the candidates of one evaluation set as an interpreted
+// program, scored under a derivative objective. Loss-only phases are one
+// srhip_eval_loss_deriv, gradient phases one srhip_eval_loss_grad_deriv; f and g are
+// Σ_c coef[c]·sum_c / wsum_c in float64, in channel order.
+struct DerivSet : copt::Set {
+  srhip_ctx* ctx;
+  srhip_dataset* ds;
+  int dtype, loss;
+  const double* params;
+  const int32_t* dir;
+  int ndir;
+  const double* coef;
+  srhip_program* prog = nullptr;
+  std::vector<int32_t> coff;
+  DerivSet(srhip_ctx* c, srhip_dataset* d, const srhip_trees* trees, int ls, const double* pr, const int32_t* dr,
+           int nd, const double* cf, const std::vector<int32_t>& members)
+      : ctx(c), ds(d), dtype(d->dtype), loss(ls), params(pr), dir(dr), ndir(nd), coef(cf) {
+    MemberTrees mt(trees, dtype, members);
+    coff = mt.coff;
+    const auto t0 = std::chrono::steady_clock::now();
+    check_rc(srhip_program_create_ex(ctx, dtype, &mt.tr, SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED,
+                                     &prog));
+    t_copt.create += secs_since(t0);
+    t_copt.ncreate += 1;
+  }
+  ~DerivSet() override {
+    int64_t inplace = 0, rebuilt = 0;
+    if (prog && srhip_program_update_stats(prog, &inplace, &rebuilt) == SRHIP_OK) t_copt.nrebuilt += rebuilt;
+    if (prog) (void)srhip_program_destroy(prog);
+  }
+  void eval(const std::vector<double>& X, bool grad, std::vector<double>& f, std::vector<double>& g) override {
+    const int n = (int)coff.size() - 1, ncol = 1 + ndir;
+    const size_t nc = (size_t)coff.back();
+    if (X.size() != nc) throw Error(SRHIP_ERR_INVALID, "constant count mismatch");
+    auto t0 = std::chrono::steady_clock::now();
+    if (dtype == SRHIP_F32) {
+      std::vector<float> c(nc);
+      for (size_t j = 0; j < nc; ++j) c[j] = (float)X[j];
+      check_rc(srhip_program_set_constants(prog, c.data()));
+    } else {
+      check_rc(srhip_program_set_constants(prog, X.data()));
+    }
+    t_copt.set += secs_since(t0);
+    std::vector<double> sums((size_t)std::max(n, 1) * ncol), gs(std::max<size_t>(nc, 1) * ncol), ws(ncol);
+    std::vector<uint8_t> ok(std::max(n, 1));
+    t0 = std::chrono::steady_clock::now();
+    if (grad)
+      check_rc(srhip_eval_loss_grad_deriv(ds, prog, loss, params, dir, ndir, sums.data(), gs.data(), ws.data(), ok.data()));
+    else
+      check_rc(srhip_eval_loss_deriv(ds, prog, loss, params, dir, ndir, sums.data(), ws.data(), ok.data()));
+    (grad ? t_copt.grad : t_copt.loss) += secs_since(t0);
+    (grad ? t_copt.ngrad : t_copt.nloss) += 1;
+    {
+      double ms = 0.0;
+      if (srhip_last_kernel_time(ctx, &ms, nullptr) == SRHIP_OK) t_copt.kernel_ms += ms;
+    }
+    auto combine = [&](const double* row) {
+      double v = 0.0;
+      for (int c = 0; c < ncol; ++c) v += coef[c] * row[c] / ws[c];
+      return v;
+    };
+    f.assign(n, 0.0);
+    for (int t = 0; t < n; ++t) {
+      const double v = combine(&sums[(size_t)t * ncol]);
+      f[t] = (ok[t] && std::isfinite(v)) ? v : INFINITY;
+    }
+    if (grad) {
+      g.assign(nc, 0.0);
+      for (int t = 0; t < n; ++t)
+        for (int32_t j = coff[t]; j < coff[t + 1]; ++j) g[j] = ok[t] ? combine(&gs[(size_t)j * ncol]) : NAN;
+    }
+  }
+};
+struct DerivFactory : copt::Factory {
+  srhip_ctx* ctx;
+  srhip_dataset* ds;
+  const srhip_trees* trees;
+  int loss;
+  const double* params;
+  const int32_t* dir;
+  int ndir;
+  const double* coef;
+  std::unique_ptr<copt::Set> make(const std::vector<int32_t>& members) override {
+    return std::unique_ptr<copt::Set>(new DerivSet(ctx, ds, trees, loss, params, dir, ndir, coef, members));
+  }
+};
+
 }  // namespace
+
+int32_t srhip_optimize_constants_deriv(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                       const srhip_constopt_options* opts, const int32_t* dir, int32_t ndir,
+                                       const double* coef, void* out_consts, double* out_loss, uint8_t* out_converged,
+                                       double* out_num_evals) {
+  return guarded([&] {
+    if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
+    if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
+    copt::Problem pb = make_problem(trees, ds->dtype);
+    srhip_ctx* c = ctx ? ctx : ds->ctx;
+    // srhip_eval_loss_grad_deriv's refusals, on a program of the input trees (never run)
+    {
+      srhip_program* probe = nullptr;
+      check_rc(srhip_program_create_ex(c, ds->dtype, trees, SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED,
+                                       &probe));
+      try {
+        check_program_vs_dataset(ds, probe, true);
+        check_deriv(ds, probe, opts->loss_kind, opts->loss_params, dir, ndir);
+        check_deriv2_fits(ds, ndir);
+      } catch (...) {
+        (void)srhip_program_destroy(probe);
+        throw;
+      }
+      (void)srhip_program_destroy(probe);
+    }
+    if (!coef) throw Error(SRHIP_ERR_INVALID, "coef is NULL");
+    for (int k = 0; k <= ndir; ++k)
+      if (!std::isfinite(coef[k])) throw Error(SRHIP_ERR_INVALID, "coefficient " + std::to_string(k) + " is not finite");
+    t_copt = CoptProfile();
+    const auto t0 = std::chrono::steady_clock::now();
+    DerivFactory fac;
+    fac.ctx = c;
+    fac.ds = ds;
+    fac.trees = trees;
+    fac.loss = opts->loss_kind;
+    fac.params = opts->loss_params;
+    fac.dir = dir;
+    fac.ndir = ndir;
+    fac.coef = coef;
+    const copt::Result r = copt::optimize(pb, make_copt_options(opts), fac);
+    write_result(r, ds->dtype, out_consts, out_loss, out_converged, out_num_evals, false);
+    t_copt.total = secs_since(t0);
+    return SRHIP_OK;
+  });
+}
 
 int32_t srhip_optimize_constants_batch(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
                                        const srhip_constopt_options* opts, void* out_consts, double* out_loss,

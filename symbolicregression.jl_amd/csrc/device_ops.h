@@ -908,6 +908,70 @@ __device__ __forceinline__ void uop_d(T x, T& f, T& fx) {
   else fx = T(0);
 }
 
+// ---- second-order rules (mixed partials ∂²ŷ/∂c∂x, grad2_interp.h) -----------------
+// f and the first partials come from bop_d / uop_d themselves (the same expressions,
+// so the same bits); the second partials are the derivatives of those first-order
+// rules as written, with their Float32 shortcuts (v_rcp_f32 in the quotient).
+// An operator whose first rule is piecewise constant (abs, relu, max, min, mod,
+// greater, logical_*, round, floor, ceil, sign) has second partials 0, and so has
+// gamma (its first rule is not provided).
+// Conventions beside the hand-made branches:
+//   safe_pow, x <= 0: fy is the constant 0 there, so fxy = fyy = 0 (the mixed
+//     partial is that of the rule as written, ∂fy/∂x, not of x^y); fxx is
+//     y·(y-1)·safe_pow(x, y-2), NaN wherever safe_pow refuses.
+//   sqrt at 0: f1 = +Inf, f2 = -Inf (at -0.0: f1 = -Inf, f2 = -Inf); through the interpreter the
+//     mixed partial there is NaN, since f1 also multiplies the operand's mixed partial (Inf · 0),
+//     as the first-order tangents of unrelated constants already are.
+//   atanh_clip: the wrap has slope 1 and curvature 0, as in uop_d.
+template <int OP, typename T>
+__device__ __forceinline__ void bop_d2(T x, T y, T& f, T& fx, T& fy, T& fxx, T& fxy, T& fyy) {
+  bop_d<OP>(x, y, f, fx, fy);
+  fxx = T(0); fxy = T(0); fyy = T(0);
+  if constexpr (OP == SRHIP_BOP_MUL) fxy = T(1);
+  else if constexpr (OP == SRHIP_BOP_DIV) {  // fx = 1/y, fy = -x/y²
+    fxy = -(fx * fx);
+    fyy = T(-2) * fy * fx;
+  } else if constexpr (OP == SRHIP_BOP_POW) {
+    const T p1 = safe_pow(x, y - T(1));  // (bop_d's own operand: one call after inlining)
+    fxx = y * (y - T(1)) * safe_pow(x, y - T(2));
+    if (x > T(0)) {
+      const T lx = m_log(x);
+      fxy = p1 + fx * lx;  // ∂/∂y of y·x^(y-1)
+      fyy = fy * lx;
+    }
+  }
+}
+
+template <int OP, typename T>
+__device__ __forceinline__ void uop_d2(T x, T& f, T& f1, T& f2) {
+  uop_d<OP>(x, f, f1);
+  if constexpr (OP == SRHIP_UOP_SQUARE) f2 = T(2);
+  else if constexpr (OP == SRHIP_UOP_CUBE) f2 = T(6) * x;
+  else if constexpr (OP == SRHIP_UOP_EXP) f2 = f;
+  else if constexpr (OP == SRHIP_UOP_LOG) f2 = -(f1 * f1);
+  else if constexpr (OP == SRHIP_UOP_LOG2) f2 = -f1 / x;
+  else if constexpr (OP == SRHIP_UOP_LOG10) f2 = -f1 / x;
+  else if constexpr (OP == SRHIP_UOP_LOG1P) f2 = -(f1 * f1);
+  else if constexpr (OP == SRHIP_UOP_SQRT) f2 = T(-0.5) * f1 / x;
+  else if constexpr (OP == SRHIP_UOP_SIN) f2 = -f;
+  else if constexpr (OP == SRHIP_UOP_COS) f2 = -f;
+  else if constexpr (OP == SRHIP_UOP_TAN) f2 = T(2) * f * f1;
+  else if constexpr (OP == SRHIP_UOP_SINH) f2 = f;
+  else if constexpr (OP == SRHIP_UOP_COSH) f2 = f;
+  else if constexpr (OP == SRHIP_UOP_TANH) f2 = T(-2) * f * f1;
+  else if constexpr (OP == SRHIP_UOP_ATAN) f2 = T(-2) * x * (f1 * f1);
+  else if constexpr (OP == SRHIP_UOP_ASINH) f2 = -x * (f1 * f1) * f1;
+  else if constexpr (OP == SRHIP_UOP_ACOSH) f2 = -x * (f1 * f1) * f1;
+  else if constexpr (OP == SRHIP_UOP_ATANH_CLIP) {
+    const T u = jl_mod(x + T(1), T(2)) - T(1);
+    f2 = T(2) * u * (f1 * f1);
+  }
+  else if constexpr (OP == SRHIP_UOP_ERF) f2 = T(-2) * x * f1;
+  else if constexpr (OP == SRHIP_UOP_ERFC) f2 = T(-2) * x * f1;
+  else if constexpr (OP == SRHIP_UOP_INV) f2 = T(-2) * f1 * f;
+  else f2 = T(0);
+}
+
 // dℓ/dŷ of the elementwise losses (r = ŷ - y; a margin loss: y·L'(y·ŷ)); the
 // parametric ones in Float64 like their values (elem_loss)
 template <typename T>

@@ -170,6 +170,58 @@ template <typename T>
 hipError_t launch_grad_finalize(const GradArgs<T>& a, double* out_sum, uint8_t* out_ok,
                                 double* out_dloss, hipStream_t stream);
 
+// ---- constant gradients of a derivative objective (grad_deriv2_f32.hip / _f64.hip) ----
+// Second-order forward mode (grad2_interp.h). A work item is two words:
+//   items[2s]     tree (24 bits) | constant group << 24
+//   items[2s + 1] direction index k (0 .. ndir-1)
+// so a call holds up to 2^24 trees, 256 constant groups per tree (256·GC constants:
+// more than the 254 a gradient program can index) and any int32 count of directions.
+// DERIV2_LOSS partial per item, 3 + 2·GC values:
+//   [0] Σ w₀·ℓ(ŷ, y) (items of k = 0)   [1] marker of the value evaluation
+//   [2] Σ w_{1+k}·ℓ(dx, Y[1+k])          [3 + j] Σ w_{1+k}·ℓ'(dx, Y[1+k])·dxc[j]
+//   [3 + GC + j] Σ w₀·ℓ'(ŷ, y)·dc[j] (items of k = 0)
+// DERIV2_OUT writes dx and dxc per row.
+enum Deriv2Mode : int { DERIV2_LOSS = 0, DERIV2_OUT = 1 };
+
+template <typename T>
+struct Deriv2Args {
+  const Ins<T>* prog;       // gradient programs (no folding)
+  const int32_t* tree_off;
+  const int32_t* items;     // [nitems][2]
+  int nitems;
+  const int32_t* const_off; // [ntrees+1]
+  const int32_t* dir;       // [ndir] feature of each direction
+  int ndir;
+  const T* X;
+  const T* y;               // [1 + ndir][n_pad]
+  const T* w;               // [1 + ndir][n_pad] or nullptr
+  int64_t n, n_pad;
+  int nfeat;
+  int ntiles, ntg, tpb, nrg;
+  int loss;
+  double lparam;
+  int GC;                   // constant tangents carried by this launch (1 or 2)
+  T* partial;               // [nrg][ntg*tpb][3 + 2·GC]
+  T* out_deriv;             // DERIV2_OUT: [ntrees][ndir][out_stride]
+  T* out_mixed;             // DERIV2_OUT: [total consts][ndir][out_stride]
+  int64_t out_stride;
+  int dyn = 0;
+};
+
+// GC and R of the variant that runs (dtype, deep, ndir): R is the one
+// srhip_eval_loss_deriv's variant has for the same call, so both reduce a row
+// group's rows in the same order.
+void deriv2_variant(int dtype, bool deep, int ndir, int* R, int* GC);
+// false: the row tile of every feature and column does not fit in LDS (no wide variant)
+bool plan_grad_deriv2(int dtype, bool deep, int ndir, int mode, bool weighted, int nfeat, int64_t n, int nitems,
+                      EvalPlan* plan);
+template <typename T>
+hipError_t launch_grad_deriv2(const EvalPlan& plan, const Deriv2Args<T>& a, int mode, hipStream_t stream);
+// out_loss [ntrees][1 + ndir], out_grad [total consts][1 + ndir], out_ok [ntrees]
+template <typename T>
+hipError_t launch_grad_deriv2_finalize(const Deriv2Args<T>& a, double* out_loss, double* out_grad, uint8_t* out_ok,
+                                       hipStream_t stream);
+
 // Σ over row groups of the gradient tree code's per-constant partials:
 // out[cidx[k]] = Σ_rg gpart[rg][cidx[k]] in fp64 (jit_grad.cpp).
 // zero a[0..na) and b[0..nb) (uint32 words) in one launch

@@ -208,7 +208,22 @@ reference's full-data optimiser either way.
 function optimize_constants_batched(dataset::Dataset{T}, members::AbstractVector{<:PopMember{T}},
                                     options::Options; device::Int=0, minibatch::Bool=false) where {T}
     isempty(members) && return Float64[]
-    # (no constant optimisation under a derivative objective on the engine: the reference's optimiser)
+    # a derivative objective: every member on all rows in one lockstep run (srhip_optimize_constants_deriv)
+    if SRHip.enabled(options) && options.loss_function isa SRHip.DerivativeObjective
+        try
+            trees = Node{T}[m.tree for m in members]
+            losses, converged, num_evals = SRHip.optimize_constants_deriv(trees, dataset, options; device=device)
+            for (m, l, c) in zip(members, losses, converged)
+                c || continue
+                m.score = loss_to_score(l, dataset.baseline_loss, m.tree, options)
+                m.loss = l
+                m.birth = get_birth_order(; deterministic=options.deterministic)
+            end
+            return num_evals
+        catch e
+            e isa SRHip.Unsupported || rethrow()
+        end
+    end
     if SRHip.enabled(options) && options.loss_function === nothing
         try
             trees = Node{T}[m.tree for m in members]

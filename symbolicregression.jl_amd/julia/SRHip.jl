@@ -1222,8 +1222,9 @@ The method `(f)(tree, dataset, options)` is the CPU definition, built from
 DynamicExpressions' `eval_tree_array` / `eval_diff_tree_array`, so the struct is a legal
 `loss_function` on its own; `enabled(options)` accepts it and `eval_loss_deriv` /
 `BatchedCallers.score_batch` score whole batches with one engine call
-(srhip_eval_loss_deriv). Not covered there (the CPU definition runs): row samples
-(`options.batching`), constant optimisation, expression losses and operators.
+(srhip_eval_loss_deriv); `optimize_constants_deriv` fits the constants under it
+(srhip_optimize_constants_deriv). Not covered there (the CPU definition runs): row samples
+(`options.batching`), expression losses and operators.
 """
 struct DerivativeObjective{T} <: Function
     coefficients::Vector{Float64}
@@ -1334,6 +1335,83 @@ function eval_loss_deriv(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, op
         losses[i] = (ok[i] == 1 && isfinite(v)) ? T(v) : T(Inf)
     end
     return losses, means, ok .== 1
+end
+
+"""
+    optimize_constants_deriv(trees, dataset, options; device=0) -> (losses, converged, num_evals)
+
+`optimize_constants_batch!` under `options.loss_function::DerivativeObjective`
+(srhip_optimize_constants_deriv): every start of every tree in one lockstep run, the loss of a
+candidate `Σ_k coefficients[k] · mean_k` over y and every derivative channel, its gradient
+from second-order forward mode (∂²ŷ/∂c∂x). Trees that converged get their constants set.
+`losses` are the objective values in `T`. `Unsupported` for expression losses, expression
+operators and datasets whose row tile does not fit in LDS (the callers fall back to the
+reference's optimiser).
+"""
+function optimize_constants_deriv(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, options::Options;
+                                  device::Int=0) where {T}
+    f = options.loss_function::DerivativeObjective{T}
+    algo = options.optimizer_algorithm == "BFGS" ? OPT_BFGS :
+           options.optimizer_algorithm == "NelderMead" ? OPT_NELDERMEAD :
+           error("Optimization function not implemented.")
+    nt = length(trees)
+    nd = length(f.directions)
+    nfeat, n = size(dataset.X)
+    size(f.dydx, 2) == n || throw(ArgumentError("dydx has $(size(f.dydx, 2)) rows, the dataset $(n)"))
+    node_off, kind, arg, const_off, consts = flatten(trees, options)
+    nr = options.optimizer_nrestarts
+    noise = Float64[]
+    for i in 1:nt
+        nc = Int(const_off[i + 1] - const_off[i])
+        nc == 0 && continue
+        for _ in 1:nr
+            append!(noise, Float64.(randn(T, nc)))
+        end
+    end
+    kindcode, param = loss_code(options.elementwise_loss)
+    params = Float64[param]
+    Xc = Matrix{T}(dataset.X)
+    Yc = Matrix{T}(undef, n, 1 + nd)
+    Yc[:, 1] .= dataset.y
+    for j in 1:nd
+        Yc[:, 1 + j] .= f.dydx[j, :]
+    end
+    weighted = f.weights !== nothing || dataset.weighted
+    Wc = weighted ? Matrix{T}(undef, n, 1 + nd) : nothing
+    if weighted
+        for k in 1:(1 + nd)
+            Wc[:, k] .= channel_weights(f, dataset, k)
+        end
+    end
+    dir = Int32.(f.directions .- 1)
+    coef = Float64.(f.coefficients)
+    out_c = similar(consts); out_l = Vector{Float64}(undef, nt)
+    out_k = Vector{UInt8}(undef, nt); out_n = Vector{Float64}(undef, nt)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve node_off kind arg const_off consts noise params Xc Yc Wc dir coef out_c out_l out_k out_n begin
+        check(ccall((:srhip_dataset_create_multi, libsrhip), Int32,
+                    (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Int64, Int32, Int32, Int64, Int64,
+                     Ptr{Ptr{Cvoid}}),
+                    context(device), dtype_code(T), X_JULIA, Xc, Yc,
+                    Wc === nothing ? Ptr{T}(C_NULL) : Wc, n, nfeat, 1 + nd, 0, n, h))
+        try
+            tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
+                                Ptr{Cvoid}(pointer(consts))))
+            opts = Ref(ConstOptOptions(algo, Int32(options.optimizer_options.iterations), Int32(nr), kindcode,
+                                       pointer(params), pointer(noise), UInt64(0)))
+            check(ccall((:srhip_optimize_constants_deriv, libsrhip), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Ref{ConstOptOptions}, Ptr{Int32}, Int32,
+                         Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}),
+                        context(device), h[], tr, opts, dir, Int32(nd), coef, out_c, out_l, out_k, out_n))
+        finally
+            destroy_dataset(h[])
+        end
+    end
+    converged = out_k .== 1
+    for i in 1:nt
+        converged[i] && set_constants(trees[i], out_c[(const_off[i] + 1):const_off[i + 1]])
+    end
+    return T.(out_l), converged, out_n
 end
 
 end # module

@@ -7,10 +7,10 @@ so that parity tests read like the reference's own tests.
 """
 from . import constants
 from ._lib import SrhipError, Unsupported, lib
-from .constant_optimization import ConstOptResult, optimize_constants_batch
+from .constant_optimization import ConstOptResult, optimize_constants_batch, optimize_constants_deriv_batch
 from .dataset import Dataset, DerivativeDataset, GroupDataset, MultiDataset
 from .engine import Context, DeviceDataset, DeviceGroup, GroupProgram, MultiDeviceDataset, Program, device_count, get_context
-from .interface import (DerivativeObjective, compile_trees, compute_complexity, eval_diff_tree_array, eval_grad_tree_array, eval_deriv_loss_batch, eval_loss, eval_loss_batch,
+from .interface import (DerivativeObjective, compile_trees, compute_complexity, eval_diff_tree_array, eval_grad_tree_array, eval_deriv_loss_batch, eval_deriv_loss_grad_batch, eval_loss, eval_loss_batch,
                         eval_loss_batch_ok, eval_loss_batch_rowsets, eval_loss_grad_batch,
                         eval_tree_array, loss_to_score, score_func, score_func_batch, score_func_batched,
                         update_baseline_loss_)

@@ -108,8 +108,9 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
     forces either where both apply. The noise array is the same either way:
     start_noise's order over the trees as given."""
     if isinstance(dataset, DerivativeDataset):
-        raise ValueError("constant optimisation under a derivative objective is not supported in this version (it needs "
-                         "∂²ŷ/∂c∂x or finite differences): optimise on dataset.target(0) to fit the value alone")
+        raise ValueError("a DerivativeDataset is not supported by optimize_constants_batch, which fits ŷ to one target: "
+                         "optimize_constants_deriv_batch fits the constants under a DerivativeObjective, and "
+                         "dataset.target(0) is the Dataset of the value alone")
     multi = isinstance(dataset, MultiDataset)
     if multi:
         from .interface import _check_targets
@@ -182,6 +183,69 @@ def optimize_constants_batch(dataset: Dataset, trees: Sequence[Node], options: O
         if cb.error is not None:
             raise cb.error
         check(rc)
+    conv = out_k[:nt].astype(bool)
+    co = flat.const_off
+    for i in np.flatnonzero(conv):
+        set_constants(trees[i], [T(v) for v in out_c[co[i]:co[i + 1]]])
+    return ConstOptResult(out_l[:nt].copy(), conv, out_n[:nt].copy())
+
+
+def optimize_constants_deriv_batch(dataset: DerivativeDataset, trees: Sequence[Node], options: Options,
+                                   rng: Optional[np.random.Generator] = None, device: Optional[int] = None,
+                                   evaluator_factory: Optional[Callable] = None, noise: Optional[np.ndarray] = None,
+                                   row_idx: Optional[np.ndarray] = None,
+                                   targets: Optional[Sequence[int]] = None) -> ConstOptResult:
+    """`optimize_constants` for many trees at once on a DerivativeDataset under
+    options.loss_function, a DerivativeObjective (srhip_optimize_constants_deriv): the constants
+    are fitted to Σ_c coefficients[c] · mean_c over y and every derivative channel, with analytic
+    gradients (∂²ŷ/∂c∂x). Trees are updated in place as optimize_constants_batch updates them;
+    `rng` / `noise` as there. The losses are the objective's values in float64. All rows are
+    scored on one device: `row_idx=`, `targets=` and `evaluator_factory=` are refused by name, as
+    are margin and expression losses."""
+    from .interface import DerivativeObjective
+
+    obj = options.loss_function
+    if not isinstance(obj, DerivativeObjective):
+        raise ValueError("constant optimisation on a DerivativeDataset is not supported without a DerivativeObjective as "
+                         "options.loss_function: optimise on dataset.target(0) to fit the value alone")
+    obj.check(dataset)
+    if row_idx is not None:
+        raise ValueError("row_idx= is not supported under a derivative objective in this version (all rows are scored)")
+    if targets is not None:
+        raise ValueError("targets= is not supported under a derivative objective: its channels are the targets")
+    if evaluator_factory is not None:
+        raise ValueError("evaluator_factory= is not supported under a derivative objective in this version")
+    loss = obj.loss(options)  # (a distance loss: margin and expression losses are refused there)
+    algorithm = getattr(options, "optimizer_algorithm", "BFGS")
+    if algorithm not in ALGORITHMS:
+        raise ValueError("Optimization function not implemented.")  # :39-41
+    T = np.dtype(dataset.T).type
+    flat = flatten(trees, options, dtype=T)
+    nrestarts = int(getattr(options, "optimizer_nrestarts", 2))
+    if noise is None:
+        noise = start_noise(flat, nrestarts, rng or np.random.default_rng())
+    noise = np.ascontiguousarray(noise, dtype=np.float64)
+    need = int(sum(nrestarts * int(flat.const_off[i + 1] - flat.const_off[i]) for i in range(flat.ntrees)))
+    if noise.shape != (need,):
+        raise ValueError(f"start noise has {noise.size} values, the trees' restarts need {need}")
+    par = None if loss.params is None else np.ascontiguousarray(loss.params, dtype=np.float64)
+    opts = ConstOptOptions(ALGORITHMS[algorithm], int(getattr(options, "optimizer_iterations", 8)), nrestarts,
+                           int(loss.kind), None if par is None else par.ctypes.data_as(C.POINTER(C.c_double)),
+                           noise.ctypes.data_as(C.POINTER(C.c_double)), 0)
+    consts = np.ascontiguousarray(flat.consts, dtype=T)
+    tr = _trees_struct(flat, consts)
+    nt = len(trees)
+    out_c = np.zeros(max(consts.size, 1), dtype=T)
+    out_l = np.zeros(max(nt, 1))
+    out_k = np.zeros(max(nt, 1), dtype=np.uint8)
+    out_n = np.zeros(max(nt, 1))
+    ptrs = [a.ctypes.data_as(C.c_void_p) for a in (out_c, out_l, out_k, out_n)]
+    dirs = np.ascontiguousarray([d - 1 for d in dataset.directions], dtype=np.int32)
+    coef = np.ascontiguousarray(obj.coefficients, dtype=np.float64)
+    dev = dataset.multi.device(device)
+    check(lib().srhip_optimize_constants_deriv(dev.ctx.handle, dev.handle, C.byref(tr), C.byref(opts),
+                                               dirs.ctypes.data_as(C.c_void_p), len(dirs),
+                                               coef.ctypes.data_as(C.c_void_p), *ptrs))
     conv = out_k[:nt].astype(bool)
     co = flat.const_off
     for i in np.flatnonzero(conv):

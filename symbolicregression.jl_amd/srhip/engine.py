@@ -457,6 +457,42 @@ class Program:
                                           _p(sums), _p(wsum), _p(ok)))
         return sums[:nt], wsum, ok[:nt].astype(bool)
 
+    def eval_loss_grad_deriv(self, ds, loss_kind: int, directions, params=None):
+        """srhip_eval_loss_grad_deriv: eval_loss_deriv's sums and their derivatives with
+        respect to every constant, in one launch: (Σ w·ℓ [ntrees, 1 + ndir], Σ w·ℓ'·∂/∂c
+        [total consts, 1 + ndir] — column 0 through ∂ŷ/∂c, column 1 + k through
+        ∂²ŷ/∂x_d∂c — Σ w per column [1 + ndir], ok). A failed tree's rows are NaN."""
+        nt = self.ntrees
+        nc = int(self.flat.const_off[-1])
+        d = np.ascontiguousarray(directions, dtype=np.int32)
+        if d.ndim != 1:
+            raise ValueError("directions must be a list of feature indices")
+        nd = len(d)
+        sums = np.zeros((max(nt, 1), 1 + nd), dtype=np.float64)
+        grads = np.zeros((max(nc, 1), 1 + nd), dtype=np.float64)
+        wsum = np.zeros(1 + nd, dtype=np.float64)
+        ok = np.zeros(max(nt, 1), dtype=np.uint8)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_eval_loss_grad_deriv(ds.handle, self.handle, int(loss_kind), _p(par), _p(d) if nd else None,
+                                               nd, _p(sums), _p(grads), _p(wsum), _p(ok)))
+        return sums[:nt], grads[:nc], wsum, ok[:nt].astype(bool)
+
+    def eval_mixed_tree_array(self, ds, directions):
+        """srhip_eval_mixed_tree_array: (∂ŷ/∂x_d [ntrees, ndir, rows], ∂²ŷ/∂x_d∂c
+        [total consts, ndir, rows], ok) for every d of directions (0-based)."""
+        nt = self.ntrees
+        nc = int(self.flat.const_off[-1])
+        d = np.ascontiguousarray(directions, dtype=np.int32)
+        if d.ndim != 1:
+            raise ValueError("directions must be a list of feature indices")
+        nd = len(d)
+        der = np.empty((nt, nd, ds.rows), dtype=self.dtype)
+        mix = np.empty((nc, nd, ds.rows), dtype=self.dtype)
+        ok = np.zeros(max(nt, 1), dtype=np.uint8)
+        check(lib().srhip_eval_mixed_tree_array(ds.handle, self.handle, _p(d) if nd else None, nd, _p(der), _p(mix),
+                                                _p(ok)))
+        return der, mix, ok[:nt].astype(bool)
+
     def eval_loss_grad_rowsets_targets(self, ds, loss_kind: int, targets, row_idx, params=None):
         """srhip_eval_loss_grad_rowsets_targets: tree t on its own rows row_idx[t]
         against column targets[t]: (Σ w·ℓ per tree, Σ w·∂ℓ/∂c per constant, Σ w per

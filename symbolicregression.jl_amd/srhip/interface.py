@@ -303,6 +303,35 @@ def eval_deriv_loss_batch(trees: Sequence[Node], dataset: DerivativeDataset, opt
     return means, ok
 
 
+def eval_deriv_loss_grad_batch(trees: Sequence[Node], dataset: DerivativeDataset, options: Options,
+                               device: Optional[int] = None):
+    """The objective values of options.loss_function (a DerivativeObjective) and their
+    gradients with respect to the trees' constants, in one fused engine call
+    (srhip_eval_loss_grad_deriv): (values [ntrees] in float64, +Inf where the tree
+    fails or the value is not finite; ∂objective/∂c [total constants, in the trees'
+    order], NaN for a failed tree; did_succeed per tree)."""
+    obj = options.loss_function
+    if not isinstance(obj, DerivativeObjective):
+        raise ValueError("eval_deriv_loss_grad_batch needs a DerivativeObjective as options.loss_function")
+    ds = obj.check(dataset)
+    loss = obj.loss(options)
+    trees = list(trees)
+    T = ds.T
+    dev = ds.multi.device(device)
+    flat = flatten(trees, options, dtype=T)
+    prog = Program(dev.ctx, flat, T, interpreted=True)
+    sums, grads, wsum, ok = prog.eval_loss_grad_deriv(dev, loss.kind, [d - 1 for d in ds.directions], loss.params)
+    with np.errstate(all="ignore"):
+        v = np.zeros(len(trees))
+        g = np.zeros(grads.shape[0])
+        for c in range(1 + ds.ndir):  # channel order, as srhip_optimize_constants_deriv
+            v = v + obj.coefficients[c] * sums[:, c] / wsum[c]
+            g = g + obj.coefficients[c] * grads[:, c] / wsum[c]
+    v[~(ok & np.isfinite(v))] = np.inf
+    g[np.repeat(~ok, np.diff(flat.const_off))] = np.nan
+    return v, g, ok
+
+
 def _eval_loss_grad_targets(trees, dataset, options: Options, device, row_idx, targets, fused):
     """eval_loss_grad_batch on a MultiDataset: one fused call (srhip_eval_loss_grad_targets,
     with row_idx srhip_eval_loss_grad_rowsets_targets), or the trees regrouped by target and
