@@ -200,13 +200,36 @@ extern "C" {
  * unweighted dataset is SRHIP_ERR_INVALID, and one that ignores feature 2 is
  * allowed on a weighted dataset (the reference would call a 2-argument function
  * with 3 arguments there); Julia promotes Float32 ^ 2.5 (a Float64 literal) to
- * Float64, the engine stays in T. These kinds always run in the interpreter
- * kernels (no tree code: srhip_last_tree_code gives 0, and the
- * srhip_jit_compile_loss hook answers SRHIP_ERR_UNSUPPORTED for them). */
+ * Float64, the engine stays in T. A handle made without
+ * SRHIP_LOSS_EXPR_TREE_CODE always runs in the interpreter kernels (no tree
+ * code: srhip_last_tree_code gives 0, and the srhip_jit_compile_loss hook
+ * answers SRHIP_ERR_UNSUPPORTED for it).
+ *
+ * Tree code (opt-in per handle, srhip_loss_expr_create_ex with
+ * SRHIP_LOSS_EXPR_TREE_CODE): the expression is compiled by the tree compiler
+ * and ends every tile of every tree of a Float32 program's loss tree code —
+ * srhip_eval_loss, _packed, _batch, _batch_ctx, on literal-constant and
+ * SRHIP_PROGRAM_VARYING_CONSTANTS programs, weighted or not. Same contract as
+ * above: ℓ in Float32 with the interpreter's operator routines (the PRECISE
+ * ones, also behind a FAST tile), constants literals of the code, no implicit
+ * weight, out_ok the candidate's alone, rows past the end add 0.
+ * srhip_last_tree_code / srhip_last_kernel_name report the launch and the
+ * srhip_jit_compile_loss hook compiles for the handle. Still interpreted, with
+ * unchanged results: Float64 programs, gradients, row sets, multi-target
+ * calls, SRHIP_PROGRAM_WIDE_TREE_CODE programs, device-group programs,
+ * derivative objectives, trees with expression operators, and an expression
+ * the tree compiler has no form for (an operator applied to constants alone). */
 #define SRHIP_EXPR_LOSS_BEGIN 1024 /* loss kinds from here on are handles of expression losses */
+/* srhip_loss_expr_create_ex flag (1u): Float32 loss tree code may run the handle. (Spelt with
+ * UINT32_C: the build's generators read every "SRHIP_LOSS_<NAME> <digits>" line as a loss id.) */
+#define SRHIP_LOSS_EXPR_TREE_CODE UINT32_C(1)
 /* consts[nconsts]: the constant leaves in stream order (as srhip_trees). */
 int32_t srhip_loss_expr_create(const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
                                const double* consts, int32_t nconsts, int32_t* out_loss_kind);
+/* The same with flags (0: srhip_loss_expr_create); a bit other than
+ * SRHIP_LOSS_EXPR_TREE_CODE is SRHIP_ERR_INVALID and creates nothing. */
+int32_t srhip_loss_expr_create_ex(const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
+                                  const double* consts, int32_t nconsts, uint32_t flags, int32_t* out_loss_kind);
 /* A destroyed (or never registered) kind >= SRHIP_EXPR_LOSS_BEGIN is
  * SRHIP_ERR_INVALID everywhere; handles are not reused. */
 int32_t srhip_loss_expr_destroy(int32_t loss_kind);

@@ -336,6 +336,8 @@ struct srhip_program {
   // SRHIP_PROGRAM_WIDE_TREE_CODE: literal loss tree code may be built wide (jit::Options::xg) and
   // stays in use on a dataset whose interpreter passes run wide (run_eval)
   bool wide_tc = false;
+  // a member of a device-group program: expression losses stay interpreted there
+  bool in_group = false;
   // gradient tree code allowed (the rerun of Periodic's handed-back trees: none)
   bool gjit_allowed = true;
   // the gradient programs were built by a call on per-tree row sets, without tree code
@@ -456,6 +458,10 @@ struct ExprLoss {
   std::vector<uint16_t> arg;
   std::vector<double> consts;
   bool uses_w = false;
+  // SRHIP_LOSS_EXPR_TREE_CODE: the handle may end the tiles of Float32 loss tree code (loss_module);
+  // lx: its stream for the tree compiler, constants rounded as the loss program's are
+  bool tree_code = false;
+  jit::LossExpr lx;
   std::vector<Ins<float>> p32;
   std::vector<Ins<double>> p64;
 };
@@ -479,8 +485,8 @@ void check_expr_loss_weights(int32_t kind, bool weighted) {
 
 // Validate a postfix loss stream and compile it. Malformed: INVALID; well formed
 // but beyond the limits (nodes, stack depth, operator tables): UNSUPPORTED.
-std::shared_ptr<const ExprLoss> expr_loss_compile(const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
-                                                  const double* consts, int32_t nconsts) {
+std::shared_ptr<ExprLoss> expr_loss_compile(const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
+                                            const double* consts, int32_t nconsts) {
   if (!kind || !arg || nnodes <= 0 || nconsts < 0 || (nconsts > 0 && !consts))
     throw Error(SRHIP_ERR_INVALID, "expression loss: null or empty node stream");
   struct N { int l = -1, r = -1; };
@@ -529,6 +535,9 @@ std::shared_ptr<const ExprLoss> expr_loss_compile(const uint8_t* kind, const uin
   e->arg.assign(arg, arg + nnodes);
   e->consts.assign(consts, consts + nconsts);
   e->uses_w = uses_w;
+  e->lx.kind = e->kind;
+  e->lx.arg = e->arg;
+  for (double c : e->consts) e->lx.consts.push_back((float)c);
   // constant index of each constant leaf
   std::vector<int> cidx((size_t)nnodes, -1);
   for (int i = 0, c = 0; i < nnodes; ++i)
@@ -1604,6 +1613,38 @@ uint64_t bits_of(double lparam) {
   return bits;
 }
 
+// The tree code of a Float32 program for an expression loss made with
+// SRHIP_LOSS_EXPR_TREE_CODE: the program's trees compiled with the handle's
+// expression as the tile tail (jit::Options::lexpr), built at the handle's
+// first evaluation and kept with the program under the handle's kind (kinds
+// are never handed out twice). Null, and the call runs in the interpreter's
+// expression-loss mode: an unflagged handle, an expression the tree compiler
+// refuses (jit::loss_expr_fits, per loss and not per tree), wide tree code, a
+// member of a device-group program. A destroyed handle is INVALID here too.
+jit::Module* expr_loss_module(const srhip_program* p, int loss) {
+  const std::shared_ptr<const ExprLoss> e = expr_loss_lookup(loss);
+  if (!e->tree_code || p->wide_tc || p->in_group || jit::xg(p->jit)) return nullptr;
+  for (const auto& l : p->jit_loss)
+    if (l.kind == loss && l.bits == 0) return l.m;
+  if (!jit::loss_expr_fits(e->lx)) {
+    p->jit_loss.push_back({loss, 0, nullptr});
+    return nullptr;
+  }
+  jit::Options jo;
+  jo.fast = jit_fast_enabled();
+  jo.memc = jit::memc(p->jit);
+  jo.lexpr = &e->lx;
+  jo.slots = column_slots(p);
+  return lazy_module<float, jit::Module>(
+      p, p->jit_loss, loss, 0, p->jit_consts, false,
+      [&](const CompiledBatch<float>& cb, std::vector<int32_t>& jl, std::vector<int32_t>& rest) {
+        jit::Stats st;
+        return jit::build(cb, p->h_jit_list, jl, rest, jo, &st);
+      },
+      [&](const std::vector<int32_t>& jl, const std::vector<int32_t>& rest) { return jl == p->h_jit_list && rest.empty(); },
+      jit::destroy);
+}
+
 // The tree code of a Float32 program for an elementwise loss: the L2 build
 // itself, or (other losses) the same trees compiled with that loss's tile
 // tail, built at the loss's first evaluation and kept with the program
@@ -1612,6 +1653,7 @@ jit::Module* loss_module(const srhip_program* p, int loss, double lparam) {
   if (!p->jit || p->nlist_j == 0) return nullptr;
   if (loss == SRHIP_LOSS_L2) return p->jit;
   static const bool on = env_on("SRHIP_JIT_LOSSES");
+  if (on && loss >= SRHIP_EXPR_LOSS_BEGIN) return expr_loss_module(p, loss);
   if (!on || loss < 0 || loss >= SRHIP_NUM_LOSSES || !jit::has_loss_routine(loss)) return nullptr;
   jit::Options jo;
   jo.fast = jit_fast_enabled();
@@ -3557,9 +3599,16 @@ int32_t srhip_op_expr_destroy(int32_t op_id) {
 
 int32_t srhip_loss_expr_create(const uint8_t* kind, const uint16_t* arg, int32_t nnodes, const double* consts,
                                int32_t nconsts, int32_t* out_loss_kind) {
+  return srhip_loss_expr_create_ex(kind, arg, nnodes, consts, nconsts, 0u, out_loss_kind);
+}
+
+int32_t srhip_loss_expr_create_ex(const uint8_t* kind, const uint16_t* arg, int32_t nnodes, const double* consts,
+                                  int32_t nconsts, uint32_t flags, int32_t* out_loss_kind) {
   return guarded([&] {
     if (!out_loss_kind) throw Error(SRHIP_ERR_INVALID, "null out_loss_kind");
-    std::shared_ptr<const ExprLoss> e = expr_loss_compile(kind, arg, nnodes, consts, nconsts);
+    if (flags & ~SRHIP_LOSS_EXPR_TREE_CODE) throw Error(SRHIP_ERR_INVALID, "expression loss: unknown flag bits");
+    std::shared_ptr<ExprLoss> e = expr_loss_compile(kind, arg, nnodes, consts, nconsts);
+    e->tree_code = (flags & SRHIP_LOSS_EXPR_TREE_CODE) != 0;
     std::lock_guard<std::mutex> lk(g_expr_mu);
     if (g_expr_next == std::numeric_limits<int32_t>::max()) throw Error(SRHIP_ERR_NOMEM, "expression loss handles exhausted");
     const int32_t id = g_expr_next++;
@@ -4382,7 +4431,16 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
     std::vector<uint8_t> bytes;
     std::string text;
     std::vector<int32_t> offs;
-    if (loss >= SRHIP_EXPR_LOSS_BEGIN) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for expression losses");
+    // an expression loss: Float32 loss code of a handle made with SRHIP_LOSS_EXPR_TREE_CODE only
+    std::shared_ptr<const ExprLoss> xloss;
+    if (loss >= SRHIP_EXPR_LOSS_BEGIN) {
+      xloss = expr_loss_lookup(loss);
+      if (!xloss->tree_code) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for expression losses");
+      if ((mode != 0 && mode != 1) || out_mode || wide)
+        throw Error(SRHIP_ERR_UNSUPPORTED, "expression losses have Float32 loss tree code only");
+      if (!jit::loss_expr_fits(xloss->lx)) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for this expression loss");
+      loss = SRHIP_LOSS_L2;
+    }
     // expression operators: live handles only, and their trees have no tree code
     const std::vector<std::shared_ptr<const ExprOp>> xops = expr_ops_of(*trees);
     if (loss < 0 || loss >= SRHIP_NUM_LOSSES) throw Error(SRHIP_ERR_INVALID, "unknown loss");
@@ -4418,6 +4476,7 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
       jo.text = !notext;  // no text: the parallel code generation of build()
       jo.loss = loss;
       jo.lparam = lbits;
+      jo.lexpr = xloss ? &xloss->lx : nullptr;
       jo.out = out_mode;
       jo.xg = wide;
       jit::compile_only(cb, candidates(cb, true), jo, &bytes, &text, &offs, nullptr);
@@ -5287,6 +5346,7 @@ srhip_group_program* create_group_program(srhip_group* g, int32_t dtype, const s
     const int32_t rc = srhip_program_create_ex(g->ctx[k], dtype, trees, flags, &gp->prog[k]);
     host_thread_cap() = 0;
     check_rc(rc);
+    gp->prog[k]->in_group = true;
     const srhip_program* p = gp->prog[k];
     HIP_CHECK(hipSetDevice(g->ctx[k]->device));
     HIP_CHECK(hipMalloc((void**)&gp->d_const_off[k], p->const_off.size() * sizeof(int32_t)));

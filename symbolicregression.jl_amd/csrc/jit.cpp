@@ -61,10 +61,12 @@ using namespace detail;
 
 
 // ---- IR ------------------------------------------------------------------------
-enum { O_VAL = 0, O_X = 1, O_C = 2 };
+// O_R (the expression loss of the tile tail): a register block that holds a
+// leaf of the loss, v = 0 the prediction, 1 the target, 2 the weight
+enum { O_VAL = 0, O_X = 1, O_C = 2, O_R = 3 };
 struct Opnd {
   int k = O_VAL;
-  int v = -1;        // value id (O_VAL) or feature (O_X)
+  int v = -1;        // value id (O_VAL), feature (O_X) or loss leaf (O_R)
   uint32_t c = 0;    // constant bits (O_C)
   int pc = -1;       // O_C: the program instruction whose immediate holds it (memory-constant code)
   bool der = false;  // O_X: a derived column (v is its column, not a dataset feature)
@@ -1228,6 +1230,8 @@ struct Gen {
       L_fail = as.label();
       as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_fail);
     }
+    // an expression loss: its operators on (ŷ, y, w), the values left in VY
+    if (lexpr) return emit_loss_expr(rreg);
     // ---- L2 loss of the tile: the residuals here, their squares in emit_tail
     // (a margin loss: the agreements ŷ·y for its routine, emit_tail_loss)
     const bool margin = loss >= SRHIP_MARGIN_LOSS_BEGIN;
@@ -1275,6 +1279,208 @@ struct Gen {
     if (as.want_text)
       as.lines.back() = "s_swappc_b64 s[" + std::to_string(S_RR) + ":" + std::to_string(S_RR + 1) + "], s[" +
                         std::to_string(S_TGT) + ":" + std::to_string(S_TGT + 1) + "]";
+  }
+
+  // ---- expression loss (Options::lexpr) -------------------------------------------
+  // The loss's operators as a second op list, emitted once per tree between the
+  // verdict and the tail. The candidate's values are dead by then, so the whole
+  // pool is the loss's: ŷ stays in the root block (moved to a pool block when
+  // that is A, B or the temp block and a routine would overwrite it), y is VY
+  // (read at the top of the tile), w is read from the tile's weight column
+  // into a pool block, constants are literals. + - * neg abs square cube are
+  // one VALU instruction per row, unpacked; every other operator is its
+  // PRECISE routine (call_precise) with the operands in A / B, whatever the
+  // tile's mode, so ℓ is the interpreter's value of the ŷ the tile computed.
+  // No taint, no guard: nothing in the loss marks or fails the tree — chk is
+  // saved in VCHKSAVE (dead after the verdict: only a redo or a bail reads it)
+  // around the routines and put back. The last operator writes VY.
+  const LossExpr* lexpr = nullptr;
+  static bool loss_ir(const LossExpr& lx, std::vector<IrOp>& lo, Opnd& lroot) {
+    std::vector<Opnd> st;
+    size_t nc = 0;
+    lo.clear();
+    for (size_t i = 0; i < lx.kind.size(); ++i) {
+      Opnd q;
+      switch (lx.kind[i]) {
+        case SRHIP_NODE_CONST:
+          if (nc >= lx.consts.size()) return false;
+          q.k = O_C;
+          q.c = fbits(lx.consts[nc++]);
+          break;
+        case SRHIP_NODE_FEATURE:
+          if (lx.arg[i] > 2) return false;
+          q.k = O_R;
+          q.v = lx.arg[i];
+          break;
+        case SRHIP_NODE_UNARY:
+        case SRHIP_NODE_BINARY: {
+          IrOp o;
+          o.un = lx.kind[i] == SRHIP_NODE_UNARY;
+          o.op = lx.arg[i];
+          if (st.size() < (o.un ? 1u : 2u) || o.op >= (o.un ? SRHIP_NUM_UOPS : SRHIP_NUM_BOPS)) return false;
+          if (!o.un) { o.b = st.back(); st.pop_back(); }
+          o.a = st.back();
+          st.pop_back();
+          // an operator on constants alone has no instruction form here (the host could fold it,
+          // with its own rounding): such a loss stays interpreted
+          if (o.a.k == O_C && (o.un || o.b.k == O_C)) return false;
+          q.k = O_VAL;
+          q.v = (int)lo.size();
+          lo.push_back(o);
+          break;
+        }
+        default: return false;
+      }
+      st.push_back(q);
+    }
+    if (st.size() != 1) return false;
+    lroot = st.back();
+    return true;
+  }
+  bool emit_loss_expr(int rreg) {
+    std::vector<IrOp> lo;
+    Opnd lroot;
+    if (!loss_ir(*lexpr, lo, lroot)) { why = "loss expression not translatable"; return false; }
+    const int n = (int)lo.size();
+    bool calls = false, usew = lroot.k == O_R && lroot.v == 2;
+    for (IrOp& o : lo) {
+      if (!is_inline(o)) {
+        o.rid = o.un ? kUopRoutine[o.op] : kBopRoutine[o.op];
+        if (o.rid < 0 || kRoutineTrig[o.rid]) { why = "loss operator without a routine"; return false; }
+        calls = true;
+      }
+      usew = usew || (o.a.k == O_R && o.a.v == 2) || (!o.un && o.b.k == O_R && o.b.v == 2);
+    }
+    // blocks: the pool is free but for ŷ
+    constexpr int kPinned = 2000;
+    for (int k = 0; k < NPOOL; ++k) pool_owner[k] = -1;
+    a_owner = b_owner = -1;
+    int lreg[3] = {rreg, VY, -1};
+    if (rreg >= VPOOL0 && rreg < VPOOL0 + R * NPOOL) {
+      pool_owner[(rreg - VPOOL0) / R] = kPinned;
+    } else if (calls || rreg == VGT) {
+      const int k = free_block();
+      mov_block_reg(VPOOL0 + R * k, rreg);
+      pool_owner[k] = kPinned;
+      lreg[0] = VPOOL0 + R * k;
+    }
+    bool wpending = false;
+    if (usew) {  // as emit_tail_loss reads it; the wait comes before its first use
+      const int k = free_block();
+      as.vop2(VOP2_ADD_U32, "v_add_u32_e32", VGT, S(S_WOFF), VLANE);
+      as.ds_read_b128(VPOOL0 + R * k, VGT, 0);
+      pool_owner[k] = kPinned;
+      lreg[2] = VPOOL0 + R * k;
+      wpending = true;
+    }
+    if (calls) as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHKSAVE, V(VCHK));
+    std::vector<int> lloc((size_t)n, (int)L_NONE);
+    auto block_of = [&](const Opnd& q) { return q.k == O_R ? lreg[q.v] : reg_of_loc(lloc[q.v]); };
+    auto wait_w = [&](const IrOp& o) {
+      if (wpending && ((o.a.k == O_R && o.a.v == 2) || (!o.un && o.b.k == O_R && o.b.v == 2))) {
+        as.waitcnt_lgkm(0);
+        wpending = false;
+      }
+    };
+    // a value's only use: its location is free again (-1: it held none of the pool or A)
+    auto release = [&](const Opnd& q) {
+      if (q.k != O_VAL) return (int)L_NONE;
+      const int l = lloc[q.v];
+      if (l == L_A) a_owner = -1;
+      else pool_owner[l] = -1;
+      return l;
+    };
+    auto load = [&](int dst, const Opnd& q) {
+      if (q.k == O_C) {
+        for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", dst + e, K(q.c));
+      } else if (block_of(q) != dst) {
+        mov_block_reg(dst, block_of(q));
+      }
+    };
+    for (int i = 0; i < n; ++i) {
+      const IrOp& o = lo[i];
+      const bool last = i == n - 1;
+      wait_w(o);
+      if (o.rid >= 0) {
+        const int va_ = o.a.k == O_VAL ? o.a.v : -1, vb_ = (!o.un && o.b.k == O_VAL) ? o.b.v : -1;
+        if (a_owner >= 0 && a_owner != va_ && a_owner != vb_) {  // a value resting in A: to the pool
+          const int k = free_block();
+          if (k < 0) { why = "register pool exhausted (loss)"; return false; }
+          mov_block_reg(VPOOL0 + R * k, VA);
+          pool_owner[k] = a_owner;
+          lloc[a_owner] = k;
+          a_owner = -1;
+        }
+        if (vb_ >= 0 && lloc[vb_] == L_A) {
+          mov_block_reg(VB, VA);
+          load(VA, o.a);
+        } else {
+          load(VA, o.a);
+          if (!o.un) load(VB, o.b);
+        }
+        release(o.a);
+        if (!o.un) release(o.b);
+        call_precise(o.rid);
+        lloc[i] = L_A;
+        a_owner = i;
+        if (last) mov_block_reg(VY, VA);
+        continue;
+      }
+      const bool ca = o.a.k == O_C, cb = !o.un && o.b.k == O_C;
+      const int sa = ca ? -1 : block_of(o.a), sb = (o.un || cb) ? -1 : block_of(o.b);
+      int freed = release(o.a);
+      if (!o.un) {
+        const int f2 = release(o.b);
+        if (freed == L_NONE) freed = f2;
+      }
+      // the next operator is a routine that takes this value first: straight into A when A is free
+      int dst = freed;
+      if (!last && lo[i + 1].rid >= 0 && lo[i + 1].a.k == O_VAL && lo[i + 1].a.v == i && a_owner < 0) dst = L_A;
+      if (dst == L_NONE) dst = free_block();
+      if (dst == L_NONE && !last) { why = "register pool exhausted (loss)"; return false; }
+      const int d = last ? VY : reg_of_loc(dst);
+      for (int e = 0; e < R; ++e) {
+        if (o.un) {
+          switch (o.op) {
+            case SRHIP_UOP_NEG: as.vop2(VOP2_XOR_B32, "v_xor_b32_e32", d + e, K(0x80000000u), sa + e); break;
+            case SRHIP_UOP_ABS: as.vop2(VOP2_AND_B32, "v_and_b32_e32", d + e, K(0x7fffffffu), sa + e); break;
+            case SRHIP_UOP_SQUARE: as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", d + e, V(sa + e), sa + e); break;
+            default: {  // CUBE = (x*x)*x
+              const int tt = d == sa ? VGT + e : d + e;
+              as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", tt, V(sa + e), sa + e);
+              as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", d + e, V(tt), sa + e);
+            }
+          }
+        } else if (o.op == SRHIP_BOP_SUB) {
+          if (cb) as.vop2(VOP2_SUBREV_F32, "v_subrev_f32_e32", d + e, K(o.b.c), sa + e);
+          else as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", d + e, ca ? K(o.a.c) : V(sa + e), sb + e);
+        } else {
+          const int opc = o.op == SRHIP_BOP_ADD ? VOP2_ADD_F32 : VOP2_MUL_F32;
+          const char* nm = o.op == SRHIP_BOP_ADD ? "v_add_f32_e32" : "v_mul_f32_e32";
+          if (cb) as.vop2(opc, nm, d + e, K(o.b.c), sa + e);
+          else as.vop2(opc, nm, d + e, ca ? K(o.a.c) : V(sa + e), sb + e);
+        }
+      }
+      if (last) break;
+      lloc[i] = dst;
+      if (dst == L_A) a_owner = i;
+      else pool_owner[dst] = i;
+    }
+    if (lroot.k != O_VAL) {  // the loss is a leaf
+      if (wpending) as.waitcnt_lgkm(0);
+      load(VY, lroot);
+    }
+    if (calls) as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHK, V(VCHKSAVE));
+    return true;
+  }
+  // its tail: rows past the end add 0, then (ℓ0 + ℓ2) + (ℓ1 + ℓ3) into the tree's
+  // sum as emit_tail_loss; no weight (an expression that wants one reads w)
+  void emit_tail_expr() {
+    emit_mask(VY);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VY, V(VY), VY + 2);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VY + 1, V(VY + 1), VY + 3);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VY, V(VY), VY + 1);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VLSUM, V(VLSUM), VY);
   }
 
   // the tile tail of a loss other than L2: ℓ(r) of the residual block VY (ℓ(a)
@@ -1333,6 +1539,8 @@ struct Gen {
   void emit_tail() {
     if (out) {
       emit_store_out();
+    } else if (lexpr) {
+      emit_tail_expr();
     } else if (loss != SRHIP_LOSS_L2) {
       emit_tail_loss();
     } else {
@@ -1366,7 +1574,7 @@ struct Gen {
     }
     // a failed tile ends the tree (out mode: every tile is stored); the
     // trimmed root mark has left already, and an L2 tail writes no chk (a
-    // loss routine may)
+    // loss routine may; an expression loss, built as L2, has put chk back)
     if (!out && !(root2 && loss == SRHIP_LOSS_L2)) {
       as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(VCHK), VCHK);
       as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_done);
@@ -1430,7 +1638,8 @@ static int xwindow_depth() {
 static bool gen_tree(const Ins<float>* prog, const Tmpl& T, bool fast_opt, bool text, std::vector<uint32_t>& out,
                      std::vector<std::string>* lines, uint64_t area_va, int32_t* off, bool* is_fast,
                      std::string* why, const DerivedMap& dm, bool memc, int loss = SRHIP_LOSS_L2,
-                     uint64_t lparam = 0, bool out_mode = false, bool xg = false) {
+                     uint64_t lparam = 0, bool out_mode = false, bool xg = false,
+                     const LossExpr* lx = nullptr) {
   std::vector<IrOp> ir;
   Opnd root;
   if (!build_ir(prog, ir, root, &dm)) { *why = "program not translatable"; return false; }
@@ -1451,6 +1660,7 @@ static bool gen_tree(const Ins<float>* prog, const Tmpl& T, bool fast_opt, bool 
     g.memc = memc;
     g.loss = loss;
     g.lparam = lparam;
+    g.lexpr = lx;
     if (subst && attempt == 0) g.gbase = dm.gbase;
     // wide code: the window's depth, then (the blocks it held ahead were the values') no look-ahead
     g.xg = xg;
@@ -1563,7 +1773,7 @@ static bool codegen_par(const CompiledBatch<float>& cb, const std::vector<int32_
     R& r = res[k];
     int32_t off;
     r.ok = cb.tree_off[t] >= 0 && gen_tree(&cb.code[cb.tree_off[t]], T, opt.fast, false, r.w, nullptr, T.area_va, &off,
-                                           &r.fast, &r.why, dm, opt.memc, opt.loss, opt.lparam, opt.out, opt.xg);
+                                           &r.fast, &r.why, dm, opt.memc, opt.loss, opt.lparam, opt.out, opt.xg, opt.lexpr);
   });
   size_t pos = words.size(), end = n;
   for (size_t k = 0; k < n; ++k) {
@@ -1584,7 +1794,7 @@ static bool codegen_par(const CompiledBatch<float>& cb, const std::vector<int32_
     std::string why;
     const int32_t t = cand[from + k];
     if (!gen_tree(&cb.code[cb.tree_off[t]], T, opt.fast, false, r.w, nullptr, T.area_va + r.start * 4, &off, &f, &why,
-                  dm, opt.memc, opt.loss, opt.lparam, opt.out, opt.xg) ||
+                  dm, opt.memc, opt.loss, opt.lparam, opt.out, opt.xg, opt.lexpr) ||
         r.w.size() != sz)
       same = false;
   });
@@ -1638,7 +1848,7 @@ static size_t codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>
     const size_t lbefore = lines ? lines->size() : 0;
     const bool okc = cb.tree_off[t] >= 0 &&
                      gen_tree(&cb.code[cb.tree_off[t]], T, opt.fast, opt.text, words, lines, T.area_va, &off, &f, &why, dm, opt.memc,
-                              opt.loss, opt.lparam, opt.out, opt.xg);
+                              opt.loss, opt.lparam, opt.out, opt.xg, opt.lexpr);
     if (okc && words.size() * 4 > T.area_bytes) {  // area full: the next part takes it
       words.resize(before);
       if (lines) lines->resize(lbefore);
@@ -1662,6 +1872,16 @@ static size_t codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>
 
 bool has_loss_routine(int loss) {
   return loss == SRHIP_LOSS_L2 || (loss >= 0 && loss < SRHIP_NUM_LOSSES && kLossRoutine[loss] >= 0);
+}
+// A dry run of the loss's code behind a root in a pool block: ŷ never takes
+// more of the pool than that, so what fits here fits behind every tree.
+bool loss_expr_fits(const LossExpr& lx) {
+  const Templates& TT = templates();
+  if (!TT.ok) return false;
+  Asm as;
+  Gen g(as, TT.large, TT.large.area_va, false);
+  g.lexpr = &lx;
+  return g.emit_loss_expr(VPOOL0);
 }
 int choose_waves(int nraw) {
   static const int forced = [] {  // SRHIP_JIT_WAVES = 1 .. 16, read once per process
@@ -1858,6 +2078,11 @@ int max_feature_read(const CompiledBatch<float>& cb, const std::vector<int32_t>&
 // wide code is literal-constant loss code: the option is dropped otherwise
 static Options checked(Options opt) {
   if (opt.memc || opt.out) opt.xg = false;
+  if (opt.lexpr) {  // the expression stands in for the table loss: the rest of the build is L2's
+    if (opt.out || opt.xg) throw Error(SRHIP_ERR_UNSUPPORTED, "jit: an expression loss with per-row output or wide code");
+    opt.loss = SRHIP_LOSS_L2;
+    opt.lparam = 0;
+  }
   return opt;
 }
 

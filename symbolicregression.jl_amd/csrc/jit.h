@@ -16,6 +16,20 @@ namespace jit {
 
 struct Module;
 
+// An expression loss (srhip.h "expression losses") for the tile tail of loss
+// tree code: the handle's postfix stream (SRHIP_NODE_*; feature 0 = ŷ, 1 = y,
+// 2 = w) and its constants already rounded to Float32, in leaf order. They
+// become literals of the code (the handle is immutable).
+struct LossExpr {
+  std::vector<uint8_t> kind;
+  std::vector<uint16_t> arg;
+  std::vector<float> consts;
+};
+// The loss compiles to a tile tail: every operator inline or with a routine
+// that hands no tile back, no operator on constants alone, and register
+// blocks enough whatever the tree before it. False: that loss runs interpreted.
+bool loss_expr_fits(const LossExpr& lx);
+
 // Options of one compilation (the defaults are the product path).
 struct Options {
   bool fast = true;       // emit the FAST-routine path + guards in eligible trees
@@ -27,6 +41,12 @@ struct Options {
   // the interpreter's); PERIODIC keeps every tree off the FAST path
   int loss = SRHIP_LOSS_L2;
   uint64_t lparam = 0;     // Float64 bits (LossFunctions' field, never rounded to Float32)
+  // an expression loss as the tile tail (jit.cpp Gen::emit_loss_expr) instead
+  // of `loss`: its operators run after the root mark and the FAST verdict,
+  // routines in the PRECISE region whatever the tile's mode, and the values
+  // are masked and summed unweighted. Not with out or xg. The caller keeps it
+  // alive for the build.
+  const LossExpr* lexpr = nullptr;
   // per-row output tree code (srhip_eval_tree_array): every tile stores its
   // root values to the tree's output rows instead of ending with a loss; the
   // PRECISE routines only (the interpreter's values, bit for bit), every tile

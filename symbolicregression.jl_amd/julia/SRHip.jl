@@ -253,9 +253,10 @@ end
 # ---- expression losses: a custom elementwise_loss written as a tree (srhip.h
 # "expression losses") ----------------------------------------------------------
 const SRHIP_EXPR_LOSS_BEGIN = Int32(1024)  # loss kinds from here on are handles of expression losses
+const SRHIP_LOSS_EXPR_TREE_CODE = UInt32(1)  # srhip_loss_expr_create_ex: Float32 loss tree code may run the handle
 
 """
-    ExprLoss(tree::Node{T}, operators)
+    ExprLoss(tree::Node{T}, operators; tree_code=false)
 
 A custom `elementwise_loss` as a tree over x1 = the prediction, x2 = the target
 and x3 = the weight, built with `operators` (an `OperatorEnum`, e.g.
@@ -264,7 +265,9 @@ handle, >= SRHIP_EXPR_LOSS_BEGIN, destroyed by the finaliser) and is itself a
 function `(x, y)` / `(x, y, w)`, so the reference's CPU path
 (src/LossFunctions.jl:17-31) evaluates the same tree. The engine sums the loss
 values as they are: a weighted loss multiplies by x3 itself, and a tree that
-reads x3 needs a weighted dataset.
+reads x3 needs a weighted dataset. `tree_code=true` lets the Float32 loss tree
+code run the expression at the end of its tiles (srhip.h lists what stays
+interpreted); the results obey the same contract.
 """
 mutable struct ExprLoss{T,O} <: Function
     tree::Node{T}
@@ -272,7 +275,7 @@ mutable struct ExprLoss{T,O} <: Function
     kind::Int32
 end
 
-function ExprLoss(tree::Node{T}, operators) where {T}
+function ExprLoss(tree::Node{T}, operators; tree_code::Bool=false) where {T}
     bin = [op_id(op, 2) for op in operators.binops]
     una = [op_id(op, 1) for op in operators.unaops]
     kind = UInt8[]; arg = UInt16[]; consts = Float64[]
@@ -291,9 +294,15 @@ function ExprLoss(tree::Node{T}, operators) where {T}
     end
     visit(tree)
     h = Ref{Int32}(0)
-    check(ccall((:srhip_loss_expr_create, libsrhip), Int32,
-                (Ptr{UInt8}, Ptr{UInt16}, Int32, Ptr{Float64}, Int32, Ptr{Int32}),
-                kind, arg, Int32(length(kind)), consts, Int32(length(consts)), h))
+    if tree_code
+        check(ccall((:srhip_loss_expr_create_ex, libsrhip), Int32,
+                    (Ptr{UInt8}, Ptr{UInt16}, Int32, Ptr{Float64}, Int32, UInt32, Ptr{Int32}),
+                    kind, arg, Int32(length(kind)), consts, Int32(length(consts)), SRHIP_LOSS_EXPR_TREE_CODE, h))
+    else
+        check(ccall((:srhip_loss_expr_create, libsrhip), Int32,
+                    (Ptr{UInt8}, Ptr{UInt16}, Int32, Ptr{Float64}, Int32, Ptr{Int32}),
+                    kind, arg, Int32(length(kind)), consts, Int32(length(consts)), h))
+    end
     l = ExprLoss{T,typeof(operators)}(tree, operators, h[])
     finalizer(l) do x
         ccall((:srhip_loss_expr_destroy, libsrhip), Int32, (Int32,), x.kind)

@@ -75,6 +75,8 @@ SIGNATURES = {
     "srhip_last_loss_launch": [C.POINTER(C.c_int32)],
     "srhip_loss_expr_create": [C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_double),
                                C.c_int32, C.POINTER(C.c_int32)],
+    "srhip_loss_expr_create_ex": [C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_double),
+                                  C.c_int32, C.c_uint32, C.POINTER(C.c_int32)],
     "srhip_loss_expr_destroy": [C.c_int32],
     "srhip_op_expr_create": [C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_double),
                              C.c_int32, C.POINTER(C.c_int32)],

@@ -24,6 +24,7 @@ LOSS = {n: i for i, n in enumerate(LOSSES)}
 MARGIN_LOSS_BEGIN = LOSS["ZEROONE"]
 # loss kinds from here on are handles of expression losses (srhip_loss_expr_create)
 EXPR_LOSS_BEGIN = 1024
+LOSS_EXPR_TREE_CODE = 1  # srhip_loss_expr_create_ex flag: Float32 loss tree code may run the handle
 # operator ids from here on are handles of expression operators (srhip_op_expr_create)
 EXPR_OP_BEGIN = 1024
 

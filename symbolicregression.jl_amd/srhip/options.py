@@ -133,12 +133,17 @@ class ExprLoss:
 
     The engine sums the loss values as they are: a weighted loss multiplies by
     x3 itself. A tree that reads x3 needs a weighted dataset (srhip.h lists the
-    limits and the deviations from the reference)."""
+    limits and the deviations from the reference).
+
+    `tree_code=True` (SRHIP_LOSS_EXPR_TREE_CODE) lets the Float32 loss tree code
+    run the expression at the end of its tiles instead of handing the whole call
+    to the interpreter; the contract is the same, and srhip.h lists the calls
+    that stay interpreted."""
 
     param = 0.0
     params = None  # no parameter: the engine ignores loss_params for these kinds
 
-    def __init__(self, tree, options):
+    def __init__(self, tree, options, tree_code=False):
         import ctypes as C
         import weakref
 
@@ -152,11 +157,12 @@ class ExprLoss:
         arg = np.ascontiguousarray(flat.arg, dtype=np.uint16)
         consts = np.ascontiguousarray(flat.consts, dtype=np.float64)
         out = C.c_int32(0)
-        check(lib().srhip_loss_expr_create(kind.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                           arg.ctypes.data_as(C.POINTER(C.c_uint16)), int(len(kind)),
-                                           consts.ctypes.data_as(C.POINTER(C.c_double)), int(len(consts)),
-                                           C.byref(out)))
+        check(lib().srhip_loss_expr_create_ex(kind.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              arg.ctypes.data_as(C.POINTER(C.c_uint16)), int(len(kind)),
+                                              consts.ctypes.data_as(C.POINTER(C.c_double)), int(len(consts)),
+                                              K.LOSS_EXPR_TREE_CODE if tree_code else 0, C.byref(out)))
         self.kind = int(out.value)
+        self.tree_code = bool(tree_code)
         self.tree = tree
         self.uses_weights = bool(np.any((kind == K.NODE_FEATURE) & (arg == 2)))
         self._finalizer = weakref.finalize(self, _destroy_expr_loss, self.kind)
