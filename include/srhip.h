@@ -378,6 +378,15 @@ int32_t srhip_program_create(srhip_ctx* ctx, int32_t dtype,
  * No effect on Float64 programs, with SRHIP_PROGRAM_INTERPRETED or with
  * SRHIP_PROGRAM_VARYING_CONSTANTS (memory-constant code is never wide). */
 #define SRHIP_PROGRAM_WIDE_TREE_CODE 4u
+/* SRHIP_PROGRAM_DERIV_TREE_CODE (opt-in): srhip_eval_loss_deriv on this program may
+ * run reverse-mode tree code ("sr_jit_deriv" / "sr_jit_deriv_w")
+ * in place of the forward-mode interpreter; see that call for when it does. The code
+ * is built at the first such call of each (dir, feature count, weights, loss,
+ * parameter), reads its constants from memory (srhip_program_set_constants needs no
+ * new code) and is independent of every other flag. No effect on Float64 programs
+ * or on any other call. The value is bit 5: bits 3 and 4 stay unknown flags
+ * (SRHIP_ERR_INVALID), as callers of earlier versions were told. */
+#define SRHIP_PROGRAM_DERIV_TREE_CODE 0x20u
 int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees* trees, uint32_t flags,
                                 srhip_program** out_prog);
 int32_t srhip_program_destroy(srhip_program* prog);
@@ -629,7 +638,7 @@ int32_t srhip_eval_loss_grad_rowsets_targets(srhip_dataset* ds, const srhip_prog
  * SRHIP_MARGIN_LOSS_BEGIN) are SRHIP_ERR_INVALID; an expression-loss handle and a
  * program that holds expression operators are SRHIP_ERR_UNSUPPORTED. The loss
  * kind and its parameter are checked as everywhere.
- * Always the forward-mode interpreter with tangents seeded at feature leaves, in
+ * The forward-mode interpreter with tangents seeded at feature leaves, in
  * kernel variants of its own ("grad_kernel_deriv<float>",
  * "grad_kernel_wide_deriv<float>" and the double forms; the wide one when the row
  * tile of every feature and column does not fit in LDS). One work item per tree
@@ -637,10 +646,25 @@ int32_t srhip_eval_loss_grad_rowsets_targets(srhip_dataset* ds, const srhip_prog
  * gives 0 and no tree code is built for such a call (the one-shot form makes its
  * program with SRHIP_PROGRAM_INTERPRETED). srhip_last_loss_launch gives the row
  * groups, tree groups and items per group of the call's last launch.
+ * On a Float32 program made with SRHIP_PROGRAM_DERIV_TREE_CODE the call runs
+ * reverse-mode tree code instead when ndir <= 4, the loss is a distance loss other
+ * than Periodic and the dataset's runs are not wide (its tile of 2 + nfeat + 2·ndir
+ * arrays, 1 + nfeat + ndir unweighted, is at most 64 arrays): one forward and one
+ * reverse pass per tree and tile whatever ndir, the per-row adjoints of each
+ * direction's feature leaves scored against that direction's column. A tree the
+ * code generator refuses (an operator outside + - * / ^ neg abs square cube exp
+ * sin cos log sqrt, more than 16 constants, an exhausted register pool) runs in
+ * the interpreter kernel in the same call. srhip_last_tree_code then gives the
+ * number of compiled trees, srhip_last_kernel_name "sr_jit_deriv" (weighted:
+ * "sr_jit_deriv_w") and srhip_last_loss_launch that launch's geometry. The flag
+ * rule and the refusals are the same; sums agree with the interpreter's within
+ * Float32 rounding of the derivative (reverse against forward accumulation), not
+ * bit for bit. When one of the conditions fails the call takes the interpreter path
+ * above, bit for bit, and srhip_last_tree_code gives 0.
  * The sums' gradients with respect to the constants and constant optimisation under
  * the objective are srhip_eval_loss_grad_deriv and srhip_optimize_constants_deriv below.
  * Not in this version: row sets; group datasets; expression losses and expression
- * operators; tree code. */
+ * operators; Float64, Periodic or ndir > 4 as tree code. */
 int32_t srhip_eval_loss_deriv(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
                               const double* loss_params, const int32_t* dir, int32_t ndir,
                               double* out_loss_sum,   /* [ntrees][1 + ndir] */
@@ -1011,6 +1035,15 @@ int32_t srhip_jit_compile(const srhip_trees* trees, int32_t fast, uint8_t* out_b
 int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int64_t* inout_nbytes,
                                char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
                                int64_t* inout_noffsets);
+/* Testing hook, same contract: the derivative tree code of srhip_eval_loss_deriv on a
+ * SRHIP_PROGRAM_DERIV_TREE_CODE program, for Float32 trees scored over the 0-based
+ * directions dir[0..ndir-1] of a dataset of nfeat features, weighted or not, under
+ * the distance loss `loss` with its parameter. SRHIP_ERR_UNSUPPORTED where that call
+ * would take the interpreter (ndir > 4, Periodic, a tile past 64 arrays). */
+int32_t srhip_jit_compile_deriv(const srhip_trees* trees, const int32_t* dir, int32_t ndir, int32_t nfeat,
+                                int32_t weighted, int32_t loss, double loss_param, uint8_t* out_bytes,
+                                int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
+                                int64_t* inout_noffsets);
 /* Testing hook, same contract: the loss tree code (grad = 0; fast: its
  * guarded FAST path) or the gradient tree code (grad = 1) of Float32 trees
  * for the elementwise loss `loss` (SRHIP_LOSS_*) with its parameter; fast

@@ -403,6 +403,14 @@ struct srhip_program {
   std::vector<GradLossJit64> gjit64_loss;  // other losses' Float64 gradient tree code (same slots)
   double* d_gconsts64 = nullptr;
   size_t gcs64_cap = 0;
+  // SRHIP_PROGRAM_DERIV_TREE_CODE (Float32): srhip_eval_loss_deriv may run the derivative
+  // tree code (jit.h DerivSpec). One module per spec, built at the spec's first call from
+  // the trees alone (constants are read from d_gconsts, uploaded when they differ from
+  // dj_consts), so it outlives set_constants; jl: its trees, in_jit: per tree
+  bool deriv_tc = false;
+  struct DerivJit { jit::DerivSpec sp; jit::DerivModule* m; std::vector<int32_t> jl; std::vector<uint8_t> in_jit; };
+  std::vector<DerivJit> djit;
+  std::vector<unsigned char> dj_consts;
   size_t gjl_cap = 0, gjc_cap = 0, gcs_cap = 0;
   // byte capacities of the device buffers above (kept across rebuilds)
   size_t code_cap = 0, toff_cap = 0, list_cap = 0;
@@ -712,6 +720,9 @@ void free_grad_device(srhip_program* p) {
   p->gjit64 = nullptr;
   for (auto& l : p->gjit64_loss) jit::destroy_grad64(l.m);
   p->gjit64_loss.clear();
+  for (auto& l : p->djit) jit::destroy_deriv(l.m);
+  p->djit.clear();
+  p->dj_consts.clear();
   if (p->d_gconsts64) (void)hipFree(p->d_gconsts64);
   p->d_gconsts64 = nullptr;
   p->gcs64_cap = 0;
@@ -2999,11 +3010,108 @@ int eval_loss_grad_targets_impl(srhip_dataset* ds, srhip_program* p, int loss, c
   return SRHIP_OK;
 }
 
+// The derivative tree code of a SRHIP_PROGRAM_DERIV_TREE_CODE program for this call's
+// (dir, features, weights, loss, parameter), built at the spec's first call and kept with
+// the program; null: the whole call runs in the interpreter (more than jit::kDerivMaxDir
+// directions, Periodic or a loss without an ℓ routine, a dataset whose runs are wide or
+// whose tile does not fit the code's literal offsets, no tree that compiles).
+srhip_program::DerivJit* deriv_module(srhip_program* p, const srhip_dataset* ds, int loss, const double* params,
+                                      const int32_t* dir, int ndir) {
+  if (!p->deriv_tc || p->dtype != SRHIP_F32 || ndir > jit::kDerivMaxDir || wide_mode() == 1 || !jit::available())
+    return nullptr;
+  jit::DerivSpec sp;
+  sp.ndir = ndir;
+  std::copy(dir, dir + ndir, sp.dir);
+  sp.nfeat = ds->nfeat;
+  sp.weighted = ds->w != nullptr;
+  sp.loss = loss;
+  sp.lparam = loss == SRHIP_LOSS_L2 ? 0 : bits_of(params ? params[0] : 0.0);
+  EvalPlan probe;  // the row tile in LDS: the same verdict for every tree count
+  if (!jit::deriv_spec_fits(sp) ||
+      !plan_geometry(4, 4, kShallowSlots, jit::deriv_narr(sp), 1, ds->rows, 1, &probe, gjit_tile_budget()))
+    return nullptr;
+  for (auto& l : p->djit)
+    if (l.sp == sp) return l.m ? &l : nullptr;
+  // gradient programs (no folding): a tree's code does not depend on its constants' values
+  const CompiledBatch<float> cb = compile_batch_par<float>(trees_of(p, p->consts.data()), /*grad=*/true, p->jit_memc);
+  std::vector<int32_t> cand;
+  for (int t = 0; t < p->ntrees; ++t)
+    if (cb.tree_off[t] >= 0 && !cb.expr[t]) cand.push_back(t);
+  std::stable_sort(cand.begin(), cand.end(), [&](int32_t x, int32_t y) {
+    return cb.cost[x] != cb.cost[y] ? cb.cost[x] > cb.cost[y] : x < y;
+  });
+  srhip_program::DerivJit dj;
+  dj.sp = sp;
+  std::vector<int32_t> rest;
+  jit::GradStats st;
+  dj.m = cand.empty() ? nullptr : jit::build_deriv(cb, p->const_off, cand, sp, dj.jl, rest, &st);
+  dj.in_jit.assign(p->ntrees, 0);
+  for (int32_t t : dj.jl) dj.in_jit[t] = 1;
+  p->djit.push_back(std::move(dj));
+  return p->djit.back().m ? &p->djit.back() : nullptr;
+}
+
+// Its launches: per code object the driver and the finalize kernel, into d_sum [nt][1 + ndir]
+// and the ok bytes. False (nothing launched): no plan for this dataset.
+bool run_deriv_tree_code(srhip_ctx* c, srhip_program* p, const srhip_dataset* ds, srhip_program::DerivJit* dj, int loss,
+                         double* d_sum, hipStream_t s) {
+  jit::DerivModule* m = dj->m;
+  const int nparts = jit::deriv_nparts(m), ndir = dj->sp.ndir;
+  std::vector<EvalPlan> plans(nparts);
+  size_t maxslots = 0;
+  for (int k = 0; k < nparts; ++k) {
+    int s0, nsl;
+    jit::deriv_part(m, k, &s0, &nsl);
+    if (!plan_geometry(4, 4, kShallowSlots, jit::deriv_narr(dj->sp), 1, ds->rows, nsl, &plans[k], gjit_tile_budget()))
+      return false;
+    maxslots = std::max(maxslots, (size_t)plans[k].nrg * nsl);
+  }
+  if (p->dj_consts != p->consts || !p->d_gconsts) {  // the constants the code reads (s_load)
+    upload_gconsts(p);
+    p->dj_consts = p->consts;
+  }
+  const int nsl_all = jit::deriv_nslots(m);
+  c->fail.ensure((size_t)nsl_all * sizeof(uint32_t));
+  c->fail_clean = false;
+  HIP_CHECK(hipMemsetAsync(c->fail.p, 0, (size_t)nsl_all * sizeof(uint32_t), s));
+  c->gpart.ensure(maxslots * (sizeof(Part<float>) + (size_t)ndir * sizeof(float)));
+  Part<float>* part = static_cast<Part<float>*>(c->gpart.p);
+  float* dpart = reinterpret_cast<float*>(part + maxslots);
+  for (int k = 0; k < nparts; ++k) {
+    int s0, nsl;
+    jit::deriv_part(m, k, &s0, &nsl);
+    const EvalPlan& plan = plans[k];
+    EvalArgs<float> a;
+    std::memset(&a, 0, sizeof(a));
+    a.fail = static_cast<uint32_t*>(c->fail.p) + s0;
+    a.nlist = nsl;
+    a.X = static_cast<const float*>(ds->X);
+    a.y = static_cast<const float*>(ds->y);
+    a.w = static_cast<const float*>(ds->w);
+    a.n = ds->rows;
+    a.n_pad = ds->n_pad;
+    a.nfeat = ds->nfeat;
+    a.ntiles = plan.ntiles;
+    a.ntg = plan.ntg;
+    a.tpb = plan.tpb;
+    a.nrg = plan.nrg;
+    a.loss = loss;
+    const int tk = timed_begin(c, s);
+    HIP_CHECK(jit::launch_deriv_code(m, k, plan, a, p->d_gconsts, part, dpart, s));
+    timed_end(c, s, tk);
+    HIP_CHECK(jit::launch_deriv_finalize(m, k, plan.nrg, a.fail, part, dpart, d_sum, static_cast<uint8_t*>(c->oks.p), s));
+    note_loss_launch(plan.nrg, plan.ntg, plan.tpb, (unsigned)plan.nrg * (unsigned)plan.ntg, plan.nrg, 1);
+  }
+  return true;
+}
+
 // srhip_eval_loss_deriv (checked by the caller): the forward-mode interpreter with its
 // tangents seeded at feature leaves (grad_kernel.h kGradLossDeriv), one work item per
 // (tree, group of kGradG directions) — one per tree, carrying ndir tangents, when
 // ndir <= 2 and the tree is shallow. Shallow trees, then deep ones; the wide variant
-// where the row tile of every feature and column does not fit in LDS. No tree code.
+// where the row tile of every feature and column does not fit in LDS. On a
+// SRHIP_PROGRAM_DERIV_TREE_CODE program (deriv_module) the trees that compile run as
+// reverse-mode tree code instead, after the interpreter's launches for the others.
 template <typename T>
 int eval_loss_deriv_impl(srhip_dataset* ds, srhip_program* p, int loss, const double* params, const int32_t* dir,
                          int ndir, double* out_sum, double* out_wsum, uint8_t* out_ok) {
@@ -3017,12 +3125,16 @@ int eval_loss_deriv_impl(srhip_dataset* ds, srhip_program* p, int loss, const do
   const int64_t rows = ds->rows;
   std::vector<int32_t> hdir((size_t)ngroups * kGradG, -1);  // (no feature index is negative)
   std::copy(dir, dir + ndir, hdir.begin());
+  srhip_program::DerivJit* dj = nullptr;
+  if constexpr (std::is_same<T, float>::value) {
+    if (rows > 0 && nt > 0) dj = deriv_module(p, ds, loss, params, dir, ndir);
+  }
   std::vector<int32_t> items;
   int nitems_of[2] = {0, 0};
   for (int cl = 0; cl < 2; ++cl) {
     std::vector<int32_t> ts;
     for (int t = 0; t < nt; ++t)
-      if (p->g_class[t] == cl) ts.push_back(t);
+      if (p->g_class[t] == cl && !(dj && dj->in_jit[t])) ts.push_back(t);
     std::stable_sort(ts.begin(), ts.end(), [&](int32_t x, int32_t y) { return p->g_cost[x] > p->g_cost[y]; });
     for (int32_t t : ts)
       for (int gi = 0; gi < ngroups; ++gi) items.push_back((int32_t)(t | (gi << 24)));
@@ -3085,6 +3197,11 @@ int eval_loss_deriv_impl(srhip_dataset* ds, srhip_program* p, int loss, const do
     timed_end(c, s, tk);
     HIP_CHECK(launch_grad_deriv_finalize<T>(a, d_sum, static_cast<uint8_t*>(c->oks.p), s));
     note_loss_launch(plan.nrg, plan.ntg, plan.tpb, (unsigned)plan.nrg * (unsigned)plan.ntg, plan.nrg, 1);
+    ran = true;
+  }
+  if (dj) {
+    if (!run_deriv_tree_code(c, p, ds, dj, loss, d_sum, s)) throw_lds(ds->nfeat);
+    c->last_jit_trees = (int)dj->jl.size();
     ran = true;
   }
   std::vector<double> hs((size_t)nt * ncol, 0.0);
@@ -3851,7 +3968,8 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
     *out_prog = nullptr;
     if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
     if (trees->ntrees < 0) throw Error(SRHIP_ERR_INVALID, "negative tree count");
-    if (flags & ~(SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED | SRHIP_PROGRAM_WIDE_TREE_CODE))
+    if (flags & ~(SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED | SRHIP_PROGRAM_WIDE_TREE_CODE |
+                  SRHIP_PROGRAM_DERIV_TREE_CODE))
       throw Error(SRHIP_ERR_INVALID, "unknown program flags");
     const int nt = trees->ntrees;
     auto* p = new srhip_program();
@@ -3861,6 +3979,7 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
     p->jit_memc = (flags & SRHIP_PROGRAM_VARYING_CONSTANTS) != 0;
     if (flags & SRHIP_PROGRAM_INTERPRETED) p->jit_allowed = false;
     p->wide_tc = (flags & SRHIP_PROGRAM_WIDE_TREE_CODE) != 0 && dtype == SRHIP_F32;
+    p->deriv_tc = (flags & SRHIP_PROGRAM_DERIV_TREE_CODE) != 0 && dtype == SRHIP_F32;
     try {
       if (nt > 0) {
         if (!trees->node_off || !trees->const_off) throw Error(SRHIP_ERR_INVALID, "null offsets");
@@ -4424,7 +4543,7 @@ std::vector<int32_t> candidates(const CompiledBatch<T>& cb, bool shallow) {
 int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes, int64_t* inout_nbytes,
                          char* out_text, int64_t* inout_ntext, int32_t* out_offsets, int64_t* inout_noffsets,
                          int loss = SRHIP_LOSS_L2, double lparam = 0.0, bool out_mode = false, bool notext = false,
-                         bool wide = false) {
+                         bool wide = false, const jit::DerivSpec* dspec = nullptr) {
   return guarded([&] {
     if (!trees || !inout_nbytes || !inout_ntext || !inout_noffsets) throw Error(SRHIP_ERR_INVALID, "null argument");
     if (!jit::available()) throw Error(SRHIP_ERR_UNSUPPORTED, std::string("tree compiler: ") + jit::unavailable_reason());
@@ -4446,7 +4565,7 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
     if (loss < 0 || loss >= SRHIP_NUM_LOSSES) throw Error(SRHIP_ERR_INVALID, "unknown loss");
     uint64_t lbits;
     std::memcpy(&lbits, &lparam, 8);
-    if (mode == 2 && !jit::has_dloss_routine(loss))
+    if (mode == 2 && !dspec && !jit::has_dloss_routine(loss))
       throw Error(SRHIP_ERR_UNSUPPORTED, "no gradient tree code for this loss");
     if (mode != 2 && mode != 5 && mode != 6 && !jit::has_loss_routine(loss))
       throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for this loss");
@@ -4467,7 +4586,8 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
     } else if (mode == 2) {  // gradient tree code
       CompiledBatch<float> cb = compile_batch<float>(*trees, /*grad=*/true);
       const std::vector<int32_t> coff(trees->const_off, trees->const_off + trees->ntrees + 1);
-      jit::compile_grad_only(cb, coff, candidates(cb, false), &bytes, &text, &offs, nullptr, loss, lbits);
+      if (dspec) jit::compile_deriv_only(cb, coff, candidates(cb, false), *dspec, &bytes, &text, &offs, nullptr);
+      else jit::compile_grad_only(cb, coff, candidates(cb, false), &bytes, &text, &offs, nullptr, loss, lbits);
     } else {
       CompiledBatch<float> cb = compile_batch<float>(*trees);
       jit::Options jo;
@@ -4517,6 +4637,25 @@ int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int
                                char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
                                int64_t* inout_noffsets) {
   return jit_compile_hook(trees, 2, out_bytes, inout_nbytes, out_text, inout_ntext, out_offsets, inout_noffsets);
+}
+
+int32_t srhip_jit_compile_deriv(const srhip_trees* trees, const int32_t* dir, int32_t ndir, int32_t nfeat,
+                                int32_t weighted, int32_t loss, double loss_param, uint8_t* out_bytes,
+                                int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
+                                int64_t* inout_noffsets) {
+  jit::DerivSpec sp;
+  if (!dir || ndir < 1 || ndir > jit::kDerivMaxDir || nfeat < 1 || loss < 0 || loss >= SRHIP_MARGIN_LOSS_BEGIN)
+    return set_error(SRHIP_ERR_UNSUPPORTED, "derivative tree code: 1..4 directions, a distance loss");
+  for (int k = 0; k < ndir; ++k)
+    if (dir[k] < 0 || dir[k] >= nfeat) return set_error(SRHIP_ERR_INVALID, "direction outside the features");
+  sp.ndir = ndir;
+  std::copy(dir, dir + ndir, sp.dir);
+  sp.nfeat = nfeat;
+  sp.weighted = weighted != 0;
+  sp.loss = loss;
+  sp.lparam = loss == SRHIP_LOSS_L2 ? 0 : bits_of(loss_param);
+  return jit_compile_hook(trees, 2, out_bytes, inout_nbytes, out_text, inout_ntext, out_offsets, inout_noffsets,
+                          SRHIP_LOSS_L2, 0.0, false, false, false, &sp);
 }
 
 int32_t srhip_jit_compile_loss(const srhip_trees* trees, int32_t grad, int32_t fast, int32_t loss, double loss_param,
@@ -5332,6 +5471,8 @@ void destroy_group_program(srhip_group_program* gp) {
 
 srhip_group_program* create_group_program(srhip_group* g, int32_t dtype, const srhip_trees* trees, uint32_t flags) {
   if (!g || !trees) throw Error(SRHIP_ERR_INVALID, "null argument");
+  if (flags & SRHIP_PROGRAM_DERIV_TREE_CODE)  // (srhip_eval_loss_deriv takes no group dataset)
+    throw Error(SRHIP_ERR_INVALID, "unknown program flags");
   std::unique_ptr<srhip_group_program> gp(new srhip_group_program());
   gp->g = g;
   gp->dtype = dtype;

@@ -245,6 +245,52 @@ bool compile_grad_only(const CompiledBatch<float>& cb, const std::vector<int32_t
                        const std::vector<int32_t>& cand, std::vector<uint8_t>* bytes, std::string* text,
                        std::vector<int32_t>* offsets, GradStats* st, int loss = SRHIP_LOSS_L2, uint64_t lparam = 0);
 
+// ---- derivative-objective tree code (jit_grad.cpp) ------------------
+// The gradient tree code's reverse pass with the feature leaves of `dir` as adjoint
+// targets and seed 1: per tile, ŷ scored against y (channel 0) and ∂ŷ/∂x_dir[k]
+// against Y[1 + k] (channel 1 + k), weighted by the channel's own W column. The
+// code holds the tile layout as literals (y, the nfeat features, Y[1..ndir], then
+// W[0..ndir] when weighted), so a module serves one (dir, nfeat, weighted, loss,
+// parameter); constants are read from memory as in the gradient tree code.
+constexpr int kDerivMaxDir = 4;
+struct DerivSpec {
+  int ndir = 0;
+  int dir[kDerivMaxDir] = {-1, -1, -1, -1};
+  int nfeat = 0;
+  bool weighted = false;
+  int loss = SRHIP_LOSS_L2;
+  uint64_t lparam = 0;
+  bool operator==(const DerivSpec& o) const {
+    return ndir == o.ndir && std::equal(dir, dir + kDerivMaxDir, o.dir) && nfeat == o.nfeat && weighted == o.weighted &&
+           loss == o.loss && lparam == o.lparam;
+  }
+};
+// ndir, the loss (a distance loss with an ℓ routine, never Periodic) and the tile's
+// LDS offsets (16-bit immediates) are ones the code generator serves
+bool deriv_spec_fits(const DerivSpec& sp);
+struct DerivModule;
+// Trees of `cand` that compile go to jit_list (slot order), the others to rest; null: none.
+DerivModule* build_deriv(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
+                         const std::vector<int32_t>& cand, const DerivSpec& sp, std::vector<int32_t>& jit_list,
+                         std::vector<int32_t>& rest, GradStats* st);
+void destroy_deriv(DerivModule* m);
+int deriv_nslots(const DerivModule* m);
+int deriv_nparts(const DerivModule* m);
+void deriv_part(const DerivModule* m, int k, int* slot0, int* nslots);
+int deriv_narr(const DerivSpec& sp);  // arrays of the row tile
+// Part `part` over its slots. a: rows, tiles and groups of the plan; a.y / a.w the
+// 1 + ndir columns n_pad apart; a.fail the part's flags. part_out [nrg][nslots]
+// {Σ w·ℓ, marker} and dpart [nrg][nslots][ndir] are the part's own.
+hipError_t launch_deriv_code(DerivModule* m, int part, const EvalPlan& plan, const EvalArgs<float>& a,
+                             const float* consts, Part<float>* part_out, float* dpart, hipStream_t stream);
+// Σ over row groups in fp64 in a fixed order into out_sum [ntrees][1 + ndir] and out_ok
+// for the part's trees; a failed or skipped tree's row is NaN
+hipError_t launch_deriv_finalize(DerivModule* m, int part, int nrg, const uint32_t* fail, const Part<float>* part_out,
+                                 const float* dpart, double* out_sum, uint8_t* out_ok, hipStream_t stream);
+bool compile_deriv_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
+                        const std::vector<int32_t>& cand, const DerivSpec& sp, std::vector<uint8_t>* bytes,
+                        std::string* text, std::vector<int32_t>* offsets, GradStats* st);
+
 // ---- Float64 tree code (jit64.cpp) ---------------------------------------------------
 // The shallow trees of a Float64 program as straight-line code with the
 // Float64 interpreter's operator routines (no FAST path), L2 loss; 2 rows per

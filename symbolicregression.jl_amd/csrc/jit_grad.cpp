@@ -239,7 +239,7 @@ struct GradGen {
   uint64_t lparam = 0;     // bits of the loss's Float64 parameter
   std::string why;
   int n = 0;
-  std::vector<uint8_t> hasc;      // value's subtree holds a constant: it needs an adjoint
+  std::vector<uint8_t> hasc;      // value's subtree holds a constant (dv: a direction feature): it needs an adjoint
   std::vector<int> last;          // last step (forward i, loss n, reverse 2n-i) that reads the value
   std::vector<int> loc;           // pool block of each value, -1 none, LOC_VA: in the routine registers VA
   // sin / cos whose operand needs an adjoint: the forward call (u_sin_pd / u_cos_pd) also leaves
@@ -274,12 +274,27 @@ struct GradGen {
   int gidx[256];
   int gnum = 0, gdone = 0;
   bool is_g(int f) const { return f >= gbase; }
+  // derivative objectives: the adjoint targets are the feature leaves
+  // of dv->dir, not the constants; seed 1; direction k's per-row adjoint is summed over the
+  // feature's occurrences in the block v[GACC + 4k ..] (the constants' accumulators of
+  // the gradient mode, unused here), then scored against Y[1 + k]; the lane's channel
+  // sums 1..ndir live in the pool's last block, which the pool never hands out
+  const DerivSpec* dv = nullptr;
+  static constexpr int DACC = GPOOL0 + R * (GNPOOL - 1);
+  static constexpr int RESERVED = 4000;  // owner[] of that block
+  int dirk(int f) const {
+    for (int k = 0; dv && k < dv->ndir; ++k)
+      if (dv->dir[k] == f) return k;
+    return -1;
+  }
+  static int dblk(int k) { return GACC + R * k; }
+  bool target(const GOpnd& q) const { return dv ? (q.k == G_X && dirk(q.v) >= 0) : q.k == G_C; }
 
   GradGen(Asm& a, const Tmpl& t, uint64_t va) : as(a), T(t), base_va(va) {}
   uint64_t cur_va() const { return base_va + as.bytes(); }
   static int blk_reg(int k) { return GPOOL0 + R * k; }
   int bstep(int i) const { return 2 * n - i; }  // reverse steps n+1 .. 2n (n: the loss)
-  bool needs_adj(const GOpnd& q) const { return q.k == G_C || (q.k == G_VAL && hasc[q.v]); }
+  bool needs_adj(const GOpnd& q) const { return target(q) || (q.k == G_VAL && hasc[q.v]); }
 
   bool analyze() {
     n = (int)ops.size();
@@ -290,8 +305,8 @@ struct GradGen {
     adj.assign(n, Adj());
     for (int i = 0; i < n; ++i) {
       GOp& o = ops[i];
-      auto hc = [&](const GOpnd& q) { return q.k == G_C || (q.k == G_VAL && hasc[q.v]); };
-      hasc[i] = o.kind == K_MAT || hc(o.a) || (o.kind == K_BIN && hc(o.b));
+      auto hc = [&](const GOpnd& q) { return needs_adj(q); };
+      hasc[i] = (o.kind == K_MAT && !dv) || hc(o.a) || (o.kind == K_BIN && hc(o.b));
       if (o.a.k == G_C && o.kind != K_MAT && o.a.ci >= nc) { why = "constant index out of range"; return false; }
       if (o.kind == K_BIN && o.b.k == G_C && o.b.ci >= nc) { why = "constant index out of range"; return false; }
       if (!g_inline(o)) {
@@ -362,7 +377,7 @@ struct GradGen {
       }
       if (xlast[f] >= 0 && (1 + f) * TILE * 4 + 3 * 4 * 64 > 65535) { why = "feature offset beyond the DS immediate"; return false; }
     }
-    if ((int)feats.size() > GNPOOL) { why = "more features than register blocks"; return false; }
+    if ((int)feats.size() > GNPOOL - (dv ? 1 : 0)) { why = "more features than register blocks"; return false; }
     return true;
   }
 
@@ -514,6 +529,14 @@ struct GradGen {
     else as.vop2(VOP2_ADD_F32, "v_add_f32_e32", GACC + ci, V(GACC + ci), TS);
   }
 
+  // direction k's block ±= blk (one occurrence of the feature)
+  void dir_add(int k, int reg, bool neg) {
+    for (int e = 0; e < R; ++e) {
+      if (neg) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", dblk(k) + e, V(dblk(k) + e), reg + e);
+      else as.vop2(VOP2_ADD_F32, "v_add_f32_e32", dblk(k) + e, V(dblk(k) + e), reg + e);
+    }
+  }
+
   // ---- forward
   bool emit_mat(int i) {
     const GOp& o = ops[i];
@@ -646,6 +669,7 @@ struct GradGen {
     // adjoint of operand q = (products already in block `reg`) with sign `neg`
     auto give = [&](const GOpnd& q, int reg, bool neg, int blk) {
       if (q.k == G_C) { acc_add(q.ci, reg, neg); return; }
+      if (q.k == G_X) { dir_add(dirk(q.v), reg, neg); return; }
       Adj a;
       a.reg = reg;
       a.blk = blk;
@@ -661,6 +685,12 @@ struct GradGen {
       *blk = k;
       return blk_reg(k);
     };
+    // a unary operator's operand in the reverse pass (a direction feature: re-read)
+    auto opreg = [&](const GOpnd& q) {
+      if (q.k != G_X) return blk_reg(loc[q.v]);
+      read_feat(XS0, q.v);
+      return (int)XS0;
+    };
     if (o.kind == K_MAT) {
       acc_add(o.a.ci, g.reg, g.neg);
     } else if (o.kind == K_BIN) {
@@ -670,11 +700,13 @@ struct GradGen {
         case SRHIP_BOP_SUB:
           if (aa) {
             if (o.a.k == G_C) acc_add(o.a.ci, g.reg, g.neg);
+            else if (o.a.k == G_X) dir_add(dirk(o.a.v), g.reg, g.neg);
             else share_adj(o.a.v, g, false);
           }
           if (ab) {
             const bool fl = o.op == SRHIP_BOP_SUB;
             if (o.b.k == G_C) acc_add(o.b.ci, g.reg, g.neg != fl);
+            else if (o.b.k == G_X) dir_add(dirk(o.b.v), g.reg, g.neg != fl);
             else share_adj(o.b.v, g, fl);
           }
           break;
@@ -773,7 +805,8 @@ struct GradGen {
       int blk;
       switch (o.op) {
         case SRHIP_UOP_NEG:
-          share_adj(o.a.v, g, true);
+          if (o.a.k == G_X) dir_add(dirk(o.a.v), g.reg, !g.neg);
+          else share_adj(o.a.v, g, true);
           break;
         case SRHIP_UOP_EXP: {
           const int d = dest(o.a, TP, &blk);
@@ -787,7 +820,7 @@ struct GradGen {
         case SRHIP_UOP_CUBE: {
           const int d = dest(o.a, TP, &blk);
           if (d < 0) return false;
-          const int ar = blk_reg(loc[o.a.v]);
+          const int ar = opreg(o.a);
           for (int e = 0; e < R; ++e) {
             if (o.op == SRHIP_UOP_SQUARE) {
               as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", d + e, K(0x40000000u), ar + e);  // 2x
@@ -803,7 +836,7 @@ struct GradGen {
         case SRHIP_UOP_LOG: {  // g / a (v_rcp_f32, as DIV's 1/b)
           const int d = dest(o.a, TP, &blk);
           if (d < 0) return false;
-          const int ar = blk_reg(loc[o.a.v]);
+          const int ar = opreg(o.a);
           // the four reciprocals first: a VALU read of a transcendental's
           // result right after it needs a wait state on gfx950 (as DIV)
           for (int e = 0; e < R; ++e) as.vop1(VOP1_RCP_F32, "v_rcp_f32_e32", d + e, V(ar + e));
@@ -826,7 +859,7 @@ struct GradGen {
         case SRHIP_UOP_ABS: {  // sign(a) (0 at 0) times g
           const int d = dest(o.a, TP, &blk);
           if (d < 0) return false;
-          const int ar = blk_reg(loc[o.a.v]);
+          const int ar = opreg(o.a);
           for (int e = 0; e < R; ++e) {
             as.vop2(VOP2_AND_B32, "v_and_b32_e32", d + e, K(0x80000000u), ar + e);
             as.vop2(VOP2_XOR_B32, "v_xor_b32_e32", d + e, gv(e), d + e);
@@ -849,7 +882,8 @@ struct GradGen {
             give(o.a, d, g.neg != !is_sin, blk);
             break;
           }
-          mov4(VA, blk_reg(loc[o.a.v]));
+          if (o.a.k == G_X) read_feat(VA, o.a.v);
+          else mov4(VA, blk_reg(loc[o.a.v]));
           routine(kUopRoutine[is_sin ? SRHIP_UOP_COS : SRHIP_UOP_SIN], false);
           const int d = dest(o.a, TP, &blk);
           if (d < 0) return false;
@@ -882,6 +916,9 @@ struct GradGen {
   bool emit_tree() {
     if (!analyze()) return false;
     for (int k = 0; k < GNPOOL; ++k) { owner[k] = -1; refs[k] = 0; }
+    if (dv) owner[GNPOOL - 1] = RESERVED;
+    // the accumulators the epilogue sums: one per constant, or (dv) one per direction
+    const int na = dv ? dv->ndir : nc, a0 = dv ? DACC : GACC;
     L_tile = as.label();
     L_done = as.label();
     // ---- prologue
@@ -902,7 +939,7 @@ struct GradGen {
     for (const GOp& o : ops)
       if (o.kind == K_UN && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS)) trig = true;
     if (has_call || trig || loss != SRHIP_LOSS_L2) set_base();
-    for (int j = 0; j < nc; ++j) as.vop1(VOP1_MOV, "v_mov_b32_e32", GACC + j, K(0));
+    for (int j = 0; j < na; ++j) as.vop1(VOP1_MOV, "v_mov_b32_e32", a0 + j, K(0));
     if (nc > 0) as.waitcnt_lgkm(0);
     as.sopc(SOPC_GE_U32, "s_cmp_ge_u32", S(S_TILE), S(S_NT));
     as.branch(SOPP_SCC1, "s_cbranch_scc1", L_done);
@@ -951,10 +988,18 @@ struct GradGen {
     for (int e = 0; e < R; ++e) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", VY + e, V(rreg + e), VY + e);
     free_values_at(n);
     free_feats_at(n);
-    emit_mask(VY);
-    if (loss != SRHIP_LOSS_L2) {
+    if (dv) {
+      emit_channel(VY, dv->weighted ? (1 + dv->nfeat + dv->ndir) * TILE * 4 : -1, VLSUM);
+      for (int e = 0; e < R * dv->ndir; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", GACC + e, K(0));
+      if (root.k == G_X && dirk(root.v) >= 0)  // ŷ = x_d: ∂ŷ/∂x_d = 1
+        for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", dblk(dirk(root.v)) + e, K(0x3f800000u));
+      if (root.k == G_VAL && hasc[root.v])  // the seed: 1
+        for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", VY + e, K(0x3f800000u));
+    } else if (loss != SRHIP_LOSS_L2) {
+      emit_mask(VY);
       if (!emit_loss_seed()) return false;
     } else {
+      emit_mask(VY);
       const int L_unw = as.label(), L_seed = as.label();
       as.sopc(SOPC_EQ_U32, "s_cmp_eq_u32", S(S_WOFF), K(0));
       as.branch(SOPP_SCC1, "s_cbranch_scc1", L_unw);
@@ -978,7 +1023,7 @@ struct GradGen {
       for (int e = 0; e < R; ++e) as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VY + e, V(VY + e), VY + e);
     }
     // ---- reverse pass
-    if (root.k == G_C) acc_add(root.ci, VY, false);
+    if (root.k == G_C && !dv) acc_add(root.ci, VY, false);
     else if (root.k == G_VAL && hasc[root.v]) {
       Adj s;
       s.reg = VY;
@@ -991,7 +1036,14 @@ struct GradGen {
       free_feats_at(bstep(i));
     }
     for (int k = 0; k < GNPOOL; ++k)
-      if (owner[k] != -1) { why = "internal: block live after the reverse pass"; return false; }
+      if (owner[k] != -1 && owner[k] != RESERVED) { why = "internal: block live after the reverse pass"; return false; }
+    // ---- (dv) channel 1 + k: ℓ(∂ŷ/∂x_dir[k] - Y[1 + k]), weighted by W[1 + k], into its accumulator
+    for (int k = 0; dv && k < dv->ndir; ++k) {
+      as.ds_read_b128(XS0, VLANE, (1 + dv->nfeat + k) * TILE * 4);
+      as.waitcnt_lgkm(0);
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", dblk(k) + e, V(dblk(k) + e), XS0 + e);
+      emit_channel(dblk(k), dv->weighted ? (2 + dv->nfeat + dv->ndir + k) * TILE * 4 : -1, DACC + k);
+    }
     // ---- next tile
     as.vop2(VOP2_ADD_U32, "v_add_u32_e32", VLANE, S(S_TILEBYTES), VLANE);
     as.sop2(SOP2_ADD_U32, "s_add_u32", S_TILE, S(S_TILE), K(1));
@@ -1001,7 +1053,7 @@ struct GradGen {
     // interp.h wave_sum: lane 63 holds the sum) and stored to this row
     // group's partial of its constant; return
     as.bind(L_done);
-    if (nc > 0) {
+    if (na > 0) {
       as.vop1(VOP1_MOV, "v_mov_b32_e32", TS + 1, K(0));
       // a DPP source must not be written by the 2 VALU instructions before:
       // the six steps run interleaved over the constants, padded with s_nop
@@ -1011,9 +1063,9 @@ struct GradGen {
           {0x142, 0xa, "row_bcast:15 row_mask:0xa"},        {0x143, 0xc, "row_bcast:31 row_mask:0xc"}};
       as.sopp(0x00, "s_nop", 1);
       for (const auto& st : steps) {
-        if (nc < 3) as.sopp(0x00, "s_nop", 2 - nc);
-        for (int j = 0; j < nc; ++j) {
-          const int a = GACC + j;
+        if (na < 3) as.sopp(0x00, "s_nop", 2 - na);
+        for (int j = 0; j < na; ++j) {
+          const int a = a0 + j;
           as.put(((uint32_t)VOP2_ADD_F32 << 25) | ((uint32_t)a << 17) | ((uint32_t)a << 9) | 0xfau);
           as.put((uint32_t)a | (st.ctrl << 8) | (0xfu << 24) | (st.row << 28));
           if (as.want_text)
@@ -1023,18 +1075,18 @@ struct GradGen {
       }
       as.sopp(0x00, "s_nop", 1);
     }
-    if (nc > 0) {
+    if (na > 0) {
       // lane 63 of each accumulator holds its sum: v_readlane_b32 s_j, v_acc_j, 63 (s0..s15: routine
       // temporaries, free here), then lane j of TS takes constant j's sum and ONE store of lanes
       // 0..nc-1 writes the tree's nc contiguous partials (one write request per tree and row group,
       // where a store per constant cost a request each: the round-5 PMC summary's 0.49 GB per dispatch)
-      for (int j = 0; j < nc; ++j) {
+      for (int j = 0; j < na; ++j) {
         as.put(0xd2890000u | (uint32_t)j);
-        as.put((uint32_t)(256 + GACC + j) | (191u << 9));
-        if (as.want_text) as.lines.push_back("v_readlane_b32 s" + std::to_string(j) + ", v" + std::to_string(GACC + j) + ", 63");
+        as.put((uint32_t)(256 + a0 + j) | (191u << 9));
+        if (as.want_text) as.lines.push_back("v_readlane_b32 s" + std::to_string(j) + ", v" + std::to_string(a0 + j) + ", 63");
       }
       as.sopp(0x00, "s_nop", 4);
-      for (int j = 0; j < nc; ++j) {  // v_writelane_b32 v[TS], s_j, j
+      for (int j = 0; j < na; ++j) {  // v_writelane_b32 v[TS], s_j, j
         as.put(0xd28a0000u | (uint32_t)TS);
         as.put((uint32_t)j | ((128u + (uint32_t)j) << 9));
         if (as.want_text)
@@ -1042,7 +1094,7 @@ struct GradGen {
       }
       as.put(0xbe80017eu | (16u << 16));  // s_mov_b64 s[16:17], exec
       if (as.want_text) as.lines.push_back("s_mov_b64 s[16:17], exec");
-      const uint32_t mask = (uint32_t)((1ull << nc) - 1);  // s_mov_b64 exec, mask (inline constant up to 64)
+      const uint32_t mask = (uint32_t)((1ull << na) - 1);  // s_mov_b64 exec, mask (inline constant up to 64)
       if (mask <= 64) {
         as.put(0xbefe0100u | (128u + mask));
       } else {
@@ -1062,6 +1114,46 @@ struct GradGen {
     as.sop1(SOP1_SETPC, "s_setpc_b64", 0, S(S_RT), "");
     if (as.want_text) as.lines.back() = "s_setpc_b64 s[" + std::to_string(S_RT) + ":" + std::to_string(S_RT + 1) + "]";
     return true;
+  }
+  // (dv) One channel of a derivative objective: Σ w·ℓ(r) over the lane's 4 rows added into
+  // `acc`, r the residual block `rb` (clobbered), w the tile column at LDS offset `woff`
+  // (< 0: unweighted). Rows past the last are set to 0 by a select (emit_mask), so a
+  // NaN in a padding row never reaches the sum. L2 inline with the arithmetic of the
+  // gradient mode's loss step; the other losses by their ℓ routine (no ℓ' here).
+  void emit_channel(int rb, int woff, int acc) {
+    if (loss == SRHIP_LOSS_L2) {
+      emit_mask(rb);
+      if (woff < 0) {
+        for (int e = 0; e < R; ++e) {
+          const Src r = V(rb + e), l = V(acc);
+          as.vop3(VOP3_FMA_F32, "v_fma_f32", acc, r, r, &l, 0, 0);
+        }
+        return;
+      }
+      as.ds_read_b128(XS1, VLANE, woff);
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", TP + e, V(rb + e), rb + e);
+      as.waitcnt_lgkm(0);
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", TP + e, V(XS1 + e), TP + e);
+      as.vop2(VOP2_ADD_F32, "v_add_f32_e32", TP, V(TP), TP + 2);
+      as.vop2(VOP2_ADD_F32, "v_add_f32_e32", TP + 1, V(TP + 1), TP + 3);
+      as.vop2(VOP2_ADD_F32, "v_add_f32_e32", TP, V(TP), TP + 1);
+      as.vop2(VOP2_ADD_F32, "v_add_f32_e32", acc, V(acc), TP);
+      return;
+    }
+    mov4(VA, rb);
+    as.sop1(SOP1_MOV, "s_mov_b32", S_K, K((uint32_t)lparam), "s" + std::to_string(S_K));
+    as.sop1(SOP1_MOV, "s_mov_b32", S_KH, K((uint32_t)(lparam >> 32)), "s" + std::to_string(S_KH));
+    routine(kGradLossRoutine[loss], true);
+    if (woff >= 0) {
+      as.ds_read_b128(XS1, VLANE, woff);
+      as.waitcnt_lgkm(0);
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", VA + e, V(XS1 + e), VA + e);
+    }
+    emit_mask(VA);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VA, V(VA), VA + 2);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VA + 1, V(VA + 1), VA + 3);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VA, V(VA), VA + 1);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", acc, V(acc), VA);
   }
   // Σ w·ℓ(r) into the lane's loss sum and the seed w·ℓ'(r) into VY (r in VY,
   // 0 past the last row), ℓ and ℓ' by the PRECISE-region loss routines of
@@ -1114,9 +1206,9 @@ using ColIndex = std::unordered_map<std::string, int>;
 // code with its columns does not fit (register pool) is compiled without them.
 bool gen_grad_tree(const Ins<float>* prog, int nc, const Tmpl& T, bool text, std::vector<uint32_t>& out,
                    std::vector<std::string>* lines, int32_t* off, std::string* why, int loss, uint64_t lparam,
-                   const ColIndex* gidx) {
+                   const ColIndex* gidx, const DerivSpec* dv = nullptr) {
   if (nc > NGACC) { *why = "more constants than accumulators"; return false; }
-  if (!has_dloss_routine(loss)) { *why = "loss without gradient routines"; return false; }
+  if (dv ? !deriv_spec_fits(*dv) : !has_dloss_routine(loss)) { *why = "loss without gradient routines"; return false; }
   std::vector<GOp> ir;
   GOpnd root;
   if (!build_gir(prog, ir, root, why)) return false;
@@ -1136,6 +1228,7 @@ bool gen_grad_tree(const Ins<float>* prog, int nc, const Tmpl& T, bool text, std
     g.root = sub ? roots : root;
     g.fuse_trig = (attempt & 1) == 0;
     if (sub) g.gbase = kGradGbase;
+    g.dv = dv;
     g.nc = nc;
     g.loss = loss;
     g.lparam = lparam;
@@ -1164,7 +1257,7 @@ size_t grad_codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>& 
                     const std::vector<int32_t>& cand, size_t from, bool text, std::vector<uint32_t>& words,
                     std::vector<std::string>* lines, std::vector<int32_t>& offs, std::vector<int32_t>& ok_trees,
                     std::vector<int32_t>& rest, GradStats* st, const Tmpl& T, int loss, uint64_t lparam,
-                    const ColIndex* gidx) {
+                    const ColIndex* gidx, const DerivSpec* dv = nullptr) {
   for (size_t k = from; k < cand.size(); ++k) {
     const int32_t t = cand[k];
     int32_t off = -1;
@@ -1173,7 +1266,7 @@ size_t grad_codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>& 
     const size_t lbefore = lines ? lines->size() : 0;
     const int nc = const_off[t + 1] - const_off[t];
     const bool okc = cb.tree_off[t] >= 0 && gen_grad_tree(&cb.code[cb.tree_off[t]], nc, T, text, words, lines, &off, &why,
-                                                                  loss, lparam, gidx);
+                                                                  loss, lparam, gidx, dv);
     if (okc && words.size() * 4 > T.area_bytes) {  // area full: the next part takes it
       words.resize(before);
       if (lines) lines->resize(lbefore);
@@ -1243,17 +1336,15 @@ void load_part(GradPart& pt, const Tmpl& T, const std::vector<uint32_t>& words, 
 }
 }  // namespace
 
-GradModule* build_grad(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
-                       const std::vector<int32_t>& cand, std::vector<int32_t>& jit_list, std::vector<int32_t>& rest,
-                       GradStats* st, int loss, uint64_t lparam) {
+namespace {
+// The code of `cand` cut into code areas (one code object and launch each, at most
+// kMaxGradParts; what is left over stays interpreted: `rest`), each laid out for the
+// small template when it fits.
+struct Chunk { std::vector<uint32_t> words; std::vector<int32_t> offs, slots; const Tmpl* T; };
+std::vector<Chunk> build_chunks(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
+                                const std::vector<int32_t>& cand, std::vector<int32_t>& rest, GradStats* st, int loss,
+                                uint64_t lparam, const ColIndex* gi, const DerivSpec* dv, size_t* total_bytes) {
   const Templates& TT = templates();
-  if (!TT.ok) { rest = cand; return nullptr; }
-  auto t0 = std::chrono::steady_clock::now();
-  Columns cols = plan_grad_columns(cb, cand);
-  ColIndex gidx;
-  for (int g = 0; g < cols.ngcol; ++g) gidx.emplace(cols.gkey[g], g);
-  const ColIndex* gi = gidx.empty() ? nullptr : &gidx;
-  struct Chunk { std::vector<uint32_t> words; std::vector<int32_t> offs, slots; const Tmpl* T; };
   std::vector<Chunk> chunks;
   size_t pos = 0;
   size_t bytes = 0;
@@ -1261,7 +1352,7 @@ GradModule* build_grad(const CompiledBatch<float>& cb, const std::vector<int32_t
     Chunk ch;
     ch.T = &TT.large;
     const size_t next = grad_codegen(cb, const_off, cand, pos, false, ch.words, nullptr, ch.offs, ch.slots, rest, st,
-                                     TT.large, loss, lparam, gi);
+                                     TT.large, loss, lparam, gi, dv);
     if (next == pos) { rest.push_back(cand[pos]); if (st) st->nrejected++; pos = next + 1; continue; }  // one tree > area
     if ((int)chunks.size() + 1 == kMaxGradParts && next < cand.size()) {  // the rest stays interpreted
       for (size_t k = next; k < cand.size(); ++k) rest.push_back(cand[k]);
@@ -1276,13 +1367,30 @@ GradModule* build_grad(const CompiledBatch<float>& cb, const std::vector<int32_t
       sm.T = &TT.small;
       std::vector<int32_t> rs;
       grad_codegen(cb, const_off, ch.slots, 0, false, sm.words, nullptr, sm.offs, sm.slots, rs, nullptr, TT.small, loss,
-                   lparam, gi);
+                   lparam, gi, dv);
       if (sm.slots != ch.slots) throw Error(SRHIP_ERR_INVALID, "jit-grad: small-template relayout differs");
       ch = std::move(sm);
     }
     bytes += ch.words.size() * 4;
     chunks.push_back(std::move(ch));
   }
+  *total_bytes = bytes;
+  return chunks;
+}
+}  // namespace
+
+GradModule* build_grad(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
+                       const std::vector<int32_t>& cand, std::vector<int32_t>& jit_list, std::vector<int32_t>& rest,
+                       GradStats* st, int loss, uint64_t lparam) {
+  const Templates& TT = templates();
+  if (!TT.ok) { rest = cand; return nullptr; }
+  auto t0 = std::chrono::steady_clock::now();
+  Columns cols = plan_grad_columns(cb, cand);
+  ColIndex gidx;
+  for (int g = 0; g < cols.ngcol; ++g) gidx.emplace(cols.gkey[g], g);
+  const ColIndex* gi = gidx.empty() ? nullptr : &gidx;
+  size_t bytes = 0;
+  std::vector<Chunk> chunks = build_chunks(cb, const_off, cand, rest, st, loss, lparam, gi, nullptr, &bytes);
   if (chunks.empty()) return nullptr;
   auto t1 = std::chrono::steady_clock::now();
   GradModule* m = new GradModule();
@@ -1397,6 +1505,180 @@ bool compile_grad_only(const CompiledBatch<float>& cb, const std::vector<int32_t
   for (int g = 0; g < cols.ngcol; ++g) gidx.emplace(cols.gkey[g], g);
   grad_codegen(cb, const_off, cand, 0, text != nullptr, words, text ? &lines : nullptr, offs, okt, rest, st, TT.large, loss,
                lparam, gidx.empty() ? nullptr : &gidx);
+  if (bytes) {
+    bytes->resize(words.size() * 4);
+    std::memcpy(bytes->data(), words.data(), bytes->size());
+  }
+  if (text) {
+    text->clear();
+    for (auto& l : lines) { *text += l; *text += '\n'; }
+  }
+  if (offsets) {
+    offsets->clear();
+    for (size_t k = 0; k < okt.size(); ++k) {
+      offsets->push_back(okt[k]);
+      offsets->push_back(offs[k]);
+    }
+  }
+  return !okt.empty();
+}
+
+// ---- derivative-objective tree code (jit.h DerivSpec) ---------------
+int deriv_narr(const DerivSpec& sp) { return 1 + sp.nfeat + sp.ndir + (sp.weighted ? 1 + sp.ndir : 0); }
+
+bool deriv_spec_fits(const DerivSpec& sp) {
+  if (sp.ndir < 1 || sp.ndir > kDerivMaxDir || sp.nfeat < 1) return false;
+  if (sp.loss != SRHIP_LOSS_L2 && (sp.loss < 0 || sp.loss >= SRHIP_MARGIN_LOSS_BEGIN || sp.loss == SRHIP_LOSS_PERIODIC ||
+                                   kGradLossRoutine[sp.loss] < 0))
+    return false;
+  // every array of a tile is read by ds_read_b128 at a 16-bit literal offset from the lane's address
+  return (size_t)(deriv_narr(sp) - 1) * TILE * 4 <= 65535;
+}
+
+struct DerivPart {
+  hipModule_t mod = nullptr;
+  hipFunction_t fn = nullptr, fn_fin = nullptr;
+  int32_t* d_off = nullptr;    // [nslots] code offsets
+  int32_t* d_cbase = nullptr;  // [nslots] first constant of the slot's tree
+  int32_t* d_tree = nullptr;   // [nslots] the slot's tree
+  int slot0 = 0, nslots = 0;
+};
+struct DerivModule {
+  std::vector<DerivPart> parts;
+  int nslots = 0;
+  DerivSpec sp;
+};
+
+DerivModule* build_deriv(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
+                         const std::vector<int32_t>& cand, const DerivSpec& sp, std::vector<int32_t>& jit_list,
+                         std::vector<int32_t>& rest, GradStats* st) {
+  const Templates& TT = templates();
+  if (!TT.ok || !deriv_spec_fits(sp)) { rest = cand; return nullptr; }
+  auto t0 = std::chrono::steady_clock::now();
+  size_t bytes = 0;
+  std::vector<Chunk> chunks = build_chunks(cb, const_off, cand, rest, st, sp.loss, sp.lparam, nullptr, &sp, &bytes);
+  if (chunks.empty()) return nullptr;
+  auto t1 = std::chrono::steady_clock::now();
+  DerivModule* m = new DerivModule();
+  m->sp = sp;
+  try {
+    for (Chunk& ch : chunks) {
+      m->parts.emplace_back();
+      DerivPart& pt = m->parts.back();
+      pt.slot0 = m->nslots;
+      pt.nslots = (int)ch.slots.size();
+      std::vector<uint8_t> img(ch.T->img, ch.T->img + ch.T->size);
+      std::memcpy(img.data() + ch.T->area_off, ch.words.data(), ch.words.size() * 4);
+      std::vector<int32_t> cbase(ch.slots.size());
+      for (size_t k = 0; k < ch.slots.size(); ++k) cbase[k] = const_off[ch.slots[k]];
+      HIP_CHECK(hipModuleLoadData(&pt.mod, img.data()));
+      HIP_CHECK(hipModuleGetFunction(&pt.fn, pt.mod, sp.weighted ? "sr_jit_deriv_w" : "sr_jit_deriv"));
+      HIP_CHECK(hipModuleGetFunction(&pt.fn_fin, pt.mod, "sr_jit_deriv_fin"));
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pt.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    160 * 1024));
+      const std::pair<int32_t**, const std::vector<int32_t>*> arrays[] = {
+          {&pt.d_off, &ch.offs}, {&pt.d_cbase, &cbase}, {&pt.d_tree, &ch.slots}};
+      for (const auto& q : arrays) {
+        HIP_CHECK(hipMalloc((void**)q.first, q.second->size() * sizeof(int32_t)));
+        HIP_CHECK(hipMemcpy(*q.first, q.second->data(), q.second->size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      }
+      m->nslots += pt.nslots;
+      jit_list.insert(jit_list.end(), ch.slots.begin(), ch.slots.end());
+    }
+  } catch (...) {
+    destroy_deriv(m);
+    throw;
+  }
+  if (st) {
+    st->ms_codegen = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    st->ms_load = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    st->code_bytes = bytes;
+    st->nparts = (int)chunks.size();
+  }
+  return m;
+}
+
+void destroy_deriv(DerivModule* m) {
+  if (!m) return;
+  for (DerivPart& pt : m->parts) {
+    for (void* q : {(void*)pt.d_off, (void*)pt.d_cbase, (void*)pt.d_tree})
+      if (q) (void)hipFree(q);
+    if (pt.mod) (void)hipModuleUnload(pt.mod);
+  }
+  delete m;
+}
+
+int deriv_nslots(const DerivModule* m) { return m ? m->nslots : 0; }
+int deriv_nparts(const DerivModule* m) { return m ? (int)m->parts.size() : 0; }
+void deriv_part(const DerivModule* m, int k, int* slot0, int* nslots) {
+  *slot0 = m->parts[k].slot0;
+  *nslots = m->parts[k].nslots;
+}
+
+struct JitDerivArgs {  // jit_template.hip
+  EvalArgs<float> e;
+  const int32_t* code_off;
+  const float* consts;
+  const int32_t* cbase;
+  Part<float>* part;
+  float* dpart;
+  int ndir;
+};
+struct JitDerivFinArgs {
+  const int32_t* tree;
+  const uint32_t* fail;
+  const Part<float>* part;
+  const float* dpart;
+  double* out_sum;
+  uint8_t* out_ok;
+  int nslots, nrg, ndir;
+};
+
+hipError_t launch_deriv_code(DerivModule* m, int part, const EvalPlan& plan, const EvalArgs<float>& a,
+                             const float* consts, Part<float>* part_out, float* dpart, hipStream_t stream) {
+  if (plan.threads != 256 || plan.tile != TILE) return hipErrorInvalidValue;
+  const DerivPart& pt = m->parts[part];
+  if (a.nlist != pt.nslots || a.nfeat != m->sp.nfeat || (a.w != nullptr) != m->sp.weighted || !a.fail)
+    return hipErrorInvalidValue;
+  const size_t lds = (size_t)deriv_narr(m->sp) * (size_t)plan.ntiles * (size_t)plan.tile * sizeof(float);
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  JitDerivArgs ja;
+  ja.e = a;
+  ja.e.list = pt.d_tree;
+  ja.e.rotate = 0;
+  ja.code_off = pt.d_off;
+  ja.consts = consts;
+  ja.cbase = pt.d_cbase;
+  ja.part = part_out;
+  ja.dpart = dpart;
+  ja.ndir = m->sp.ndir;
+  size_t sz = sizeof(ja);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ja, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  note_kernel(m->sp.weighted ? "sr_jit_deriv_w" : "sr_jit_deriv");
+  return hipModuleLaunchKernel(pt.fn, (unsigned)a.nrg * (unsigned)a.ntg, 1, 1, (unsigned)plan.threads, 1, 1,
+                               (unsigned)lds, stream, nullptr, cfg);
+}
+
+hipError_t launch_deriv_finalize(DerivModule* m, int part, int nrg, const uint32_t* fail, const Part<float>* part_out,
+                                 const float* dpart, double* out_sum, uint8_t* out_ok, hipStream_t stream) {
+  const DerivPart& pt = m->parts[part];
+  JitDerivFinArgs fa{pt.d_tree, fail, part_out, dpart, out_sum, out_ok, pt.nslots, nrg, m->sp.ndir};
+  size_t sz = sizeof(fa);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &fa, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  return hipModuleLaunchKernel(pt.fn_fin, (unsigned)((pt.nslots + 63) / 64), 1, 1, 256, 1, 1, 0, stream, nullptr, cfg);
+}
+
+bool compile_deriv_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
+                        const std::vector<int32_t>& cand, const DerivSpec& sp, std::vector<uint8_t>* bytes,
+                        std::string* text, std::vector<int32_t>* offsets, GradStats* st) {
+  const Templates& TT = templates();
+  if (!TT.ok) throw Error(SRHIP_ERR_UNSUPPORTED, std::string("jit templates unavailable: ") + TT.why);
+  if (!deriv_spec_fits(sp)) throw Error(SRHIP_ERR_UNSUPPORTED, "derivative tree code: directions, loss or features outside its limits");
+  std::vector<uint32_t> words;
+  std::vector<std::string> lines;
+  std::vector<int32_t> offs, okt, rest;
+  grad_codegen(cb, const_off, cand, 0, text != nullptr, words, text ? &lines : nullptr, offs, okt, rest, st, TT.large,
+               sp.loss, sp.lparam, nullptr, &sp);
   if (bytes) {
     bytes->resize(words.size() * 4);
     std::memcpy(bytes->data(), words.data(), bytes->size());

@@ -1110,3 +1110,157 @@ __device__ __forceinline__ void jit_grad_dl_body(const JitGradArgs& ja) {
 }
 extern "C" __global__ void __launch_bounds__(256) sr_jit_grad_dl(JitGradArgs ja) { jit_grad_dl_body<false>(ja); }
 extern "C" __global__ void __launch_bounds__(256) sr_jit_grad_dlw(JitGradArgs ja) { jit_grad_dl_body<true>(ja); }
+
+// ---- derivative-objective tree code (jit_grad.cpp GradGen::dv) -----
+// The gradient driver's shape: one workgroup = (row group, tree group), trees dealt to
+// waves round-robin. The row tile holds y, the features, Y[1..ndir] and, when weighted,
+// W[0..ndir] (a.y / a.w: 1 + ndir columns, n_pad apart), at the offsets the code holds
+// as literals. A tree's code leaves Σ w₀·ℓ(ŷ − y) in LSUM and the marker in CHK, and
+// itself stores its ndir channel sums (summed over the wave) to this row group's
+// partials of its slot. Partials are per (row group, slot): the finalize kernel below
+// needs no work-group geometry.
+struct JitDerivArgs {
+  EvalArgs<float> e;        // rows, tiles, groups; list: the slots' trees; fail: their flags
+  const int32_t* code_off;  // [nlist] byte offset of each slot's code
+  const float* consts;      // [total constants + 16] the program's constants
+  const int32_t* cbase;     // [nlist] first constant of the slot's tree
+  Part<float>* part;        // [nrg][nlist] channel 0: {Σ w·ℓ, marker}
+  float* dpart;             // [nrg][nlist][ndir] channels 1..ndir
+  int ndir;
+};
+
+template <bool W>
+__device__ __forceinline__ void jit_deriv_body(const JitDerivArgs& ja) {
+  const EvalArgs<float>& a = ja.e;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* sX = reinterpret_cast<float*>(smem);
+  const int ncol = 1 + ja.ndir;
+  const int narr = 1 + a.nfeat + ja.ndir + (W ? ncol : 0);
+  const int rg = blockIdx.x / a.ntg;
+  const int g = blockIdx.x - rg * a.ntg;
+  const int rows = a.ntiles * TILE;
+  const int64_t row0 = (int64_t)rg * rows;
+  {
+    constexpr int V = TILE / 4;
+    const int total = a.ntiles * narr * V;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+      const int v = idx % V;
+      const int tk = idx / V;
+      const int k = tk % narr;
+      const int t = tk / narr;
+      const float* src = k == 0            ? a.y
+                         : k <= a.nfeat    ? a.X + (size_t)(k - 1) * a.n_pad
+                         : k < a.nfeat + ncol ? a.y + (size_t)(k - a.nfeat) * a.n_pad
+                                           : a.w + (size_t)(k - a.nfeat - ncol) * a.n_pad;
+      reinterpret_cast<float4*>(sX + (size_t)tk * TILE)[v] =
+          reinterpret_cast<const float4*>(src + row0 + (int64_t)t * TILE)[v];
+    }
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int64_t rem = a.n - row0;
+  const int nt_valid = (int)min((int64_t)a.ntiles, (rem + TILE - 1) / TILE);
+  const int last_valid = (int)(rem - (int64_t)(nt_valid - 1) * TILE);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nwaves = (int)(blockDim.x >> 6);
+  auto slot_of = [&](int i) { return i * a.ntg + ((i & 1) ? (a.ntg - 1 - g) : g); };
+  auto sld = [&](const int32_t* p, int s) {
+    return __builtin_amdgcn_readfirstlane(((const __attribute__((address_space(4))) int32_t*)(p))[s]);
+  };
+  auto ld_flag = [&](int slot) { return __hip_atomic_load(a.fail + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  uint64_t area;
+  asm volatile(
+      "s_getpc_b64 s[88:89]\n"
+      "s_add_u32 s88, s88, sr_jit_code@rel32@lo+4\n"
+      "s_addc_u32 s89, s89, sr_jit_code@rel32@hi+12"
+      : "={s[88:89]}"(area)
+      :
+      : "scc");
+  const uint32_t lds_lane = (uint32_t)reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) float*)sX) +
+                            (uint32_t)lane * 16u;
+  const uint32_t tilebytes = (uint32_t)__builtin_amdgcn_readfirstlane(narr * TILE * 4);
+  const uint32_t woff = W ? (uint32_t)__builtin_amdgcn_readfirstlane((a.nfeat + ncol) * TILE * 4) : 0u;  // W[0] (the code holds its own literals)
+  const uint32_t lane4 = (uint32_t)lane * R;
+  const uint32_t partial = (uint32_t)last_valid;
+  const uint32_t nt_u = (uint32_t)nt_valid;
+
+  int m = wave < a.tpb ? (a.tpb - wave + nwaves - 1) / nwaves : 0;
+  while (m > 0 && slot_of(wave + (m - 1) * nwaves) >= a.nlist) --m;
+  m = __builtin_amdgcn_readfirstlane(m);
+  uint32_t fnext = m > 0 ? ld_flag(slot_of(wave)) : 0u;
+  Part<float>* dst = ja.part + (size_t)rg * (size_t)a.nlist;
+  float* ddst = ja.dpart + (size_t)rg * (size_t)a.nlist * (size_t)ja.ndir;
+  for (int k = 0; k < m; ++k) {
+    const int i = __builtin_amdgcn_readfirstlane(wave + k * nwaves);
+    const int s = __builtin_amdgcn_readfirstlane(slot_of(i));
+    const bool more = k + 1 < m;
+    const bool skip = __builtin_amdgcn_readfirstlane((int)fnext) != 0;
+    if (more) fnext = ld_flag(slot_of(wave + (k + 1) * nwaves));
+    float lsum = 0.0f, chk = skip ? __builtin_nanf("") : 0.0f;
+    if (!skip) {
+      const uint64_t target = area + (uint32_t)sld(ja.code_off, s);
+      const uint64_t cptr = sgpr64(reinterpret_cast<uint64_t>(ja.consts + sld(ja.cbase, s)));
+      const uint64_t gptr = sgpr64(reinterpret_cast<uint64_t>(ddst + (size_t)s * (size_t)ja.ndir));
+      uint32_t la = lds_lane;
+      uint32_t tile = 0, status;
+      asm volatile("s_swappc_b64 s[76:77], %[tgt]"
+                   : "+{v42}"(lsum), "+{v40}"(chk), "+{v41}"(la), "+{s64}"(tile), "={s69}"(status)
+                   : [tgt] "s"(target), "{v43}"(lane4), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
+                     "{s68}"(woff), "{s[78:79]}"(cptr), "{s[84:85]}"(gptr)
+                   : SR_JIT_GRAD_CLOBBERS, "memory");
+      (void)status;
+    }
+    // a skipped tree writes no channel partials: finalize gives it a NaN row
+    lsum = wave_sum(lsum);
+    chk = __builtin_amdgcn_ballot_w64(chk != chk) != 0 ? __builtin_nanf("") : 0.0f;
+    if (lane == 0) dst[s] = Part<float>{lsum, chk};
+    if (!skip && chk != chk && lane == 0)
+      __hip_atomic_store(a.fail + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256) sr_jit_deriv(JitDerivArgs ja) { jit_deriv_body<false>(ja); }
+extern "C" __global__ void __launch_bounds__(256) sr_jit_deriv_w(JitDerivArgs ja) { jit_deriv_body<true>(ja); }
+
+// Σ over the row groups of a derivative launch in fp64 — lane group w takes the row
+// groups rg ≡ w (mod 4) in ascending order, the four are added in a fixed tree — into
+// out_sum [ntrees][1 + ndir] and out_ok; a tree that failed (or that a row group
+// skipped after another's failure) gets a NaN row, as deriv_finalize_kernel gives it.
+struct JitDerivFinArgs {
+  const int32_t* tree;   // [nslots]
+  const uint32_t* fail;  // [nslots]
+  const Part<float>* part;
+  const float* dpart;
+  double* out_sum;
+  uint8_t* out_ok;
+  int nslots, nrg, ndir;
+};
+extern "C" __global__ void __launch_bounds__(256) sr_jit_deriv_fin(JitDerivFinArgs fa) {
+  constexpr int S = 6;  // marker, channel 0, up to 4 directions
+  __shared__ double sh[4][S][64];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int s = blockIdx.x * 64 + lane;
+  double acc[S];
+  for (int k = 0; k < S; ++k) acc[k] = 0.0;
+  if (s < fa.nslots) {
+    for (int rg = w; rg < fa.nrg; rg += 4) {
+      const Part<float> q = fa.part[(size_t)rg * fa.nslots + s];
+      acc[0] += (double)q.chk;
+      acc[1] += (double)q.sum;
+      const float* d = fa.dpart + ((size_t)rg * fa.nslots + s) * fa.ndir;
+      for (int k = 0; k < fa.ndir; ++k) acc[2 + k] += (double)d[k];
+    }
+  }
+  for (int k = 0; k < S; ++k) sh[w][k][lane] = acc[k];
+  __syncthreads();
+  if (w == 0 && s < fa.nslots) {
+    for (int k = 0; k < S; ++k) acc[k] = (sh[0][k][lane] + sh[1][k][lane]) + (sh[2][k][lane] + sh[3][k][lane]);
+    const bool ok = !__builtin_isnan(acc[0]) && fa.fail[s] == 0u;
+    const int t = fa.tree[s];
+    double* row = fa.out_sum + (size_t)t * (1 + fa.ndir);
+    for (int k = 0; k <= fa.ndir; ++k) row[k] = ok ? acc[1 + k] : __builtin_nan("");
+    fa.out_ok[t] = ok ? 1 : 0;
+  }
+}

@@ -341,6 +341,9 @@ const PROGRAM_INTERPRETED = UInt32(2)  # no loss / output tree code (per-tree ro
 # features from X in device memory (SRHIP_PROGRAM_WIDE_TREE_CODE), so trees that
 # read features from index 63 on and datasets too wide for LDS keep tree code
 const PROGRAM_WIDE_TREE_CODE = UInt32(4)
+# deriv_tree_code (opt-in): srhip_eval_loss_deriv on a Float32 program may run reverse-mode
+# tree code (SRHIP_PROGRAM_DERIV_TREE_CODE; eval_loss_deriv's tree_code keyword)
+const PROGRAM_DERIV_TREE_CODE = UInt32(32)
 function Program(trees::AbstractVector{Node{T}}, options::Options, device::Int=0;
                  varying_constants::Bool=false, wide_tree_code::Bool=false) where {T}
     node_off, kind, arg, const_off, consts = flatten(trees, options)
@@ -1283,17 +1286,19 @@ function (f::DerivativeObjective{T})(tree::Node{T}, dataset::Dataset{T}, options
 end
 
 """
-    eval_loss_deriv(trees, dataset, options; device=0) -> (losses, means, ok)
+    eval_loss_deriv(trees, dataset, options; device=0, tree_code=false) -> (losses, means, ok)
 
 The derivative objective `options.loss_function::DerivativeObjective` for every tree in one
 engine call (srhip_eval_loss_deriv): `losses[i] = T(Σ_k coefficients[k] · means[i, k])`,
 `T(Inf)` where the tree fails or the result is not finite; `means` is (ntrees, 1 + ndir) in
 Float64. The columns `[y; dydx]` go up once per call next to `dataset.X`
 (srhip_dataset_create_multi). `Unsupported` for expression losses and expression operators
-(the callers fall back to the CPU definition).
+(the callers fall back to the CPU definition). `tree_code=true` scores Float32 batches of up
+to 4 directions as reverse-mode tree code (SRHIP_PROGRAM_DERIV_TREE_CODE); every other call
+runs in the interpreter as without it.
 """
 function eval_loss_deriv(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, options::Options;
-                         device::Int=0) where {T}
+                         device::Int=0, tree_code::Bool=false) where {T}
     f = options.loss_function::DerivativeObjective{T}
     nt = length(trees)
     nd = length(f.directions)
@@ -1329,10 +1334,25 @@ function eval_loss_deriv(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, op
         try
             tr = Ref(SrhipTrees(Int32(nt), pointer(node_off), pointer(kind), pointer(arg), pointer(const_off),
                                 Ptr{Cvoid}(pointer(consts))))
-            check(ccall((:srhip_eval_loss_deriv_batch_ctx, libsrhip), Int32,
-                        (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Int32, Ptr{Float64}, Ptr{Int32}, Int32,
-                         Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
-                        context(device), h[], tr, kindcode, params, dir, Int32(nd), sums, wsum, ok))
+            if tree_code
+                prog = Ref{Ptr{Cvoid}}(C_NULL)
+                check(ccall((:srhip_program_create_ex, libsrhip), Int32,
+                            (Ptr{Cvoid}, Int32, Ref{SrhipTrees}, UInt32, Ptr{Ptr{Cvoid}}),
+                            context(device), dtype_code(T), tr, PROGRAM_INTERPRETED | PROGRAM_DERIV_TREE_CODE, prog))
+                try
+                    check(ccall((:srhip_eval_loss_deriv, libsrhip), Int32,
+                                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}, Int32,
+                                 Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                                h[], prog[], kindcode, params, dir, Int32(nd), sums, wsum, ok))
+                finally
+                    ccall((:srhip_program_destroy, libsrhip), Int32, (Ptr{Cvoid},), prog[])
+                end
+            else
+                check(ccall((:srhip_eval_loss_deriv_batch_ctx, libsrhip), Int32,
+                            (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Int32, Ptr{Float64}, Ptr{Int32}, Int32,
+                             Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                            context(device), h[], tr, kindcode, params, dir, Int32(nd), sums, wsum, ok))
+            end
         finally
             destroy_dataset(h[])
         end

@@ -161,6 +161,9 @@ SIGNATURES = {
     "srhip_program_shared_columns": [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)],
     "srhip_jit_compile": [C.POINTER(Trees), C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_char_p,
                           C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)],
+    "srhip_jit_compile_deriv": [C.POINTER(Trees), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                C.c_void_p, C.POINTER(C.c_int64), C.c_char_p, C.POINTER(C.c_int64), C.c_void_p,
+                                C.POINTER(C.c_int64)],
     "srhip_jit_compile_grad": [C.POINTER(Trees), C.c_void_p, C.POINTER(C.c_int64), C.c_char_p,
                                C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)],
     "srhip_jit_compile_loss": [C.POINTER(Trees), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p,

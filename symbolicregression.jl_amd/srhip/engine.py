@@ -233,10 +233,13 @@ class Program:
     wide_tree_code (SRHIP_PROGRAM_WIDE_TREE_CODE, opt-in): Float32 literal-constant
     loss tree code may read its features from X in device memory, so trees that
     read features past the LDS tile's reach (index 63 on) and datasets too wide
-    for LDS keep their tree code."""
+    for LDS keep their tree code.
+    deriv_tree_code (SRHIP_PROGRAM_DERIV_TREE_CODE, opt-in): eval_loss_deriv on a
+    Float32 program runs reverse-mode tree code when ndir <= 4, the loss is a distance
+    loss other than Periodic and the dataset is not wide; otherwise the interpreter."""
 
     def __init__(self, ctx: Context, flat: FlatTrees, dtype, varying_constants: bool = False,
-                 interpreted: bool = False, wide_tree_code: bool = False):
+                 interpreted: bool = False, wide_tree_code: bool = False, deriv_tree_code: bool = False):
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self.flat = flat
@@ -254,7 +257,8 @@ class Program:
         check(lib().srhip_program_create_ex(ctx.handle, dtype_code(self.dtype), C.byref(tr),
                                             (K.PROGRAM_VARYING_CONSTANTS if varying_constants else 0)
                                             | (K.PROGRAM_INTERPRETED if interpreted else 0)
-                                            | (K.PROGRAM_WIDE_TREE_CODE if wide_tree_code else 0), C.byref(h)))
+                                            | (K.PROGRAM_WIDE_TREE_CODE if wide_tree_code else 0)
+                                            | (K.PROGRAM_DERIV_TREE_CODE if deriv_tree_code else 0), C.byref(h)))
         self.handle = h
         self.ntrees = flat.ntrees
 
@@ -731,20 +735,27 @@ def _trees_struct(flat: FlatTrees, consts: np.ndarray) -> Trees:
 
 
 def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bool = False, loss=None,
-                out: bool = False, text: bool = True, wide: bool = False):
+                out: bool = False, text: bool = True, wide: bool = False, deriv=None):
     """Tree compiler without a device (srhip_jit_compile, or with grad=True
     srhip_jit_compile_grad: the reverse-mode gradient tree code; memc: the
     memory-constant loss tree code; loss: a Loss other than L2, through
     srhip_jit_compile_loss; out: the per-row output code of
     srhip_eval_tree_array; wide: Float32 literal-constant loss code that
     reads its features from X in device memory): (code bytes, assembly text,
-    {tree id: byte offset})."""
+    {tree id: byte offset}). deriv=(directions (0-based), nfeat, weighted): the
+    derivative tree code of eval_loss_deriv (srhip_jit_compile_deriv), under `loss`
+    (default L2)."""
     f64 = np.dtype(flat.consts.dtype) == np.float64
     consts = np.ascontiguousarray(flat.consts, dtype=np.float64 if f64 else np.float32)
     tr = _trees_struct(flat, consts)
     nb, nt, no = C.c_int64(0), C.c_int64(0), C.c_int64(0)
 
     def call(*bufs):
+        if deriv is not None:
+            d = np.ascontiguousarray(deriv[0], dtype=np.int32)
+            kind, param = (0, 0.0) if loss is None else (int(loss.kind), float(loss.param))
+            return lib().srhip_jit_compile_deriv(C.byref(tr), _p(d), len(d), int(deriv[1]), int(bool(deriv[2])), kind, param,
+                                                 bufs[0], C.byref(nb), bufs[1], C.byref(nt), bufs[2], C.byref(no))
         if f64 and grad:  # the Float64 gradient tree code (jit64.cpp GradGen64)
             kind, param = (0, 0.0) if loss is None else (int(loss.kind), float(loss.param))
             return lib().srhip_jit_compile_loss(C.byref(tr), 1, 8, kind, param, bufs[0], C.byref(nb), bufs[1],

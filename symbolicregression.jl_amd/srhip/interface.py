@@ -213,10 +213,12 @@ class DerivativeObjective:
     options.loss_function anywhere; eval_loss_batch_ok recognises it on a
     DerivativeDataset and scores the whole batch in one fused engine call
     (eval_deriv_loss_batch). `eval_tree_array` / `eval_diff_tree_array` replace the
-    two evaluators of the per-tree call (tests run it on a CPU evaluator)."""
+    two evaluators of the per-tree call (tests run it on a CPU evaluator).
+    `tree_code=True` (SRHIP_PROGRAM_DERIV_TREE_CODE) lets the fused call run Float32
+    batches as reverse-mode tree code (up to 4 directions, no Periodic loss)."""
 
     def __init__(self, coefficients: Sequence[float], elementwise_loss=None, eval_tree_array=None,
-                 eval_diff_tree_array=None):
+                 eval_diff_tree_array=None, tree_code: bool = False):
         c = np.asarray(coefficients, dtype=np.float64)
         if c.ndim != 1 or len(c) < 2:
             raise ValueError("coefficients must hold one value per channel: y, then one per direction")
@@ -229,6 +231,7 @@ class DerivativeObjective:
         self.elementwise_loss = elementwise_loss
         self._eval = eval_tree_array
         self._diff = eval_diff_tree_array
+        self.tree_code = bool(tree_code)
 
     def loss(self, options: Options):
         loss = self.elementwise_loss if self.elementwise_loss is not None else options.elementwise_loss
@@ -281,13 +284,18 @@ class DerivativeObjective:
 
 
 def eval_deriv_loss_batch(trees: Sequence[Node], dataset: DerivativeDataset, options: Options,
-                          device: Optional[int] = None, elementwise_loss=None):
+                          device: Optional[int] = None, elementwise_loss=None, tree_code: Optional[bool] = None):
     """The channel means of a derivative objective for many trees in one fused
     engine call (srhip_eval_loss_deriv): (means [ntrees, 1 + ndir] in float64 —
     column 0 the weighted mean of ℓ(ŷ, y), column 1 + j that of
     ℓ(∂ŷ/∂x_d, dydx[j]) along d = dataset.directions[j] — and did_succeed per
     tree). A failed tree's row is NaN. ℓ is elementwise_loss (default:
-    options.elementwise_loss), a distance loss."""
+    options.elementwise_loss), a distance loss. tree_code (default: that of
+    options.loss_function when it is a DerivativeObjective): the program is made with
+    deriv_tree_code (see Program)."""
+    if tree_code is None:
+        tree_code = bool(getattr(options.loss_function, "tree_code", False)) and isinstance(options.loss_function,
+                                                                                             DerivativeObjective)
     if not isinstance(dataset, DerivativeDataset):
         raise ValueError("eval_deriv_loss_batch scores a DerivativeDataset")
     loss = elementwise_loss if elementwise_loss is not None else options.elementwise_loss
@@ -296,7 +304,7 @@ def eval_deriv_loss_batch(trees: Sequence[Node], dataset: DerivativeDataset, opt
     trees = list(trees)
     T = dataset.T
     dev = dataset.multi.device(device)
-    prog = Program(dev.ctx, flatten(trees, options, dtype=T), T, interpreted=True)
+    prog = Program(dev.ctx, flatten(trees, options, dtype=T), T, interpreted=True, deriv_tree_code=bool(tree_code))
     sums, wsum, ok = prog.eval_loss_deriv(dev, loss.kind, [d - 1 for d in dataset.directions], loss.params)
     with np.errstate(invalid="ignore", divide="ignore"):
         means = sums / wsum[None, :]
