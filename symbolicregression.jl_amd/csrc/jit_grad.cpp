@@ -837,9 +837,28 @@ struct GradGen {
           const int d = dest(o.a, TP, &blk);
           if (d < 0) return false;
           const int ar = opreg(o.a);
+          // v_rcp_f32 flushes a subnormal operand (the result is Inf) and a subnormal result (0), and
+          // log's domain reaches both (1/5e-39 = 2e38, 1/3e38 = 3.3e-39). a > 0 here (a row with
+          // a <= 0 failed the forward pass): a is brought into [2^-64, 2^64] by an exact power of
+          // two s in TR, and 1/a = s·rcp(a·s), which rounds again only where it is subnormal: that
+          // last v_mul_f32 keeps a subnormal product because the template's kernels run with Float32
+          // denormals enabled (the compiler's default MODE for gfx950; cube's subnormal 3x² relies on it too)
+          for (int e = 0; e < R; ++e) {
+            as.vop1(VOP1_MOV, "v_mov_b32_e32", TR + e, K(0x3f800000u));
+            as.vop1(VOP1_MOV, "v_mov_b32_e32", TQ + e, K(0x5f800000u));  // 2^64
+            as.vopc(VOPC_GT_F32, "v_cmp_gt_f32_e32", K(0x1f800000u), ar + e);  // 2^-64 > a
+            as.sopp(0x00, "s_nop", 1);
+            as.vop2(VOP2_CNDMASK, "v_cndmask_b32_e32", TR + e, V(TR + e), TQ + e, ", vcc");
+            as.vop1(VOP1_MOV, "v_mov_b32_e32", TQ + e, K(0x1f800000u));  // 2^-64
+            as.vopc(VOPC_LT_F32, "v_cmp_lt_f32_e32", K(0x5f800000u), ar + e);  // 2^64 < a
+            as.sopp(0x00, "s_nop", 1);
+            as.vop2(VOP2_CNDMASK, "v_cndmask_b32_e32", TR + e, V(TR + e), TQ + e, ", vcc");
+          }
+          for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", TQ + e, V(TR + e), ar + e);
           // the four reciprocals first: a VALU read of a transcendental's
           // result right after it needs a wait state on gfx950 (as DIV)
-          for (int e = 0; e < R; ++e) as.vop1(VOP1_RCP_F32, "v_rcp_f32_e32", d + e, V(ar + e));
+          for (int e = 0; e < R; ++e) as.vop1(VOP1_RCP_F32, "v_rcp_f32_e32", d + e, V(TQ + e));
+          for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", d + e, V(TR + e), d + e);
           for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", d + e, gv(e), d + e);
           give(o.a, d, g.neg, blk);
           break;
