@@ -215,19 +215,44 @@ extern "C" {
  * weight, out_ok the candidate's alone, rows past the end add 0.
  * srhip_last_tree_code / srhip_last_kernel_name report the launch and the
  * srhip_jit_compile_loss hook compiles for the handle. Still interpreted, with
- * unchanged results: Float64 programs, gradients, row sets, multi-target
+ * unchanged results: Float64 programs, gradients (unless the handle also carries
+ * SRHIP_LOSS_EXPR_GRAD_TREE_CODE, below), row sets, multi-target
  * calls, SRHIP_PROGRAM_WIDE_TREE_CODE programs, device-group programs,
  * derivative objectives, trees with expression operators, and an expression
- * the tree compiler has no form for (an operator applied to constants alone). */
+ * the tree compiler has no form for (an operator applied to constants alone).
+ *
+ * Gradient tree code (opt-in per handle, SRHIP_LOSS_EXPR_GRAD_TREE_CODE,
+ * independent of the flag above): srhip_eval_loss_grad and its _batch /
+ * _batch_ctx / packed kin, and the gradient phases of
+ * srhip_optimize_constants_batch / _cb, run the reverse-mode gradient tree code
+ * on a Float32 program: per tile the candidate's forward pass, the expression's
+ * forward pass (Σ ℓ), one reverse sweep over the expression with the prediction
+ * leaf as the adjoint target (the seed dℓ/dŷ, summed over every occurrence of
+ * the prediction), then the candidate's reverse pass. Same contract: ℓ in
+ * Float32 by the PRECISE routines, no implicit weight, out_ok the candidate's
+ * alone, a non-finite ℓ or seed gives non-finite sums with ok = 1, rows past
+ * the end add 0 and seed 0. The sums agree with the interpreter's within
+ * rounding, not bit for bit (reverse accumulation, v_rcp_f32 in the division
+ * rule). The expression's operators are + - * / ^ neg abs square cube exp sin
+ * cos log sqrt, none applied to constants alone; another expression is
+ * interpreted whole. srhip_last_tree_code reports the compiled trees,
+ * srhip_last_kernel_name the gradient driver, and srhip_jit_compile_loss with
+ * grad = 1 compiles for the handle. Still interpreted, with unchanged results:
+ * a handle without the flag, Float64 programs, row sets, device-group and wide
+ * programs, trees with expression operators, and trees the code generator
+ * refuses (register pool: never spilled). */
 #define SRHIP_EXPR_LOSS_BEGIN 1024 /* loss kinds from here on are handles of expression losses */
 /* srhip_loss_expr_create_ex flag (1u): Float32 loss tree code may run the handle. (Spelt with
  * UINT32_C: the build's generators read every "SRHIP_LOSS_<NAME> <digits>" line as a loss id.) */
 #define SRHIP_LOSS_EXPR_TREE_CODE UINT32_C(1)
+/* srhip_loss_expr_create_ex flag (4u; 2u stays invalid): Float32 gradient tree code may run the handle. */
+#define SRHIP_LOSS_EXPR_GRAD_TREE_CODE UINT32_C(4)
 /* consts[nconsts]: the constant leaves in stream order (as srhip_trees). */
 int32_t srhip_loss_expr_create(const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
                                const double* consts, int32_t nconsts, int32_t* out_loss_kind);
 /* The same with flags (0: srhip_loss_expr_create); a bit other than
- * SRHIP_LOSS_EXPR_TREE_CODE is SRHIP_ERR_INVALID and creates nothing. */
+ * SRHIP_LOSS_EXPR_TREE_CODE and SRHIP_LOSS_EXPR_GRAD_TREE_CODE is
+ * SRHIP_ERR_INVALID and creates nothing. */
 int32_t srhip_loss_expr_create_ex(const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
                                   const double* consts, int32_t nconsts, uint32_t flags, int32_t* out_loss_kind);
 /* A destroyed (or never registered) kind >= SRHIP_EXPR_LOSS_BEGIN is

@@ -469,6 +469,8 @@ struct ExprLoss {
   // SRHIP_LOSS_EXPR_TREE_CODE: the handle may end the tiles of Float32 loss tree code (loss_module);
   // lx: its stream for the tree compiler, constants rounded as the loss program's are
   bool tree_code = false;
+  // SRHIP_LOSS_EXPR_GRAD_TREE_CODE: the Float32 gradient tree code may run it (expr_grad_module)
+  bool grad_tree_code = false;
   jit::LossExpr lx;
   std::vector<Ins<float>> p32;
   std::vector<Ins<double>> p64;
@@ -1751,6 +1753,35 @@ jit::GradModule* grad_module(srhip_program* p, int loss, double lparam) {
       [&](const std::vector<int32_t>& gjl, const std::vector<int32_t>&) { return gjl == p->h_gjl; }, jit::destroy_grad);
 }
 
+// The gradient tree code of a Float32 program for an expression loss made with
+// SRHIP_LOSS_EXPR_GRAD_TREE_CODE: the L2 build's candidates
+// compiled with the handle's expression between the forward and the reverse
+// pass, built at the handle's first gradient and kept with the program under
+// the handle's kind. The code reads the tree's constants from memory and holds
+// the loss's own as literals (the handle is immutable), so it outlives
+// set_constants. Null, and the gradients run in grad_kernel's expression mode:
+// an unflagged handle, an expression the generator refuses (per loss, cached),
+// a wide or device-group program, a different slot layout. A destroyed handle
+// is INVALID here, before any build.
+jit::GradModule* expr_grad_module(srhip_program* p, int loss) {
+  const std::shared_ptr<const ExprLoss> e = expr_loss_lookup(loss);
+  if (!p->gjit || !e->grad_tree_code || p->wide_tc || p->in_group) return nullptr;
+  for (const auto& l : p->gjit_loss)
+    if (l.kind == loss && l.bits == 0) return l.m;
+  static const bool on = env_on("SRHIP_JIT_LOSSES");
+  if (!on || !jit::loss_expr_grad_fits(e->lx)) {
+    p->gjit_loss.push_back({loss, 0, nullptr});
+    return nullptr;
+  }
+  return lazy_module<float, jit::GradModule>(
+      p, p->gjit_loss, loss, 0, p->gjit_consts, true,
+      [&](const CompiledBatch<float>& cb, std::vector<int32_t>& gjl, std::vector<int32_t>& rest) {
+        jit::GradStats st;
+        return jit::build_grad(cb, p->const_off, p->h_gcand, gjl, rest, &st, SRHIP_LOSS_L2, 0, &e->lx);
+      },
+      [&](const std::vector<int32_t>& gjl, const std::vector<int32_t>&) { return gjl == p->h_gjl; }, jit::destroy_grad);
+}
+
 // The same for a Float64 program (jit64.cpp GradGen64): the L2 build, or the
 // same candidates compiled with that loss's seed; null: interpreted.
 jit::GradModule64* grad_module64(srhip_program* p, int loss, double lparam) {
@@ -2651,7 +2682,7 @@ void run_grad(srhip_ctx* c, srhip_program* p, int mode, const srhip_dataset* ds,
   bool use_gjit = false;
   if constexpr (std::is_same<T, float>::value) {
     jit::GradModule* gm = (p->gjit && !rs && !tgt && mode == GRAD_LOSS && ds->rows > 0 && wide_mode() != 1)
-                              ? grad_module(p, loss, lparam)
+                              ? (loss >= SRHIP_EXPR_LOSS_BEGIN ? expr_grad_module(p, loss) : grad_module(p, loss, lparam))
                               : nullptr;
     if (gm) {
       const int nparts = jit::grad_nparts(gm);
@@ -3723,9 +3754,11 @@ int32_t srhip_loss_expr_create_ex(const uint8_t* kind, const uint16_t* arg, int3
                                   int32_t nconsts, uint32_t flags, int32_t* out_loss_kind) {
   return guarded([&] {
     if (!out_loss_kind) throw Error(SRHIP_ERR_INVALID, "null out_loss_kind");
-    if (flags & ~SRHIP_LOSS_EXPR_TREE_CODE) throw Error(SRHIP_ERR_INVALID, "expression loss: unknown flag bits");
+    if (flags & ~(SRHIP_LOSS_EXPR_TREE_CODE | SRHIP_LOSS_EXPR_GRAD_TREE_CODE))
+      throw Error(SRHIP_ERR_INVALID, "expression loss: unknown flag bits");
     std::shared_ptr<ExprLoss> e = expr_loss_compile(kind, arg, nnodes, consts, nconsts);
     e->tree_code = (flags & SRHIP_LOSS_EXPR_TREE_CODE) != 0;
+    e->grad_tree_code = (flags & SRHIP_LOSS_EXPR_GRAD_TREE_CODE) != 0;
     std::lock_guard<std::mutex> lk(g_expr_mu);
     if (g_expr_next == std::numeric_limits<int32_t>::max()) throw Error(SRHIP_ERR_NOMEM, "expression loss handles exhausted");
     const int32_t id = g_expr_next++;
@@ -4554,10 +4587,16 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
     std::shared_ptr<const ExprLoss> xloss;
     if (loss >= SRHIP_EXPR_LOSS_BEGIN) {
       xloss = expr_loss_lookup(loss);
-      if (!xloss->tree_code) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for expression losses");
-      if ((mode != 0 && mode != 1) || out_mode || wide)
-        throw Error(SRHIP_ERR_UNSUPPORTED, "expression losses have Float32 loss tree code only");
-      if (!jit::loss_expr_fits(xloss->lx)) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for this expression loss");
+      if (mode == 2 && !dspec) {  // its gradient tree code: SRHIP_LOSS_EXPR_GRAD_TREE_CODE handles only
+        if (!xloss->grad_tree_code) throw Error(SRHIP_ERR_UNSUPPORTED, "no gradient tree code for expression losses");
+        if (!jit::loss_expr_grad_fits(xloss->lx))
+          throw Error(SRHIP_ERR_UNSUPPORTED, "no gradient tree code for this expression loss");
+      } else {
+        if (!xloss->tree_code) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for expression losses");
+        if ((mode != 0 && mode != 1) || out_mode || wide)
+          throw Error(SRHIP_ERR_UNSUPPORTED, "expression losses have Float32 loss and gradient tree code only");
+        if (!jit::loss_expr_fits(xloss->lx)) throw Error(SRHIP_ERR_UNSUPPORTED, "no tree code for this expression loss");
+      }
       loss = SRHIP_LOSS_L2;
     }
     // expression operators: live handles only, and their trees have no tree code
@@ -4587,7 +4626,8 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
       CompiledBatch<float> cb = compile_batch<float>(*trees, /*grad=*/true);
       const std::vector<int32_t> coff(trees->const_off, trees->const_off + trees->ntrees + 1);
       if (dspec) jit::compile_deriv_only(cb, coff, candidates(cb, false), *dspec, &bytes, &text, &offs, nullptr);
-      else jit::compile_grad_only(cb, coff, candidates(cb, false), &bytes, &text, &offs, nullptr, loss, lbits);
+      else jit::compile_grad_only(cb, coff, candidates(cb, false), &bytes, &text, &offs, nullptr, loss, lbits,
+                                  xloss ? &xloss->lx : nullptr);
     } else {
       CompiledBatch<float> cb = compile_batch<float>(*trees);
       jit::Options jo;

@@ -224,9 +224,15 @@ struct GradStats {
   size_t code_bytes = 0;
   double ms_codegen = 0.0, ms_load = 0.0;
 };
+// lexpr: an expression loss instead of `loss`: Σ ℓ and the seed dℓ/dŷ by a
+// forward and a reverse sweep over the expression inside the tile, the prediction leaf as the
+// adjoint target; its constants are literals of the code. The caller keeps it alive for the call.
 GradModule* build_grad(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
                        const std::vector<int32_t>& cand, std::vector<int32_t>& jit_list, std::vector<int32_t>& rest,
-                       GradStats* st, int loss = SRHIP_LOSS_L2, uint64_t lparam = 0);
+                       GradStats* st, int loss = SRHIP_LOSS_L2, uint64_t lparam = 0, const LossExpr* lexpr = nullptr);
+// the gradient tree code takes this expression (operators with a reverse rule only, none on
+// constants alone); the counterpart of loss_expr_fits. False: its gradients run interpreted
+bool loss_expr_grad_fits(const LossExpr& lx);
 void destroy_grad(GradModule* m);
 int grad_nslots(const GradModule* m);
 // the module's code objects: consecutive slot ranges, one launch each
@@ -243,7 +249,8 @@ hipError_t launch_grad_code(GradModule* m, int part, const EvalPlan& plan, const
 const Columns& grad_columns(const GradModule* m);
 bool compile_grad_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
                        const std::vector<int32_t>& cand, std::vector<uint8_t>* bytes, std::string* text,
-                       std::vector<int32_t>* offsets, GradStats* st, int loss = SRHIP_LOSS_L2, uint64_t lparam = 0);
+                       std::vector<int32_t>* offsets, GradStats* st, int loss = SRHIP_LOSS_L2, uint64_t lparam = 0,
+                       const LossExpr* lexpr = nullptr);
 
 // ---- derivative-objective tree code (jit_grad.cpp) ------------------
 // The gradient tree code's reverse pass with the feature leaves of `dir` as adjoint

@@ -31,6 +31,9 @@
 //              1/b by v_rcp_f32 (the interpreter's rules, device_ops.h uop_d /
 //              bop_d); subtrees without constants get no reverse code at all
 //   epilogue   accumulators to the wave's LDS scratch, return
+// Expression losses (jit.h LossExpr): the loss step is the handle's expression,
+// forward (Σ ℓ) and reverse (the seed dℓ/dŷ, the prediction leaf as the adjoint target), by the same
+// emitters and reverse rules as the candidate's operators (GradGen::append_loss, emit_loss_expr).
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -67,11 +70,12 @@ enum : int { VOP1_RCP_F32 = 0x22, VOPC_NEQ_F32 = 0x4d, VOP3_MUL_F32 = 0x105 };
 const int kSinCosPd[2] = SR_JIT_SINCOS_PD_ROUTINE;
 
 // ---- IR: the accumulator machine of a gradient program, renamed ----------------
-enum { G_VAL = 0, G_X = 1, G_C = 2 };
+enum { G_VAL = 0, G_X = 1, G_C = 2, G_P = 3, G_Y = 4, G_W = 5 };  // G_P / G_Y / G_W: ŷ, y, w of a loss expression
 struct GOpnd {
   int k = G_VAL;
   int v = -1;   // value id (G_VAL) or feature (G_X)
   int ci = -1;  // constant index within the tree (G_C)
+  bool p = false;  // the candidate's root read by a loss expression: its adjoint goes to the seed block
 };
 enum { K_UN = 0, K_BIN = 1, K_MAT = 2 };  // K_MAT: a constant broadcast into a block
 struct GOp {
@@ -227,6 +231,62 @@ bool gir_substitute(std::vector<GOp>& ops, GOpnd& root, const std::unordered_map
   return true;
 }
 
+// ---- expression losses (jit.h LossExpr) ---------------------------
+// The handle's postfix stream as GOps, once per module: value ids count from 0,
+// the prediction is G_P (GradGen::append_loss puts the candidate's root there),
+// constant j of the loss is G_C j (appended behind the tree's own). Refused: an
+// operator outside kGradUops / kGradBops, an operator on constants alone.
+struct LossIR {
+  std::vector<GOp> ops;
+  GOpnd root;
+  std::vector<uint32_t> cbits;  // the constants: literals of the code
+};
+bool build_loss_ir(const LossExpr& lx, LossIR& L, std::string* why) {
+  std::vector<GOpnd> st;
+  L = LossIR();
+  for (size_t i = 0; i < lx.kind.size(); ++i) {
+    GOpnd q;
+    switch (lx.kind[i]) {
+      case SRHIP_NODE_CONST: {
+        if (L.cbits.size() >= lx.consts.size()) { *why = "loss expression: constant missing"; return false; }
+        uint32_t b;
+        std::memcpy(&b, &lx.consts[L.cbits.size()], 4);
+        q.k = G_C;
+        q.ci = (int)L.cbits.size();
+        L.cbits.push_back(b);
+        break;
+      }
+      case SRHIP_NODE_FEATURE:
+        if (lx.arg[i] > 2) { *why = "loss expression: feature index"; return false; }
+        q.k = lx.arg[i] == 0 ? G_P : lx.arg[i] == 1 ? G_Y : G_W;
+        break;
+      case SRHIP_NODE_UNARY:
+      case SRHIP_NODE_BINARY: {
+        GOp o;
+        o.kind = lx.kind[i] == SRHIP_NODE_UNARY ? K_UN : K_BIN;
+        o.op = lx.arg[i];
+        const bool un = o.kind == K_UN;
+        if (st.size() < (un ? 1u : 2u) || o.op >= (un ? SRHIP_NUM_UOPS : SRHIP_NUM_BOPS)) { *why = "loss expression: malformed"; return false; }
+        if (!(((un ? kGradUops : kGradBops) >> o.op) & 1u)) { *why = "loss operator without gradient code"; return false; }
+        if (!un) { o.b = st.back(); st.pop_back(); }
+        o.a = st.back();
+        st.pop_back();
+        if (o.a.k == G_C && (un || o.b.k == G_C)) { *why = "loss operator on constants alone"; return false; }
+        if (!g_inline(o) && (un ? kUopRoutine[o.op] : kBopRoutine[o.op]) < 0) { *why = "loss operator without routine"; return false; }
+        q.k = G_VAL;
+        q.v = (int)L.ops.size();
+        L.ops.push_back(o);
+        break;
+      }
+      default: *why = "loss expression: node kind"; return false;
+    }
+    st.push_back(q);
+  }
+  if (st.size() != 1) { *why = "loss expression: malformed"; return false; }
+  L.root = st.back();
+  return true;
+}
+
 // ---- code generation of one tree ---------------------------------------------------
 struct GradGen {
   Asm& as;
@@ -288,7 +348,50 @@ struct GradGen {
     return -1;
   }
   static int dblk(int k) { return GACC + R * k; }
-  bool target(const GOpnd& q) const { return dv ? (q.k == G_X && dirk(q.v) >= 0) : q.k == G_C; }
+  bool target(const GOpnd& q) const { return dv ? (q.k == G_X && dirk(q.v) >= 0) : (q.k == G_C && q.ci < nc); }
+  // expression loss: ops[m0 ..] are the loss's operators, appended behind
+  // the candidate's (append_loss); its values and adjoints share the pool and the timeline
+  // (forward m0 .. n-1, Σ ℓ at n, reverse down to m0, then the candidate's reverse pass).
+  // The prediction is the candidate's root, flagged p: every occurrence adds its adjoint
+  // into the seed block (pool block `sblk`, the dir_add technique), which is masked and
+  // moved to VY as the candidate's seed. y is VY, w a pool block from the loss's start to
+  // its last use, the loss's constants literals in s[SC0 + nc ..], never adjoint targets.
+  const LossIR* lir = nullptr;
+  int m0 = 0, nlc = 0;
+  GOpnd lroot;
+  int wblk = -1, wlast = -1, sblk = -1, sreg = -1;
+  static constexpr int W_OWNER = 5000, SEED_OWNER = 5001;
+  // a loss whose reverse rules call no routine keeps the seed and the unit adjoint of its root in
+  // routine temporaries (the rules' own scratch ends below, XS0 is read for feature operands only,
+  // which a loss has none of) instead of two pool blocks
+  static constexpr int SEED_TMP = 24;
+  bool append_loss(const LossIR& L) {
+    lir = &L;
+    nlc = (int)L.cbits.size();
+    if (nc + nlc > NGACC) { why = "more constants than registers (loss expression)"; return false; }
+    if (root.k == G_C) {  // a constant root in a block: the loss's rules read it, K_MAT's rule sums its adjoint
+      GOp mt;
+      mt.kind = K_MAT;
+      mt.a = root;
+      ops.push_back(mt);
+      root = GOpnd();
+      root.v = (int)ops.size() - 1;
+    }
+    m0 = (int)ops.size();
+    auto fix = [&](GOpnd q) {
+      if (q.k == G_VAL) q.v += m0;
+      if (q.k == G_C) q.ci += nc;
+      if (q.k == G_P) { q = root; q.p = true; }
+      return q;
+    };
+    for (GOp o : L.ops) {
+      o.a = fix(o.a);
+      if (o.kind == K_BIN) o.b = fix(o.b);
+      ops.push_back(o);
+    }
+    lroot = fix(L.root);
+    return true;
+  }
 
   GradGen(Asm& a, const Tmpl& t, uint64_t va) : as(a), T(t), base_va(va) {}
   uint64_t cur_va() const { return base_va + as.bytes(); }
@@ -307,8 +410,8 @@ struct GradGen {
       GOp& o = ops[i];
       auto hc = [&](const GOpnd& q) { return needs_adj(q); };
       hasc[i] = (o.kind == K_MAT && !dv) || hc(o.a) || (o.kind == K_BIN && hc(o.b));
-      if (o.a.k == G_C && o.kind != K_MAT && o.a.ci >= nc) { why = "constant index out of range"; return false; }
-      if (o.kind == K_BIN && o.b.k == G_C && o.b.ci >= nc) { why = "constant index out of range"; return false; }
+      if (o.a.k == G_C && o.kind != K_MAT && o.a.ci >= nc + nlc) { why = "constant index out of range"; return false; }
+      if (o.kind == K_BIN && o.b.k == G_C && o.b.ci >= nc + nlc) { why = "constant index out of range"; return false; }
       if (!g_inline(o)) {
         o.rid = o.kind == K_UN ? kUopRoutine[o.op] : kBopRoutine[o.op];
         if (o.rid < 0) { why = "operator without routine"; return false; }
@@ -320,6 +423,7 @@ struct GradGen {
         const GOpnd& q = s ? o.b : o.a;
         if (s && o.kind != K_BIN) break;
         if (q.k == G_VAL) { ops[q.v].consumer = i; last[q.v] = std::max(last[q.v], i); }
+        if (q.k == G_W) wlast = std::max(wlast, i);
       }
     }
     if (root.k == G_C && root.ci >= nc) { why = "constant index out of range"; return false; }
@@ -331,6 +435,7 @@ struct GradGen {
       if (!hasc[i] || o.kind == K_MAT) continue;
       auto use = [&](const GOpnd& q) {
         if (q.k == G_VAL) last[q.v] = std::max(last[q.v], bstep(i));
+        if (q.k == G_W) wlast = std::max(wlast, bstep(i));
         if (q.k == G_X && q.v >= 0 && q.v < 256 && is_g(q.v)) xg_rev[q.v] = std::max(xg_rev[q.v], bstep(i));
       };
       if (o.kind == K_BIN) {
@@ -352,6 +457,8 @@ struct GradGen {
       }
     }
     if (root.k == G_VAL) last[root.v] = std::max(last[root.v], n);  // read by the loss step
+    if (lir && lroot.k == G_VAL) last[lroot.v] = std::max(last[lroot.v], n);
+    if (lir && lroot.k == G_W) wlast = std::max(wlast, n);
     // features: those read by inline operators (or as the root) are preloaded per tile
     for (int f = 0; f < 256; ++f) { xblk[f] = -1; xlast[f] = -1; load_idx[f] = -1; xinl[f] = false; }
     auto usef = [&](const GOpnd& q, int i, bool inl) {
@@ -394,6 +501,7 @@ struct GradGen {
   void free_feats_at(int step) {
     for (int f : feats)
       if (xlast[f] == step && xblk[f] >= 0 && owner[xblk[f]] == 1000 + f) owner[xblk[f]] = -1;
+    if (wblk >= 0 && wlast == step) { owner[wblk] = -1; wblk = -1; }
   }
   int new_adj_block(int v) {
     const int k = free_block();
@@ -462,6 +570,8 @@ struct GradGen {
   Src fsrc(const GOpnd& q, int e) const {  // forward operand source
     if (q.k == G_C) return S(SC0 + q.ci);
     if (q.k == G_X) return V(blk_reg(xblk[q.v]) + e);
+    if (q.k == G_Y) return V(VY + e);
+    if (q.k == G_W) return V(blk_reg(wblk) + e);
     return V(vreg(q.v) + e);
   }
   int vreg(int v) const { return loc[v] == LOC_VA ? VA : loc[v] == LOC_VB ? VB : blk_reg(loc[v]); }
@@ -537,6 +647,15 @@ struct GradGen {
     }
   }
 
+  // the seed block ±= blk (one occurrence of the prediction in a loss expression)
+  void seed_add(int reg, bool neg) {
+    const int s = sreg;
+    for (int e = 0; e < R; ++e) {
+      if (neg) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", s + e, V(s + e), reg + e);
+      else as.vop2(VOP2_ADD_F32, "v_add_f32_e32", s + e, V(s + e), reg + e);
+    }
+  }
+
   // ---- forward
   bool emit_mat(int i) {
     const GOp& o = ops[i];
@@ -608,6 +727,7 @@ struct GradGen {
       return;
     }
     if (q.k == G_X) { read_feat(dst, q.v); return; }
+    if (q.k == G_Y || q.k == G_W) { mov4(dst, q.k == G_Y ? VY : blk_reg(wblk)); return; }
     if (vreg(q.v) == dst) return;  // already there (a result kept in VA)
     mov4(dst, vreg(q.v));
   }
@@ -627,8 +747,22 @@ struct GradGen {
         operand_to(VA, o.a);
         if (o.kind == K_BIN) operand_to(VB, o.b);
       }
+      // exp in a loss expression: the routine clamps a NaN operand to a finite value and marks it, and
+      // the loss part drops the mark, so the NaN is put back by a select (ℓ of that row is non-finite)
+      const bool nanfix = lir && i >= m0 && o.kind == K_UN && o.op == SRHIP_UOP_EXP;
+      int kn = -1;
+      if (nanfix) {
+        kn = free_block();
+        if (kn < 0) { why = "register pool exhausted"; return false; }
+        mov4(blk_reg(kn), VA);
+      }
       free_values_at(i);
       routine(fused(i) ? kSinCosPd[o.op == SRHIP_UOP_COS ? 1 : 0] : o.rid, true);
+      for (int e = 0; nanfix && e < R; ++e) {
+        as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(blk_reg(kn) + e), blk_reg(kn) + e);
+        as.sopp(0x00, "s_nop", 1);
+        as.vop2(VOP2_CNDMASK, "v_cndmask_b32_e32", VA + e, V(VA + e), blk_reg(kn) + e, ", vcc");
+      }
       if (fused(i)) {  // the reverse factor out of VB before anything reuses it
         const int kd = free_block();
         if (kd < 0) { why = "register pool exhausted (sin / cos factor)"; return false; }
@@ -661,6 +795,8 @@ struct GradGen {
       if (q.k == G_C) return S(SC0 + q.ci);
       if (q.k == G_X && is_g(q.v)) return V(blk_reg(xblk[q.v]) + e);  // a column: in its block
       if (q.k == G_X) return V(scratch + e);
+      if (q.k == G_Y) return V(VY + e);
+      if (q.k == G_W) return V(blk_reg(wblk) + e);
       return V(blk_reg(loc[q.v]) + e);
     };
     auto fetch = [&](const GOpnd& q, int scratch) {
@@ -668,6 +804,7 @@ struct GradGen {
     };
     // adjoint of operand q = (products already in block `reg`) with sign `neg`
     auto give = [&](const GOpnd& q, int reg, bool neg, int blk) {
+      if (q.p) { seed_add(reg, neg); return; }
       if (q.k == G_C) { acc_add(q.ci, reg, neg); return; }
       if (q.k == G_X) { dir_add(dirk(q.v), reg, neg); return; }
       Adj a;
@@ -679,7 +816,7 @@ struct GradGen {
     // a block for the adjoint of q (pool if q is a value, scratch `tmp` for a constant)
     auto dest = [&](const GOpnd& q, int tmp, int* blk) {
       *blk = -2;
-      if (q.k != G_VAL) return tmp;
+      if (q.k != G_VAL || q.p) return tmp;
       const int k = new_adj_block(q.v);
       if (k < 0) return -1;
       *blk = k;
@@ -699,13 +836,15 @@ struct GradGen {
         case SRHIP_BOP_ADD:
         case SRHIP_BOP_SUB:
           if (aa) {
-            if (o.a.k == G_C) acc_add(o.a.ci, g.reg, g.neg);
+            if (o.a.p) seed_add(g.reg, g.neg);
+            else if (o.a.k == G_C) acc_add(o.a.ci, g.reg, g.neg);
             else if (o.a.k == G_X) dir_add(dirk(o.a.v), g.reg, g.neg);
             else share_adj(o.a.v, g, false);
           }
           if (ab) {
             const bool fl = o.op == SRHIP_BOP_SUB;
-            if (o.b.k == G_C) acc_add(o.b.ci, g.reg, g.neg != fl);
+            if (o.b.p) seed_add(g.reg, g.neg != fl);
+            else if (o.b.k == G_C) acc_add(o.b.ci, g.reg, g.neg != fl);
             else if (o.b.k == G_X) dir_add(dirk(o.b.v), g.reg, g.neg != fl);
             else share_adj(o.b.v, g, fl);
           }
@@ -782,7 +921,7 @@ struct GradGen {
           fetch(o.b, XS1);
           for (int e = 0; e < R; ++e) as.vop1(VOP1_RCP_F32, "v_rcp_f32_e32", TR + e, rsrc(o.b, XS1, e));
           int blk_a = -2;
-          const int ra = (aa && o.a.k == G_VAL) ? dest(o.a, TQ, &blk_a) : TQ;
+          const int ra = (aa && o.a.k == G_VAL && !o.a.p) ? dest(o.a, TQ, &blk_a) : TQ;
           if (ra < 0) return false;
           for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", ra + e, gv(e), TR + e);
           if (aa) give(o.a, ra, g.neg, blk_a);
@@ -805,7 +944,8 @@ struct GradGen {
       int blk;
       switch (o.op) {
         case SRHIP_UOP_NEG:
-          if (o.a.k == G_X) dir_add(dirk(o.a.v), g.reg, !g.neg);
+          if (o.a.p) seed_add(g.reg, !g.neg);
+          else if (o.a.k == G_X) dir_add(dirk(o.a.v), g.reg, !g.neg);
           else share_adj(o.a.v, g, true);
           break;
         case SRHIP_UOP_EXP: {
@@ -960,6 +1100,8 @@ struct GradGen {
     if (has_call || trig || loss != SRHIP_LOSS_L2) set_base();
     for (int j = 0; j < na; ++j) as.vop1(VOP1_MOV, "v_mov_b32_e32", a0 + j, K(0));
     if (nc > 0) as.waitcnt_lgkm(0);
+    for (int j = 0; j < nlc; ++j)  // the loss's constants behind the tree's own (after the load, which may be wider than nc)
+      as.sop1(SOP1_MOV, "s_mov_b32", SC0 + nc + j, K(lir->cbits[(size_t)j]), "s" + std::to_string(SC0 + nc + j));
     as.sopc(SOPC_GE_U32, "s_cmp_ge_u32", S(S_TILE), S(S_NT));
     as.branch(SOPP_SCC1, "s_cbranch_scc1", L_done);
     // ---- tile: forward
@@ -979,14 +1121,9 @@ struct GradGen {
       load_idx[f] = nloads++;
       as.ds_read_b128(blk_reg((int)j), VLANE, (1 + f) * TILE * 4);
     }
-    for (int i = 0; i < n; ++i) {
-      const GOp& o = ops[i];
-      bool ok;
-      if (o.kind == K_MAT) ok = emit_mat(i);
-      else if (g_inline(o)) ok = emit_inline(i);
-      else ok = emit_call(i);
-      if (!ok) return false;
-    }
+    const int mc = lir ? m0 : n;  // the candidate's operators
+    for (int i = 0; i < mc; ++i)
+      if (!emit_forward(i)) return false;
     // root value → rreg
     int rreg;
     if (root.k == G_VAL) rreg = blk_reg(loc[root.v]);
@@ -1004,10 +1141,18 @@ struct GradGen {
     as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(VCHK), VCHK);
     as.branch(SOPP_VCCNZ, "s_cbranch_vccnz", L_done);
     // ---- loss of the tile and the seed 2·w·r (masked rows: r = 0)
-    for (int e = 0; e < R; ++e) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", VY + e, V(rreg + e), VY + e);
-    free_values_at(n);
-    free_feats_at(n);
-    if (dv) {
+    if (lir) {
+      if (!emit_loss_expr()) {
+        if (why.rfind("register pool exhausted", 0) == 0) why = "register pool exhausted (loss expression)";
+        return false;
+      }
+    } else {
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", VY + e, V(rreg + e), VY + e);
+      free_values_at(n);
+      free_feats_at(n);
+    }
+    if (lir) {  // its seed is in VY already
+    } else if (dv) {
       emit_channel(VY, dv->weighted ? (1 + dv->nfeat + dv->ndir) * TILE * 4 : -1, VLSUM);
       for (int e = 0; e < R * dv->ndir; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", GACC + e, K(0));
       if (root.k == G_X && dirk(root.v) >= 0)  // ŷ = x_d: ∂ŷ/∂x_d = 1
@@ -1049,7 +1194,7 @@ struct GradGen {
       s.blk = -1;
       adj[root.v] = s;
     }
-    for (int i = n - 1; i >= 0; --i) {
+    for (int i = mc - 1; i >= 0; --i) {
       if (hasc[i] && !emit_reverse(i)) return false;
       free_values_at(bstep(i));
       free_feats_at(bstep(i));
@@ -1132,6 +1277,78 @@ struct GradGen {
     }
     as.sop1(SOP1_SETPC, "s_setpc_b64", 0, S(S_RT), "");
     if (as.want_text) as.lines.back() = "s_setpc_b64 s[" + std::to_string(S_RT) + ":" + std::to_string(S_RT + 1) + "]";
+    return true;
+  }
+  bool emit_forward(int i) {
+    const GOp& o = ops[i];
+    return o.kind == K_MAT ? emit_mat(i) : g_inline(o) ? emit_inline(i) : emit_call(i);
+  }
+  // The loss expression of a tile, between the failure exit and the candidate's reverse
+  // pass: forward (PRECISE routines), Σ ℓ into VLSUM, reverse with adjoint 1 at the loss's
+  // root into the seed block, the seed to VY. Rows past the last add 0 to the sum and seed
+  // 0, both by a select. Nothing here may fail the tree: VCHK is saved around the part.
+  bool emit_loss_expr() {
+    bool calls = false;
+    for (int i = m0; i < n; ++i) calls = calls || !g_inline(ops[i]);
+    if (calls) as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHKSAVE, V(VCHK));
+    if (wlast >= 0) {  // the tile's weight column, as the L2 step reads it
+      wblk = free_block();
+      if (wblk < 0) { why = "register pool exhausted"; return false; }
+      owner[wblk] = W_OWNER;
+      as.vop2(VOP2_ADD_U32, "v_add_u32_e32", VGT, S(S_WOFF), VLANE);
+      as.ds_read_b128(blk_reg(wblk), VGT, 0);
+      as.waitcnt_lgkm(0);
+    }
+    for (int i = m0; i < n; ++i)
+      if (!emit_forward(i)) return false;
+    // Σ ℓ: a masked copy, (ℓ0 + ℓ2) + (ℓ1 + ℓ3), the order of emit_loss_seed
+    if (lroot.k == G_X) wait_for_feat(lroot.v);
+    for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", TP + e, fsrc(lroot, e));
+    emit_mask(TP);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", TP, V(TP), TP + 2);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", TP + 1, V(TP + 1), TP + 3);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", TP, V(TP), TP + 1);
+    as.vop2(VOP2_ADD_F32, "v_add_f32_e32", VLSUM, V(VLSUM), TP);
+    const bool rev = root.k == G_VAL && hasc[root.v];  // else: no constant to seed
+    free_values_at(n);
+    free_feats_at(n);
+    if (rev) {
+      bool rcalls = false;
+      for (int i = m0; i < n; ++i)
+        rcalls = rcalls || (hasc[i] && (ops[i].kind == K_BIN ? ops[i].op == SRHIP_BOP_POW
+                                                             : (ops[i].op == SRHIP_UOP_SIN || ops[i].op == SRHIP_UOP_COS)));
+      sreg = SEED_TMP;
+      if (rcalls) {
+        sblk = free_block();
+        if (sblk < 0) { why = "register pool exhausted"; return false; }
+        owner[sblk] = SEED_OWNER;
+        sreg = blk_reg(sblk);
+      }
+      for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", sreg + e, K(lroot.p ? 0x3f800000u : 0u));
+      if (lroot.k == G_VAL && !lroot.p && hasc[lroot.v]) {  // the adjoint of the loss's root: 1
+        Adj a;
+        a.reg = XS0;
+        if (rcalls) {
+          a.blk = new_adj_block(lroot.v);
+          if (a.blk < 0) return false;
+          a.reg = blk_reg(a.blk);
+        }
+        for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", a.reg + e, K(0x3f800000u));
+        adj[lroot.v] = a;
+      }
+    }
+    for (int i = n - 1; i >= m0; --i) {
+      if (rev && hasc[i] && !emit_reverse(i)) return false;
+      free_values_at(bstep(i));
+      free_feats_at(bstep(i));
+    }
+    if (rev) {
+      emit_mask(sreg);
+      mov4(VY, sreg);
+      if (sblk >= 0) owner[sblk] = -1;
+      sblk = -1;
+    }
+    if (calls) as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHK, V(VCHKSAVE));
     return true;
   }
   // (dv) One channel of a derivative objective: Σ w·ℓ(r) over the lane's 4 rows added into
@@ -1225,9 +1442,9 @@ using ColIndex = std::unordered_map<std::string, int>;
 // code with its columns does not fit (register pool) is compiled without them.
 bool gen_grad_tree(const Ins<float>* prog, int nc, const Tmpl& T, bool text, std::vector<uint32_t>& out,
                    std::vector<std::string>* lines, int32_t* off, std::string* why, int loss, uint64_t lparam,
-                   const ColIndex* gidx, const DerivSpec* dv = nullptr) {
+                   const ColIndex* gidx, const DerivSpec* dv = nullptr, const LossIR* lx = nullptr) {
   if (nc > NGACC) { *why = "more constants than accumulators"; return false; }
-  if (dv ? !deriv_spec_fits(*dv) : !has_dloss_routine(loss)) { *why = "loss without gradient routines"; return false; }
+  if (dv ? !deriv_spec_fits(*dv) : !lx && !has_dloss_routine(loss)) { *why = "loss without gradient routines"; return false; }
   std::vector<GOp> ir;
   GOpnd root;
   if (!build_gir(prog, ir, root, why)) return false;
@@ -1251,7 +1468,7 @@ bool gen_grad_tree(const Ins<float>* prog, int nc, const Tmpl& T, bool text, std
     g.nc = nc;
     g.loss = loss;
     g.lparam = lparam;
-    ok = g.emit_tree();
+    ok = (!lx || g.append_loss(*lx)) && g.emit_tree();
     if (!ok) *why = g.why;
   }
   if (!ok) return false;
@@ -1276,7 +1493,7 @@ size_t grad_codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>& 
                     const std::vector<int32_t>& cand, size_t from, bool text, std::vector<uint32_t>& words,
                     std::vector<std::string>* lines, std::vector<int32_t>& offs, std::vector<int32_t>& ok_trees,
                     std::vector<int32_t>& rest, GradStats* st, const Tmpl& T, int loss, uint64_t lparam,
-                    const ColIndex* gidx, const DerivSpec* dv = nullptr) {
+                    const ColIndex* gidx, const DerivSpec* dv = nullptr, const LossIR* lx = nullptr) {
   for (size_t k = from; k < cand.size(); ++k) {
     const int32_t t = cand[k];
     int32_t off = -1;
@@ -1285,7 +1502,7 @@ size_t grad_codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>& 
     const size_t lbefore = lines ? lines->size() : 0;
     const int nc = const_off[t + 1] - const_off[t];
     const bool okc = cb.tree_off[t] >= 0 && gen_grad_tree(&cb.code[cb.tree_off[t]], nc, T, text, words, lines, &off, &why,
-                                                                  loss, lparam, gidx, dv);
+                                                                  loss, lparam, gidx, dv, lx);
     if (okc && words.size() * 4 > T.area_bytes) {  // area full: the next part takes it
       words.resize(before);
       if (lines) lines->resize(lbefore);
@@ -1362,7 +1579,8 @@ namespace {
 struct Chunk { std::vector<uint32_t> words; std::vector<int32_t> offs, slots; const Tmpl* T; };
 std::vector<Chunk> build_chunks(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
                                 const std::vector<int32_t>& cand, std::vector<int32_t>& rest, GradStats* st, int loss,
-                                uint64_t lparam, const ColIndex* gi, const DerivSpec* dv, size_t* total_bytes) {
+                                uint64_t lparam, const ColIndex* gi, const DerivSpec* dv, size_t* total_bytes,
+                                const LossIR* lx = nullptr) {
   const Templates& TT = templates();
   std::vector<Chunk> chunks;
   size_t pos = 0;
@@ -1371,7 +1589,7 @@ std::vector<Chunk> build_chunks(const CompiledBatch<float>& cb, const std::vecto
     Chunk ch;
     ch.T = &TT.large;
     const size_t next = grad_codegen(cb, const_off, cand, pos, false, ch.words, nullptr, ch.offs, ch.slots, rest, st,
-                                     TT.large, loss, lparam, gi, dv);
+                                     TT.large, loss, lparam, gi, dv, lx);
     if (next == pos) { rest.push_back(cand[pos]); if (st) st->nrejected++; pos = next + 1; continue; }  // one tree > area
     if ((int)chunks.size() + 1 == kMaxGradParts && next < cand.size()) {  // the rest stays interpreted
       for (size_t k = next; k < cand.size(); ++k) rest.push_back(cand[k]);
@@ -1386,7 +1604,7 @@ std::vector<Chunk> build_chunks(const CompiledBatch<float>& cb, const std::vecto
       sm.T = &TT.small;
       std::vector<int32_t> rs;
       grad_codegen(cb, const_off, ch.slots, 0, false, sm.words, nullptr, sm.offs, sm.slots, rs, nullptr, TT.small, loss,
-                   lparam, gi, dv);
+                   lparam, gi, dv, lx);
       if (sm.slots != ch.slots) throw Error(SRHIP_ERR_INVALID, "jit-grad: small-template relayout differs");
       ch = std::move(sm);
     }
@@ -1400,16 +1618,20 @@ std::vector<Chunk> build_chunks(const CompiledBatch<float>& cb, const std::vecto
 
 GradModule* build_grad(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
                        const std::vector<int32_t>& cand, std::vector<int32_t>& jit_list, std::vector<int32_t>& rest,
-                       GradStats* st, int loss, uint64_t lparam) {
+                       GradStats* st, int loss, uint64_t lparam, const LossExpr* lexpr) {
   const Templates& TT = templates();
   if (!TT.ok) { rest = cand; return nullptr; }
+  LossIR lir;
+  std::string lwhy;
+  if (lexpr && !build_loss_ir(*lexpr, lir, &lwhy)) { rest = cand; return nullptr; }
   auto t0 = std::chrono::steady_clock::now();
   Columns cols = plan_grad_columns(cb, cand);
   ColIndex gidx;
   for (int g = 0; g < cols.ngcol; ++g) gidx.emplace(cols.gkey[g], g);
   const ColIndex* gi = gidx.empty() ? nullptr : &gidx;
   size_t bytes = 0;
-  std::vector<Chunk> chunks = build_chunks(cb, const_off, cand, rest, st, loss, lparam, gi, nullptr, &bytes);
+  std::vector<Chunk> chunks = build_chunks(cb, const_off, cand, rest, st, loss, lparam, gi, nullptr, &bytes,
+                                           lexpr ? &lir : nullptr);
   if (chunks.empty()) return nullptr;
   auto t1 = std::chrono::steady_clock::now();
   GradModule* m = new GradModule();
@@ -1453,6 +1675,12 @@ void destroy_grad(GradModule* m) {
 bool has_dloss_routine(int loss) {
   return loss == SRHIP_LOSS_L2 ||
          (loss >= 0 && loss < SRHIP_MARGIN_LOSS_BEGIN && kGradLossRoutine[loss] >= 0 && kDLossRoutine[loss] >= 0);
+}
+
+bool loss_expr_grad_fits(const LossExpr& lx) {
+  LossIR lir;
+  std::string why;
+  return templates().ok && build_loss_ir(lx, lir, &why) && (int)lir.cbits.size() <= NGACC;
 }
 
 int grad_nslots(const GradModule* m) { return m ? m->nslots : 0; }
@@ -1513,9 +1741,12 @@ hipError_t launch_grad_code(GradModule* m, int part, const EvalPlan& plan, const
 
 bool compile_grad_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
                        const std::vector<int32_t>& cand, std::vector<uint8_t>* bytes, std::string* text,
-                       std::vector<int32_t>* offsets, GradStats* st, int loss, uint64_t lparam) {
+                       std::vector<int32_t>* offsets, GradStats* st, int loss, uint64_t lparam, const LossExpr* lexpr) {
   const Templates& TT = templates();
   if (!TT.ok) throw Error(SRHIP_ERR_UNSUPPORTED, std::string("jit templates unavailable: ") + TT.why);
+  LossIR lir;
+  std::string lwhy;
+  if (lexpr && !build_loss_ir(*lexpr, lir, &lwhy)) throw Error(SRHIP_ERR_UNSUPPORTED, "no gradient tree code for this expression loss: " + lwhy);
   std::vector<uint32_t> words;
   std::vector<std::string> lines;
   std::vector<int32_t> offs, okt, rest;
@@ -1523,7 +1754,7 @@ bool compile_grad_only(const CompiledBatch<float>& cb, const std::vector<int32_t
   ColIndex gidx;
   for (int g = 0; g < cols.ngcol; ++g) gidx.emplace(cols.gkey[g], g);
   grad_codegen(cb, const_off, cand, 0, text != nullptr, words, text ? &lines : nullptr, offs, okt, rest, st, TT.large, loss,
-               lparam, gidx.empty() ? nullptr : &gidx);
+               lparam, gidx.empty() ? nullptr : &gidx, nullptr, lexpr ? &lir : nullptr);
   if (bytes) {
     bytes->resize(words.size() * 4);
     std::memcpy(bytes->data(), words.data(), bytes->size());

@@ -254,9 +254,10 @@ end
 # "expression losses") ----------------------------------------------------------
 const SRHIP_EXPR_LOSS_BEGIN = Int32(1024)  # loss kinds from here on are handles of expression losses
 const SRHIP_LOSS_EXPR_TREE_CODE = UInt32(1)  # srhip_loss_expr_create_ex: Float32 loss tree code may run the handle
+const SRHIP_LOSS_EXPR_GRAD_TREE_CODE = UInt32(4)  # ... and the Float32 gradient tree code (constant optimisation)
 
 """
-    ExprLoss(tree::Node{T}, operators; tree_code=false)
+    ExprLoss(tree::Node{T}, operators; tree_code=false, grad_tree_code=false)
 
 A custom `elementwise_loss` as a tree over x1 = the prediction, x2 = the target
 and x3 = the weight, built with `operators` (an `OperatorEnum`, e.g.
@@ -267,7 +268,9 @@ function `(x, y)` / `(x, y, w)`, so the reference's CPU path
 values as they are: a weighted loss multiplies by x3 itself, and a tree that
 reads x3 needs a weighted dataset. `tree_code=true` lets the Float32 loss tree
 code run the expression at the end of its tiles (srhip.h lists what stays
-interpreted); the results obey the same contract.
+interpreted); the results obey the same contract. `grad_tree_code=true` does the
+same for the constants' gradients: the Float32 gradient tree code runs the
+expression's forward and reverse sweep inside its tiles.
 """
 mutable struct ExprLoss{T,O} <: Function
     tree::Node{T}
@@ -276,6 +279,17 @@ mutable struct ExprLoss{T,O} <: Function
 end
 
 function ExprLoss(tree::Node{T}, operators; tree_code::Bool=false) where {T}
+    return expr_loss(tree, operators, tree_code ? SRHIP_LOSS_EXPR_TREE_CODE : UInt32(0))
+end
+
+# the operator enums of DynamicExpressions (what `options.operators` is): both keywords
+function ExprLoss(tree::Node{T}, operators::DynamicExpressions.AbstractOperatorEnum; tree_code::Bool=false,
+                  grad_tree_code::Bool=false) where {T}
+    return expr_loss(tree, operators, (tree_code ? SRHIP_LOSS_EXPR_TREE_CODE : UInt32(0)) |
+                                      (grad_tree_code ? SRHIP_LOSS_EXPR_GRAD_TREE_CODE : UInt32(0)))
+end
+
+function expr_loss(tree::Node{T}, operators, flags::UInt32) where {T}
     bin = [op_id(op, 2) for op in operators.binops]
     una = [op_id(op, 1) for op in operators.unaops]
     kind = UInt8[]; arg = UInt16[]; consts = Float64[]
@@ -294,10 +308,10 @@ function ExprLoss(tree::Node{T}, operators; tree_code::Bool=false) where {T}
     end
     visit(tree)
     h = Ref{Int32}(0)
-    if tree_code
+    if flags != 0
         check(ccall((:srhip_loss_expr_create_ex, libsrhip), Int32,
                     (Ptr{UInt8}, Ptr{UInt16}, Int32, Ptr{Float64}, Int32, UInt32, Ptr{Int32}),
-                    kind, arg, Int32(length(kind)), consts, Int32(length(consts)), SRHIP_LOSS_EXPR_TREE_CODE, h))
+                    kind, arg, Int32(length(kind)), consts, Int32(length(consts)), flags, h))
     else
         check(ccall((:srhip_loss_expr_create, libsrhip), Int32,
                     (Ptr{UInt8}, Ptr{UInt16}, Int32, Ptr{Float64}, Int32, Ptr{Int32}),

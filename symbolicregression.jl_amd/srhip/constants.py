@@ -26,6 +26,7 @@ MARGIN_LOSS_BEGIN = LOSS["ZEROONE"]
 # loss kinds from here on are handles of expression losses (srhip_loss_expr_create)
 EXPR_LOSS_BEGIN = 1024
 LOSS_EXPR_TREE_CODE = 1  # srhip_loss_expr_create_ex flag: Float32 loss tree code may run the handle
+LOSS_EXPR_GRAD_TREE_CODE = 4  # ... flag: the Float32 gradient tree code may run the handle (2 is invalid)
 # operator ids from here on are handles of expression operators (srhip_op_expr_create)
 EXPR_OP_BEGIN = 1024
 

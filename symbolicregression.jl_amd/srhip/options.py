@@ -138,12 +138,15 @@ class ExprLoss:
     `tree_code=True` (SRHIP_LOSS_EXPR_TREE_CODE) lets the Float32 loss tree code
     run the expression at the end of its tiles instead of handing the whole call
     to the interpreter; the contract is the same, and srhip.h lists the calls
-    that stay interpreted."""
+    that stay interpreted. `grad_tree_code=True` (SRHIP_LOSS_EXPR_GRAD_TREE_CODE,
+    independent of the first) lets the Float32 gradient tree code compute the
+    loss sums and the constants' gradients under the expression (constant
+    optimisation's gradient phases) instead of the forward-mode interpreter."""
 
     param = 0.0
     params = None  # no parameter: the engine ignores loss_params for these kinds
 
-    def __init__(self, tree, options, tree_code=False):
+    def __init__(self, tree, options, tree_code=False, grad_tree_code=False):
         import ctypes as C
         import weakref
 
@@ -160,9 +163,11 @@ class ExprLoss:
         check(lib().srhip_loss_expr_create_ex(kind.ctypes.data_as(C.POINTER(C.c_uint8)),
                                               arg.ctypes.data_as(C.POINTER(C.c_uint16)), int(len(kind)),
                                               consts.ctypes.data_as(C.POINTER(C.c_double)), int(len(consts)),
-                                              K.LOSS_EXPR_TREE_CODE if tree_code else 0, C.byref(out)))
+                                              (K.LOSS_EXPR_TREE_CODE if tree_code else 0) |
+                                              (K.LOSS_EXPR_GRAD_TREE_CODE if grad_tree_code else 0), C.byref(out)))
         self.kind = int(out.value)
         self.tree_code = bool(tree_code)
+        self.grad_tree_code = bool(grad_tree_code)
         self.tree = tree
         self.uses_weights = bool(np.any((kind == K.NODE_FEATURE) & (arg == 2)))
         self._finalizer = weakref.finalize(self, _destroy_expr_loss, self.kind)
