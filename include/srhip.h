@@ -412,6 +412,14 @@ int32_t srhip_program_create(srhip_ctx* ctx, int32_t dtype,
  * or on any other call. The value is bit 5: bits 3 and 4 stay unknown flags
  * (SRHIP_ERR_INVALID), as callers of earlier versions were told. */
 #define SRHIP_PROGRAM_DERIV_TREE_CODE 0x20u
+/* SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE (opt-in): srhip_eval_objective_grad_deriv on this
+ * program may run the objective's gradient tree code ("sr_jit_deriv_grad" /
+ * "sr_jit_deriv_grad_w") in place of the second-order interpreter; see
+ * that call. Built per (dir, feature count, weights, loss, parameter) at the first such
+ * call, kept with the program, constants and coefficients read at run time. Independent of
+ * SRHIP_PROGRAM_DERIV_TREE_CODE; no effect on Float64 programs or on any other call.
+ * Refused (SRHIP_ERR_UNSUPPORTED) for a device-group program. */
+#define SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE 0x40u
 int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees* trees, uint32_t flags,
                                 srhip_program** out_prog);
 int32_t srhip_program_destroy(srhip_program* prog);
@@ -735,6 +743,37 @@ int32_t srhip_eval_loss_grad_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, 
                                              int32_t loss_kind, const double* loss_params, const int32_t* dir,
                                              int32_t ndir, double* out_loss_sum, double* out_grad_sum,
                                              double* out_weight_sum, uint8_t* out_ok);
+/* The whole objective's gradient in one call: with q_c = coef[c] / out_weight_sum[c],
+ * out_grad [const_off[ntrees]] = Σ_c q_c · (column c of srhip_eval_loss_grad_deriv's
+ * out_grad_sum) in float64, beside out_loss_sum [ntrees][1 + ndir] (that call's sums).
+ * On a Float32 program made with SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE, under the limits of
+ * srhip_eval_loss_deriv's tree code (ndir <= 4, a distance loss with a derivative routine,
+ * never Periodic, a tile of at most 64 arrays, <= 16 constants per tree), every tree the
+ * code generator takes runs as tree code: per tile a forward pass, a reverse pass to the
+ * direction leaves (the channel sums and the seeds s_c = q_c·w_c·ℓ'), a forward tangent
+ * along Σ_k s_k e_dir[k] and one reverse sweep over (value, tangent) to the constants,
+ * whatever ndir and the constant count (operators + - * / neg abs square cube exp sin
+ * cos log sqrt; q_c rounded once to float). Its loss sums equal srhip_eval_loss_deriv's
+ * tree code bit for bit. Trees it refuses run "grad_kernel_deriv2<float>" in the same
+ * call, launched first, their columns combined with q_c in float64; without the flag or
+ * past a limit every tree does, and srhip_last_tree_code gives 0. A subtree without a
+ * direction feature contributes an exact 0 tangent where forward mode computes 0·∞ = NaN.
+ * Refusals (outputs untouched): those of srhip_eval_loss_grad_deriv, coef NULL or not
+ * finite. srhip_last_tree_code gives the compiled tree count. When both paths run in one
+ * call, srhip_last_kernel_time covers the launches of both and srhip_last_kernel_name gives
+ * the tree code's driver (launched last). The float64
+ * combination rounds each product q_c·column_c and adds them in channel order. */
+int32_t srhip_eval_objective_grad_deriv(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                        const double* loss_params, const int32_t* dir, int32_t ndir,
+                                        const double* coef /*[1 + ndir]*/, double* out_loss_sum,
+                                        double* out_grad /*[const_off[ntrees]]*/, double* out_weight_sum,
+                                        uint8_t* out_ok);
+/* The same on a temporary program of `trees`; flags: SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE or 0 */
+int32_t srhip_eval_objective_grad_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                                  int32_t loss_kind, const double* loss_params, const int32_t* dir,
+                                                  int32_t ndir, const double* coef, uint32_t flags,
+                                                  double* out_loss_sum, double* out_grad, double* out_weight_sum,
+                                                  uint8_t* out_ok);
 /* Per row, for few trees: out_deriv [ntrees][ndir][rows] = ∂ŷ/∂x_dir[k] and out_mixed
  * [const_off[ntrees]][ndir][rows] = ∂²ŷ/∂x_dir[k]∂c_j, of the dataset's dtype (the
  * companion of srhip_eval_grad_tree_array; "grad_kernel_deriv2_out<float>"). Any
@@ -851,6 +890,15 @@ int32_t srhip_optimize_constants_deriv(srhip_ctx* ctx, srhip_dataset* ds, const 
                                        const srhip_constopt_options* opts, const int32_t* dir, int32_t ndir,
                                        const double* coef /* [1 + ndir] */, void* out_consts, double* out_loss,
                                        uint8_t* out_converged, double* out_num_evals);
+/* srhip_optimize_constants_deriv with flags: 0 is that call. With
+ * SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE the evaluation sets' programs are made with both
+ * derivative tree-code flags: loss-only phases run srhip_eval_loss_deriv's tree code,
+ * gradient phases srhip_eval_objective_grad_deriv, whose out_grad is the gradient as it
+ * stands (the two phases' loss sums agree bit for bit). Any other bit: SRHIP_ERR_INVALID. */
+int32_t srhip_optimize_constants_deriv_ex(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                          const srhip_constopt_options* opts, const int32_t* dir, int32_t ndir,
+                                          const double* coef /* [1 + ndir] */, uint32_t flags, void* out_consts,
+                                          double* out_loss, uint8_t* out_converged, double* out_num_evals);
 /* Where the last srhip_optimize_constants_batch call of this thread spent
  * its time: out[0..8] = total, program builds, set_constants, loss calls,
  * gradient calls, the kernels inside those calls (HIP events) — seconds —
@@ -858,7 +906,9 @@ int32_t srhip_optimize_constants_deriv(srhip_ctx* ctx, srhip_dataset* ds, const 
  * rebuilds inside set_constants, then the builds' tree-code generation and
  * code-object load times (s), then (srhip_optimize_constants_rowsets) the
  * sets' sample gathers (s) and the number of evaluations run on row segments
- * (the first n of these 14 written). The rest of the total is the host
+ * and (srhip_optimize_constants_deriv_ex) the number of gradient calls in
+ * which the objective's gradient tree code ran
+ * (the first n of these 15 written). The rest of the total is the host
  * optimiser's own algebra. */
 int32_t srhip_constopt_profile(double* out, int32_t n);
 /* The same optimiser over any evaluator (row-sharded datasets whose partials
@@ -1069,6 +1119,12 @@ int32_t srhip_jit_compile_deriv(const srhip_trees* trees, const int32_t* dir, in
                                 int32_t weighted, int32_t loss, double loss_param, uint8_t* out_bytes,
                                 int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
                                 int64_t* inout_noffsets);
+/* Testing hook, same contract: the objective's gradient tree code
+ * (srhip_eval_objective_grad_deriv on a SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE program). */
+int32_t srhip_jit_compile_deriv_grad(const srhip_trees* trees, const int32_t* dir, int32_t ndir, int32_t nfeat,
+                                     int32_t weighted, int32_t loss, double loss_param, uint8_t* out_bytes,
+                                     int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext,
+                                     int32_t* out_offsets, int64_t* inout_noffsets);
 /* Testing hook, same contract: the loss tree code (grad = 0; fast: its
  * guarded FAST path) or the gradient tree code (grad = 1) of Float32 trees
  * for the elementwise loss `loss` (SRHIP_LOSS_*) with its parameter; fast

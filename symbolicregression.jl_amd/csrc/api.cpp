@@ -408,6 +408,7 @@ struct srhip_program {
   // the trees alone (constants are read from d_gconsts, uploaded when they differ from
   // dj_consts), so it outlives set_constants; jl: its trees, in_jit: per tree
   bool deriv_tc = false;
+  bool deriv_gtc = false;  // SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE: srhip_eval_objective_grad_deriv's (specs with grad set)
   struct DerivJit { jit::DerivSpec sp; jit::DerivModule* m; std::vector<int32_t> jl; std::vector<uint8_t> in_jit; };
   std::vector<DerivJit> djit;
   std::vector<unsigned char> dj_consts;
@@ -3047,8 +3048,8 @@ int eval_loss_grad_targets_impl(srhip_dataset* ds, srhip_program* p, int loss, c
 // directions, Periodic or a loss without an ℓ routine, a dataset whose runs are wide or
 // whose tile does not fit the code's literal offsets, no tree that compiles).
 srhip_program::DerivJit* deriv_module(srhip_program* p, const srhip_dataset* ds, int loss, const double* params,
-                                      const int32_t* dir, int ndir) {
-  if (!p->deriv_tc || p->dtype != SRHIP_F32 || ndir > jit::kDerivMaxDir || wide_mode() == 1 || !jit::available())
+                                      const int32_t* dir, int ndir, bool grad = false) {
+  if (!(grad ? p->deriv_gtc : p->deriv_tc) || p->dtype != SRHIP_F32 || ndir > jit::kDerivMaxDir || wide_mode() == 1 || !jit::available())
     return nullptr;
   jit::DerivSpec sp;
   sp.ndir = ndir;
@@ -3057,6 +3058,7 @@ srhip_program::DerivJit* deriv_module(srhip_program* p, const srhip_dataset* ds,
   sp.weighted = ds->w != nullptr;
   sp.loss = loss;
   sp.lparam = loss == SRHIP_LOSS_L2 ? 0 : bits_of(params ? params[0] : 0.0);
+  sp.grad = grad;
   EvalPlan probe;  // the row tile in LDS: the same verdict for every tree count
   if (!jit::deriv_spec_fits(sp) ||
       !plan_geometry(4, 4, kShallowSlots, jit::deriv_narr(sp), 1, ds->rows, 1, &probe, gjit_tile_budget()))
@@ -3280,7 +3282,7 @@ void check_deriv2_fits(const srhip_dataset* ds, int ndir) {
 template <typename T>
 int run_deriv2(srhip_dataset* ds, srhip_program* p, int mode, int loss, const double* params, const int32_t* dir,
                int ndir, double* out_loss, double* out_grad, double* out_wsum, void* out_deriv, void* out_mixed,
-               uint8_t* out_ok) {
+               uint8_t* out_ok, const std::vector<uint8_t>* skip = nullptr) {  // skip[t]: not run (its outputs: unspecified)
   srhip_ctx* c = p->ctx;
   build_grad_program<T>(p, false);
   hipStream_t s = c->stream;
@@ -3297,7 +3299,7 @@ int run_deriv2(srhip_dataset* ds, srhip_program* p, int mode, int loss, const do
     gc_of[cl] = GC;
     std::vector<int32_t> ts;
     for (int t = 0; t < nt; ++t)
-      if (p->g_class[t] == cl) ts.push_back(t);
+      if (p->g_class[t] == cl && !(skip && (*skip)[t])) ts.push_back(t);
     std::stable_sort(ts.begin(), ts.end(), [&](int32_t x, int32_t y) { return p->g_cost[x] > p->g_cost[y]; });
     int n = 0;
     for (int32_t t : ts) {
@@ -3430,6 +3432,137 @@ int run_deriv2(srhip_dataset* ds, srhip_program* p, int mode, int loss, const do
   }
   if (out_wsum)
     for (int k = 0; k < ncol; ++k) out_wsum[k] = !ds->w ? (double)rows : ds->t_sum_w[(size_t)k];
+  return SRHIP_OK;
+}
+
+// The objective's gradient tree code of one call (deriv_module with grad): per code object the
+// driver and its finalize kernel, into d_sum [nt][1 + ndir], d_grad [nconst] and the ok bytes.
+// The plans are run_deriv_tree_code's, so the loss sums are that call's bit for bit.
+bool run_deriv_grad_tree_code(srhip_ctx* c, srhip_program* p, const srhip_dataset* ds, srhip_program::DerivJit* dj,
+                              int loss, const float* q, double* d_sum, double* d_grad, hipStream_t s) {
+  jit::DerivModule* m = dj->m;
+  const int nparts = jit::deriv_nparts(m), ndir = dj->sp.ndir, nconst = p->const_off.back();
+  std::vector<EvalPlan> plans(nparts);
+  size_t maxslots = 0, maxg = 0;
+  for (int k = 0; k < nparts; ++k) {
+    int s0, nsl;
+    jit::deriv_part(m, k, &s0, &nsl);
+    if (!plan_geometry(4, 4, kShallowSlots, jit::deriv_narr(dj->sp), 1, ds->rows, nsl, &plans[k], gjit_tile_budget()))
+      return false;
+    maxslots = std::max(maxslots, (size_t)plans[k].nrg * nsl);
+    maxg = std::max(maxg, (size_t)plans[k].nrg * (size_t)std::max(nconst, 1));
+  }
+  if (p->dj_consts != p->consts || !p->d_gconsts) {
+    upload_gconsts(p);
+    p->dj_consts = p->consts;
+  }
+  const int nsl_all = jit::deriv_nslots(m);
+  c->fail.ensure((size_t)nsl_all * sizeof(uint32_t));
+  c->fail_clean = false;
+  HIP_CHECK(hipMemsetAsync(c->fail.p, 0, (size_t)nsl_all * sizeof(uint32_t), s));
+  c->gpart.ensure(maxslots * (sizeof(Part<float>) + (size_t)ndir * sizeof(float)) + maxg * sizeof(float));
+  Part<float>* part = static_cast<Part<float>*>(c->gpart.p);
+  float* dpart = reinterpret_cast<float*>(part + maxslots);
+  float* gpart = dpart + maxslots * (size_t)ndir;
+  for (int k = 0; k < nparts; ++k) {
+    int s0, nsl;
+    jit::deriv_part(m, k, &s0, &nsl);
+    const EvalPlan& plan = plans[k];
+    EvalArgs<float> a;
+    std::memset(&a, 0, sizeof(a));
+    a.fail = static_cast<uint32_t*>(c->fail.p) + s0;
+    a.nlist = nsl;
+    a.X = static_cast<const float*>(ds->X);
+    a.y = static_cast<const float*>(ds->y);
+    a.w = static_cast<const float*>(ds->w);
+    a.n = ds->rows;
+    a.n_pad = ds->n_pad;
+    a.nfeat = ds->nfeat;
+    a.ntiles = plan.ntiles;
+    a.ntg = plan.ntg;
+    a.tpb = plan.tpb;
+    a.nrg = plan.nrg;
+    a.loss = loss;
+    const int tk = timed_begin(c, s);
+    HIP_CHECK(jit::launch_deriv_grad_code(m, k, plan, a, p->d_gconsts, q, part, dpart, gpart, nconst, s));
+    timed_end(c, s, tk);
+    HIP_CHECK(jit::launch_deriv_grad_finalize(m, k, plan.nrg, a.fail, part, dpart, gpart, nconst, d_sum, d_grad,
+                                              static_cast<uint8_t*>(c->oks.p), s));
+    note_loss_launch(plan.nrg, plan.ntg, plan.tpb, (unsigned)plan.nrg * (unsigned)plan.ntg, plan.nrg, 1);
+  }
+  return true;
+}
+
+// srhip_eval_objective_grad_deriv (checked by the caller). Trees outside the tree code (all of
+// them without the flag or past a limit) run run_deriv2 first, their columns combined with
+// q_c = coef_c / wsum_c in float64 in channel order; the others run the gradient tree code.
+template <typename T>
+int eval_objective_grad_deriv_impl(srhip_dataset* ds, srhip_program* p, int loss, const double* params,
+                                   const int32_t* dir, int ndir, const double* coef, double* out_sum, double* out_grad,
+                                   double* out_wsum, uint8_t* out_ok) {
+  srhip_ctx* c = p->ctx;
+  const int nt = p->ntrees, ncol = 1 + ndir, nconst = p->const_off.back();
+  const int64_t rows = ds->rows;
+  check_deriv2_fits(ds, ndir);  // (the interpreter's share and the wide refusal, before any launch)
+  std::vector<double> ws(ncol), q(ncol);
+  for (int k = 0; k < ncol; ++k) {
+    ws[k] = !ds->w ? (double)rows : ds->t_sum_w[(size_t)k];
+    q[k] = coef[k] / ws[k];
+  }
+  build_grad_program<T>(p, false);
+  srhip_program::DerivJit* dj = nullptr;
+  if constexpr (std::is_same<T, float>::value) {
+    if (rows > 0 && nt > 0) dj = deriv_module(p, ds, loss, params, dir, ndir, true);
+  }
+  int nrest = 0;
+  for (int t = 0; t < nt; ++t) nrest += !(dj && dj->in_jit[t]);
+  std::vector<double> sums((size_t)std::max(nt, 1) * ncol, 0.0), grad((size_t)std::max(nconst, 1), 0.0);
+  std::vector<uint8_t> ok((size_t)std::max(nt, 1), 1);
+  const bool interp = nrest > 0 || !dj;
+  if (interp) {
+    std::vector<double> cols((size_t)std::max(nconst, 1) * ncol, 0.0);
+    run_deriv2<T>(ds, p, DERIV2_LOSS, loss, params, dir, ndir, sums.data(), cols.data(), nullptr, nullptr, nullptr,
+                  ok.data(), dj ? &dj->in_jit : nullptr);
+    for (int j = 0; j < nconst; ++j) {
+#pragma clang fp contract(off)  // each product rounded, then added in channel order: a caller can repeat it exactly
+      double g = 0.0;
+      for (int k = 0; k < ncol; ++k) {
+        const double term = q[k] * cols[(size_t)j * ncol + k];
+        g += term;
+      }
+      grad[(size_t)j] = g;
+    }
+  }
+  c->last_jit_trees = 0;
+  if (dj) {
+    hipStream_t s = c->stream;
+    if (!interp) timing_reset(c);  // (else the interpreter's launches of this call stay in the time)
+    float qf[1 + jit::kDerivMaxDir] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < ncol; ++k) qf[k] = (float)q[k];
+    c->dloss.ensure(std::max<size_t>((size_t)nt * ncol + (size_t)nconst, 1) * sizeof(double));
+    c->oks.ensure(std::max<size_t>(nt, 1));
+    double* d_sum = static_cast<double*>(c->dloss.p);
+    double* d_grad = d_sum + (size_t)nt * ncol;
+    if (!run_deriv_grad_tree_code(c, p, ds, dj, loss, qf, d_sum, d_grad, s)) throw_lds(ds->nfeat);
+    std::vector<double> hs((size_t)nt * ncol), hg((size_t)std::max(nconst, 1));
+    c->h_ok.assign(nt, 1);
+    HIP_CHECK(hipMemcpyAsync(hs.data(), d_sum, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (nconst > 0) HIP_CHECK(hipMemcpyAsync(hg.data(), d_grad, (size_t)nconst * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(c->h_ok.data(), c->oks.p, nt, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    timing_finish(c);
+    c->last_jit_trees = (int)dj->jl.size();
+    for (int32_t t : dj->jl) {
+      const bool fail = p->g_static_fail[t] || !c->h_ok[t];
+      ok[t] = fail ? 0 : 1;
+      for (int k = 0; k < ncol; ++k) sums[(size_t)t * ncol + k] = fail ? NAN : hs[(size_t)t * ncol + k];
+      for (int j = p->const_off[t]; j < p->const_off[t + 1]; ++j) grad[(size_t)j] = fail ? NAN : hg[(size_t)j];
+    }
+  }
+  if (out_ok) std::copy(ok.begin(), ok.begin() + nt, out_ok);
+  if (out_sum) std::copy(sums.begin(), sums.begin() + (size_t)nt * ncol, out_sum);
+  if (out_grad) std::copy(grad.begin(), grad.begin() + nconst, out_grad);
+  if (out_wsum) std::copy(ws.begin(), ws.end(), out_wsum);
   return SRHIP_OK;
 }
 
@@ -4002,7 +4135,7 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
     if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
     if (trees->ntrees < 0) throw Error(SRHIP_ERR_INVALID, "negative tree count");
     if (flags & ~(SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED | SRHIP_PROGRAM_WIDE_TREE_CODE |
-                  SRHIP_PROGRAM_DERIV_TREE_CODE))
+                  SRHIP_PROGRAM_DERIV_TREE_CODE | SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE))
       throw Error(SRHIP_ERR_INVALID, "unknown program flags");
     const int nt = trees->ntrees;
     auto* p = new srhip_program();
@@ -4013,6 +4146,7 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
     if (flags & SRHIP_PROGRAM_INTERPRETED) p->jit_allowed = false;
     p->wide_tc = (flags & SRHIP_PROGRAM_WIDE_TREE_CODE) != 0 && dtype == SRHIP_F32;
     p->deriv_tc = (flags & SRHIP_PROGRAM_DERIV_TREE_CODE) != 0 && dtype == SRHIP_F32;
+    p->deriv_gtc = (flags & SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE) != 0 && dtype == SRHIP_F32;
     try {
       if (nt > 0) {
         if (!trees->node_off || !trees->const_off) throw Error(SRHIP_ERR_INVALID, "null offsets");
@@ -4393,6 +4527,38 @@ int32_t srhip_eval_loss_grad_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, 
   });
 }
 
+int32_t srhip_eval_objective_grad_deriv(srhip_dataset* ds, const srhip_program* prog, int32_t loss_kind,
+                                        const double* loss_params, const int32_t* dir, int32_t ndir, const double* coef,
+                                        double* out_loss_sum, double* out_grad, double* out_weight_sum,
+                                        uint8_t* out_ok) {
+  return guarded([&] {
+    check_program_vs_dataset(ds, prog, true);
+    check_deriv(ds, prog, loss_kind, loss_params, dir, ndir);
+    if (!coef) throw Error(SRHIP_ERR_INVALID, "coef is NULL");
+    for (int k = 0; k <= ndir; ++k)
+      if (!std::isfinite(coef[k])) throw Error(SRHIP_ERR_INVALID, "coefficient " + std::to_string(k) + " is not finite");
+    CALL_SCOPE(prog->ctx);
+    auto* p = const_cast<srhip_program*>(prog);  // gradient programs are built lazily
+    return by_dtype(ds->dtype, [&](auto t) {
+      return eval_objective_grad_deriv_impl<decltype(t)>(ds, p, loss_kind, loss_params, dir, ndir, coef, out_loss_sum,
+                                                         out_grad, out_weight_sum, out_ok);
+    });
+  });
+}
+
+int32_t srhip_eval_objective_grad_deriv_batch_ctx(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                                  int32_t loss_kind, const double* loss_params, const int32_t* dir,
+                                                  int32_t ndir, const double* coef, uint32_t flags,
+                                                  double* out_loss_sum, double* out_grad, double* out_weight_sum,
+                                                  uint8_t* out_ok) {
+  if (!ds) return set_error(SRHIP_ERR_INVALID, "null dataset");
+  if (flags & ~SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE) return set_error(SRHIP_ERR_INVALID, "unknown flags");
+  return with_temp_program(ctx ? ctx : ds->ctx, ds, trees, SRHIP_PROGRAM_INTERPRETED | flags, [&](srhip_program* p) {
+    return srhip_eval_objective_grad_deriv(ds, p, loss_kind, loss_params, dir, ndir, coef, out_loss_sum, out_grad,
+                                           out_weight_sum, out_ok);
+  });
+}
+
 int32_t srhip_eval_mixed_tree_array(srhip_dataset* ds, const srhip_program* prog, const int32_t* dir, int32_t ndir,
                                     void* out_deriv, void* out_mixed, uint8_t* out_ok) {
   return guarded([&] {
@@ -4679,11 +4845,30 @@ int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int
   return jit_compile_hook(trees, 2, out_bytes, inout_nbytes, out_text, inout_ntext, out_offsets, inout_noffsets);
 }
 
+static int32_t jit_compile_deriv_hook(bool grad, const srhip_trees* trees, const int32_t* dir, int32_t ndir,
+                                      int32_t nfeat, int32_t weighted, int32_t loss, double loss_param,
+                                      uint8_t* out_bytes, int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext,
+                                      int32_t* out_offsets, int64_t* inout_noffsets);
 int32_t srhip_jit_compile_deriv(const srhip_trees* trees, const int32_t* dir, int32_t ndir, int32_t nfeat,
                                 int32_t weighted, int32_t loss, double loss_param, uint8_t* out_bytes,
                                 int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
                                 int64_t* inout_noffsets) {
+  return jit_compile_deriv_hook(false, trees, dir, ndir, nfeat, weighted, loss, loss_param, out_bytes, inout_nbytes,
+                                out_text, inout_ntext, out_offsets, inout_noffsets);
+}
+int32_t srhip_jit_compile_deriv_grad(const srhip_trees* trees, const int32_t* dir, int32_t ndir, int32_t nfeat,
+                                     int32_t weighted, int32_t loss, double loss_param, uint8_t* out_bytes,
+                                     int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext,
+                                     int32_t* out_offsets, int64_t* inout_noffsets) {
+  return jit_compile_deriv_hook(true, trees, dir, ndir, nfeat, weighted, loss, loss_param, out_bytes, inout_nbytes,
+                                out_text, inout_ntext, out_offsets, inout_noffsets);
+}
+static int32_t jit_compile_deriv_hook(bool grad, const srhip_trees* trees, const int32_t* dir, int32_t ndir,
+                                      int32_t nfeat, int32_t weighted, int32_t loss, double loss_param,
+                                      uint8_t* out_bytes, int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext,
+                                      int32_t* out_offsets, int64_t* inout_noffsets) {
   jit::DerivSpec sp;
+  sp.grad = grad;
   if (!dir || ndir < 1 || ndir > jit::kDerivMaxDir || nfeat < 1 || loss < 0 || loss >= SRHIP_MARGIN_LOSS_BEGIN)
     return set_error(SRHIP_ERR_UNSUPPORTED, "derivative tree code: 1..4 directions, a distance loss");
   for (int k = 0; k < ndir; ++k)
@@ -4834,6 +5019,7 @@ void write_result(const copt::Result& r, int dtype, void* out_consts, double* ou
 struct CoptProfile {
   double total = 0, create = 0, set = 0, loss = 0, grad = 0, kernel_ms = 0;
   int64_t ncreate = 0, nloss = 0, ngrad = 0, nrebuilt = 0;
+  int64_t ngrad_tc = 0;  // gradient calls of a derivative objective in which tree code ran
   double jit_codegen_ms = 0, jit_load_ms = 0;  // of the builds (tree code)
   // srhip_optimize_constants_rowsets: the sets' gathers (wall), evaluations run on row segments
   double gather = 0;
@@ -5145,13 +5331,15 @@ struct DerivSet : copt::Set {
   const double* coef;
   srhip_program* prog = nullptr;
   std::vector<int32_t> coff;
+  bool tree_code;  // srhip_optimize_constants_deriv_ex: both derivative tree codes, g from the objective's gradient call
   DerivSet(srhip_ctx* c, srhip_dataset* d, const srhip_trees* trees, int ls, const double* pr, const int32_t* dr,
-           int nd, const double* cf, const std::vector<int32_t>& members)
-      : ctx(c), ds(d), dtype(d->dtype), loss(ls), params(pr), dir(dr), ndir(nd), coef(cf) {
+           int nd, const double* cf, const std::vector<int32_t>& members, bool tc)
+      : ctx(c), ds(d), dtype(d->dtype), loss(ls), params(pr), dir(dr), ndir(nd), coef(cf), tree_code(tc) {
     MemberTrees mt(trees, dtype, members);
     coff = mt.coff;
     const auto t0 = std::chrono::steady_clock::now();
-    check_rc(srhip_program_create_ex(ctx, dtype, &mt.tr, SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED,
+    check_rc(srhip_program_create_ex(ctx, dtype, &mt.tr, SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED |
+                                     (tc ? SRHIP_PROGRAM_DERIV_TREE_CODE | SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE : 0u),
                                      &prog));
     t_copt.create += secs_since(t0);
     t_copt.ncreate += 1;
@@ -5177,7 +5365,10 @@ struct DerivSet : copt::Set {
     std::vector<double> sums((size_t)std::max(n, 1) * ncol), gs(std::max<size_t>(nc, 1) * ncol), ws(ncol);
     std::vector<uint8_t> ok(std::max(n, 1));
     t0 = std::chrono::steady_clock::now();
-    if (grad)
+    if (grad && tree_code)
+      check_rc(srhip_eval_objective_grad_deriv(ds, prog, loss, params, dir, ndir, coef, sums.data(), gs.data(), ws.data(),
+                                               ok.data()));
+    else if (grad)
       check_rc(srhip_eval_loss_grad_deriv(ds, prog, loss, params, dir, ndir, sums.data(), gs.data(), ws.data(), ok.data()));
     else
       check_rc(srhip_eval_loss_deriv(ds, prog, loss, params, dir, ndir, sums.data(), ws.data(), ok.data()));
@@ -5186,6 +5377,8 @@ struct DerivSet : copt::Set {
     {
       double ms = 0.0;
       if (srhip_last_kernel_time(ctx, &ms, nullptr) == SRHIP_OK) t_copt.kernel_ms += ms;
+      int32_t ntc = 0;
+      if (grad && tree_code && srhip_last_tree_code(ctx, &ntc) == SRHIP_OK && ntc > 0) t_copt.ngrad_tc += 1;
     }
     auto combine = [&](const double* row) {
       double v = 0.0;
@@ -5200,7 +5393,8 @@ struct DerivSet : copt::Set {
     if (grad) {
       g.assign(nc, 0.0);
       for (int t = 0; t < n; ++t)
-        for (int32_t j = coff[t]; j < coff[t + 1]; ++j) g[j] = ok[t] ? combine(&gs[(size_t)j * ncol]) : NAN;
+        for (int32_t j = coff[t]; j < coff[t + 1]; ++j)
+          g[j] = !ok[t] ? NAN : tree_code ? gs[(size_t)j] : combine(&gs[(size_t)j * ncol]);
     }
   }
 };
@@ -5213,8 +5407,9 @@ struct DerivFactory : copt::Factory {
   const int32_t* dir;
   int ndir;
   const double* coef;
+  bool tree_code = false;
   std::unique_ptr<copt::Set> make(const std::vector<int32_t>& members) override {
-    return std::unique_ptr<copt::Set>(new DerivSet(ctx, ds, trees, loss, params, dir, ndir, coef, members));
+    return std::unique_ptr<copt::Set>(new DerivSet(ctx, ds, trees, loss, params, dir, ndir, coef, members, tree_code));
   }
 };
 
@@ -5224,7 +5419,16 @@ int32_t srhip_optimize_constants_deriv(srhip_ctx* ctx, srhip_dataset* ds, const 
                                        const srhip_constopt_options* opts, const int32_t* dir, int32_t ndir,
                                        const double* coef, void* out_consts, double* out_loss, uint8_t* out_converged,
                                        double* out_num_evals) {
+  return srhip_optimize_constants_deriv_ex(ctx, ds, trees, opts, dir, ndir, coef, 0u, out_consts, out_loss, out_converged,
+                                           out_num_evals);
+}
+
+int32_t srhip_optimize_constants_deriv_ex(srhip_ctx* ctx, srhip_dataset* ds, const srhip_trees* trees,
+                                          const srhip_constopt_options* opts, const int32_t* dir, int32_t ndir,
+                                          const double* coef, uint32_t flags, void* out_consts, double* out_loss,
+                                          uint8_t* out_converged, double* out_num_evals) {
   return guarded([&] {
+    if (flags & ~SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE) throw Error(SRHIP_ERR_INVALID, "unknown flags");
     if (!ds) throw Error(SRHIP_ERR_INVALID, "null dataset");
     if (!opts) throw Error(SRHIP_ERR_INVALID, "null options");
     copt::Problem pb = make_problem(trees, ds->dtype);
@@ -5258,6 +5462,7 @@ int32_t srhip_optimize_constants_deriv(srhip_ctx* ctx, srhip_dataset* ds, const 
     fac.dir = dir;
     fac.ndir = ndir;
     fac.coef = coef;
+    fac.tree_code = (flags & SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE) != 0;
     const copt::Result r = copt::optimize(pb, make_copt_options(opts), fac);
     write_result(r, ds->dtype, out_consts, out_loss, out_converged, out_num_evals, false);
     t_copt.total = secs_since(t0);
@@ -5292,10 +5497,10 @@ int32_t srhip_constopt_profile(double* out, int32_t n) {
   return guarded([&] {
     if (!out || n < 0) throw Error(SRHIP_ERR_INVALID, "null output");
     const CoptProfile& q = t_copt;
-    const double v[14] = {q.total, q.create, q.set, q.loss, q.grad, q.kernel_ms * 1e-3,
+    const double v[15] = {q.total, q.create, q.set, q.loss, q.grad, q.kernel_ms * 1e-3,
                           (double)q.ncreate, (double)q.nloss, (double)q.ngrad, (double)q.nrebuilt,
-                          q.jit_codegen_ms * 1e-3, q.jit_load_ms * 1e-3, q.gather, (double)q.nseg};
-    for (int32_t i = 0; i < n && i < 14; ++i) out[i] = v[i];
+                          q.jit_codegen_ms * 1e-3, q.jit_load_ms * 1e-3, q.gather, (double)q.nseg, (double)q.ngrad_tc};
+    for (int32_t i = 0; i < n && i < 15; ++i) out[i] = v[i];
     return SRHIP_OK;
   });
 }
@@ -5513,6 +5718,8 @@ srhip_group_program* create_group_program(srhip_group* g, int32_t dtype, const s
   if (!g || !trees) throw Error(SRHIP_ERR_INVALID, "null argument");
   if (flags & SRHIP_PROGRAM_DERIV_TREE_CODE)  // (srhip_eval_loss_deriv takes no group dataset)
     throw Error(SRHIP_ERR_INVALID, "unknown program flags");
+  if (flags & SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE)
+    throw Error(SRHIP_ERR_UNSUPPORTED, "a device-group program takes no derivative-objective tree code");
   std::unique_ptr<srhip_group_program> gp(new srhip_group_program());
   gp->g = g;
   gp->dtype = dtype;

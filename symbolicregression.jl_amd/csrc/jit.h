@@ -267,9 +267,12 @@ struct DerivSpec {
   bool weighted = false;
   int loss = SRHIP_LOSS_L2;
   uint64_t lparam = 0;
+  // the objective's gradient tree code: the channel sums and, in the same
+  // pass, Σ_c q_c·∂(channel c)/∂c_j of every constant of the tree; q_c are launch arguments
+  bool grad = false;
   bool operator==(const DerivSpec& o) const {
     return ndir == o.ndir && std::equal(dir, dir + kDerivMaxDir, o.dir) && nfeat == o.nfeat && weighted == o.weighted &&
-           loss == o.loss && lparam == o.lparam;
+           loss == o.loss && lparam == o.lparam && grad == o.grad;
   }
 };
 // ndir, the loss (a distance loss with an ℓ routine, never Periodic) and the tile's
@@ -297,6 +300,24 @@ hipError_t launch_deriv_finalize(DerivModule* m, int part, int nrg, const uint32
 bool compile_deriv_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
                         const std::vector<int32_t>& cand, const DerivSpec& sp, std::vector<uint8_t>* bytes,
                         std::string* text, std::vector<int32_t>* offsets, GradStats* st);
+// ---- the objective's gradient tree code (DerivSpec::grad) ------------
+// A module built from a spec with grad set. q [1 + ndir]: coef_c / wsum_c rounded to float.
+// gpart [nrg][nconst] takes the per-row-group Σ_c q_c·∂(channel c)/∂c_j partials; the
+// finalize kernel sums them (and the channel partials, as launch_deriv_finalize) in fp64
+// into out_grad [nconst]; a failed or skipped tree's sums and gradients are NaN.
+hipError_t launch_deriv_grad_code(DerivModule* m, int part, const EvalPlan& plan, const EvalArgs<float>& a,
+                                  const float* consts, const float* q, Part<float>* part_out, float* dpart, float* gpart,
+                                  int nconst, hipStream_t stream);
+hipError_t launch_deriv_grad_finalize(DerivModule* m, int part, int nrg, const uint32_t* fail,
+                                      const Part<float>* part_out, const float* dpart, const float* gpart, int nconst,
+                                      double* out_sum, double* out_grad, uint8_t* out_ok, hipStream_t stream);
+// compile_deriv_only for a spec with grad set (the same call: the spec selects the mode)
+inline bool compile_deriv_grad_only(const CompiledBatch<float>& cb, const std::vector<int32_t>& const_off,
+                                    const std::vector<int32_t>& cand, DerivSpec sp, std::vector<uint8_t>* bytes,
+                                    std::string* text, std::vector<int32_t>* offsets, GradStats* st) {
+  sp.grad = true;
+  return compile_deriv_only(cb, const_off, cand, sp, bytes, text, offsets, st);
+}
 
 // ---- Float64 tree code (jit64.cpp) ---------------------------------------------------
 // The shallow trees of a Float64 program as straight-line code with the

@@ -71,6 +71,10 @@ const int kSinCosPd[2] = SR_JIT_SINCOS_PD_ROUTINE;
 
 // ---- IR: the accumulator machine of a gradient program, renamed ----------------
 enum { G_VAL = 0, G_X = 1, G_C = 2, G_P = 3, G_Y = 4, G_W = 5 };  // G_P / G_Y / G_W: ŷ, y, w of a loss expression
+// the objective's gradient mode (GradGen::dg): G_S the seed block of direction v (a tangent leaf),
+// G_K a literal (its bits in v); BOP_SGNMUL(a, t) = sign(a)·t (0 at a = 0), abs's tangent rule
+enum { G_S = 6, G_K = 7 };
+constexpr int BOP_SGNMUL = 100;
 struct GOpnd {
   int k = G_VAL;
   int v = -1;   // value id (G_VAL) or feature (G_X)
@@ -96,7 +100,7 @@ bool g_inline(const GOp& o) {
   if (o.kind == K_MAT) return true;
   return o.kind == K_UN ? (o.op == SRHIP_UOP_NEG || o.op == SRHIP_UOP_ABS || o.op == SRHIP_UOP_SQUARE ||
                            o.op == SRHIP_UOP_CUBE)
-                        : (o.op == SRHIP_BOP_ADD || o.op == SRHIP_BOP_SUB || o.op == SRHIP_BOP_MUL);
+                        : (o.op == SRHIP_BOP_ADD || o.op == SRHIP_BOP_SUB || o.op == SRHIP_BOP_MUL || o.op == BOP_SGNMUL);
 }
 
 bool build_gir(const Ins<float>* p, std::vector<GOp>& ops, GOpnd& root, std::string* why) {
@@ -309,7 +313,11 @@ struct GradGen {
   std::vector<int> dloc;
   bool fused(int i) const {
     const GOp& o = ops[i];
-    return fuse_trig && o.kind == K_UN && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS) && needs_adj(o.a) &&
+    // dg: decided as the dv code decides it (by the direction leaves, for the candidate's operators only), so
+    // phase 1 stays that code; the factor block then also serves phase 2 (emit_reverse)
+    const bool na = !dg() ? needs_adj(o.a)
+                          : i < mt && ((o.a.k == G_X && dirk(o.a.v) >= 0) || (o.a.k == G_VAL && has1[o.a.v]));
+    return fuse_trig && o.kind == K_UN && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS) && na &&
            kSinCosPd[o.op == SRHIP_UOP_COS ? 1 : 0] >= 0;
   }
   static constexpr int LOC_VA = -7, LOC_VB = -8;
@@ -347,8 +355,116 @@ struct GradGen {
       if (dv->dir[k] == f) return k;
     return -1;
   }
-  static int dblk(int k) { return GACC + R * k; }
-  bool target(const GOpnd& q) const { return dv ? (q.k == G_X && dirk(q.v) >= 0) : (q.k == G_C && q.ci < nc); }
+  int dblk(int k) const { return dg() ? blk_reg(GNPOOL - 2 - k) : GACC + R * k; }
+  bool target(const GOpnd& q) const {
+    return dv && phase != 2 ? (q.k == G_X && dirk(q.v) >= 0) : (q.k == G_C && q.ci < nc);
+  }
+  // the objective's gradient (dv->grad): per tile
+  //   phase 1  the dv code: forward v, reverse with seed 1 to the direction leaves (d_k), the
+  //            channel sums; new: the seeds s_0 (a pool block) and s_k (in d_k's block);
+  //   tangent  ops[mt ..], appended by append_tangent: the forward tangent t along Σ_k s_k e_dir[k]
+  //            written as operators over (v, t) — t_leaf = G_S k, f' and f'' spelled with the
+  //            candidate's own operators — emitted by the forward emitters;
+  //   phase 2  one reverse sweep over ops[n-1 .. 0] with the constants as targets, seeded with
+  //            v̄_root = s_0 and t̄_root = 1. A value now has several consumers (its own parent and
+  //            tangent operators), so an adjoint that arrives second is added (accum).
+  // The direction blocks move to the pool's top (the constants' accumulators are live across
+  // tiles here), q_c arrive in s[SQ0 ..], the direction partials' pointer in s[SDPTR:SDPTR+1].
+  // Timeline: forward i | loss mt | reverse-1 2mt-i | tangent mt+2+j | t-root dies mt+n+2 |
+  // reverse-2 mt+2n+2-i.
+  static constexpr int SQ0 = 92, SDPTR = 98;
+  bool dg() const { return dv && dv->grad; }
+  int phase = 0;   // dg: 1 / 2 (above); 0 otherwise
+  int mt = -1;     // dg: the candidate's operator count (ops[mt ..]: the tangent)
+  GOpnd troot;     // dg: the root's tangent (k < 0: none that a constant reaches)
+  std::vector<uint8_t> has1, has2;  // hasc of the two phases
+  int fstep(int i) const { return mt >= 0 && i >= mt ? mt + 2 + i : i; }
+  bool append_tangent() {
+    mt = (int)ops.size();
+    troot.k = -1;
+    phase = 1;
+    if (nc == 0 || root.k != G_VAL) return true;
+    auto none = [] { GOpnd q; q.k = -1; return q; };
+    std::vector<GOpnd> tan((size_t)mt, none());
+    auto tof = [&](const GOpnd& q) {
+      if (q.k == G_VAL) return tan[(size_t)q.v];
+      GOpnd s = none();
+      if (q.k == G_X && dirk(q.v) >= 0) { s.k = G_S; s.v = dirk(q.v); }
+      return s;
+    };
+    auto lit = [](float f) { GOpnd q; q.k = G_K; std::memcpy(&q.v, &f, 4); return q; };
+    auto val = [](int i) { GOpnd q; q.v = i; return q; };
+    auto push = [&](int kind, int op, const GOpnd& a, const GOpnd& b) {
+      GOp o;
+      o.kind = kind;
+      o.op = op;
+      o.a = a;
+      o.b = b;
+      ops.push_back(o);
+      return val((int)ops.size() - 1);
+    };
+    auto bin = [&](int op, const GOpnd& a, const GOpnd& b) { return push(K_BIN, op, a, b); };
+    auto un = [&](int op, const GOpnd& a) { return push(K_UN, op, a, GOpnd()); };
+    for (int i = 0; i < mt; ++i) {
+      const GOp o = ops[(size_t)i];
+      if (o.kind == K_MAT) continue;
+      const GOpnd ta = tof(o.a);
+      GOpnd t = none();
+      if (o.kind == K_UN) {
+        if (ta.k < 0) continue;
+        switch (o.op) {
+          case SRHIP_UOP_NEG: t = un(SRHIP_UOP_NEG, ta); break;
+          case SRHIP_UOP_ABS: t = bin(BOP_SGNMUL, o.a, ta); break;
+          case SRHIP_UOP_SQUARE: t = bin(SRHIP_BOP_MUL, bin(SRHIP_BOP_MUL, o.a, lit(2.0f)), ta); break;
+          case SRHIP_UOP_CUBE:
+            t = bin(SRHIP_BOP_MUL, bin(SRHIP_BOP_MUL, un(SRHIP_UOP_SQUARE, o.a), lit(3.0f)), ta);
+            break;
+          case SRHIP_UOP_EXP: t = bin(SRHIP_BOP_MUL, val(i), ta); break;
+          case SRHIP_UOP_SIN: t = bin(SRHIP_BOP_MUL, un(SRHIP_UOP_COS, o.a), ta); break;
+          case SRHIP_UOP_COS: t = un(SRHIP_UOP_NEG, bin(SRHIP_BOP_MUL, un(SRHIP_UOP_SIN, o.a), ta)); break;
+          case SRHIP_UOP_LOG: t = bin(SRHIP_BOP_DIV, ta, o.a); break;
+          case SRHIP_UOP_SQRT: t = bin(SRHIP_BOP_DIV, ta, bin(SRHIP_BOP_MUL, val(i), lit(2.0f))); break;
+          default: why = "unary operator without tangent code"; return false;
+        }
+      } else {
+        const GOpnd tb = tof(o.b);
+        if (ta.k < 0 && tb.k < 0) continue;
+        switch (o.op) {
+          case SRHIP_BOP_ADD: t = ta.k < 0 ? tb : tb.k < 0 ? ta : bin(SRHIP_BOP_ADD, ta, tb); break;
+          case SRHIP_BOP_SUB: t = tb.k < 0 ? ta : ta.k < 0 ? un(SRHIP_UOP_NEG, tb) : bin(SRHIP_BOP_SUB, ta, tb); break;
+          case SRHIP_BOP_MUL: {
+            const GOpnd pa = ta.k < 0 ? none() : bin(SRHIP_BOP_MUL, ta, o.b);
+            const GOpnd pb = tb.k < 0 ? none() : bin(SRHIP_BOP_MUL, o.a, tb);
+            t = pa.k < 0 ? pb : pb.k < 0 ? pa : bin(SRHIP_BOP_ADD, pa, pb);
+            break;
+          }
+          case SRHIP_BOP_DIV: {  // (t_a - q·t_b) / b, q the quotient itself
+            GOpnd num = ta;
+            if (tb.k >= 0) {
+              const GOpnd m = bin(SRHIP_BOP_MUL, val(i), tb);
+              num = ta.k < 0 ? un(SRHIP_UOP_NEG, m) : bin(SRHIP_BOP_SUB, ta, m);
+            }
+            t = bin(SRHIP_BOP_DIV, num, o.b);
+            break;
+          }
+          default: why = "binary operator without tangent code"; return false;
+        }
+      }
+      tan[(size_t)i] = t;
+    }
+    // the tangent is emitted only when a constant reaches the root's (else ∂t_root/∂c = 0)
+    std::vector<uint8_t> dep(ops.size(), 0);
+    for (size_t i = 0; i < ops.size(); ++i) {
+      auto d = [&](const GOpnd& q) { return q.k == G_C || (q.k == G_VAL && dep[(size_t)q.v]); };
+      dep[i] = ops[i].kind == K_MAT || d(ops[i].a) || (ops[i].kind == K_BIN && d(ops[i].b));
+    }
+    troot = tan[(size_t)root.v];
+    if (troot.k != G_VAL || !dep[(size_t)troot.v]) {
+      troot.k = -1;
+      ops.resize((size_t)mt);
+    }
+    return true;
+  }
   // expression loss: ops[m0 ..] are the loss's operators, appended behind
   // the candidate's (append_loss); its values and adjoints share the pool and the timeline
   // (forward m0 .. n-1, Σ ℓ at n, reverse down to m0, then the candidate's reverse pass).
@@ -396,7 +512,9 @@ struct GradGen {
   GradGen(Asm& a, const Tmpl& t, uint64_t va) : as(a), T(t), base_va(va) {}
   uint64_t cur_va() const { return base_va + as.bytes(); }
   static int blk_reg(int k) { return GPOOL0 + R * k; }
-  int bstep(int i) const { return 2 * n - i; }  // reverse steps n+1 .. 2n (n: the loss)
+  int bstep(int i) const {  // reverse steps n+1 .. 2n (n: the loss); dg: the timeline above
+    return phase == 2 ? mt + 2 * n + 2 - i : phase == 1 ? 2 * mt - i : 2 * n - i;
+  }
   bool needs_adj(const GOpnd& q) const { return target(q) || (q.k == G_VAL && hasc[q.v]); }
 
   bool analyze() {
@@ -409,7 +527,7 @@ struct GradGen {
     for (int i = 0; i < n; ++i) {
       GOp& o = ops[i];
       auto hc = [&](const GOpnd& q) { return needs_adj(q); };
-      hasc[i] = (o.kind == K_MAT && !dv) || hc(o.a) || (o.kind == K_BIN && hc(o.b));
+      hasc[i] = (o.kind == K_MAT && (!dv || phase == 2)) || hc(o.a) || (o.kind == K_BIN && hc(o.b));
       if (o.a.k == G_C && o.kind != K_MAT && o.a.ci >= nc + nlc) { why = "constant index out of range"; return false; }
       if (o.kind == K_BIN && o.b.k == G_C && o.b.ci >= nc + nlc) { why = "constant index out of range"; return false; }
       if (!g_inline(o)) {
@@ -422,7 +540,7 @@ struct GradGen {
       for (int s = 0; s < 2; ++s) {
         const GOpnd& q = s ? o.b : o.a;
         if (s && o.kind != K_BIN) break;
-        if (q.k == G_VAL) { ops[q.v].consumer = i; last[q.v] = std::max(last[q.v], i); }
+        if (q.k == G_VAL) { ops[q.v].consumer = i; last[q.v] = std::max(last[q.v], fstep(i)); }
         if (q.k == G_W) wlast = std::max(wlast, i);
       }
     }
@@ -430,7 +548,9 @@ struct GradGen {
     // reverse-pass reads of saved values (operands and own results)
     int xg_rev[256];
     for (int f = 0; f < 256; ++f) xg_rev[f] = -1;
-    for (int i = 0; i < n; ++i) {
+    if (dg()) has1 = hasc;
+    auto rev_reads = [&](int hi) {
+    for (int i = 0; i < hi; ++i) {
       const GOp& o = ops[i];
       if (!hasc[i] || o.kind == K_MAT) continue;
       auto use = [&](const GOpnd& q) {
@@ -450,13 +570,33 @@ struct GradGen {
           use(o.a);
           use(o.b);
           if (ab) last[i] = std::max(last[i], bstep(i));
+        } else if (o.op == BOP_SGNMUL) {
+          if (ab) use(o.a);
         }
       } else {
         if (o.op == SRHIP_UOP_EXP || o.op == SRHIP_UOP_SQRT) last[i] = std::max(last[i], bstep(i));
         else if (o.op != SRHIP_UOP_NEG && !fused(i)) use(o.a);  // fused sin / cos: the factor in dloc[i]
       }
     }
-    if (root.k == G_VAL) last[root.v] = std::max(last[root.v], n);  // read by the loss step
+    };
+    const int lstep = dg() ? mt : n;  // the loss step
+    if (!dg()) {
+      rev_reads(n);
+    } else {  // both reverse sweeps' reads; hasc is phase 1's until emit_tree switches
+      rev_reads(mt);
+      has1 = hasc;
+      phase = 2;
+      for (int i = 0; i < n; ++i) {
+        const GOp& o = ops[i];
+        hasc[i] = o.kind == K_MAT || needs_adj(o.a) || (o.kind == K_BIN && needs_adj(o.b));
+      }
+      rev_reads(n);
+      has2 = hasc;
+      hasc = has1;
+      phase = 1;
+      if (troot.k == G_VAL) last[troot.v] = std::max(last[troot.v], mt + n + 2);  // (a DIV root's quotient is read again)
+    }
+    if (root.k == G_VAL) last[root.v] = std::max(last[root.v], lstep);  // read by the loss step
     if (lir && lroot.k == G_VAL) last[lroot.v] = std::max(last[lroot.v], n);
     if (lir && lroot.k == G_W) wlast = std::max(wlast, n);
     // features: those read by inline operators (or as the root) are preloaded per tile
@@ -473,10 +613,10 @@ struct GradGen {
     };
     for (int i = 0; i < n; ++i) {
       const bool inl = g_inline(ops[i]);
-      if (!usef(ops[i].a, i, inl)) { why = "feature index"; return false; }
-      if (ops[i].kind == K_BIN && !usef(ops[i].b, i, inl)) { why = "feature index"; return false; }
+      if (!usef(ops[i].a, fstep(i), inl)) { why = "feature index"; return false; }
+      if (ops[i].kind == K_BIN && !usef(ops[i].b, fstep(i), inl)) { why = "feature index"; return false; }
     }
-    if (!usef(root, n, true)) { why = "feature index"; return false; }
+    if (!usef(root, lstep, true)) { why = "feature index"; return false; }
     for (int f = 0; f < 256; ++f) {
       if (is_g(f)) {
         xlast[f] = std::max(xlast[f], xg_rev[f]);
@@ -484,7 +624,7 @@ struct GradGen {
       }
       if (xlast[f] >= 0 && (1 + f) * TILE * 4 + 3 * 4 * 64 > 65535) { why = "feature offset beyond the DS immediate"; return false; }
     }
-    if ((int)feats.size() > GNPOOL - (dv ? 1 : 0)) { why = "more features than register blocks"; return false; }
+    if ((int)feats.size() > GNPOOL - (dv ? 1 : 0) - (dg() ? dv->ndir : 0)) { why = "more features than register blocks"; return false; }
     return true;
   }
 
@@ -514,7 +654,31 @@ struct GradGen {
     if (a.blk < 0) return;
     if (--refs[a.blk] == 0) owner[a.blk] = -1;
   }
+  // (dg, phase 2) value v already holds an adjoint: block `reg` (sign `neg`) is added to it, in
+  // place when v alone references its block, else into a new one
+  void accum(int v, int reg, bool neg) {
+    const Adj a = adj[v];
+    const bool priv = a.blk >= 0 && refs[a.blk] == 1;
+    int k = a.blk, d = a.reg;
+    if (!priv) {
+      k = new_adj_block(v);
+      if (k < 0) return;
+      d = blk_reg(k);
+    }
+    for (int e = 0; e < R; ++e) {
+      if (a.neg == neg) as.vop2(VOP2_ADD_F32, "v_add_f32_e32", d + e, V(a.reg + e), reg + e);
+      else if (!a.neg) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", d + e, V(a.reg + e), reg + e);
+      else as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", d + e, V(reg + e), a.reg + e);
+    }
+    if (!priv) release_adj(a);
+    Adj r;
+    r.reg = d;
+    r.blk = k;
+    r.neg = a.neg && neg;
+    adj[v] = r;
+  }
   void share_adj(int v, const Adj& g, bool flip) {
+    if (phase == 2 && adj[v].reg >= 0) { accum(v, g.reg, g.neg != flip); return; }
     Adj a = g;
     a.neg = g.neg != flip;
     if (a.blk >= 0) ++refs[a.blk];
@@ -572,6 +736,8 @@ struct GradGen {
     if (q.k == G_X) return V(blk_reg(xblk[q.v]) + e);
     if (q.k == G_Y) return V(VY + e);
     if (q.k == G_W) return V(blk_reg(wblk) + e);
+    if (q.k == G_S) return V(dblk(q.v) + e);
+    if (q.k == G_K) return K((uint32_t)q.v);
     return V(vreg(q.v) + e);
   }
   int vreg(int v) const { return loc[v] == LOC_VA ? VA : loc[v] == LOC_VB ? VB : blk_reg(loc[v]); }
@@ -582,7 +748,7 @@ struct GradGen {
   // an inline result whose one use is the next operation, a routine call,
   // is written straight into the call's argument registers: VA or VB (0: no)
   int arg_reg_for(int i) const {
-    if (i + 1 >= n || last[i] != i + 1 || (root.k == G_VAL && root.v == i)) return 0;
+    if (i + 1 >= n || i + 1 == mt || last[i] != fstep(i + 1) || (root.k == G_VAL && root.v == i)) return 0;
     const GOp& c = ops[i + 1];
     if (c.kind == K_MAT || g_inline(c)) return 0;
     const bool a = c.a.k == G_VAL && c.a.v == i, b = c.kind == K_BIN && c.b.k == G_VAL && c.b.v == i;
@@ -590,7 +756,7 @@ struct GradGen {
     return a ? VA : b ? VB : 0;
   }
   bool keep_in_va(int i) const {
-    if (i + 1 >= n || last[i] != i + 1 || (root.k == G_VAL && root.v == i)) return false;
+    if (i + 1 >= n || i + 1 == mt || last[i] != fstep(i + 1) || (root.k == G_VAL && root.v == i)) return false;
     const GOp& c = ops[i + 1];
     if (c.kind == K_MAT) return false;
     return (c.a.k == G_VAL && c.a.v == i) || (c.kind == K_BIN && c.b.k == G_VAL && c.b.v == i);
@@ -676,8 +842,8 @@ struct GradGen {
       if (o.kind == K_BIN) b[e] = fsrc(o.b, e);
     }
     // blocks dying here may hold the result (rows are independent)
-    free_values_at(i);
-    free_feats_at(i);
+    free_values_at(fstep(i));
+    free_feats_at(fstep(i));
     const int areg = arg_reg_for(i);
     const int k = areg ? -1 : free_block();
     if (!areg && k < 0) { why = "register pool exhausted"; return false; }
@@ -696,7 +862,7 @@ struct GradGen {
           }
         }
       } else {
-        const bool cb = o.b.k == G_C;
+        const bool cb = o.b.k == G_C || o.b.k == G_K;
         switch (o.op) {
           case SRHIP_BOP_ADD:
           case SRHIP_BOP_MUL: {
@@ -704,6 +870,15 @@ struct GradGen {
             const char* nm = o.op == SRHIP_BOP_ADD ? "v_add_f32_e32" : "v_mul_f32_e32";
             if (cb) as.vop2(opc, nm, d + e, b[e], a[e].enc - 256);
             else as.vop2(opc, nm, d + e, a[e], b[e].enc - 256);
+            break;
+          }
+          case BOP_SGNMUL: {  // sign(a)·b, 0 at a = 0 (d may be a's or b's block)
+            const int ar = a[e].enc - 256;
+            as.vop2(VOP2_AND_B32, "v_and_b32_e32", VGT + e, K(0x80000000u), ar);
+            as.vopc(VOPC_NEQ_F32, "v_cmp_neq_f32_e32", K(0), ar);
+            as.vop2(VOP2_XOR_B32, "v_xor_b32_e32", d + e, b[e], VGT + e);
+            as.sopp(0x00, "s_nop", 1);
+            as.vop2(VOP2_CNDMASK, "v_cndmask_b32_e32", d + e, K(0), d + e, ", vcc");
             break;
           }
           default:  // SUB
@@ -728,6 +903,7 @@ struct GradGen {
     }
     if (q.k == G_X) { read_feat(dst, q.v); return; }
     if (q.k == G_Y || q.k == G_W) { mov4(dst, q.k == G_Y ? VY : blk_reg(wblk)); return; }
+    if (q.k == G_S) { mov4(dst, dblk(q.v)); return; }
     if (vreg(q.v) == dst) return;  // already there (a result kept in VA)
     mov4(dst, vreg(q.v));
   }
@@ -737,7 +913,7 @@ struct GradGen {
       const bool kr = o.b.k == G_C;
       operand_to(VA, kr ? o.a : o.b);
       as.sop1(SOP1_MOV, "s_mov_b32", S_K, S(SC0 + (kr ? o.b.ci : o.a.ci)), "s" + std::to_string(S_K));
-      free_values_at(i);
+      free_values_at(fstep(i));
       routine(o.krid, true);  // the forward runs the PRECISE region's routines
     } else {
       if (o.kind == K_BIN && in_va(o.b)) {  // VB first: VA still holds it
@@ -756,7 +932,7 @@ struct GradGen {
         if (kn < 0) { why = "register pool exhausted"; return false; }
         mov4(blk_reg(kn), VA);
       }
-      free_values_at(i);
+      free_values_at(fstep(i));
       routine(fused(i) ? kSinCosPd[o.op == SRHIP_UOP_COS ? 1 : 0] : o.rid, true);
       for (int e = 0; nanfix && e < R; ++e) {
         as.vopc(VOPC_U_F32, "v_cmp_u_f32_e32", V(blk_reg(kn) + e), blk_reg(kn) + e);
@@ -771,7 +947,7 @@ struct GradGen {
         dloc[i] = kd;
       }
     }
-    free_feats_at(i);
+    free_feats_at(fstep(i));
     if (keep_in_va(i)) {
       loc[i] = LOC_VA;
       return true;
@@ -797,6 +973,8 @@ struct GradGen {
       if (q.k == G_X) return V(scratch + e);
       if (q.k == G_Y) return V(VY + e);
       if (q.k == G_W) return V(blk_reg(wblk) + e);
+      if (q.k == G_S) return V(dblk(q.v) + e);
+      if (q.k == G_K) return K((uint32_t)q.v);
       return V(blk_reg(loc[q.v]) + e);
     };
     auto fetch = [&](const GOpnd& q, int scratch) {
@@ -807,6 +985,11 @@ struct GradGen {
       if (q.p) { seed_add(reg, neg); return; }
       if (q.k == G_C) { acc_add(q.ci, reg, neg); return; }
       if (q.k == G_X) { dir_add(dirk(q.v), reg, neg); return; }
+      if (phase == 2 && adj[q.v].reg >= 0) {  // a second consumer's share
+        accum(q.v, reg, neg);
+        if (blk >= 0) owner[blk] = -1;
+        return;
+      }
       Adj a;
       a.reg = reg;
       a.blk = blk;
@@ -816,7 +999,7 @@ struct GradGen {
     // a block for the adjoint of q (pool if q is a value, scratch `tmp` for a constant)
     auto dest = [&](const GOpnd& q, int tmp, int* blk) {
       *blk = -2;
-      if (q.k != G_VAL || q.p) return tmp;
+      if (q.k != G_VAL || q.p || (phase == 2 && adj[q.v].reg >= 0)) return tmp;
       const int k = new_adj_block(q.v);
       if (k < 0) return -1;
       *blk = k;
@@ -917,6 +1100,23 @@ struct GradGen {
           }
           break;
         }
+        case BOP_SGNMUL:  // ∂t = sign(a)·g (0 at a = 0); nothing for a (abs'' = 0)
+          if (ab) {
+            fetch(o.a, XS0);
+            int blk;
+            const int d = dest(o.b, TP, &blk);
+            if (d < 0) return false;
+            for (int e = 0; e < R; ++e) {
+              const int ar = rsrc(o.a, XS0, e).enc - 256;
+              as.vop2(VOP2_AND_B32, "v_and_b32_e32", d + e, K(0x80000000u), ar);
+              as.vop2(VOP2_XOR_B32, "v_xor_b32_e32", d + e, gv(e), d + e);
+              as.vopc(VOPC_NEQ_F32, "v_cmp_neq_f32_e32", K(0), ar);
+              as.sopp(0x00, "s_nop", 1);
+              as.vop2(VOP2_CNDMASK, "v_cndmask_b32_e32", d + e, K(0), d + e, ", vcc");
+            }
+            give(o.b, d, g.neg, blk);
+          }
+          break;
         default: {  // DIV: q = a / b; ∂a = g / b, ∂b = -(g / b) q
           fetch(o.b, XS1);
           for (int e = 0; e < R; ++e) as.vop1(VOP1_RCP_F32, "v_rcp_f32_e32", TR + e, rsrc(o.b, XS1, e));
@@ -1036,8 +1236,10 @@ struct GradGen {
             if (d < 0) return false;
             const int fr = blk_reg(dloc[i]);
             for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", d + e, gv(e), fr + e);
-            owner[dloc[i]] = -1;
-            dloc[i] = -1;
+            if (!(phase == 1 && has2[i])) {  // (dg: phase 2 reads the factor again)
+              owner[dloc[i]] = -1;
+              dloc[i] = -1;
+            }
             give(o.a, d, g.neg != !is_sin, blk);
             break;
           }
@@ -1052,7 +1254,7 @@ struct GradGen {
       }
     }
     release_adj(g);
-    return true;
+    return phase != 2 || why.empty();  // (accum's block)
   }
 
   // the last, partial tile: rows past `partial` get 0 in block `reg`
@@ -1076,8 +1278,9 @@ struct GradGen {
     if (!analyze()) return false;
     for (int k = 0; k < GNPOOL; ++k) { owner[k] = -1; refs[k] = 0; }
     if (dv) owner[GNPOOL - 1] = RESERVED;
+    for (int k = 0; dg() && k < dv->ndir; ++k) owner[GNPOOL - 2 - k] = RESERVED;  // d_k, then s_k
     // the accumulators the epilogue sums: one per constant, or (dv) one per direction
-    const int na = dv ? dv->ndir : nc, a0 = dv ? DACC : GACC;
+    const int na = dv && !dg() ? dv->ndir : nc, a0 = dv && !dg() ? DACC : GACC;
     L_tile = as.label();
     L_done = as.label();
     // ---- prologue
@@ -1099,6 +1302,7 @@ struct GradGen {
       if (o.kind == K_UN && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS)) trig = true;
     if (has_call || trig || loss != SRHIP_LOSS_L2) set_base();
     for (int j = 0; j < na; ++j) as.vop1(VOP1_MOV, "v_mov_b32_e32", a0 + j, K(0));
+    for (int j = 0; dg() && j < dv->ndir; ++j) as.vop1(VOP1_MOV, "v_mov_b32_e32", DACC + j, K(0));
     if (nc > 0) as.waitcnt_lgkm(0);
     for (int j = 0; j < nlc; ++j)  // the loss's constants behind the tree's own (after the load, which may be wider than nc)
       as.sop1(SOP1_MOV, "s_mov_b32", SC0 + nc + j, K(lir->cbits[(size_t)j]), "s" + std::to_string(SC0 + nc + j));
@@ -1121,7 +1325,8 @@ struct GradGen {
       load_idx[f] = nloads++;
       as.ds_read_b128(blk_reg((int)j), VLANE, (1 + f) * TILE * 4);
     }
-    const int mc = lir ? m0 : n;  // the candidate's operators
+    const int mc = lir ? m0 : dg() ? mt : n;  // the candidate's operators
+    if (dg()) { phase = 1; hasc = has1; }
     for (int i = 0; i < mc; ++i)
       if (!emit_forward(i)) return false;
     // root value → rreg
@@ -1148,13 +1353,20 @@ struct GradGen {
       }
     } else {
       for (int e = 0; e < R; ++e) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", VY + e, V(rreg + e), VY + e);
-      free_values_at(n);
-      free_feats_at(n);
+      free_values_at(dg() ? mt : n);
+      free_feats_at(dg() ? mt : n);
     }
+    int s0blk = -1;  // (dg) s_0, from here to its last use in phase 2
     if (lir) {  // its seed is in VY already
     } else if (dv) {
       emit_channel(VY, dv->weighted ? (1 + dv->nfeat + dv->ndir) * TILE * 4 : -1, VLSUM);
-      for (int e = 0; e < R * dv->ndir; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", GACC + e, K(0));
+      if (dg() && nc > 0 && (root.k == G_C || (root.k == G_VAL && has2[root.v]))) {
+        s0blk = new_adj_block(root.k == G_VAL ? root.v : 0);
+        if (s0blk < 0) return false;
+        emit_seed(blk_reg(s0blk), VY, dv->weighted ? (1 + dv->nfeat + dv->ndir) * TILE * 4 : -1, SQ0);
+      }
+      for (int k = 0; k < dv->ndir; ++k)
+        for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", dblk(k) + e, K(0));
       if (root.k == G_X && dirk(root.v) >= 0)  // ŷ = x_d: ∂ŷ/∂x_d = 1
         for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", dblk(dirk(root.v)) + e, K(0x3f800000u));
       if (root.k == G_VAL && hasc[root.v])  // the seed: 1
@@ -1199,7 +1411,7 @@ struct GradGen {
       free_values_at(bstep(i));
       free_feats_at(bstep(i));
     }
-    for (int k = 0; k < GNPOOL; ++k)
+    for (int k = 0; !dg() && k < GNPOOL; ++k)
       if (owner[k] != -1 && owner[k] != RESERVED) { why = "internal: block live after the reverse pass"; return false; }
     // ---- (dv) channel 1 + k: ℓ(∂ŷ/∂x_dir[k] - Y[1 + k]), weighted by W[1 + k], into its accumulator
     for (int k = 0; dv && k < dv->ndir; ++k) {
@@ -1207,7 +1419,10 @@ struct GradGen {
       as.waitcnt_lgkm(0);
       for (int e = 0; e < R; ++e) as.vop2(VOP2_SUB_F32, "v_sub_f32_e32", dblk(k) + e, V(dblk(k) + e), XS0 + e);
       emit_channel(dblk(k), dv->weighted ? (2 + dv->nfeat + dv->ndir + k) * TILE * 4 : -1, DACC + k);
+      if (dg() && troot.k == G_VAL)
+        emit_seed(dblk(k), dblk(k), dv->weighted ? (2 + dv->nfeat + dv->ndir + k) * TILE * 4 : -1, SQ0 + 1 + k);
     }
+    if (dg() && !emit_objective_grad(s0blk)) return false;
     // ---- next tile
     as.vop2(VOP2_ADD_U32, "v_add_u32_e32", VLANE, S(S_TILEBYTES), VLANE);
     as.sop2(SOP2_ADD_U32, "s_add_u32", S_TILE, S(S_TILE), K(1));
@@ -1217,6 +1432,7 @@ struct GradGen {
     // interp.h wave_sum: lane 63 holds the sum) and stored to this row
     // group's partial of its constant; return
     as.bind(L_done);
+    auto store_sums = [&](int a0, int na, int sptr) {
     if (na > 0) {
       as.vop1(VOP1_MOV, "v_mov_b32_e32", TS + 1, K(0));
       // a DPP source must not be written by the 2 VALU instructions before:
@@ -1268,15 +1484,78 @@ struct GradGen {
       if (as.want_text) as.lines.push_back("s_mov_b64 exec, " + std::to_string(mask));
       // global_store_dword v[VLANE4] (= 4·lane), v[TS], s[SGPTR:SGPTR+1]
       as.put(0xdc708000u);
-      as.put((uint32_t)VLANE4 | ((uint32_t)TS << 8) | ((uint32_t)SGPTR << 16));
+      as.put((uint32_t)VLANE4 | ((uint32_t)TS << 8) | ((uint32_t)sptr << 16));
       if (as.want_text)
         as.lines.push_back("global_store_dword v" + std::to_string(VLANE4) + ", v" + std::to_string(TS) + ", s[" +
-                           std::to_string(SGPTR) + ":" + std::to_string(SGPTR + 1) + "]");
+                           std::to_string(sptr) + ":" + std::to_string(sptr + 1) + "]");
       as.put(0xbefe0110u);  // s_mov_b64 exec, s[16:17]
       if (as.want_text) as.lines.push_back("s_mov_b64 exec, s[16:17]");
     }
+    };
+    store_sums(a0, na, SGPTR);
+    if (dg()) store_sums(DACC, dv->ndir, SDPTR);  // the channel partials beside the constants'
     as.sop1(SOP1_SETPC, "s_setpc_b64", 0, S(S_RT), "");
     if (as.want_text) as.lines.back() = "s_setpc_b64 s[" + std::to_string(S_RT) + ":" + std::to_string(S_RT + 1) + "]";
+    return true;
+  }
+  // (dg) The seed of one channel into block `dst`: q·w·ℓ'(r), 0 past the last row. Called right
+  // after emit_channel on the same residual block `rb`: under L2 rb is masked already and XS1
+  // still holds the weights; the other losses call their ℓ' routine on rb.
+  void emit_seed(int dst, int rb, int woff, int q) {
+    if (loss == SRHIP_LOSS_L2) {
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_ADD_F32, "v_add_f32_e32", dst + e, V(rb + e), rb + e);
+      if (woff >= 0)
+        for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", dst + e, V(XS1 + e), dst + e);
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", dst + e, S(q), dst + e);
+      return;
+    }
+    mov4(VA, rb);
+    as.sop1(SOP1_MOV, "s_mov_b32", S_K, K((uint32_t)lparam), "s" + std::to_string(S_K));
+    as.sop1(SOP1_MOV, "s_mov_b32", S_KH, K((uint32_t)(lparam >> 32)), "s" + std::to_string(S_KH));
+    routine(kDLossRoutine[loss], true);
+    if (woff >= 0) {
+      as.ds_read_b128(XS1, VLANE, woff);
+      as.waitcnt_lgkm(0);
+      for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", VA + e, V(XS1 + e), VA + e);
+    }
+    for (int e = 0; e < R; ++e) as.vop2(VOP2_MUL_F32, "v_mul_f32_e32", dst + e, S(q), VA + e);
+    emit_mask(dst);
+  }
+  // (dg) After the channels: the tangent forward, then the reverse sweep over (v, t) with the
+  // constants as targets. Nothing here may fail the tree: VCHK is saved around the part.
+  bool emit_objective_grad(int s0blk) {
+    if (nc > 0 && (has_call || troot.k == G_VAL)) as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHKSAVE, V(VCHK));
+    for (int j = mt; j < n; ++j)
+      if (!emit_forward(j)) return false;
+    free_values_at(mt + n + 2);
+    phase = 2;
+    hasc = has2;
+    adj.assign(n, Adj());
+    if (s0blk >= 0 && root.k == G_C) {
+      acc_add(root.ci, blk_reg(s0blk), false);
+      owner[s0blk] = -1;
+    } else if (s0blk >= 0) {
+      Adj a;
+      a.reg = blk_reg(s0blk);
+      a.blk = s0blk;
+      adj[root.v] = a;
+    }
+    if (troot.k == G_VAL) {  // t̄_root = 1
+      Adj a;
+      a.blk = new_adj_block(troot.v);
+      if (a.blk < 0) return false;
+      a.reg = blk_reg(a.blk);
+      for (int e = 0; e < R; ++e) as.vop1(VOP1_MOV, "v_mov_b32_e32", a.reg + e, K(0x3f800000u));
+      adj[troot.v] = a;
+    }
+    for (int i = n - 1; i >= 0; --i) {
+      if (nc > 0 && hasc[i] && !emit_reverse(i)) return false;
+      free_values_at(bstep(i));
+      free_feats_at(bstep(i));
+    }
+    if (nc > 0 && (has_call || troot.k == G_VAL)) as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHK, V(VCHKSAVE));
+    for (int k = 0; k < GNPOOL; ++k)
+      if (owner[k] != -1 && owner[k] != RESERVED) { why = "internal: block live after the reverse sweeps"; return false; }
     return true;
   }
   bool emit_forward(int i) {
@@ -1455,7 +1734,27 @@ bool gen_grad_tree(const Ins<float>* prog, int nc, const Tmpl& T, bool text, std
   Asm as;
   bool ok = false;
   // a tree whose fused sin / cos factors exhaust the register pool is compiled without them
+  const bool dgm = dv && dv->grad;
+  bool trig = false;
+  for (const GOp& o : ir) trig = trig || (o.kind == K_UN && (o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS));
   for (int attempt = subst ? 0 : 2; attempt < 4 && !ok; ++attempt) {
+    if (dgm && (attempt & 1)) {
+      // The objective's gradient keeps phase 1 the dv code (its channel sums are that code's bit for bit), so it
+      // drops the factors only where the dv code of this tree drops them too; else the tree is refused.
+      if (!trig) break;  // (the same code again)
+      DerivSpec plain = *dv;
+      plain.grad = false;
+      Asm a2;
+      GradGen g2(a2, T, T.area_va + start * 4);
+      g2.ops = ir;
+      g2.root = root;
+      g2.fuse_trig = true;
+      g2.dv = &plain;
+      g2.nc = nc;
+      g2.loss = loss;
+      g2.lparam = lparam;
+      if (g2.emit_tree()) { *why = "register pool exhausted (sin / cos factors kept for both sweeps)"; break; }
+    }
     as = Asm();
     as.want_text = text;
     GradGen g(as, T, T.area_va + start * 4);
@@ -1468,7 +1767,7 @@ bool gen_grad_tree(const Ins<float>* prog, int nc, const Tmpl& T, bool text, std
     g.nc = nc;
     g.loss = loss;
     g.lparam = lparam;
-    ok = (!lx || g.append_loss(*lx)) && g.emit_tree();
+    ok = (!lx || g.append_loss(*lx)) && (!(dv && dv->grad) || g.append_tangent()) && g.emit_tree();
     if (!ok) *why = g.why;
   }
   if (!ok) return false;
@@ -1781,6 +2080,7 @@ bool deriv_spec_fits(const DerivSpec& sp) {
   if (sp.loss != SRHIP_LOSS_L2 && (sp.loss < 0 || sp.loss >= SRHIP_MARGIN_LOSS_BEGIN || sp.loss == SRHIP_LOSS_PERIODIC ||
                                    kGradLossRoutine[sp.loss] < 0))
     return false;
+  if (sp.grad && !has_dloss_routine(sp.loss)) return false;  // the seeds need ℓ'
   // every array of a tile is read by ds_read_b128 at a 16-bit literal offset from the lane's address
   return (size_t)(deriv_narr(sp) - 1) * TILE * 4 <= 65535;
 }
@@ -1791,6 +2091,7 @@ struct DerivPart {
   int32_t* d_off = nullptr;    // [nslots] code offsets
   int32_t* d_cbase = nullptr;  // [nslots] first constant of the slot's tree
   int32_t* d_tree = nullptr;   // [nslots] the slot's tree
+  int32_t* d_ncon = nullptr;   // [nslots] its constant count (a spec with grad)
   int slot0 = 0, nslots = 0;
 };
 struct DerivModule {
@@ -1819,15 +2120,19 @@ DerivModule* build_deriv(const CompiledBatch<float>& cb, const std::vector<int32
       pt.nslots = (int)ch.slots.size();
       std::vector<uint8_t> img(ch.T->img, ch.T->img + ch.T->size);
       std::memcpy(img.data() + ch.T->area_off, ch.words.data(), ch.words.size() * 4);
-      std::vector<int32_t> cbase(ch.slots.size());
-      for (size_t k = 0; k < ch.slots.size(); ++k) cbase[k] = const_off[ch.slots[k]];
+      std::vector<int32_t> cbase(ch.slots.size()), ncon(ch.slots.size());
+      for (size_t k = 0; k < ch.slots.size(); ++k) {
+        cbase[k] = const_off[ch.slots[k]];
+        ncon[k] = const_off[ch.slots[k] + 1] - cbase[k];
+      }
       HIP_CHECK(hipModuleLoadData(&pt.mod, img.data()));
-      HIP_CHECK(hipModuleGetFunction(&pt.fn, pt.mod, sp.weighted ? "sr_jit_deriv_w" : "sr_jit_deriv"));
-      HIP_CHECK(hipModuleGetFunction(&pt.fn_fin, pt.mod, "sr_jit_deriv_fin"));
+      HIP_CHECK(hipModuleGetFunction(&pt.fn, pt.mod, sp.grad ? (sp.weighted ? "sr_jit_deriv_grad_w" : "sr_jit_deriv_grad")
+                                                             : (sp.weighted ? "sr_jit_deriv_w" : "sr_jit_deriv")));
+      HIP_CHECK(hipModuleGetFunction(&pt.fn_fin, pt.mod, sp.grad ? "sr_jit_deriv_grad_fin" : "sr_jit_deriv_fin"));
       HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pt.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     160 * 1024));
       const std::pair<int32_t**, const std::vector<int32_t>*> arrays[] = {
-          {&pt.d_off, &ch.offs}, {&pt.d_cbase, &cbase}, {&pt.d_tree, &ch.slots}};
+          {&pt.d_off, &ch.offs}, {&pt.d_cbase, &cbase}, {&pt.d_tree, &ch.slots}, {&pt.d_ncon, &ncon}};
       for (const auto& q : arrays) {
         HIP_CHECK(hipMalloc((void**)q.first, q.second->size() * sizeof(int32_t)));
         HIP_CHECK(hipMemcpy(*q.first, q.second->data(), q.second->size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1851,7 +2156,7 @@ DerivModule* build_deriv(const CompiledBatch<float>& cb, const std::vector<int32
 void destroy_deriv(DerivModule* m) {
   if (!m) return;
   for (DerivPart& pt : m->parts) {
-    for (void* q : {(void*)pt.d_off, (void*)pt.d_cbase, (void*)pt.d_tree})
+    for (void* q : {(void*)pt.d_off, (void*)pt.d_cbase, (void*)pt.d_tree, (void*)pt.d_ncon})
       if (q) (void)hipFree(q);
     if (pt.mod) (void)hipModuleUnload(pt.mod);
   }
@@ -1886,7 +2191,7 @@ struct JitDerivFinArgs {
 
 hipError_t launch_deriv_code(DerivModule* m, int part, const EvalPlan& plan, const EvalArgs<float>& a,
                              const float* consts, Part<float>* part_out, float* dpart, hipStream_t stream) {
-  if (plan.threads != 256 || plan.tile != TILE) return hipErrorInvalidValue;
+  if (plan.threads != 256 || plan.tile != TILE || m->sp.grad) return hipErrorInvalidValue;
   const DerivPart& pt = m->parts[part];
   if (a.nlist != pt.nslots || a.nfeat != m->sp.nfeat || (a.w != nullptr) != m->sp.weighted || !a.fail)
     return hipErrorInvalidValue;
@@ -1913,6 +2218,63 @@ hipError_t launch_deriv_finalize(DerivModule* m, int part, int nrg, const uint32
                                  const float* dpart, double* out_sum, uint8_t* out_ok, hipStream_t stream) {
   const DerivPart& pt = m->parts[part];
   JitDerivFinArgs fa{pt.d_tree, fail, part_out, dpart, out_sum, out_ok, pt.nslots, nrg, m->sp.ndir};
+  size_t sz = sizeof(fa);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &fa, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  return hipModuleLaunchKernel(pt.fn_fin, (unsigned)((pt.nslots + 63) / 64), 1, 1, 256, 1, 1, 0, stream, nullptr, cfg);
+}
+
+struct JitDerivGradArgs {  // jit_template.hip
+  JitDerivArgs d;
+  float* gpart;
+  int nconst;
+  float q[1 + kDerivMaxDir];
+};
+struct JitDerivGradFinArgs {
+  JitDerivFinArgs f;
+  const int32_t* cbase;
+  const int32_t* ncon;
+  const float* gpart;
+  double* out_grad;
+  int nconst;
+};
+
+hipError_t launch_deriv_grad_code(DerivModule* m, int part, const EvalPlan& plan, const EvalArgs<float>& a,
+                                  const float* consts, const float* q, Part<float>* part_out, float* dpart, float* gpart,
+                                  int nconst, hipStream_t stream) {
+  if (plan.threads != 256 || plan.tile != TILE || !m->sp.grad) return hipErrorInvalidValue;
+  const DerivPart& pt = m->parts[part];
+  if (a.nlist != pt.nslots || a.nfeat != m->sp.nfeat || (a.w != nullptr) != m->sp.weighted || !a.fail)
+    return hipErrorInvalidValue;
+  const size_t lds = (size_t)deriv_narr(m->sp) * (size_t)plan.ntiles * (size_t)plan.tile * sizeof(float);
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  JitDerivGradArgs ja;
+  std::memset(&ja, 0, sizeof(ja));
+  ja.d.e = a;
+  ja.d.e.list = pt.d_tree;
+  ja.d.e.rotate = 0;
+  ja.d.code_off = pt.d_off;
+  ja.d.consts = consts;
+  ja.d.cbase = pt.d_cbase;
+  ja.d.part = part_out;
+  ja.d.dpart = dpart;
+  ja.d.ndir = m->sp.ndir;
+  ja.gpart = gpart;
+  ja.nconst = nconst;
+  for (int c = 0; c <= m->sp.ndir; ++c) ja.q[c] = q[c];
+  size_t sz = sizeof(ja);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ja, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  note_kernel(m->sp.weighted ? "sr_jit_deriv_grad_w" : "sr_jit_deriv_grad");
+  return hipModuleLaunchKernel(pt.fn, (unsigned)a.nrg * (unsigned)a.ntg, 1, 1, (unsigned)plan.threads, 1, 1,
+                               (unsigned)lds, stream, nullptr, cfg);
+}
+
+hipError_t launch_deriv_grad_finalize(DerivModule* m, int part, int nrg, const uint32_t* fail,
+                                      const Part<float>* part_out, const float* dpart, const float* gpart, int nconst,
+                                      double* out_sum, double* out_grad, uint8_t* out_ok, hipStream_t stream) {
+  if (!m->sp.grad) return hipErrorInvalidValue;
+  const DerivPart& pt = m->parts[part];
+  JitDerivGradFinArgs fa{{pt.d_tree, fail, part_out, dpart, out_sum, out_ok, pt.nslots, nrg, m->sp.ndir},
+                         pt.d_cbase, pt.d_ncon, gpart, out_grad, nconst};
   size_t sz = sizeof(fa);
   void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &fa, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   return hipModuleLaunchKernel(pt.fn_fin, (unsigned)((pt.nslots + 63) / 64), 1, 1, 256, 1, 1, 0, stream, nullptr, cfg);

@@ -1264,3 +1264,175 @@ extern "C" __global__ void __launch_bounds__(256) sr_jit_deriv_fin(JitDerivFinAr
     fa.out_ok[t] = ok ? 1 : 0;
   }
 }
+
+// ---- the objective's gradient tree code (jit_grad.cpp GradGen::dg) ----
+// sr_jit_deriv's shape and tile. A tree's code leaves channel 0 in LSUM and the marker in
+// CHK as there, and itself stores (summed over the wave) its ndir channel sums to dpart and
+// Σ_c q_c·∂(channel c)/∂c_j of each of its constants to this row group's gpart. The
+// coefficients q_c = coef_c / wsum_c reach the code in s92..s96 (never literals: they
+// change between calls), the channel partials' address in s[98:99].
+// The staging, the dealing of trees to waves and the flag prefetch repeat jit_deriv_body line
+// for line (that kernel's source stays untouched so that its resource usage cannot move):
+// the two must change together.
+struct JitDerivGradArgs {
+  JitDerivArgs d;
+  float* gpart;  // [nrg][nconst]
+  int nconst;
+  float q[5];
+};
+
+template <bool W>
+__device__ __forceinline__ void jit_deriv_grad_body(const JitDerivGradArgs& jg) {
+  const JitDerivArgs& ja = jg.d;
+  const EvalArgs<float>& a = ja.e;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* sX = reinterpret_cast<float*>(smem);
+  const int ncol = 1 + ja.ndir;
+  const int narr = 1 + a.nfeat + ja.ndir + (W ? ncol : 0);
+  const int rg = blockIdx.x / a.ntg;
+  const int g = blockIdx.x - rg * a.ntg;
+  const int rows = a.ntiles * TILE;
+  const int64_t row0 = (int64_t)rg * rows;
+  {
+    constexpr int V = TILE / 4;
+    const int total = a.ntiles * narr * V;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+      const int v = idx % V;
+      const int tk = idx / V;
+      const int k = tk % narr;
+      const int t = tk / narr;
+      const float* src = k == 0            ? a.y
+                         : k <= a.nfeat    ? a.X + (size_t)(k - 1) * a.n_pad
+                         : k < a.nfeat + ncol ? a.y + (size_t)(k - a.nfeat) * a.n_pad
+                                           : a.w + (size_t)(k - a.nfeat - ncol) * a.n_pad;
+      reinterpret_cast<float4*>(sX + (size_t)tk * TILE)[v] =
+          reinterpret_cast<const float4*>(src + row0 + (int64_t)t * TILE)[v];
+    }
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int64_t rem = a.n - row0;
+  const int nt_valid = (int)min((int64_t)a.ntiles, (rem + TILE - 1) / TILE);
+  const int last_valid = (int)(rem - (int64_t)(nt_valid - 1) * TILE);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nwaves = (int)(blockDim.x >> 6);
+  auto slot_of = [&](int i) { return i * a.ntg + ((i & 1) ? (a.ntg - 1 - g) : g); };
+  auto sld = [&](const int32_t* p, int s) {
+    return __builtin_amdgcn_readfirstlane(((const __attribute__((address_space(4))) int32_t*)(p))[s]);
+  };
+  auto ld_flag = [&](int slot) { return __hip_atomic_load(a.fail + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  uint64_t area;
+  asm volatile(
+      "s_getpc_b64 s[88:89]\n"
+      "s_add_u32 s88, s88, sr_jit_code@rel32@lo+4\n"
+      "s_addc_u32 s89, s89, sr_jit_code@rel32@hi+12"
+      : "={s[88:89]}"(area)
+      :
+      : "scc");
+  const uint32_t lds_lane = (uint32_t)reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) float*)sX) +
+                            (uint32_t)lane * 16u;
+  const uint32_t tilebytes = (uint32_t)__builtin_amdgcn_readfirstlane(narr * TILE * 4);
+  const uint32_t woff = W ? (uint32_t)__builtin_amdgcn_readfirstlane((a.nfeat + ncol) * TILE * 4) : 0u;
+  const uint32_t lane4 = (uint32_t)lane * R;
+  const uint32_t partial = (uint32_t)last_valid;
+  const uint32_t nt_u = (uint32_t)nt_valid;
+  auto qbits = [&](int c) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(jg.q[c])); };
+  const uint32_t q0 = qbits(0), q1 = qbits(1), q2 = qbits(2), q3 = qbits(3), q4 = qbits(4);
+
+  int m = wave < a.tpb ? (a.tpb - wave + nwaves - 1) / nwaves : 0;
+  while (m > 0 && slot_of(wave + (m - 1) * nwaves) >= a.nlist) --m;
+  m = __builtin_amdgcn_readfirstlane(m);
+  uint32_t fnext = m > 0 ? ld_flag(slot_of(wave)) : 0u;
+  Part<float>* dst = ja.part + (size_t)rg * (size_t)a.nlist;
+  float* ddst = ja.dpart + (size_t)rg * (size_t)a.nlist * (size_t)ja.ndir;
+  float* gdst = jg.gpart + (size_t)rg * (size_t)jg.nconst;
+  for (int k = 0; k < m; ++k) {
+    const int i = __builtin_amdgcn_readfirstlane(wave + k * nwaves);
+    const int s = __builtin_amdgcn_readfirstlane(slot_of(i));
+    const bool more = k + 1 < m;
+    const bool skip = __builtin_amdgcn_readfirstlane((int)fnext) != 0;
+    if (more) fnext = ld_flag(slot_of(wave + (k + 1) * nwaves));
+    float lsum = 0.0f, chk = skip ? __builtin_nanf("") : 0.0f;
+    if (!skip) {
+      const int cb = sld(ja.cbase, s);
+      const uint64_t target = area + (uint32_t)sld(ja.code_off, s);
+      const uint64_t cptr = sgpr64(reinterpret_cast<uint64_t>(ja.consts + cb));
+      const uint64_t gptr = sgpr64(reinterpret_cast<uint64_t>(gdst + cb));
+      const uint64_t dptr = sgpr64(reinterpret_cast<uint64_t>(ddst + (size_t)s * (size_t)ja.ndir));
+      uint32_t la = lds_lane;
+      uint32_t tile = 0, status;
+      asm volatile("s_swappc_b64 s[76:77], %[tgt]"
+                   : "+{v42}"(lsum), "+{v40}"(chk), "+{v41}"(la), "+{s64}"(tile), "={s69}"(status)
+                   : [tgt] "s"(target), "{v43}"(lane4), "{s65}"(nt_u), "{s66}"(partial), "{s67}"(tilebytes),
+                     "{s68}"(woff), "{s[78:79]}"(cptr), "{s[84:85]}"(gptr), "{s[98:99]}"(dptr), "{s92}"(q0),
+                     "{s93}"(q1), "{s94}"(q2), "{s95}"(q3), "{s96}"(q4)
+                   : SR_JIT_GRAD_CLOBBERS, "memory");
+      (void)status;
+    }
+    // a skipped tree writes no partials: finalize gives it NaN sums and NaN gradients
+    lsum = wave_sum(lsum);
+    chk = __builtin_amdgcn_ballot_w64(chk != chk) != 0 ? __builtin_nanf("") : 0.0f;
+    if (lane == 0) dst[s] = Part<float>{lsum, chk};
+    if (!skip && chk != chk && lane == 0)
+      __hip_atomic_store(a.fail + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256) sr_jit_deriv_grad(JitDerivGradArgs ja) { jit_deriv_grad_body<false>(ja); }
+extern "C" __global__ void __launch_bounds__(256) sr_jit_deriv_grad_w(JitDerivGradArgs ja) { jit_deriv_grad_body<true>(ja); }
+
+// sr_jit_deriv_fin's sums (the same order, so the channel sums equal that kernel's bit for
+// bit), then each constant of the slot's tree: Σ over the row groups of its gpart column in
+// fp64, lane group w the row groups rg ≡ w (mod 4) ascending, the four added in a fixed
+// tree, into out_grad [nconst]; NaN for a tree that failed or was skipped.
+struct JitDerivGradFinArgs {
+  JitDerivFinArgs f;
+  const int32_t* cbase;  // [nslots]
+  const int32_t* ncon;   // [nslots]
+  const float* gpart;    // [nrg][nconst]
+  double* out_grad;
+  int nconst;
+};
+extern "C" __global__ void __launch_bounds__(256) sr_jit_deriv_grad_fin(JitDerivGradFinArgs ga) {
+  const JitDerivFinArgs& fa = ga.f;
+  constexpr int S = 6;
+  __shared__ double sh[4][S][64];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int s = blockIdx.x * 64 + lane;
+  const bool in = s < fa.nslots;
+  double acc[S];
+  for (int k = 0; k < S; ++k) acc[k] = 0.0;
+  if (in) {
+    for (int rg = w; rg < fa.nrg; rg += 4) {
+      const Part<float> q = fa.part[(size_t)rg * fa.nslots + s];
+      acc[0] += (double)q.chk;
+      acc[1] += (double)q.sum;
+      const float* d = fa.dpart + ((size_t)rg * fa.nslots + s) * fa.ndir;
+      for (int k = 0; k < fa.ndir; ++k) acc[2 + k] += (double)d[k];
+    }
+  }
+  for (int k = 0; k < S; ++k) sh[w][k][lane] = acc[k];
+  __syncthreads();
+  bool ok = false;
+  if (w == 0 && in) {
+    for (int k = 0; k < S; ++k) acc[k] = (sh[0][k][lane] + sh[1][k][lane]) + (sh[2][k][lane] + sh[3][k][lane]);
+    ok = !__builtin_isnan(acc[0]) && fa.fail[s] == 0u;
+    const int t = fa.tree[s];
+    double* row = fa.out_sum + (size_t)t * (1 + fa.ndir);
+    for (int k = 0; k <= fa.ndir; ++k) row[k] = ok ? acc[1 + k] : __builtin_nan("");
+    fa.out_ok[t] = ok ? 1 : 0;
+  }
+  const int cb = in ? ga.cbase[s] : 0, nc = in ? ga.ncon[s] : 0;
+  for (int j = 0; j < SR_JIT_G_NGACC; ++j) {  // uniform trip count: the barriers are reached by all
+    double a = 0.0;
+    if (j < nc)
+      for (int rg = w; rg < fa.nrg; rg += 4) a += (double)ga.gpart[(size_t)rg * ga.nconst + cb + j];
+    __syncthreads();
+    sh[w][0][lane] = a;
+    __syncthreads();
+    if (w == 0 && j < nc)
+      ga.out_grad[cb + j] = ok ? (sh[0][0][lane] + sh[1][0][lane]) + (sh[2][0][lane] + sh[3][0][lane]) : __builtin_nan("");
+  }
+}

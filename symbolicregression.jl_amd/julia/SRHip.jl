@@ -1381,7 +1381,7 @@ function eval_loss_deriv(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, op
 end
 
 """
-    optimize_constants_deriv(trees, dataset, options; device=0) -> (losses, converged, num_evals)
+    optimize_constants_deriv(trees, dataset, options; device=0, grad_tree_code=false) -> (losses, converged, num_evals)
 
 `optimize_constants_batch!` under `options.loss_function::DerivativeObjective`
 (srhip_optimize_constants_deriv): every start of every tree in one lockstep run, the loss of a
@@ -1389,10 +1389,12 @@ candidate `Σ_k coefficients[k] · mean_k` over y and every derivative channel, 
 from second-order forward mode (∂²ŷ/∂c∂x). Trees that converged get their constants set.
 `losses` are the objective values in `T`. `Unsupported` for expression losses, expression
 operators and datasets whose row tile does not fit in LDS (the callers fall back to the
-reference's optimiser).
+reference's optimiser). `grad_tree_code=true` (srhip_optimize_constants_deriv_ex with
+SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE): Float32 candidates run the derivative tree codes, the
+gradient phases as the objective's one-pass gradient tree code.
 """
 function optimize_constants_deriv(trees::AbstractVector{Node{T}}, dataset::Dataset{T}, options::Options;
-                                  device::Int=0) where {T}
+                                  device::Int=0, grad_tree_code::Bool=false) where {T}
     f = options.loss_function::DerivativeObjective{T}
     algo = options.optimizer_algorithm == "BFGS" ? OPT_BFGS :
            options.optimizer_algorithm == "NelderMead" ? OPT_NELDERMEAD :
@@ -1442,10 +1444,11 @@ function optimize_constants_deriv(trees::AbstractVector{Node{T}}, dataset::Datas
                                 Ptr{Cvoid}(pointer(consts))))
             opts = Ref(ConstOptOptions(algo, Int32(options.optimizer_options.iterations), Int32(nr), kindcode,
                                        pointer(params), pointer(noise), UInt64(0)))
-            check(ccall((:srhip_optimize_constants_deriv, libsrhip), Int32,
+            check(ccall((:srhip_optimize_constants_deriv_ex, libsrhip), Int32,
                         (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SrhipTrees}, Ref{ConstOptOptions}, Ptr{Int32}, Int32,
-                         Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}),
-                        context(device), h[], tr, opts, dir, Int32(nd), coef, out_c, out_l, out_k, out_n))
+                         Ptr{Float64}, UInt32, Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}),
+                        context(device), h[], tr, opts, dir, Int32(nd), coef,
+                        grad_tree_code ? UInt32(0x40) : UInt32(0), out_c, out_l, out_k, out_n))
         finally
             destroy_dataset(h[])
         end

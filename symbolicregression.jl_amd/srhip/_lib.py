@@ -136,6 +136,15 @@ SIGNATURES = {
     "srhip_eval_loss_grad_deriv_batch_ctx": [C.c_void_p, C.c_void_p, C.POINTER(Trees), C.c_int32, C.c_void_p,
                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "srhip_eval_mixed_tree_array": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    # derivative objectives: the whole objective's gradient (one-pass gradient tree code)
+    "srhip_eval_objective_grad_deriv": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "srhip_eval_objective_grad_deriv_batch_ctx": [C.c_void_p, C.c_void_p, C.POINTER(Trees), C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p],
+    "srhip_optimize_constants_deriv_ex": [C.c_void_p, C.c_void_p, C.POINTER(Trees), C.POINTER(ConstOptOptions),
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p],
     "srhip_optimize_constants_deriv": [C.c_void_p, C.c_void_p, C.POINTER(Trees), C.POINTER(ConstOptOptions),
                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p],
@@ -164,6 +173,9 @@ SIGNATURES = {
     "srhip_jit_compile_deriv": [C.POINTER(Trees), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                 C.c_void_p, C.POINTER(C.c_int64), C.c_char_p, C.POINTER(C.c_int64), C.c_void_p,
                                 C.POINTER(C.c_int64)],
+    "srhip_jit_compile_deriv_grad": [C.POINTER(Trees), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.c_char_p, C.POINTER(C.c_int64),
+                                     C.c_void_p, C.POINTER(C.c_int64)],
     "srhip_jit_compile_grad": [C.POINTER(Trees), C.c_void_p, C.POINTER(C.c_int64), C.c_char_p,
                                C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)],
     "srhip_jit_compile_loss": [C.POINTER(Trees), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p,

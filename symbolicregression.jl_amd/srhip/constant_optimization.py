@@ -33,6 +33,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
+from . import constants as K
 from ._lib import CONSTOPT_EVAL_FN, ConstOptOptions, check, lib
 from .dataset import Dataset, DerivativeDataset, GroupDataset, MultiDataset
 from .engine import _trees_struct
@@ -243,9 +244,11 @@ def optimize_constants_deriv_batch(dataset: DerivativeDataset, trees: Sequence[N
     dirs = np.ascontiguousarray([d - 1 for d in dataset.directions], dtype=np.int32)
     coef = np.ascontiguousarray(obj.coefficients, dtype=np.float64)
     dev = dataset.multi.device(device)
-    check(lib().srhip_optimize_constants_deriv(dev.ctx.handle, dev.handle, C.byref(tr), C.byref(opts),
-                                               dirs.ctypes.data_as(C.c_void_p), len(dirs),
-                                               coef.ctypes.data_as(C.c_void_p), *ptrs))
+    # grad_tree_code: both derivative tree codes in the evaluation sets' programs (srhip.h)
+    flags = K.PROGRAM_DERIV_GRAD_TREE_CODE if getattr(obj, "grad_tree_code", False) else 0
+    check(lib().srhip_optimize_constants_deriv_ex(dev.ctx.handle, dev.handle, C.byref(tr), C.byref(opts),
+                                                  dirs.ctypes.data_as(C.c_void_p), len(dirs),
+                                                  coef.ctypes.data_as(C.c_void_p), flags, *ptrs))
     conv = out_k[:nt].astype(bool)
     co = flat.const_off
     for i in np.flatnonzero(conv):
@@ -338,10 +341,10 @@ def _consts_of(tree: Node):
 def last_profile() -> dict:
     """Where the last optimize_constants_batch call of this thread spent its
     time (srhip_constopt_profile): seconds and call counts."""
-    out = (C.c_double * 14)()
-    check(lib().srhip_constopt_profile(out, 14))
+    out = (C.c_double * 15)()
+    check(lib().srhip_constopt_profile(out, 15))
     keys = ("total_s", "create_s", "set_constants_s", "loss_s", "grad_s", "kernel_s", "n_create", "n_loss", "n_grad",
-            "n_rebuilt", "jit_codegen_s", "jit_load_s", "gather_s", "n_segment_evals")
+            "n_rebuilt", "jit_codegen_s", "jit_load_s", "gather_s", "n_segment_evals", "n_grad_tree_code")
     d = dict(zip(keys, (float(v) for v in out)))
     d["host_s"] = (d["total_s"] - d["create_s"] - d["set_constants_s"] - d["loss_s"] - d["grad_s"]
                    - d["gather_s"])

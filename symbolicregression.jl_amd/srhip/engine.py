@@ -236,10 +236,13 @@ class Program:
     for LDS keep their tree code.
     deriv_tree_code (SRHIP_PROGRAM_DERIV_TREE_CODE, opt-in): eval_loss_deriv on a
     Float32 program runs reverse-mode tree code when ndir <= 4, the loss is a distance
-    loss other than Periodic and the dataset is not wide; otherwise the interpreter."""
+    loss other than Periodic and the dataset is not wide; otherwise the interpreter.
+    deriv_grad_tree_code (SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE, opt-in): under the same
+    limits eval_objective_grad_deriv runs the objective's one-pass gradient tree code."""
 
     def __init__(self, ctx: Context, flat: FlatTrees, dtype, varying_constants: bool = False,
-                 interpreted: bool = False, wide_tree_code: bool = False, deriv_tree_code: bool = False):
+                 interpreted: bool = False, wide_tree_code: bool = False, deriv_tree_code: bool = False,
+                 deriv_grad_tree_code: bool = False):
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self.flat = flat
@@ -258,7 +261,9 @@ class Program:
                                             (K.PROGRAM_VARYING_CONSTANTS if varying_constants else 0)
                                             | (K.PROGRAM_INTERPRETED if interpreted else 0)
                                             | (K.PROGRAM_WIDE_TREE_CODE if wide_tree_code else 0)
-                                            | (K.PROGRAM_DERIV_TREE_CODE if deriv_tree_code else 0), C.byref(h)))
+                                            | (K.PROGRAM_DERIV_TREE_CODE if deriv_tree_code else 0)
+                                            | (K.PROGRAM_DERIV_GRAD_TREE_CODE if deriv_grad_tree_code else 0),
+                                            C.byref(h)))
         self.handle = h
         self.ntrees = flat.ntrees
 
@@ -480,6 +485,30 @@ class Program:
         check(lib().srhip_eval_loss_grad_deriv(ds.handle, self.handle, int(loss_kind), _p(par), _p(d) if nd else None,
                                                nd, _p(sums), _p(grads), _p(wsum), _p(ok)))
         return sums[:nt], grads[:nc], wsum, ok[:nt].astype(bool)
+
+    def eval_objective_grad_deriv(self, ds, loss_kind: int, directions, coefficients, params=None):
+        """srhip_eval_objective_grad_deriv: the gradient of Σ_c coefficients[c] · mean_c with
+        respect to every constant in one call: (Σ w·ℓ [ntrees, 1 + ndir], gradient [total
+        consts] in float64, Σ w per column [1 + ndir], ok). On a deriv_grad_tree_code program
+        the trees the code generator takes run as one-pass gradient tree code."""
+        nt = self.ntrees
+        nc = int(self.flat.const_off[-1])
+        d = np.ascontiguousarray(directions, dtype=np.int32)
+        if d.ndim != 1:
+            raise ValueError("directions must be a list of feature indices")
+        nd = len(d)
+        coef = np.ascontiguousarray(coefficients, dtype=np.float64)
+        if coef.shape != (1 + nd,):
+            raise ValueError("coefficients must hold one value per channel (1 + ndir)")
+        sums = np.zeros((max(nt, 1), 1 + nd), dtype=np.float64)
+        grad = np.zeros(max(nc, 1), dtype=np.float64)
+        wsum = np.zeros(1 + nd, dtype=np.float64)
+        ok = np.zeros(max(nt, 1), dtype=np.uint8)
+        par = None if params is None else np.asarray(params, dtype=np.float64)
+        check(lib().srhip_eval_objective_grad_deriv(ds.handle, self.handle, int(loss_kind), _p(par),
+                                                    _p(d) if nd else None, nd, _p(coef), _p(sums), _p(grad), _p(wsum),
+                                                    _p(ok)))
+        return sums[:nt], grad[:nc], wsum, ok[:nt].astype(bool)
 
     def eval_mixed_tree_array(self, ds, directions):
         """srhip_eval_mixed_tree_array: (∂ŷ/∂x_d [ntrees, ndir, rows], ∂²ŷ/∂x_d∂c
@@ -735,7 +764,7 @@ def _trees_struct(flat: FlatTrees, consts: np.ndarray) -> Trees:
 
 
 def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bool = False, loss=None,
-                out: bool = False, text: bool = True, wide: bool = False, deriv=None):
+                out: bool = False, text: bool = True, wide: bool = False, deriv=None, deriv_grad: bool = False):
     """Tree compiler without a device (srhip_jit_compile, or with grad=True
     srhip_jit_compile_grad: the reverse-mode gradient tree code; memc: the
     memory-constant loss tree code; loss: a Loss other than L2, through
@@ -744,7 +773,8 @@ def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bo
     reads its features from X in device memory): (code bytes, assembly text,
     {tree id: byte offset}). deriv=(directions (0-based), nfeat, weighted): the
     derivative tree code of eval_loss_deriv (srhip_jit_compile_deriv), under `loss`
-    (default L2)."""
+    (default L2); with deriv_grad=True the objective's gradient tree code
+    (srhip_jit_compile_deriv_grad)."""
     f64 = np.dtype(flat.consts.dtype) == np.float64
     consts = np.ascontiguousarray(flat.consts, dtype=np.float64 if f64 else np.float32)
     tr = _trees_struct(flat, consts)
@@ -754,8 +784,9 @@ def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bo
         if deriv is not None:
             d = np.ascontiguousarray(deriv[0], dtype=np.int32)
             kind, param = (0, 0.0) if loss is None else (int(loss.kind), float(loss.param))
-            return lib().srhip_jit_compile_deriv(C.byref(tr), _p(d), len(d), int(deriv[1]), int(bool(deriv[2])), kind, param,
-                                                 bufs[0], C.byref(nb), bufs[1], C.byref(nt), bufs[2], C.byref(no))
+            fn = lib().srhip_jit_compile_deriv_grad if deriv_grad else lib().srhip_jit_compile_deriv
+            return fn(C.byref(tr), _p(d), len(d), int(deriv[1]), int(bool(deriv[2])), kind, param,
+                      bufs[0], C.byref(nb), bufs[1], C.byref(nt), bufs[2], C.byref(no))
         if f64 and grad:  # the Float64 gradient tree code (jit64.cpp GradGen64)
             kind, param = (0, 0.0) if loss is None else (int(loss.kind), float(loss.param))
             return lib().srhip_jit_compile_loss(C.byref(tr), 1, 8, kind, param, bufs[0], C.byref(nb), bufs[1],

@@ -215,10 +215,13 @@ class DerivativeObjective:
     (eval_deriv_loss_batch). `eval_tree_array` / `eval_diff_tree_array` replace the
     two evaluators of the per-tree call (tests run it on a CPU evaluator).
     `tree_code=True` (SRHIP_PROGRAM_DERIV_TREE_CODE) lets the fused call run Float32
-    batches as reverse-mode tree code (up to 4 directions, no Periodic loss)."""
+    batches as reverse-mode tree code (up to 4 directions, no Periodic loss).
+    `grad_tree_code=True` (SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE) lets
+    optimize_constants_deriv_batch and eval_deriv_objective_grad_batch run the objective's
+    one-pass gradient tree code under the same limits (mirrors ExprLoss(grad_tree_code=True))."""
 
     def __init__(self, coefficients: Sequence[float], elementwise_loss=None, eval_tree_array=None,
-                 eval_diff_tree_array=None, tree_code: bool = False):
+                 eval_diff_tree_array=None, tree_code: bool = False, grad_tree_code: bool = False):
         c = np.asarray(coefficients, dtype=np.float64)
         if c.ndim != 1 or len(c) < 2:
             raise ValueError("coefficients must hold one value per channel: y, then one per direction")
@@ -232,6 +235,7 @@ class DerivativeObjective:
         self._eval = eval_tree_array
         self._diff = eval_diff_tree_array
         self.tree_code = bool(tree_code)
+        self.grad_tree_code = bool(grad_tree_code)
 
     def loss(self, options: Options):
         loss = self.elementwise_loss if self.elementwise_loss is not None else options.elementwise_loss
@@ -309,6 +313,34 @@ def eval_deriv_loss_batch(trees: Sequence[Node], dataset: DerivativeDataset, opt
     with np.errstate(invalid="ignore", divide="ignore"):
         means = sums / wsum[None, :]
     return means, ok
+
+
+def eval_deriv_objective_grad_batch(trees: Sequence[Node], dataset: DerivativeDataset, options: Options,
+                                    device: Optional[int] = None, grad_tree_code: Optional[bool] = None):
+    """eval_deriv_loss_grad_batch through srhip_eval_objective_grad_deriv: the engine combines
+    the channels itself, and with grad_tree_code (default: that of options.loss_function) the
+    Float32 trees the code generator takes run as one-pass gradient tree code. Returns (values
+    [ntrees] in float64, +Inf where failed; ∂objective/∂c [total constants], NaN for a failed
+    tree; did_succeed per tree)."""
+    obj = options.loss_function
+    if not isinstance(obj, DerivativeObjective):
+        raise ValueError("eval_deriv_objective_grad_batch needs a DerivativeObjective as options.loss_function")
+    ds = obj.check(dataset)
+    loss = obj.loss(options)
+    trees = list(trees)
+    T = ds.T
+    dev = ds.multi.device(device)
+    flat = flatten(trees, options, dtype=T)
+    tc = obj.grad_tree_code if grad_tree_code is None else bool(grad_tree_code)
+    prog = Program(dev.ctx, flat, T, interpreted=True, deriv_grad_tree_code=tc)
+    sums, g, wsum, ok = prog.eval_objective_grad_deriv(dev, loss.kind, [d - 1 for d in ds.directions], obj.coefficients,
+                                                       loss.params)
+    with np.errstate(all="ignore"):
+        v = np.zeros(len(trees))
+        for c in range(1 + ds.ndir):
+            v = v + obj.coefficients[c] * sums[:, c] / wsum[c]
+    v[~(ok & np.isfinite(v))] = np.inf
+    return v, g, ok
 
 
 def eval_deriv_loss_grad_batch(trees: Sequence[Node], dataset: DerivativeDataset, options: Options,
