@@ -302,9 +302,10 @@ int32_t srhip_loss_expr_eval(int32_t loss_kind, int32_t dtype, const void* yhat,
  * handle does not disturb programs that exist. Deviation from the reference, as
  * for expression losses: a Float64 literal in a Julia body promotes a Float32
  * argument to Float64, the engine stays in T. Trees whose program holds such an
- * operator always run in the 16-slot interpreter kernels (no tree code: the
- * srhip_jit_compile* hooks leave them out); the other trees of the program keep
- * their kernels. */
+ * operator run in the 16-slot interpreter kernels (no tree code: the
+ * srhip_jit_compile* hooks leave them out) unless the program was made with
+ * SRHIP_PROGRAM_EXPR_OP_TREE_CODE; the other trees of the program keep their
+ * kernels. */
 #define SRHIP_EXPR_OP_BEGIN 1024 /* operator ids from here on are handles of expression operators */
 /* arity 1 or 2; consts[nconsts]: the constant leaves in stream order. */
 int32_t srhip_op_expr_create(int32_t arity, const uint8_t* kind, const uint16_t* arg, int32_t nnodes,
@@ -420,6 +421,20 @@ int32_t srhip_program_create(srhip_ctx* ctx, int32_t dtype,
  * SRHIP_PROGRAM_DERIV_TREE_CODE; no effect on Float64 programs or on any other call.
  * Refused (SRHIP_ERR_UNSUPPORTED) for a device-group program. */
 #define SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE 0x40u
+/* SRHIP_PROGRAM_EXPR_OP_TREE_CODE (opt-in): the Float32 loss tree code of this program
+ * also compiles the trees that hold expression operators, under rules 1-6 of "expression
+ * operators" above: every computed argument is checked, the body runs in line with
+ * nothing inside it checked, and an argument is read as often as the body names it. It
+ * serves them wherever the program's loss tree code serves the other trees: srhip_eval_loss
+ * and the calls that share its modules, every table loss and flagged expression loss,
+ * literal- and memory-constant code (srhip_program_set_constants keeps working; body
+ * constants never move). A tree the compiler refuses (its values do not fit the register
+ * blocks) stays in the 16-slot interpreter kernels, beside compiled neighbours. Still
+ * interpreted for such trees: per-row outputs, gradients, Float64, wide and
+ * derivative-objective tree code, per-tree row sets and targets. No effect on Float64
+ * programs, with SRHIP_PROGRAM_INTERPRETED, or on the member programs of a device
+ * group. */
+#define SRHIP_PROGRAM_EXPR_OP_TREE_CODE 0x80u
 int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees* trees, uint32_t flags,
                                 srhip_program** out_prog);
 int32_t srhip_program_destroy(srhip_program* prog);
@@ -1105,6 +1120,13 @@ int32_t srhip_program_shared_columns(const srhip_program* prog, char* out_text, 
 int32_t srhip_jit_compile(const srhip_trees* trees, int32_t fast, uint8_t* out_bytes, int64_t* inout_nbytes,
                           char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
                           int64_t* inout_noffsets);
+/* srhip_jit_compile with a word of SRHIP_PROGRAM_* flags: with
+ * SRHIP_PROGRAM_EXPR_OP_TREE_CODE (and none of fast's bits 2, 3 and 5) the trees that
+ * hold expression operators are compiled too; every other flag is ignored, and with
+ * flags = 0 the answer is srhip_jit_compile's. */
+int32_t srhip_jit_compile_ex(const srhip_trees* trees, int32_t fast, uint32_t flags, uint8_t* out_bytes,
+                             int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
+                             int64_t* inout_noffsets);
 /* Testing hook, same contract: the gradient tree code (reverse-mode ∂L/∂c,
  * the fast path of srhip_eval_loss_grad) of Float32 trees. */
 int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int64_t* inout_nbytes,

@@ -312,6 +312,13 @@ struct srhip_program {
   jit::Module64* jit64 = nullptr;  // Float64 programs: the same slots as Float64 tree code (jit64.cpp)
   int nlist_j = 0;
   std::vector<int32_t> h_jit_list;  // the trees of those slots, in slot order
+  // SRHIP_PROGRAM_EXPR_OP_TREE_CODE (Float32): trees that hold expression operators are
+  // offered to the loss tree code too (jit::Options::exprops). The nlist_je of them that
+  // compile are the last of the nlist_j tree-code slots: a call that runs no tree code on
+  // them (per-row outputs, row sets, per-tree targets) runs those slots in the deep
+  // OPSET_EXPR interpreter pass (run_eval); the refused ones stay in the deep list.
+  bool expr_tc = false;
+  int nlist_je = 0;
   // the same trees' tree code for other elementwise losses (jit::Options::loss),
   // built at a loss's first evaluation; null m: that loss runs interpreted
   struct LossJit { int kind; uint64_t bits; jit::Module* m; };
@@ -1228,9 +1235,17 @@ void build_program(srhip_program* p) {
   free_loss_jits(p);
   p->h_jit_list.clear();
   p->nlist_j = 0;
+  p->nlist_je = 0;
   p->jit_stats = jit::Stats();
   if constexpr (std::is_same<T, float>::value) {
-    if (p->jit_allowed && (jit_wanted((int)a.size()) || (p->jit_forced && jit::available() && !a.empty()))) {
+    // SRHIP_PROGRAM_EXPR_OP_TREE_CODE: the trees with expression-operator code (all in b) are
+    // candidates too, after the shallow ones
+    std::vector<int32_t> xc;
+    if (p->expr_tc && p->jit_allowed)
+      for (int32_t t : b)
+        if (cb.expr[t]) xc.push_back(t);
+    const int ncand = (int)(a.size() + xc.size());
+    if (p->jit_allowed && (jit_wanted(ncand) || (p->jit_forced && jit::available() && ncand > 0))) {
       std::vector<int32_t> jl, rest;
       jit::Options jo;
       jo.fast = jit_fast_enabled();
@@ -1238,13 +1253,25 @@ void build_program(srhip_program* p) {
       // wide code when a candidate reads a feature past the LDS tile's reach (features 0 .. 62)
       jo.xg = p->wide_tc && !jo.memc && jit::max_feature_read(cb, a) >= 63;
       jo.slots = column_slots(p);
-      p->jit = jit::build(cb, a, jl, rest, jo, &p->jit_stats);
+      jo.exprops = !xc.empty() && !jo.xg;  // (wide code takes none: they stay in the deep list)
+      std::vector<int32_t> cand(a);
+      if (jo.exprops) cand.insert(cand.end(), xc.begin(), xc.end());
+      p->jit = jit::build(cb, cand, jl, rest, jo, &p->jit_stats);
       if (p->jit) {
         p->nlist_j = (int)jl.size();
         p->h_jit_list = jl;
         p->jit_consts = p->consts;
+        // the compiled ones lead the list, the operator trees last among them (jl is in candidate
+        // order); a refused operator tree keeps its place in the deep list
         a = jl;
-        a.insert(a.end(), rest.begin(), rest.end());
+        for (int32_t t : rest)
+          if (!cb.expr[t]) a.push_back(t);
+        std::vector<char> compiled((size_t)p->ntrees, 0);
+        for (int32_t t : jl) {
+          compiled[(size_t)t] = 1;
+          p->nlist_je += cb.expr[t] ? 1 : 0;
+        }
+        b.erase(std::remove_if(b.begin(), b.end(), [&](int32_t t) { return compiled[(size_t)t] != 0; }), b.end());
       }
     }
   } else {
@@ -1433,7 +1460,7 @@ void rerun_bailed(srhip_ctx* c, const srhip_program* p, jit::Module* jm, const E
   (void)jplan;
   if constexpr (std::is_same<T, float>::value) {
     hipStream_t s = c->stream;
-    const int nj = p->nlist_j;
+    const int nj = jit::nslots(jm);
     if (!jit::module_bails(jm)) return;  // no routine hands a tile back: the finalize copied the counters
     std::vector<uint32_t> flags((size_t)nj + 2);
     HIP_CHECK(hipMemcpyAsync(flags.data(), jit::bail_flags(jm), flags.size() * sizeof(uint32_t),
@@ -1461,7 +1488,9 @@ void rerun_bailed(srhip_ctx* c, const srhip_program* p, jit::Module* jm, const E
     HIP_CHECK(hipMemcpyAsync(c->bail_list.p, bl.data(), bl.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(c->bail_fail.p, 0, (size_t)nb * sizeof(uint32_t), s));
     EvalPlan plan;
-    plan_interp(p->dtype, false, OPSET_FULL, MODE_LOSS, ja.w != nullptr, nfeat, rows, nb, &plan);
+    // (a handed-back tree may hold expression-operator code: the deep kernel runs any program)
+    plan_interp(p->dtype, p->nlist_je > 0, p->nlist_je > 0 ? (int)OPSET_EXPR : (int)OPSET_FULL, MODE_LOSS, ja.w != nullptr,
+                nfeat, rows, nb, &plan);
     EvalArgs<T> a = ja;
     a.contig = 0;  // the interpreter kernel deals its slots in snake order
     a.rotate = 0;
@@ -1470,7 +1499,7 @@ void rerun_bailed(srhip_ctx* c, const srhip_program* p, jit::Module* jm, const E
     a.fail = static_cast<uint32_t*>(c->bail_fail.p);
     a.nlist = nb;
     a.ti_rec = nullptr;
-    if (ti_enabled() && !plan.wide) {
+    if (ti_enabled() && !plan.wide && p->nlist_je == 0) {  // (the shallow kernel's records)
       c->ti_rec.ensure((size_t)nb * 64 * sizeof(uint4));
       HIP_CHECK(launch_ti_records(reinterpret_cast<const Ins<float>*>(a.prog), a.list_off, nb,
                                   (uint32_t)(plan.ntiles * plan.tile * sizeof(T)), static_cast<uint4*>(c->ti_rec.p), s));
@@ -1649,6 +1678,7 @@ jit::Module* expr_loss_module(const srhip_program* p, int loss) {
   jo.memc = jit::memc(p->jit);
   jo.lexpr = &e->lx;
   jo.slots = column_slots(p);
+  jo.exprops = p->nlist_je > 0;
   return lazy_module<float, jit::Module>(
       p, p->jit_loss, loss, 0, p->jit_consts, false,
       [&](const CompiledBatch<float>& cb, std::vector<int32_t>& jl, std::vector<int32_t>& rest) {
@@ -1676,6 +1706,7 @@ jit::Module* loss_module(const srhip_program* p, int loss, double lparam) {
   jo.loss = loss;
   jo.lparam = bits_of(lparam);
   jo.slots = column_slots(p);
+  jo.exprops = p->nlist_je > 0;
   return lazy_module<float, jit::Module>(
       p, p->jit_loss, loss, jo.lparam, p->jit_consts, false,
       [&](const CompiledBatch<float>& cb, std::vector<int32_t>& jl, std::vector<int32_t>& rest) {
@@ -1724,13 +1755,16 @@ jit::Module* out_module(const srhip_program* p) {
   jo.fast = false;
   jo.memc = jit::memc(p->jit);
   jo.out = true;
+  // (no per-row output code for expression-operator trees: the slots before them)
+  const std::vector<int32_t> plain(p->h_jit_list.begin(), p->h_jit_list.end() - p->nlist_je);
+  if (plain.empty()) return nullptr;
   return lazy_module<float, jit::Module>(
       p, p->jit_loss, -2, 0, p->jit_consts, false,
       [&](const CompiledBatch<float>& cb, std::vector<int32_t>& jl, std::vector<int32_t>& rest) {
         jit::Stats st;
-        return jit::build(cb, p->h_jit_list, jl, rest, jo, &st);
+        return jit::build(cb, plain, jl, rest, jo, &st);
       },
-      [&](const std::vector<int32_t>& jl, const std::vector<int32_t>& rest) { return jl == p->h_jit_list && rest.empty(); },
+      [&](const std::vector<int32_t>& jl, const std::vector<int32_t>& rest) { return jl == plain && rest.empty(); },
       jit::destroy);
 }
 
@@ -2148,8 +2182,10 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
     }
   }
   const bool use_jit = jm != nullptr || jm64 != nullptr;
-  c->last_jit_trees = (use_jit && rows > 0) ? p->nlist_j : 0;
-  const int nj = use_jit ? p->nlist_j : 0;
+  // the slots this call's tree code runs: all nlist_j, or (per-row output code of a program with
+  // compiled expression-operator trees, out_module) the ones before those
+  const int nj = jm ? jit::nslots(jm) : jm64 ? p->nlist_j : 0;
+  c->last_jit_trees = rows > 0 ? nj : 0;
   // failure flags (and the tree code's bail flags): the finalize kernels of
   // the previous call left them clean; one clearing launch only after a new
   // buffer, an interrupted call or a path that leaves them set (gradients,
@@ -2187,7 +2223,15 @@ void run_eval(srhip_ctx* c, const srhip_program* p, int mode, const T* X, const 
       }
     }
   }
-  launches.push_back({0, nj, p->nlist_a - nj, -1});
+  if (p->nlist_je > 0 && nj < p->nlist_j) {
+    // compiled expression-operator trees that this call runs interpreted: the deep pass
+    const int xs = p->nlist_j - p->nlist_je;
+    launches.push_back({0, nj, std::max(xs - nj, 0), -1});
+    launches.push_back({1, std::max(nj, xs), p->nlist_j - std::max(nj, xs), -1});
+    launches.push_back({0, p->nlist_j, p->nlist_a - p->nlist_j, -1});
+  } else {
+    launches.push_back({0, nj, p->nlist_a - nj, -1});
+  }
   launches.push_back({1, p->nlist_a, p->nlist_b, -1});
   const float* shared_cols = nullptr;  // the shared-subtree columns of the tree-code parts
   for (size_t li = 0; li < launches.size(); ++li) {
@@ -4135,7 +4179,7 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
     if (dtype != SRHIP_F32 && dtype != SRHIP_F64) throw Error(SRHIP_ERR_UNSUPPORTED, "dtype must be F32 or F64");
     if (trees->ntrees < 0) throw Error(SRHIP_ERR_INVALID, "negative tree count");
     if (flags & ~(SRHIP_PROGRAM_VARYING_CONSTANTS | SRHIP_PROGRAM_INTERPRETED | SRHIP_PROGRAM_WIDE_TREE_CODE |
-                  SRHIP_PROGRAM_DERIV_TREE_CODE | SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE))
+                  SRHIP_PROGRAM_DERIV_TREE_CODE | SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE | SRHIP_PROGRAM_EXPR_OP_TREE_CODE))
       throw Error(SRHIP_ERR_INVALID, "unknown program flags");
     const int nt = trees->ntrees;
     auto* p = new srhip_program();
@@ -4147,6 +4191,7 @@ int32_t srhip_program_create_ex(srhip_ctx* ctx, int32_t dtype, const srhip_trees
     p->wide_tc = (flags & SRHIP_PROGRAM_WIDE_TREE_CODE) != 0 && dtype == SRHIP_F32;
     p->deriv_tc = (flags & SRHIP_PROGRAM_DERIV_TREE_CODE) != 0 && dtype == SRHIP_F32;
     p->deriv_gtc = (flags & SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE) != 0 && dtype == SRHIP_F32;
+    p->expr_tc = (flags & SRHIP_PROGRAM_EXPR_OP_TREE_CODE) != 0 && dtype == SRHIP_F32;
     try {
       if (nt > 0) {
         if (!trees->node_off || !trees->const_off) throw Error(SRHIP_ERR_INVALID, "null offsets");
@@ -4732,17 +4777,20 @@ namespace {
 // the trees a tree compiler is offered: compiled, no expression-operator code, and
 // (loss and output code) within the shallow interpreter's slots
 template <typename T>
-std::vector<int32_t> candidates(const CompiledBatch<T>& cb, bool shallow) {
+std::vector<int32_t> candidates(const CompiledBatch<T>& cb, bool shallow, bool exprops = false) {
   std::vector<int32_t> cand;
   for (int t = 0; t < cb.ntrees; ++t)
     if (cb.tree_off[t] >= 0 && (!shallow || cb.need[t] <= kShallowSlots) && !cb.expr[t]) cand.push_back(t);
+  // SRHIP_PROGRAM_EXPR_OP_TREE_CODE: the trees with expression-operator code after them, as build_program
+  for (int t = 0; t < cb.ntrees && exprops; ++t)
+    if (cb.tree_off[t] >= 0 && cb.expr[t]) cand.push_back(t);
   return cand;
 }
 
 int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes, int64_t* inout_nbytes,
                          char* out_text, int64_t* inout_ntext, int32_t* out_offsets, int64_t* inout_noffsets,
                          int loss = SRHIP_LOSS_L2, double lparam = 0.0, bool out_mode = false, bool notext = false,
-                         bool wide = false, const jit::DerivSpec* dspec = nullptr) {
+                         bool wide = false, const jit::DerivSpec* dspec = nullptr, bool exprops = false) {
   return guarded([&] {
     if (!trees || !inout_nbytes || !inout_ntext || !inout_noffsets) throw Error(SRHIP_ERR_INVALID, "null argument");
     if (!jit::available()) throw Error(SRHIP_ERR_UNSUPPORTED, std::string("tree compiler: ") + jit::unavailable_reason());
@@ -4805,7 +4853,8 @@ int32_t jit_compile_hook(const srhip_trees* trees, int mode, uint8_t* out_bytes,
       jo.lexpr = xloss ? &xloss->lx : nullptr;
       jo.out = out_mode;
       jo.xg = wide;
-      jit::compile_only(cb, candidates(cb, true), jo, &bytes, &text, &offs, nullptr);
+      jo.exprops = exprops && !out_mode && !wide;
+      jit::compile_only(cb, candidates(cb, true, jo.exprops), jo, &bytes, &text, &offs, nullptr);
     }
     if ((int64_t)bytes.size() > *inout_nbytes || (int64_t)text.size() + 1 > *inout_ntext ||
         (int64_t)offs.size() > *inout_noffsets) {
@@ -4837,6 +4886,16 @@ int32_t srhip_jit_compile(const srhip_trees* trees, int32_t fast, uint8_t* out_b
   return jit_compile_hook(trees, (fast & 2) ? ((fast & 1) ? 4 : 3) : ((fast & 1) ? 1 : 0), out_bytes, inout_nbytes,
                           out_text, inout_ntext, out_offsets, inout_noffsets, SRHIP_LOSS_L2, 0.0, (fast & 4) != 0,
                           (fast & 16) != 0, (fast & 32) != 0);
+}
+
+int32_t srhip_jit_compile_ex(const srhip_trees* trees, int32_t fast, uint32_t flags, uint8_t* out_bytes,
+                             int64_t* inout_nbytes, char* out_text, int64_t* inout_ntext, int32_t* out_offsets,
+                             int64_t* inout_noffsets) {
+  if (!(flags & SRHIP_PROGRAM_EXPR_OP_TREE_CODE) || (fast & 8))
+    return srhip_jit_compile(trees, fast, out_bytes, inout_nbytes, out_text, inout_ntext, out_offsets, inout_noffsets);
+  return jit_compile_hook(trees, (fast & 2) ? ((fast & 1) ? 4 : 3) : ((fast & 1) ? 1 : 0), out_bytes, inout_nbytes,
+                          out_text, inout_ntext, out_offsets, inout_noffsets, SRHIP_LOSS_L2, 0.0, (fast & 4) != 0,
+                          (fast & 16) != 0, (fast & 32) != 0, nullptr, true);
 }
 
 int32_t srhip_jit_compile_grad(const srhip_trees* trees, uint8_t* out_bytes, int64_t* inout_nbytes,
@@ -5731,7 +5790,9 @@ srhip_group_program* create_group_program(srhip_group* g, int32_t dtype, const s
   std::lock_guard<std::mutex> lk(g->mu);
   auto st = run_members(g, [&](int k) {
     host_thread_cap() = cap;
-    const int32_t rc = srhip_program_create_ex(g->ctx[k], dtype, trees, flags, &gp->prog[k]);
+    // (member programs keep expression-operator trees interpreted)
+    const int32_t rc = srhip_program_create_ex(g->ctx[k], dtype, trees, flags & ~SRHIP_PROGRAM_EXPR_OP_TREE_CODE,
+                                               &gp->prog[k]);
     host_thread_cap() = 0;
     check_rc(rc);
     gp->prog[k]->in_group = true;

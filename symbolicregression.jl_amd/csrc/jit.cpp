@@ -78,7 +78,11 @@ struct IrOp {
   int rid = -1;      // routine, -1: inline
   int krid = -1;     // constant-operand routine variant (constant in s_k), -1: none
   bool taint = false, zs = false;
-  int consumer = -1, cpos = 0;
+  int consumer = -1, cpos = 0;  // the last operation that reads the value, and as which operand
+  // expression operators (Options::exprops): an operation of an operator's body (nothing inside a
+  // body marks or fails the tree), and a computed argument, folded into chk once it is there
+  bool body = false, argmark = false;
+  int nuse = 0;  // operand references: a body may read an argument several times
 };
 
 constexpr uint32_t kFastUops = (1u << SRHIP_UOP_NEG) | (1u << SRHIP_UOP_ABS) | (1u << SRHIP_UOP_SQUARE) |
@@ -112,6 +116,7 @@ struct DerivedMap {
   // (Columns::slot), column gbase + number of the tree code; empty: none (memory-constant or per-row output code)
   std::unordered_map<std::string, int> gidx;
   int gbase = 1 << 30;
+  bool xops = false;  // build_ir takes the micro-instructions of expression operators (Options::exprops)
   void set_shared(const Columns& c) {
     gidx.clear();
     for (int g = 0; g < c.ngcol; ++g) gidx.emplace(c.gkey[g], c.slot(g));
@@ -133,7 +138,20 @@ bool is_routine_uop(int op) {
 
 // Program (compile.cpp) → IR: the accumulator machine with register renaming;
 // u(x_f) of a derived column becomes a read of that column.
-bool build_ir(const Ins<float>* p, std::vector<IrOp>& ops, Opnd& root, const DerivedMap* dm = nullptr) {
+// Expression operators (xops, or dm->xops; refused otherwise): the program carries the
+// expansion (compile.cpp emit_xop) — each computed argument followed by OP_MARK and held
+// in a reserved slot, then the body in line with the no-mark flag on every instruction,
+// reading the slots with OP_LDS0 + k / OP_POP0 + k. OP_MARK sets `argmark` on the value
+// in acc, a flagged operator becomes a `body` operation, a slot read yields the slot's
+// operand: a value may then have several consumers (IrOp::nuse). A body's u(x_f) on a bound
+// feature may read the derived column like any other (the column holds the routine's own
+// PRECISE value, Inf where it overflows, and reading it marks nothing); an argument that
+// is u(x_f) itself does not: the mark wants a value of the tree's own. Shared-subtree
+// columns, whose non-finite rows are NaN-poisoned, never stand in for a body's inside
+// (subtree_keys).
+bool build_ir(const Ins<float>* p, std::vector<IrOp>& ops, Opnd& root, const DerivedMap* dm = nullptr,
+              bool xops = false) {
+  xops = xops || (dm && dm->xops);
   ops.clear();
   Opnd acc, tmp, slot[kMaxSlots];
   for (int pc = 0;; ++pc) {
@@ -154,22 +172,31 @@ bool build_ir(const Ins<float>* p, std::vector<IrOp>& ops, Opnd& root, const Der
     if (opc == OP_LDC) { acc = C(imm); continue; }
     if (opc >= OP_PUSH0 && opc < OP_PUSH0 + kMaxSlots) { slot[opc - OP_PUSH0] = acc; continue; }
     if (opc >= OP_POP0 && opc < OP_POP0 + kMaxSlots) { tmp = slot[opc - OP_POP0]; continue; }
+    const bool body = xops && (code & kNoMark) != 0;
+    if (opc >= kNumOpcodes) {
+      if (!xops) return false;
+      if (opc >= OP_LDS0 && opc < OP_LDS0 + kMaxSlots) { acc = slot[opc - OP_LDS0]; continue; }
+      if (opc != OP_MARK || acc.k != O_VAL) return false;
+      ops[(size_t)acc.v].argmark = true;
+      continue;
+    }
     if (opc >= OP_UN0 && opc < OP_BIN0) {
-      if (dm && acc.k == O_X && !acc.der) {
+      if (dm && acc.k == O_X && !acc.der && !(xops && (int)(p[pc + 1].code & 0xffu) == OP_MARK)) {
         const int c = dm->col(opc - OP_UN0, acc.v);
         if (c >= 0) { acc = X(c); acc.der = true; continue; }
       }
-      IrOp o; o.un = true; o.op = opc - OP_UN0; o.a = acc;
+      IrOp o; o.un = true; o.op = opc - OP_UN0; o.a = acc; o.body = body;
       if (acc.k != O_VAL && !(o.un && is_inline(o) && acc.k == O_X)) {
         // a unary operator on a leaf (only with constant folding off): keep it simple
-        if (acc.k == O_C) return false;
+        // (a body applies its operators to whatever the argument is: a constant leaf too)
+        if (acc.k == O_C && !body) return false;
       }
       acc = val(o);
       continue;
     }
     const int v = (opc - OP_BIN0) / SRHIP_NUM_BOPS;
     const int b = (opc - OP_BIN0) % SRHIP_NUM_BOPS;
-    IrOp o; o.un = false; o.op = b;
+    IrOp o; o.un = false; o.op = b; o.body = body;
     uint32_t g;
     std::memcpy(&g, &imm, 4);
     switch (v) {
@@ -221,6 +248,7 @@ static void subtree_keys(const std::vector<IrOp>& ops, const Columns* cols, Subt
   si.routine.assign(n, 0);
   for (size_t i = 0; i < n; ++i) {
     const IrOp& o = ops[i];
+    if (o.body || o.argmark) continue;  // no column stands in for a body's inside or for a checked argument
     const bool inl = is_inline(o);
     int f = inl ? 8 : 120, p = inl ? 8 : 260;
     bool r = !inl;
@@ -547,6 +575,9 @@ struct Gen {
   bool exp_tainted(const IrOp& o) const {
     return o.un && o.op == SRHIP_UOP_EXP && o.a.k == O_VAL && ops[o.a.v].taint;
   }
+  // the FAST exp's range guard: every exp outside a body, and a body's (PRECISE) exp of a
+  // FAST-derived argument, whose rounding it amplifies all the same
+  bool exp_guarded(const IrOp& o) const { return o.un && o.op == SRHIP_UOP_EXP && (!o.body || exp_tainted(o)); }
   int reg_of_loc(int l) const { return l == L_A ? VA : l == L_B ? VB : VPOOL0 + R * l; }
 
   bool analyze() {
@@ -571,9 +602,11 @@ struct Gen {
       for (int s = 0; s < 2; ++s) {
         const Opnd& q = s ? o.b : o.a;
         if (s && o.un) break;
-        if (q.k == O_VAL) { ops[q.v].consumer = i; ops[q.v].cpos = s; }
+        if (q.k == O_VAL) { ops[q.v].consumer = i; ops[q.v].cpos = s; ops[q.v].nuse++; }
       }
     }
+    uses_left.assign((size_t)n, 0);
+    for (int i = 0; i < n; ++i) uses_left[(size_t)i] = ops[i].nuse;
     // a loss routine that hands a tile back (Float32 Periodic beyond its Cody-Waite range)
     if (!out && loss_bails(loss)) has_trig = true;
     if (memc) {
@@ -603,7 +636,8 @@ struct Gen {
     fast = elig && (trans || pdiv);
     for (int i = 0; i < n; ++i) {
       IrOp& o = ops[i];
-      o.taint = o.un && (o.op == SRHIP_UOP_EXP || o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS);
+      // (a body's routines run PRECISE whatever the tile's mode, call_body: no FAST rounding of their own)
+      o.taint = o.un && !o.body && (o.op == SRHIP_UOP_EXP || o.op == SRHIP_UOP_SIN || o.op == SRHIP_UOP_COS);
       if (o.a.k == O_VAL && ops[o.a.v].taint) o.taint = true;
       if (!o.un && o.b.k == O_VAL && ops[o.b.v].taint) o.taint = true;
     }
@@ -627,7 +661,7 @@ struct Gen {
     }
     if (fast) {
       for (auto& o : ops) {
-        if (o.un && o.op == SRHIP_UOP_EXP) g_exp = true;
+        if (exp_guarded(o)) g_exp = true;
         if (trig_of_tainted(o)) g_trig = true;
         if (trig_small(o)) g_can = true;  // its guard shares the cancellation accumulator
         if (o.taint && o.zs) {
@@ -770,13 +804,79 @@ struct Gen {
     if (issued) { as.waitcnt_lgkm(0); waited = nloads; }
   }
 
-  // value v leaves its location (its last use)
-  void release_val(int v) {
+  // one use of value v is done; at its last use it leaves its location (true). An argument
+  // of an expression operator is read once per occurrence in the body (uses_left).
+  std::vector<int> uses_left;
+  bool release_val(int v) {
+    if (--uses_left[(size_t)v] > 0) return false;
     const int l = loc[v];
     if (l == L_A) { if (a_owner == v) a_owner = -1; }
     else if (l == L_B) { if (b_owner == v) b_owner = -1; }
     else if (l >= 0 && pool_owner[l] == v) pool_owner[l] = -1;
+    return true;
   }
+  // operand references to value v in operation o
+  static int refs(const IrOp& o, int v) {
+    return (o.a.k == O_VAL && o.a.v == v ? 1 : 0) + (!o.un && o.b.k == O_VAL && o.b.v == v ? 1 : 0);
+  }
+  // A routine overwrites A (and a binary one B): an operand that is read again after
+  // operation i moves to a pool block first and is handed over as a copy.
+  bool keep_operand(int i, int v, bool binary) {
+    if (v < 0 || uses_left[(size_t)v] <= refs(ops[i], v)) return true;
+    const int l = loc[v];
+    if (l != L_A && !(binary && l == L_B)) return true;
+    const int k = free_block();
+    if (k < 0) { why = "register pool exhausted (argument kept)"; return false; }
+    mov_block_reg(VPOOL0 + R * k, l == L_A ? VA : VB);
+    (l == L_A ? a_owner : b_owner) = -1;
+    pool_owner[k] = v;
+    loc[v] = k;
+    return true;
+  }
+  // ---- expression operators (IrOp::body / argmark) ----
+  // A computed argument is folded into chk where it was computed, in the root mark's
+  // untrimmed form: (r0, r1)·0 + (r2, r3), then both halves into chk.
+  void emit_argmark(int reg) {
+    const Src z = K(0);
+    if (packed) {
+      const Src r01 = V(reg), r23 = V(reg + 2);
+      as.vop3p(VOP3P_FMA_F32, "v_pk_fma_f32", VGT, r01, z, &r23, 0, 5, 0, 0);
+    }
+    for (int e = 0; e < (packed ? 2 : R); ++e) {
+      const Src r = V((packed ? VGT : reg) + e), c = V(VCHK);
+      as.vop3(VOP3_FMA_F32, "v_fma_f32", VCHK, r, z, &c, 0, 0);
+    }
+  }
+  // Routines mark chk when handed a non-finite operand, and nothing inside a body may: a
+  // body that calls one runs between a save and a restore of chk. VCHKSAVE is the redo's
+  // and the bail's in a tree that has either; there the save takes a register of a free
+  // pool block for the length of the body (bodies never nest: one location is enough).
+  int body_save = -1, body_blk = -1;
+  bool body_begin(int i) {
+    bool calls = false;
+    for (int j = i; j < (int)ops.size() && ops[j].body; ++j) {
+      calls = calls || ops[j].rid >= 0;
+      if (ops[j].argmark) break;
+    }
+    if (!calls) return true;
+    if (fast || has_trig) {
+      body_blk = free_block();
+      if (body_blk < 0) { why = "register pool exhausted (body chk)"; return false; }
+      pool_owner[body_blk] = kBodySave;
+      body_save = VPOOL0 + R * body_blk;
+    } else {
+      body_save = VCHKSAVE;
+    }
+    as.vop1(VOP1_MOV, "v_mov_b32_e32", body_save, V(VCHK));
+    return true;
+  }
+  void body_end() {
+    if (body_save < 0) return;
+    as.vop1(VOP1_MOV, "v_mov_b32_e32", VCHK, V(body_save));
+    if (body_blk >= 0) pool_owner[body_blk] = -1;
+    body_save = body_blk = -1;
+  }
+  static constexpr int kBodySave = 3000;
   void release_x(int f, int i) {
     if (xlast[f] == i && xblk[f] >= 0 && pool_owner[xblk[f]] == 1000 + f) pool_owner[xblk[f]] = -1;
   }
@@ -826,6 +926,7 @@ struct Gen {
     const int va_ = o.a.k == O_VAL ? o.a.v : -1;
     const int vb_ = (!o.un && o.b.k == O_VAL) ? o.b.v : -1;
     wait_for2(o);
+    if (!keep_operand(i, va_, !o.un) || !keep_operand(i, vb_, !o.un)) return false;
     // routines keep B: a unary call leaves its owner there
     if (!evict(L_A, va_, vb_) || (!o.un && !evict(L_B, va_, vb_))) return false;
     // move the operands into A (lhs) and B (rhs)
@@ -856,7 +957,7 @@ struct Gen {
     if (!o.un && o.b.k == O_X) release_x(o.b.v, i);
     a_owner = -1;
     if (!o.un) b_owner = -1;
-    if (fast && o.un && o.op == SRHIP_UOP_EXP) {  // max |x| over the rows, two per instruction
+    if (fast && exp_guarded(o)) {  // max |x| over the rows, two per instruction
       // a FAST-derived x counts 87/16 times its size: |x| > 16 fires the 87 check
       int src = VA;
       if (exp_tainted(o)) {
@@ -877,7 +978,8 @@ struct Gen {
       }
     const bool tsmall = fast && trig_small(o);
     if (tsmall) mov_block_reg(VGT, VA);  // u, for the condition check after the call
-    call_routine(o.rid);
+    if (o.body) call_body(o.rid);
+    else call_routine(o.rid);
     loc[i] = L_A;
     a_owner = i;
     if (tsmall) {  // fires when 2^-k·|u| - |sin/cos u| > 0 (or NaN)
@@ -902,16 +1004,16 @@ struct Gen {
     const Opnd& q = kr ? o.a : o.b;
     const int vq = q.k == O_VAL ? q.v : -1;
     wait_for(q);
-    if (!evict(L_A, vq, -1)) return false;
+    if (!keep_operand(i, vq, false) || !evict(L_A, vq, -1)) return false;
     const int lq = vq >= 0 ? loc[vq] : L_NONE;
     if (lq != L_A) {
       bool issued = false;
       operand_to(VA, q, &issued);
       wait_direct(issued);
     }
-    if (vq >= 0) release_val(vq);
+    const bool last = vq >= 0 && release_val(vq);
     if (q.k == O_X) release_x(q.v, i);
-    if (vq >= 0 && lq == L_B) b_owner = -1;
+    if (last && lq == L_B) b_owner = -1;
     a_owner = -1;
     const uint32_t cb = kr ? o.b.c : o.a.c;
     if (memc) as.sop1(SOP1_MOV, "s_mov_b32", S_K, S(creg(kr ? o.b : o.a)), "s" + std::to_string(S_K));
@@ -934,7 +1036,8 @@ struct Gen {
     // chain bounds |c| from below, nothing bounds it from above); any other c
     // goes straight to the compiled routine, where the packed one would send it
     if (!memc && !kr && o.op == SRHIP_BOP_DIV && !(ac >= 0x1p-45f && ac <= 0x1p45f)) rid = full_routine(rid);
-    call_routine(rid);
+    if (o.body) call_body(rid);
+    else call_routine(rid);
     loc[i] = L_A;
     a_owner = i;
     if (fast && o.taint && o.zs && o.op == SRHIP_BOP_DIV) guard_min(VA);
@@ -979,8 +1082,7 @@ struct Gen {
     auto rel = [&](int v) {
       if (v < 0) return;
       const int l = loc[v];
-      release_val(v);
-      if (l >= 0 && freed < 0) freed = l;
+      if (release_val(v) && l >= 0 && freed < 0) freed = l;
     };
     rel(va_);
     rel(vb_);
@@ -997,7 +1099,15 @@ struct Gen {
     if (dst == L_NONE) dst = freed >= 0 ? freed : free_block();
     if (dst == L_NONE) { why = "register pool exhausted"; return false; }
     const int d = reg_of_loc(dst);
-    const bool ca = o.a.k == O_C, cb = !o.un && o.b.k == O_C;
+    bool ca = o.a.k == O_C;
+    const bool cb = !o.un && o.b.k == O_C;
+    if (o.un && ca && o.body) {  // a body's operator on a constant argument: the constant into the block first
+      for (int e = 0; e < R; ++e) {
+        as.vop1(VOP1_MOV, "v_mov_b32_e32", d + e, a[e]);
+        a[e] = V(d + e);
+      }
+      ca = false;
+    }
     const bool pk_bin = packed && !o.un && !(ca && cb) &&
                         (o.op == SRHIP_BOP_ADD || o.op == SRHIP_BOP_SUB || o.op == SRHIP_BOP_MUL);
     const bool pk_un = packed && o.un && !ca && (o.op == SRHIP_UOP_SQUARE || o.op == SRHIP_UOP_CUBE);
@@ -1044,7 +1154,7 @@ struct Gen {
         }
       }
     }
-    if (o.un && (o.a.k == O_C)) { why = "unary operator on a constant"; return false; }
+    if (o.un && ca) { why = "unary operator on a constant"; return false; }
     loc[i] = dst;
     if (dst == L_A) a_owner = i;
     else if (dst == L_B) b_owner = i;
@@ -1150,10 +1260,22 @@ struct Gen {
     gdone = 0;
     if (xg) gnum = 0;
     std::fill(loc.begin(), loc.end(), (int)L_NONE);
+    for (size_t v = 0; v < uses_left.size(); ++v) uses_left[v] = ops[v].nuse;
+    bool inbody = false;
     for (int i = 0; i < (int)ops.size(); ++i) {
       if (xg && !xwindow(i)) return false;
+      if (ops[i].body && !inbody) {
+        if (!body_begin(i)) return false;
+        inbody = true;
+      }
       if (ops[i].rid >= 0) { if (!emit_call(i)) return false; }
       else if (!emit_inline(i)) return false;
+      // a body ends at its last operation, or where its result is the next operator's argument
+      if (inbody && (ops[i].argmark || i + 1 == (int)ops.size() || !ops[i + 1].body)) {
+        body_end();
+        inbody = false;
+      }
+      if (ops[i].argmark) emit_argmark(reg_of_loc(loc[i]));
     }
     // root value
     int rreg;
@@ -1279,6 +1401,21 @@ struct Gen {
     if (as.want_text)
       as.lines.back() = "s_swappc_b64 s[" + std::to_string(S_RR) + ":" + std::to_string(S_RR + 1) + "], s[" +
                         std::to_string(S_TGT) + ":" + std::to_string(S_TGT + 1) + "]";
+  }
+
+  // A routine of an expression operator's body: the PRECISE one whatever the tile's mode, as
+  // the expression loss's. An opaque function's value is then the interpreter's for the
+  // argument it is given, in a FAST tile too: the expansion of such a tree reads most
+  // u(x_f) of a body from PRECISE columns, which a body may not (no shared-subtree column
+  // inside one), and a FAST value in their place reaches the loss through the consumers'
+  // cancellations. A trig routine may still hand the tile back.
+  void call_body(int rid) {
+    call_precise(rid);
+    if (kRoutineTrig[rid]) {
+      as.sopc(SOPC_LG_U64, "s_cmp_lg_u64", S(S_FLAG), K(0),
+              "s[" + std::to_string(S_FLAG) + ":" + std::to_string(S_FLAG + 1) + "]");
+      as.branch(SOPP_SCC1, "s_cbranch_scc1", L_bail);
+    }
   }
 
   // ---- expression loss (Options::lexpr) -------------------------------------------
@@ -1764,6 +1901,7 @@ static bool codegen_par(const CompiledBatch<float>& cb, const std::vector<int32_
                         const Columns& cols, size_t* stop) {
   DerivedMap dm;
   dm.cols = &cols;
+  dm.xops = opt.exprops;
   dm.set_shared(cols);
   const size_t n = cand.size() - from;
   struct R { std::vector<uint32_t> w; bool ok = false, fast = false; std::string why; size_t start = 0; };
@@ -1838,6 +1976,7 @@ static size_t codegen(const CompiledBatch<float>& cb, const std::vector<int32_t>
   }
   DerivedMap dm;
   dm.cols = &cols;
+  dm.xops = opt.exprops;
   dm.set_shared(cols);
   for (size_t k = from; k < cand.size(); ++k) {
     const int32_t t = cand[k];
@@ -1909,7 +2048,7 @@ size_t lds_per_workgroup(int waves) {
 // precise: the tree code runs its routines PRECISE (the gradient code's
 // forward), so an occurrence saves the PRECISE price; env: the cap's variable.
 static void plan_shared(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand, bool on, Columns& c,
-                        bool precise = false, const char* env = "SRHIP_JIT_GCOLS", int dflt = 32) {
+                        bool precise = false, const char* env = "SRHIP_JIT_GCOLS", int dflt = 32, bool xops = false) {
   const int gmax = env_int(env, dflt, 0, kMaxGlobalCols);  // read per build: A/B tests
   const int room = std::min(gmax, 255 - c.gbase());
   if (!on || room <= 0) return;
@@ -1922,6 +2061,7 @@ static void plan_shared(const CompiledBatch<float>& cb, const std::vector<int32_
   std::unordered_map<std::string, Info> info;
   DerivedMap dm;
   dm.cols = &c;
+  dm.xops = xops;
   std::vector<IrOp> ir;
   Opnd root;
   SubtreeInfo si;
@@ -1993,9 +2133,10 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
   std::vector<Cnt> cnt;
   constexpr int min_uses = 4;
   for (int32_t t : cand) {
-    if (cb.tree_off[t] < 0 || !build_ir(&cb.code[cb.tree_off[t]], ir, root)) continue;
+    if (cb.tree_off[t] < 0 || !build_ir(&cb.code[cb.tree_off[t]], ir, root, nullptr, opt.exprops)) continue;
     for (const IrOp& o : ir) {
-      if (o.un && o.a.k == O_X && !o.a.der && is_routine_uop(o.op)) {
+      // (an operator's argument reads no derived column: build_ir)
+      if (o.un && o.a.k == O_X && !o.a.der && is_routine_uop(o.op) && !o.argmark) {
         const uint32_t key = ((uint32_t)o.op << 16) | (uint32_t)o.a.v;
         auto it = std::find_if(cnt.begin(), cnt.end(), [&](const Cnt& q) { return q.key == key; });
         if (it == cnt.end()) cnt.push_back({key, 1}); else ++it->n;
@@ -2014,6 +2155,7 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
     for (size_t k = 0; k < ch.size(); ++k) tmp.der[k] = ch[k];
     DerivedMap dm;
     dm.cols = &tmp;
+    dm.xops = opt.exprops;
     int m = -1;
     for (int32_t t : cand) {
       if (cb.tree_off[t] < 0 || !build_ir(&cb.code[cb.tree_off[t]], ir, root, &dm)) continue;
@@ -2050,7 +2192,7 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
   }
   c.nder = (int)chosen.size();
   for (int k = 0; k < c.nder; ++k) c.der[k] = chosen[k];
-  plan_shared(cb, cand, !opt.out && !opt.memc, c);
+  plan_shared(cb, cand, !opt.out && !opt.memc, c, false, "SRHIP_JIT_GCOLS", 32, opt.exprops);
   // the columns' numbers from the context's registry (the bound plan_shared observes); a batch with
   // more columns than the registry has slots keeps its own numbering and the per-call derive pass
   if (opt.slots && c.ngcol > 0) {
@@ -2060,12 +2202,12 @@ static Columns plan_columns(const CompiledBatch<float>& cb, const std::vector<in
   return c;
 }
 
-int max_feature_read(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand) {
+int max_feature_read(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand, bool exprops) {
   std::vector<IrOp> ir;
   Opnd root;
   int m = -1;
   for (int32_t t : cand) {
-    if (cb.tree_off[t] < 0 || !build_ir(&cb.code[cb.tree_off[t]], ir, root)) continue;
+    if (cb.tree_off[t] < 0 || !build_ir(&cb.code[cb.tree_off[t]], ir, root, nullptr, exprops)) continue;
     for (const IrOp& o : ir) {
       if (o.a.k == O_X) m = std::max(m, o.a.v);
       if (!o.un && o.b.k == O_X) m = std::max(m, o.b.v);
@@ -2078,6 +2220,7 @@ int max_feature_read(const CompiledBatch<float>& cb, const std::vector<int32_t>&
 // wide code is literal-constant loss code: the option is dropped otherwise
 static Options checked(Options opt) {
   if (opt.memc || opt.out) opt.xg = false;
+  if (opt.out || opt.xg) opt.exprops = false;  // loss code that stages its features in LDS only
   if (opt.lexpr) {  // the expression stands in for the table loss: the rest of the build is L2's
     if (opt.out || opt.xg) throw Error(SRHIP_ERR_UNSUPPORTED, "jit: an expression loss with per-row output or wide code");
     opt.loss = SRHIP_LOSS_L2;

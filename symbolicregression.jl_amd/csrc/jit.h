@@ -64,6 +64,13 @@ struct Options {
   // call and from program to program (api.cpp column pool); null: column g of
   // the build is number g
   SlotRegistry* slots = nullptr;
+  // expression operators (SRHIP_PROGRAM_EXPR_OP_TREE_CODE): the
+  // candidates may hold expression-operator code (CompiledBatch::expr), compiled under
+  // the opaque-function rules of srhip.h — each computed argument folded into chk, the
+  // body in line with chk put back after it, its arguments read as often as it names
+  // them. Loss code only (dropped with out or xg). A tree the register pool cannot
+  // hold is refused like any other.
+  bool exprops = false;
 };
 
 // Derived columns: a routine unary operator applied to a dataset feature,
@@ -116,7 +123,7 @@ bool memc(const Module* m);
 // the module is wide loss tree code (Options::xg)
 bool xg(const Module* m);
 // the largest feature index the candidates' code reads (-1: none)
-int max_feature_read(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand);
+int max_feature_read(const CompiledBatch<float>& cb, const std::vector<int32_t>& cand, bool exprops = false);
 // waves per workgroup of the loss tree code for a batch whose code reads
 // `nraw` raw features: 8 from 10 features on (twice the LDS per workgroup, so
 // a wide row tile still fits four times; config #5's shard 20.26 -> 17.10 ms,

@@ -358,12 +358,17 @@ const PROGRAM_WIDE_TREE_CODE = UInt32(4)
 # deriv_tree_code (opt-in): srhip_eval_loss_deriv on a Float32 program may run reverse-mode
 # tree code (SRHIP_PROGRAM_DERIV_TREE_CODE; eval_loss_deriv's tree_code keyword)
 const PROGRAM_DERIV_TREE_CODE = UInt32(32)
+# expr_op_tree_code (opt-in): the Float32 loss tree code also compiles the trees that hold
+# expression operators (SRHIP_PROGRAM_EXPR_OP_TREE_CODE); a tree it refuses stays interpreted
+const PROGRAM_EXPR_OP_TREE_CODE = UInt32(128)
 function Program(trees::AbstractVector{Node{T}}, options::Options, device::Int=0;
-                 varying_constants::Bool=false, wide_tree_code::Bool=false) where {T}
+                 varying_constants::Bool=false, wide_tree_code::Bool=false,
+                 expr_op_tree_code::Bool=false) where {T}
     node_off, kind, arg, const_off, consts = flatten(trees, options)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     flags = (varying_constants ? PROGRAM_VARYING_CONSTANTS : UInt32(0)) |
-            (wide_tree_code ? PROGRAM_WIDE_TREE_CODE : UInt32(0))
+            (wide_tree_code ? PROGRAM_WIDE_TREE_CODE : UInt32(0)) |
+            (expr_op_tree_code ? PROGRAM_EXPR_OP_TREE_CODE : UInt32(0))
     GC.@preserve node_off kind arg const_off consts begin
         tr = Ref(SrhipTrees(Int32(length(trees)), pointer(node_off), pointer(kind), pointer(arg),
                             pointer(const_off), Ptr{Cvoid}(pointer(consts))))

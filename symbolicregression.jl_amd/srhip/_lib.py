@@ -170,6 +170,8 @@ SIGNATURES = {
     "srhip_program_shared_columns": [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)],
     "srhip_jit_compile": [C.POINTER(Trees), C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_char_p,
                           C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)],
+    "srhip_jit_compile_ex": [C.POINTER(Trees), C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(C.c_int64), C.c_char_p,
+                             C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)],
     "srhip_jit_compile_deriv": [C.POINTER(Trees), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                 C.c_void_p, C.POINTER(C.c_int64), C.c_char_p, C.POINTER(C.c_int64), C.c_void_p,
                                 C.POINTER(C.c_int64)],

@@ -4,6 +4,7 @@ tests/test_abi.py)."""
 F32, F64 = 0, 1
 PROGRAM_VARYING_CONSTANTS = 1  # srhip_program_create_ex flag (include/srhip.h)
 PROGRAM_INTERPRETED = 2  # srhip_program_create_ex flag: no loss / output tree code (include/srhip.h)
+PROGRAM_EXPR_OP_TREE_CODE = 128  # srhip_program_create_ex flag: Float32 loss tree code also compiles trees that hold expression operators
 PROGRAM_WIDE_TREE_CODE = 4  # srhip_program_create_ex flag: Float32 loss tree code may read its features from X in memory
 PROGRAM_DERIV_TREE_CODE = 32  # srhip_program_create_ex flag: srhip_eval_loss_deriv may run reverse-mode tree code (Float32)
 PROGRAM_DERIV_GRAD_TREE_CODE = 64  # srhip_program_create_ex flag: srhip_eval_objective_grad_deriv may run the objective's gradient tree code (Float32)

@@ -238,11 +238,20 @@ class Program:
     Float32 program runs reverse-mode tree code when ndir <= 4, the loss is a distance
     loss other than Periodic and the dataset is not wide; otherwise the interpreter.
     deriv_grad_tree_code (SRHIP_PROGRAM_DERIV_GRAD_TREE_CODE, opt-in): under the same
-    limits eval_objective_grad_deriv runs the objective's one-pass gradient tree code."""
+    limits eval_objective_grad_deriv runs the objective's one-pass gradient tree code.
+    expr_op_tree_code (SRHIP_PROGRAM_EXPR_OP_TREE_CODE, opt-in): the Float32 loss tree
+    code also compiles the trees that hold expression operators (ExprOp); a tree it
+    refuses stays in the interpreter."""
 
     def __init__(self, ctx: Context, flat: FlatTrees, dtype, varying_constants: bool = False,
                  interpreted: bool = False, wide_tree_code: bool = False, deriv_tree_code: bool = False,
-                 deriv_grad_tree_code: bool = False):
+                 deriv_grad_tree_code: bool = False, expr_op_tree_code: bool = False):
+        self.flags = ((K.PROGRAM_VARYING_CONSTANTS if varying_constants else 0)
+                      | (K.PROGRAM_INTERPRETED if interpreted else 0)
+                      | (K.PROGRAM_WIDE_TREE_CODE if wide_tree_code else 0)
+                      | (K.PROGRAM_DERIV_TREE_CODE if deriv_tree_code else 0)
+                      | (K.PROGRAM_DERIV_GRAD_TREE_CODE if deriv_grad_tree_code else 0)
+                      | (K.PROGRAM_EXPR_OP_TREE_CODE if expr_op_tree_code else 0))
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self.flat = flat
@@ -257,13 +266,7 @@ class Program:
             consts.ctypes.data_as(C.c_void_p),
         )
         h = C.c_void_p()
-        check(lib().srhip_program_create_ex(ctx.handle, dtype_code(self.dtype), C.byref(tr),
-                                            (K.PROGRAM_VARYING_CONSTANTS if varying_constants else 0)
-                                            | (K.PROGRAM_INTERPRETED if interpreted else 0)
-                                            | (K.PROGRAM_WIDE_TREE_CODE if wide_tree_code else 0)
-                                            | (K.PROGRAM_DERIV_TREE_CODE if deriv_tree_code else 0)
-                                            | (K.PROGRAM_DERIV_GRAD_TREE_CODE if deriv_grad_tree_code else 0),
-                                            C.byref(h)))
+        check(lib().srhip_program_create_ex(ctx.handle, dtype_code(self.dtype), C.byref(tr), self.flags, C.byref(h)))
         self.handle = h
         self.ntrees = flat.ntrees
 
@@ -764,7 +767,8 @@ def _trees_struct(flat: FlatTrees, consts: np.ndarray) -> Trees:
 
 
 def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bool = False, loss=None,
-                out: bool = False, text: bool = True, wide: bool = False, deriv=None, deriv_grad: bool = False):
+                out: bool = False, text: bool = True, wide: bool = False, deriv=None, deriv_grad: bool = False,
+                expr_ops: bool = False):
     """Tree compiler without a device (srhip_jit_compile, or with grad=True
     srhip_jit_compile_grad: the reverse-mode gradient tree code; memc: the
     memory-constant loss tree code; loss: a Loss other than L2, through
@@ -774,7 +778,8 @@ def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bo
     {tree id: byte offset}). deriv=(directions (0-based), nfeat, weighted): the
     derivative tree code of eval_loss_deriv (srhip_jit_compile_deriv), under `loss`
     (default L2); with deriv_grad=True the objective's gradient tree code
-    (srhip_jit_compile_deriv_grad)."""
+    (srhip_jit_compile_deriv_grad). expr_ops: srhip_jit_compile_ex with
+    SRHIP_PROGRAM_EXPR_OP_TREE_CODE, which compiles the trees that hold expression operators too."""
     f64 = np.dtype(flat.consts.dtype) == np.float64
     consts = np.ascontiguousarray(flat.consts, dtype=np.float64 if f64 else np.float32)
     tr = _trees_struct(flat, consts)
@@ -804,10 +809,12 @@ def jit_compile(flat: FlatTrees, fast: bool = True, grad: bool = False, memc: bo
         if grad:
             return lib().srhip_jit_compile_grad(C.byref(tr), bufs[0], C.byref(nb), bufs[1], C.byref(nt), bufs[2],
                                                 C.byref(no))
-        return lib().srhip_jit_compile(C.byref(tr), int(fast) | (2 if memc else 0) | (4 if out else 0) |
-                                       (0 if text else 16) | (32 if wide else 0), bufs[0],
-                                       C.byref(nb), bufs[1],
-                                       C.byref(nt), bufs[2], C.byref(no))
+        bits = int(fast) | (2 if memc else 0) | (4 if out else 0) | (0 if text else 16) | (32 if wide else 0)
+        if expr_ops:
+            return lib().srhip_jit_compile_ex(C.byref(tr), bits, K.PROGRAM_EXPR_OP_TREE_CODE, bufs[0], C.byref(nb),
+                                              bufs[1], C.byref(nt), bufs[2], C.byref(no))
+        return lib().srhip_jit_compile(C.byref(tr), bits, bufs[0], C.byref(nb), bufs[1], C.byref(nt), bufs[2],
+                                       C.byref(no))
 
     rc = call(None, None, None)
     if rc != -1:
