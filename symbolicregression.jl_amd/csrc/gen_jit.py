@@ -474,11 +474,22 @@ def manual_div(rg):
     difference of 96, no denormal reciprocal or quotient), v_div_fmas_f32 is a
     plain fma and v_div_fixup_f32 returns its input, so hipcc's IEEE sequence
     reduces to rcp, e = 1 - b*r, r += e*r, q = a*r, e = a - b*q, q += e*r,
-    e = a - b*q, q += e*r — the same roundings, here two rows per v_pk_*_f32
-    instruction. Rows out of the range (0, Inf, extreme exponents) send all
-    four to the compiled routine (b_div_full), which marks b; so b needs no
-    mark here: an infinite b (whose quotient would lose it) never takes
-    this path, and a NaN b gives a NaN quotient."""
+    e = a - b*q, q += e*r. The body stops after the first residual step:
+    rcp, e = 1 - b*r, y = r + e*r, q = a*y, s = a - b*q, q + s*y, two rows
+    per v_pk_*_f32 instruction (4 v_rcp_f32 + 10 packed). With y = RN(1/b)
+    and q = RN(a*y) that value already is RN(a/b) (Markstein), so the second
+    residual step changed nothing; and on gfx950 one Newton step on v_rcp_f32
+    gives y = RN(1/b) at every divisor significand. Both are measured, not
+    quoted: tools/div_short_sweep.hip compares this sequence with hipcc's
+    a / b on the device over all 2^46 pairs of significands, no mismatch
+    (profiles/div_short_exhaustive.json). tools/check_div_short.c shows what
+    that rests on: with a reciprocal one ulp beside RN(1/b) the sequence
+    misrounds at a few divisors (0x1.fffffep0 among them), which this
+    hardware's v_rcp_f32 does not return there. Rows out of the range (0,
+    Inf, extreme exponents) send all four to the compiled routine
+    (b_div_full), which marks b; so b needs no mark here: an infinite b
+    (whose quotient would lose it) never takes this path, and a NaN b gives
+    a NaN quotient."""
     neg0 = " neg_lo:[1,0,0] neg_hi:[1,0,0]"
     return ["v_max3_f32 v0, |v32|, |v33|, |v34|",
             "v_min3_f32 v1, |v32|, |v33|, |v34|",
@@ -505,10 +516,6 @@ def manual_div(rg):
             "v_pk_fma_f32 v[4:5], v[8:9], v[4:5], v[4:5]",
             "v_pk_mul_f32 v[10:11], v[32:33], v[2:3]",
             "v_pk_mul_f32 v[12:13], v[34:35], v[4:5]",
-            "v_pk_fma_f32 v[6:7], v[36:37], v[10:11], v[32:33]" + neg0,
-            "v_pk_fma_f32 v[8:9], v[38:39], v[12:13], v[34:35]" + neg0,
-            "v_pk_fma_f32 v[10:11], v[6:7], v[2:3], v[10:11]",
-            "v_pk_fma_f32 v[12:13], v[8:9], v[4:5], v[12:13]",
             "v_pk_fma_f32 v[6:7], v[36:37], v[10:11], v[32:33]" + neg0,
             "v_pk_fma_f32 v[8:9], v[38:39], v[12:13], v[34:35]" + neg0,
             "v_pk_fma_f32 v[32:33], v[6:7], v[2:3], v[10:11]",
@@ -548,10 +555,6 @@ def manual_div_lc(rg):
             f"v_pk_mul_f32 v[12:13], {cp}, v[4:5] op_sel:[1,0]",
             f"v_pk_fma_f32 v[6:7], v[32:33], v[10:11], {cp} op_sel:[0,0,1]" + neg0,
             f"v_pk_fma_f32 v[8:9], v[34:35], v[12:13], {cp} op_sel:[0,0,1]" + neg0,
-            "v_pk_fma_f32 v[10:11], v[6:7], v[2:3], v[10:11]",
-            "v_pk_fma_f32 v[12:13], v[8:9], v[4:5], v[12:13]",
-            f"v_pk_fma_f32 v[6:7], v[32:33], v[10:11], {cp} op_sel:[0,0,1]" + neg0,
-            f"v_pk_fma_f32 v[8:9], v[34:35], v[12:13], {cp} op_sel:[0,0,1]" + neg0,
             "v_pk_fma_f32 v[32:33], v[6:7], v[2:3], v[10:11]",
             "v_pk_fma_f32 v[34:35], v[8:9], v[4:5], v[12:13]"]
 
@@ -564,6 +567,13 @@ def manual_div_lc(rg):
 # which the FAST verdict (jit.cpp) answers by redoing the tile with the
 # PRECISE region, whose bodies stay two-sided (tools/check_div_range.c).
 DIV_FAST_MIN = "0x26800000"  # 2^-50
+
+# Least slot size (bytes) of a routine in both regions. The packed divisions
+# keep the slots they had with the longer sequence (two residual steps: 240 and
+# 208 bytes in the PRECISE region), so that no later routine's entry offset
+# moves with their length: generated tree code holds those offsets. The fill
+# after a routine's return is never executed.
+SLOT_MIN = {"b_div": 256, "b_div_lc": 256}
 
 
 def manual_div_fast(rg):
@@ -736,7 +746,7 @@ def build(hipcc, outdir, R):
               for l in b] for n, b in fb.items()}
     pb = {n: [l.replace("@DIVRC@", ".Lsrent_prec_b_div_rc").replace("@DIVFULL@", ".Lsrent_prec_b_div_full")
               .replace("@LCFULL@", ".Lsrent_prec_b_div_lc_full") for l in b] for n, b in pb.items()}
-    slot = {n: (max(fs[n], ps[n]) + 63) // 64 * 64 for n in names}
+    slot = {n: max((max(fs[n], ps[n]) + 63) // 64 * 64, SLOT_MIN.get(n, 0)) for n in names}
     text = ["s_endpgm"]
     for region, bodies, sizes in (("fast", fb, fs), ("prec", pb, ps)):
         text.append(".p2align 8")

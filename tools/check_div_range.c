@@ -6,7 +6,10 @@
  *   b_div     a / b    r = rcp(b); e = fma(-b, r, 1); r = fma(e, r, r); q = a*r;
  *                      e = fma(-b, q, a); q = fma(e, r, q); e = fma(-b, q, a); q = fma(e, r, q)
  *                      kept when min(|a|, |rcp(b)|) >= 2^k
- *   b_div_lc  c / a    the same sequence with the constant as the numerator,
+ *                      (the bodies have since dropped the second residual
+ *                      step: tools/check_div_short.c `range` is this model
+ *                      for the sequence they run now)
+ *   b_div_lc  c / a   the same sequence with the constant as the numerator,
  *                      kept when min(|c|, |rcp(a)|) >= 2^k
  *   b_div_rk  a / c    y = RN(1/c) from the host, |c| in [2^-60, 2^60];
  *                      q = a*y; r = fma(-c, q, a); q = fma(r, y, q)
