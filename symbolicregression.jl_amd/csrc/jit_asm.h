@@ -334,7 +334,9 @@ struct Asm {
         ", s[" + std::to_string(saddr) + ":" + std::to_string(saddr + 1) + "]" + (off ? " offset:" + std::to_string(off) : ""));
   }
   void waitcnt_vm(int n) { sopp(0x0c, "s_waitcnt", 0x0f70 | (n & 15), false); if (want_text) lines.back() = "s_waitcnt vmcnt(" + std::to_string(n) + ")"; }
-  void waitcnt_lgkm(int n) { sopp(0x0c, "s_waitcnt", 0xc07f | (n << 8), false); if (want_text) lines.back() = "s_waitcnt lgkmcnt(" + std::to_string(n) + ")"; }
+  // lgkmcnt is a 4-bit field ([11:8]): with more than 16 loads in flight (the gradient pools
+  // preload up to 20 features) the count saturates at 15, which waits for no less
+  void waitcnt_lgkm(int n) { n = n > 15 ? 15 : n; sopp(0x0c, "s_waitcnt", 0xc07f | (n << 8), false); if (want_text) lines.back() = "s_waitcnt lgkmcnt(" + std::to_string(n) + ")"; }
 
   void finish() {
     for (const Fix& f : fix) {
